@@ -2,7 +2,7 @@
 """Benchmark of the Vine5LinkMovingBase hot path on MI355X (BASELINE.json: env-steps/sec at 16384 envs per GPU,
 PPO iters/sec).
 
-    python bench.py --gpus 1 --steps K --warmup W [--mode ppo|env] [--num-envs 16384]
+    python bench.py --gpus 1 --steps K --warmup W [--mode ppo|env] [--num-envs 16384] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One rank per GPU; every rank owns `num_envs` independent envs (weak scaling, BASELINE configs 3/4).
@@ -10,15 +10,26 @@ mode=ppo (default once the learner is available): a "step" is one full PPO itera
   inference + env step] + GAE + mini-epoch updates with the RCCL gradient all-reduce; value = env-steps/sec of the
   whole job (N x horizon x ranks / iteration time), ppo_iters_per_sec reported beside it.
 mode=env: a "step" is one VecTask.step over resident random actions (the hand-written HIP kernel alone).
-Rank 0 prints ONE JSON line.  The `roofline` object prices the env-step kernel (`roofline.kernel`: four lanes per env up
-to 16384 envs, one lane per env beyond) with HIP events recorded on the launching stream inside the timed region; `cpu_baseline` times the CPU oracle
-(oracle/, OpenMP over envs) on a bounded sample of the same workload on this host's cores.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line (headline `value`,
+`ms_per_step` = wall time of one timed step); everything else takes runs of its own and needs --full:
+  * `roofline` prices the env-step kernel (`roofline.kernel`: four lanes per env up to 16384 envs, one lane per env beyond)
+    with HIP events recorded on the launching stream inside the timed region (mode=env and --no-graph: present without
+    --full as well, the events are part of the timed region) or, for graph-replayed PPO iterations, the same kernel
+    replayed from a hipGraph after it; `roofline.saturated` the kernel at 2^20 envs;
+  * `env_only`, `other_precision`, `extra_*_rollout`, `ppo_kernel_rooflines` (mode=ppo): see bench_support.run_ppo_bench;
+  * `configs`: the other BASELINE configurations; `cpu_baseline` times the CPU oracle (oracle/, OpenMP over envs) on a
+    bounded sample of the same workload on this host's cores.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; bounded by a fixed row sample):
+the env's step outputs, and for mode=ppo the model state, the per-optimiser-step loss statistics and the iteration's
+dataset.  Inputs are seeded: the same arguments give the same inputs on every run.
 """
 import argparse
 import json
 import os
 import sys
 import time
+
+import numpy as np
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
@@ -47,6 +58,12 @@ def parse_args():
                         "(rank r owns envs [r n/W, (r+1) n/W) of the SAME batch: same seed, VineConfig.env_id_offset)")
     p.add_argument("--randomize", type=int, default=1, help="task.vine_randomize (task YAML default: True)")
     p.add_argument("--obs-type", default="POS_AND_FD_VEL_AND_OBJ_INFO")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: roofline of the env-step kernel, the saturated kernel, "
+                        "the other BASELINE configurations, the other precisions, per-kernel rooflines, the CPU baseline "
+                        "(each still switched off by its --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true", help="ppo mode: skip the run in the other update precision")
@@ -378,6 +395,28 @@ def cpu_baseline(args, seconds, mode, cfg):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 32768          # per-sample arrays of the PPO dataset (16 x 16384 rows by default): a fixed row sample
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array of `arrays` ({name: tensor}) as out_dir/<name>.npy: floating tensors keep float64 or become
+    float32, integer and boolean ones become float32 (exact below 2^24).  Arrays of more than DUMP_SAMPLE_ROWS rows whose
+    name starts with "dataset_" are cut to a fixed, seeded sample of their rows (the same rows on every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if name.startswith("dataset_") and a.ndim >= 1 and a.shape[0] > DUMP_SAMPLE_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            a = a[rows]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit("--dump-outputs: more than %d MB of outputs (at %s)" % (DUMP_MAX_BYTES >> 20, name))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     # stdout carries exactly ONE line, the JSON result: anything the libraries print on the way (e.g. the action /
@@ -390,6 +429,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.manual_seed(42 + rank)          # the model's initial weights: the same inputs on every run (--dump-outputs)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the product has no CPU path")
     # Rehearsal hook (one-GPU box): VINE_BENCH_SHARE_DEVICE=1 maps every rank onto cuda:0 and uses gloo, so the
@@ -446,9 +486,15 @@ def main():
         elapsed = time.perf_counter() - t0
         kernel_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
         units_per_step = n
+        outputs = {"env_obs": env.obs_buf, "env_rew": env.rew_buf, "env_reset": env.reset_buf,
+                   "env_progress": env.progress_buf, "env_timeout": env.timeout_buf}
     else:
         from vine_robot_isaacgymenvs_amd.learning.bench_support import run_ppo_bench
-        elapsed, kernel_ms, units_per_step, extra = run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank)
+        # (outputs: bench_support.last_iteration_outputs of the last timed iteration when --dump-outputs is given)
+        elapsed, kernel_ms, units_per_step, extra, outputs = run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
 
     t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
@@ -457,9 +503,6 @@ def main():
 
     if rank == 0:
         value = units_per_step * world * steps / elapsed
-        algo_bytes = ALGO_BYTES_PER_ENV_STEP[env.num_obs] * n
-        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(kernel_instance(env))
         out = {
             "metric": ("env-steps/sec Vine5LinkMovingBase %d envs over %d GPUs" % (n * world, world)) if strong
                       else "env-steps/sec Vine5LinkMovingBase %d envs per GPU" % n,
@@ -471,16 +514,21 @@ def main():
                                    "(BASELINE.json configs[2]; x8 ranks = configs[3])"
                                    % (n, env.num_obs, bool(args.randomize), mode),
                        "mode": mode, "num_envs_per_gpu": n, "parallelism": "env-sharded dp%d" % world},
+        }
+        if kernel_ms is not None:         # (graph-replayed PPO iterations: timed after the steps, --full only)
+            algo_bytes = ALGO_BYTES_PER_ENV_STEP[env.num_obs] * n
+            achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(kernel_instance(env))
             # achieved / peak / frac: the mandated HBM pricing of the algorithmic bytes.  `bound` names what really limits the
             # kernel (fp32 VALU issue: ~85 flop per algorithmic byte, working set resident in L2) and `compute` prices it.
-            "roofline": {"bound": "valu", "kernel": env.step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
-                         "kernel_ms_method": ("HIP events around every eager launch of the timed region" if (mode == "env" or args.no_graph)
-                                              else "64 launches replayed from a hipGraph, one event pair around 8 replays"),
-                         "trace_kernel_us": trace_kernel_us(kernel_instance(env)),
-                         "compute": compute_roofline(env.step_kernel_name, n, kernel_ms, kernel_instance(env))},
-        }
+            out["roofline"] = {
+                "bound": "valu", "kernel": env.step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": kernel_ms,
+                "kernel_ms_method": ("HIP events around every eager launch of the timed region" if (mode == "env" or args.no_graph)
+                                     else "64 launches replayed from a hipGraph, one event pair around 8 replays"),
+                "trace_kernel_us": trace_kernel_us(kernel_instance(env)),
+                "compute": compute_roofline(env.step_kernel_name, n, kernel_ms, kernel_instance(env))}
         out.update(extra)
         if mode == "ppo":
             # env step kernel f32; rollout inference f32 (the reference's); the update takes the reference's
@@ -489,11 +537,11 @@ def main():
             # narrower 16-bit-rollout variant of round 2, `extra_native_f32_mfma_rollout` the rollout's LSTM step on the
             # native fp32 matrix-core instruction instead of exact bf16-piece products, `extra_split9_rollout` the 9-pair form of the (6-pair, two-accumulator) default.
             out["dtype"] = "f32 (env step, rollout inference); " + str(extra.get("update_precision", ""))
-        if world == 1 and not args.no_saturated:
+        if args.full and world == 1 and not args.no_saturated and "roofline" in out:
             out["roofline"]["saturated"] = saturated_env_rate(args, local_rank)
-        if world == 1 and not args.no_other_configs:
+        if args.full and world == 1 and not args.no_other_configs:
             out["configs"] = other_config_rates(args, local_rank, mode=mode)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_baseline_seconds, mode, cfg)
         print(json.dumps(out), file=real_stdout, flush=True)
     env.close()

@@ -10,7 +10,8 @@ top but that are not installed (isaacgym, gym, wandb, rl_games-free paths only),
 reference's ``vec_task.py`` and ``Vine5LinkMovingBase.py`` *from where they lie* under
 /root/reference, builds the real task object through its real ``__init__`` on top of a
 ``FakeGym`` tensor API, and records inputs/outputs of the reference functions as small ``.npz``
-files.  Nothing of the reference's source is copied; the fixtures are data.
+files (F11: the composed configuration values, as JSON).  Nothing of the reference's source is
+copied; the fixtures are data.
 
 PhysX is not available: for the step-sequencing fixture (F6) ``FakeGym.simulate`` integrates
 the articulation with this repo's CPU oracle (float32 build).  F6 therefore pins the
@@ -18,6 +19,7 @@ reference's ORDER of operations (reset-next-step, stale tip, 4x actuation, FIFO,
 not PhysX numerics.
 """
 import importlib.util
+import json
 import logging
 import math
 import os
@@ -824,7 +826,20 @@ def f10_rollout_bookkeeping(out):
         finished_count=np.array([int(x.shape[0]) for x in snap["upd_r"]], np.int64))
 
 
+def f11_reference_cfg():
+    """F11: the reference's own cfg directory (isaacgymenvs/cfg) composed by this package's loader for
+    task=Vine5LinkMovingBase, every value resolved: a nested dict, written as JSON (tests/test_config.py)."""
+    from vine_robot_isaacgymenvs_amd.utils import config as cf
+    ref = cf.load_config(overrides=["task=Vine5LinkMovingBase"], config_dir=os.path.join(REF, "isaacgymenvs", "cfg"))
+    path = os.path.join(HERE, "f11_reference_cfg.json")
+    with open(path, "w") as f:
+        json.dump(ref, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("%-40s %7.1f KiB" % ("f11_reference_cfg.json", os.path.getsize(path) / 1024))
+
+
 def main():
+    f11_reference_cfg()
     install_stubs()
     vt, v5 = load_reference()
     out = {}

@@ -251,6 +251,21 @@ def ppo_iteration_rate(env, cfg, steps=20, warmup=3, amp=None, use_graphs=True):
             "hipgraphs_active": dict(agent.graph_status), "iterations_timed": steps}
 
 
+def last_iteration_outputs(agent, env):
+    """What one PPO iteration hands its caller, as copies: the model after the update (every floating tensor of its state
+    dict, in key order, concatenated), the learning rate, the loss statistics of every optimiser step (rows of a_loss,
+    c_loss, b_loss, entropy, kl, ...), the dataset the update trained on, and the env's outputs of the rollout's last step."""
+    state = [v.detach().float().flatten() for v in agent.model.state_dict().values() if torch.is_floating_point(v)]
+    out = {"model_state": torch.cat(state), "lr": agent.lr.detach().reshape(-1).clone(),
+           "loss_stats": agent._stat_rows.clone()}
+    for k, v in agent.dataset.items():
+        if torch.is_tensor(v):
+            out["dataset_" + k] = v.clone()
+    for k in ("obs", "rew", "reset", "progress", "timeout"):
+        out["env_" + k] = getattr(env, k + "_buf").clone()
+    return out
+
+
 def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
     from .a2c_continuous import A2CAgent
 
@@ -302,29 +317,34 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
         k = elapsed / (play + upd)
         play, upd = play * k, upd * k
 
-    # env step alone (resident random actions), same process, right after the timed region
-    g = torch.Generator(device=agent.device).manual_seed(1)
-    pool = [torch.rand((env.num_envs, 2), device=agent.device, generator=g) * 2 - 1 for _ in range(16)]
-    pairs = []
-    n_env_only = 500
-    for i in range(50):
-        orig(pool[i % 16], env.obs_buf)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(n_env_only):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        orig(pool[i % 16], env.obs_buf)
-        e1.record()
-        pairs.append((e0, e1))
-    torch.cuda.synchronize()
-    env_only_s = time.perf_counter() - t1
-    env_only_kernel_ms = sum(a.elapsed_time(b) for a, b in pairs) / len(pairs)
+    # bench.py --dump-outputs: what the last timed iteration computed, copied before anything below runs
+    outputs = last_iteration_outputs(agent, env) if getattr(args, "dump_outputs", None) else None
+    full = bool(getattr(args, "full", False))
+
+    # --full only: env step alone (resident random actions), same process, right after the timed region
+    env_only = env_only_kernel_ms = graph_kernel_ms = None
+    if full:
+        g = torch.Generator(device=agent.device).manual_seed(1)
+        pool = [torch.rand((env.num_envs, 2), device=agent.device, generator=g) * 2 - 1 for _ in range(16)]
+        pairs = []
+        n_env_only = 500
+        for i in range(50):
+            orig(pool[i % 16], env.obs_buf)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(n_env_only):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            orig(pool[i % 16], env.obs_buf)
+            e1.record()
+            pairs.append((e0, e1))
+        torch.cuda.synchronize()
+        env_only_s = time.perf_counter() - t1
+        env_only_kernel_ms = sum(a.elapsed_time(b) for a, b in pairs) / len(pairs)
     # the same kernel as the DEVICE runs it inside the rollout graph: 64 launches captured into one hipGraph and replayed,
     # timed by ONE pair of events around the replays -- event pairs around single eager launches are host-bound (25.7 us for
     # a kernel whose trace duration is 23.1 us); the graph form leaves only the ~1 us between two nodes
-    graph_kernel_ms = None
-    if conf["use_graphs"] and getattr(env, "graph_capturable", True):
+    if full and conf["use_graphs"] and getattr(env, "graph_capturable", True):
         try:
             gcap = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
@@ -343,8 +363,13 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
             del gcap
         except RuntimeError:
             torch.cuda.synchronize()
+    if full:
+        env_only = {"env_steps_per_sec": env.num_envs * world * n_env_only / env_only_s, "kernel_ms": env_only_kernel_ms,
+                    "graph_replayed_kernel_ms": graph_kernel_ms,
+                    "steps": n_env_only, "note": "VecTask.step alone on resident random actions, per-rank x ranks"}
     # kernel duration inside the timed region when it was launched eagerly; otherwise (launches live inside the
     # replayed hipGraph, where no event can be recorded) the same kernel replayed back to back from a graph just above
+    # (--full; None without it)
     kernel_ms = (sum(a.elapsed_time(b) for a, b in events) / len(events) if events
                  else (graph_kernel_ms if graph_kernel_ms is not None else env_only_kernel_ms))
     in_sync = None
@@ -411,7 +436,7 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
                 "ppo_iters_per_sec": steps / e2, "rollout_ms": p2 * k2 / steps * 1e3, "update_ms": u2 * k2 / steps * 1e3}
 
     other = lp16_rollout = native_f32_rollout = split_other_rollout = None
-    if world == 1 and not getattr(args, "no_secondary", False) and not agent.mixed_precision:
+    if full and world == 1 and not getattr(args, "no_secondary", False) and not agent.mixed_precision:
         # the same PPO iteration in the OTHER update precision (fp32 <-> 16-bit operands), and -- an extra, NARROWER than the
         # reference's fp32 rollout -- with 16-bit GEMM operands in the rollout inference as well (the round-2 configuration);
         # same env, same process: reported beside the headline so that all of them are always visible
@@ -424,7 +449,7 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
             other_terms = 9 if (agent._fast or {}).get("f32_split", 0) == 6 else 6
             split_other_rollout = (other_terms, rerun(rollout_f32_terms=other_terms))
     ppo_kernels = None
-    if world == 1 and agent.fused_mixed and not getattr(args, "no_secondary", False):
+    if full and world == 1 and agent.fused_mixed and not getattr(args, "no_secondary", False):
         try:
             ppo_kernels = ppo_path_rooflines(agent)
         except (AssertionError, RuntimeError, KeyError, ValueError) as err:
@@ -442,9 +467,7 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
         # several ranks: where the gradient all-reduce ran (inside the mini-epoch graph, or eagerly between per-step graphs)
         # and what the collective probe said -- top level, next to replicas_in_sync (also under ppo.collective_in_graph)
         "collective_in_graph": getattr(agent, "collective_capture", None) if (world > 1 or conf["multi_gpu"]) else None,
-        "env_only": {"env_steps_per_sec": env.num_envs * world * n_env_only / env_only_s, "kernel_ms": env_only_kernel_ms,
-                     "graph_replayed_kernel_ms": graph_kernel_ms,
-                     "steps": n_env_only, "note": "VecTask.step alone on resident random actions, per-rank x ranks"},
+        "env_only": env_only,
         "ppo_iters_per_sec": steps / elapsed,
         "rollout_env_steps_per_sec": frames * world * steps / max(play, 1e-9),
         "rollout_ms": play / steps * 1e3, "update_ms": upd / steps * 1e3,
@@ -458,4 +481,8 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
                 # several ranks: did the RCCL all-reduce go INTO the mini-epoch graph (probe outcome), or between per-step graphs
                 "collective_in_graph": getattr(agent, "collective_capture", None)},
     }
-    return elapsed, kernel_ms, frames, extra
+    if not full:          # (measured by --full runs only: absent rather than null)
+        for k in ("ppo_kernel_rooflines", "other_precision", "extra_lp16_rollout", "extra_native_f32_mfma_rollout",
+                  "extra_split_other_rollout", "env_only"):
+            del extra[k]
+    return elapsed, kernel_ms, frames, extra, outputs
