@@ -1432,11 +1432,13 @@ def test_default_loss_kernel_against_reference_text_golden_per_sample():
 @pytest.mark.gpu
 def test_fused_update_equals_stock_update():
     """One optimiser step of the agent through the fused path and through the stock composition, from the same
-    weights and minibatch: same loss statistics, same updated parameters (to fp32 reduction-order noise)."""
+    weights and minibatch: same loss statistics, same updated parameters (to fp32 reduction-order noise).  Adam's first
+    step moves every parameter by about lr * sign(g) whatever the gradient's size, so the gradient blocks of the first
+    optimiser step are compared as well, tensor by tensor, before Adam consumes them."""
     from vine_robot_isaacgymenvs_amd import load_config
     from vine_robot_isaacgymenvs_amd.learning.a2c_continuous import A2CAgent
     from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
-    outs = []
+    outs, firsts = [], []
     for use_fused in (True, False):
         cfg = load_config(overrides=["num_envs=512", "minibatch_size=2048"])
         cfg["task"]["seed"] = 42
@@ -1452,16 +1454,32 @@ def test_fused_update_equals_stock_update():
         agent.game_rewards.mean, agent.game_rewards.current_size = torch.zeros(1, device="cuda:0"), torch.zeros((), device="cuda:0")
         agent.game_lengths.mean, agent.game_lengths.current_size = torch.zeros(1, device="cuda:0"), torch.zeros((), device="cuda:0")
         agent.obs = agent.env_reset()["obs"]
+        first, step = {}, agent.truncate_gradients_and_step
+
+        def capture_first_then_step():
+            if not first:
+                first.update((k, p.grad.detach().clone()) for k, p in agent.model.named_parameters())
+            step()
+        agent.truncate_gradients_and_step = capture_first_then_step
         torch.manual_seed(5)
         play, upd, stats = agent.train_epoch()
         torch.cuda.synchronize()
         outs.append((torch.cat([p.detach().flatten() for p in agent.model.parameters()]),
                      {k: float(v) for k, v in stats.items()}))
+        firsts.append(first)
         env.close()
     (p1, s1), (p2, s2) = outs
     for k in s1:
         assert abs(s1[k] - s2[k]) < 2e-3 * (1 + abs(s2[k])), (k, s1[k], s2[k])
     assert float((p1 - p2).abs().max()) < 2e-3      # 4 Adam steps of 3e-4.. lr: identical sign pattern of the updates
+    g1, g2 = firsts
+    assert set(g1) == set(g2) and len(g1) == len(list(agent.model.parameters()))
+    for k in g2:
+        ref = g2[k].double()
+        d = g1[k].double() - ref
+        assert float(ref.abs().max()) > 0.0, k
+        mx, rms = float(d.abs().max() / ref.abs().max()), float(d.norm() / ref.norm())
+        assert mx < 1e-4 and rms < 1e-4, (k, mx, rms)
 
 
 @pytest.mark.gpu
