@@ -1,0 +1,393 @@
+"""CAPTURE_VIDEO on the GPU: the render kernel against the float64 reference (tests/render_reference.py), the device-side
+capture schedule on the eager, fused and graph-replayed step paths, and the harvest / writer end to end."""
+import glob
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import helpers, render_reference as rr
+from vine_robot_isaacgymenvs_amd import abi, native
+from vine_robot_isaacgymenvs_amd.utils import apng, tfevents
+
+pytestmark = pytest.mark.gpu
+
+# How far fp32 arithmetic can move a shape boundary relative to the float64 reference, in metres.  MEASURED is the largest
+# |float32 - float64| coordinate of any shape corner over the states of test_kernel_matches_reference (forward
+# kinematics restated in numpy float32, render_reference.corner_error: every case prints its own figure and the test
+# asserts none exceeds MEASURED); coordinates are of magnitude 1 (one fp32 ulp there is 1.2e-7) and the chain of five
+# links accumulates a few roundings.  The pixel-centre arithmetic of the kernel (three fp32 operations on coordinates of
+# the same magnitude) and its inside tests add about as much again: DELTA = 4 x MEASURED.
+MEASURED = 1.5e-7            # largest figure printed by the eight cases: 1.27e-7 (shelf, 16384 envs, 1 step), rounded up
+DELTA = 4 * MEASURED
+MAX_EXCLUDED = 0.01          # at most 1 % of a frame may lie inside the band (the issue's condition, asserted)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _rcfg(lib, **over):
+    c = abi.VineRenderConfig()
+    native.check(lib.vine_render_config_default(c), lib)
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def _render(env, rcfg, views, progress=True):
+    """vine_render through the C ABI on a tests/hip_env.HipEnv -> uint8 [rows * H, cols * W]."""
+    v = torch.as_tensor(views, dtype=torch.int32, device=env.dev)
+    out = torch.full(rcfg.frame_shape, 255, dtype=torch.uint8, device=env.dev)
+    native.check(env.lib.vine_render(env.h, rcfg, v.data_ptr(), env.progress_t.data_ptr() if progress else None,
+                                     out.data_ptr(), _stream()), env.lib)
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _compare(img, ref, dist, what):
+    band = dist <= DELTA
+    share = float(band.mean())
+    wrong = (img != ref) & ~band
+    print("%s: %.4f %% of the frame within %.1e m of a boundary, %d pixels differ outside it, %d inside"
+          % (what, 100 * share, DELTA, int(wrong.sum()), int(((img != ref) & band).sum())))
+    assert share <= MAX_EXCLUDED, what
+    return int(wrong.sum())
+
+
+def _cfg(kind, n):
+    """Free space, shelf and pipe configurations (the F6 fixtures' obstacle placements, episodes of 60 steps so that
+    resets occur within a few hundred steps)."""
+    cfg = helpers.f6_cfg(n, 1, 0, {"free": False, "shelf": "shelf", "pipe": "pipe"}[kind])
+    cfg.max_episode_length = 60
+    cfg.seed = 1234
+    return cfg
+
+
+def _drive(env, steps, seed):
+    g = torch.Generator(device=env.dev).manual_seed(seed)
+    for _ in range(steps):
+        env.step_t(torch.rand((env.n, 2), device=env.dev, generator=g) * 2.4 - 1.2, sync=False)
+    torch.cuda.synchronize()
+
+
+CASES = [("free", 64, 0), ("free", 64, 1), ("free", 16384, 300), ("shelf", 64, 300), ("shelf", 16384, 1),
+         ("pipe", 64, 300), ("pipe", 16384, 0), ("pipe", 32768, 200)]
+
+
+@pytest.mark.parametrize("kind,n,steps", CASES)
+def test_kernel_matches_reference(kind, n, steps):
+    """Every pixel whose centre is farther than DELTA from every shape boundary equals the float64 reference: one view at
+    the default size, a 4 x 4 grid, and a width that is not a multiple of the 4-pixel store (whose rows are then not
+    4-byte aligned either).  Env counts cover both step kernels (four lanes per env up to 16384, one lane beyond)."""
+    from tests.hip_env import HipEnv
+    cfg = _cfg(kind, n)
+    env = HipEnv(cfg)
+    try:
+        _drive(env, steps, seed=n + steps)
+        state, progress = env.state, env.progress
+        params = rr.params_from_config(cfg)
+        step = n // 16
+        grid_envs = [(3 + i * step) % n for i in range(16)]
+        worst = 0.0
+        for name, over, views in (("1 view 400x225", {}, [n // 10]),
+                                  ("4x4 grid 160x90", dict(width=160, height=90, num_views=16, grid_cols=4,
+                                                           metres_per_pixel=2.0 / 160, centre_y=-0.1), grid_envs),
+                                  ("3 views in 2 columns, 203x117", dict(width=203, height=117, num_views=3, grid_cols=2,
+                                                                         metres_per_pixel=0.008, centre_z=0.803), grid_envs[:3])):
+            rcfg = _rcfg(env.lib, **over)
+            view = rr.view_from_config(rcfg)
+            img = _render(env, rcfg, views)
+            ref, dist = rr.render_grid(state, views, params, view, rcfg.grid_cols, progress)
+            assert img.shape == ref.shape
+            assert _compare(img, ref, dist, "%s %d envs %d steps, %s" % (kind, n, steps, name)) == 0
+            worst = max([worst] + [rr.corner_error(state, e, params, view, progress[e]) for e in views])
+            if kind != "free" and not over:      # (coarser views may miss a 5 mm wall between two pixel centres)
+                assert np.isin(img, (abi.VR_SHELF, abi.VR_PIPE)).any()
+            assert (img == abi.VR_LINK_A).any() and (img == abi.VR_CART).any()
+        print("largest |fp32 - fp64| shape-corner coordinate: %.3e m (MEASURED = %.1e)" % (worst, MEASURED))
+        assert worst <= MEASURED
+        if steps >= 200:
+            assert progress.min() < 20 and np.unique(progress).size > 5      # resets happened on the way
+    finally:
+        env.close()
+
+
+def test_comparison_detects_a_small_change():
+    """Negative controls: one joint angle off by 0.05 rad, or the target two pixels away, fails the comparison."""
+    from tests.hip_env import HipEnv
+    cfg = _cfg("shelf", 64)
+    env = HipEnv(cfg)
+    try:
+        _drive(env, 40, seed=5)
+        rcfg = _rcfg(env.lib)
+        view, params = rr.view_from_config(rcfg), rr.params_from_config(cfg)
+        e = 6
+        img = _render(env, rcfg, [e])
+        state = env.state
+        ref, dist = rr.render(state, e, params, view, env.progress[e])
+        assert _compare(img, ref, dist, "unchanged") == 0
+        bent = state.copy()
+        bent[abi.VF_Q0 + 3, e] += 0.05
+        ref, dist = rr.render(bent, e, params, view, env.progress[e])
+        assert _compare(img, ref, dist, "joint 2 + 0.05 rad") > 0
+        moved = state.copy()
+        moved[abi.VF_TARGET_Y, e] += 2 * view["metres_per_pixel"]
+        ref, dist = rr.render(moved, e, params, view, env.progress[e])
+        assert _compare(img, ref, dist, "target + 2 px") > 0
+    finally:
+        env.close()
+
+
+def test_out_of_range_view_is_background_and_bad_configs_are_refused():
+    from tests.hip_env import HipEnv
+    env = HipEnv(_cfg("free", 64))
+    try:
+        rcfg = _rcfg(env.lib, width=64, height=32, num_views=2, grid_cols=2)
+        img = _render(env, rcfg, [5, 64])
+        assert (img[:, :64] != abi.VR_BACKGROUND).any() and (img[:, 64:] == abi.VR_BACKGROUND).all()
+        bad = _rcfg(env.lib, num_frames=20, capture_every=10)
+        out = torch.zeros(16, dtype=torch.uint8, device=env.dev)
+        v = torch.zeros(1, dtype=torch.int32, device=env.dev)
+        assert env.lib.vine_render(env.h, bad, v.data_ptr(), None, out.data_ptr(), _stream()) == abi.ERR_INVALID_ARG
+    finally:
+        env.close()
+
+
+# ------------------------------------------------------------------------------------------------ the task class
+def _task(n=256, video=True, **env_over):
+    from vine_robot_isaacgymenvs_amd import load_task_config
+    from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
+    cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % n])
+    cfg["seed"] = 42
+    cfg["env"]["CAPTURE_VIDEO"] = video
+    cfg["env"].update(env_over)
+    return isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg, rl_device="cuda:0", sim_device="cuda:0", graphics_device_id=0,
+                                                    headless=True)
+
+
+def _collect(env):
+    """Harvested windows of a task, {last step: frames}, through the writer thread's hook."""
+    got = {}
+    env.video.on_frames = lambda frames, last: got.__setitem__(last, frames)
+    return got
+
+
+def _render_task(env, state=None, progress=None):
+    """vine_render of the task's handle with its capture config (optionally of a snapshot put back for the call)."""
+    v = env.video
+    keep = (env.state.clone(), env.progress_buf.clone())
+    if state is not None:
+        env.state.copy_(state)
+        env.progress_buf.copy_(progress)
+    out = torch.empty(v.frame_shape, dtype=torch.uint8, device=env.device)
+    native.check(v.lib.vine_render(v.handle, v.rcfg, v.view_envs.data_ptr(), env.progress_buf.data_ptr(), out.data_ptr(),
+                                   _stream()), v.lib)
+    torch.cuda.synchronize()
+    env.state.copy_(keep[0])
+    env.progress_buf.copy_(keep[1])
+    return out.cpu().numpy()
+
+
+def test_schedule_eager_step(tmp_path):
+    """VecTask.step across two windows (capture_every 40, 10 frames): the harvested ring equals vine_render of the state
+    snapshots of the window's steps byte for byte; a canary behind the ring stays intact; moving the step count moves
+    the window."""
+    env = _task(CAPTURE_VIDEO_EVERY=40, CAPTURE_VIDEO_FRAMES=10, CAPTURE_VIDEO_WIDTH=203, CAPTURE_VIDEO_HEIGHT=117,
+                CAPTURE_VIDEO_DIR=str(tmp_path))
+    try:
+        v = env.video
+        # the ring re-bound to the front of a larger buffer whose tail is a canary
+        nbytes = v.ring.numel()
+        big = torch.full((nbytes + 4096,), 0xA5, dtype=torch.uint8, device=env.device)
+        v.ring = big[:nbytes].view(v.ring.shape)
+        v.ring.zero_()
+        v.host = torch.empty(v.ring.shape, dtype=torch.uint8, pin_memory=True)
+        got = _collect(env)
+        g = torch.Generator(device=env.device).manual_seed(3)
+        actions = torch.rand((60, env.num_envs, 2), device=env.device, generator=g) * 2 - 1
+        snaps = []
+        for t in range(52):
+            env.step(actions[t])
+            snaps.append((env.state.clone(), env.progress_buf.clone()))
+        torch.cuda.synchronize()
+        v.drain()
+        assert sorted(got) == [9, 49] and v.skipped == []
+        for last in (9, 49):
+            want = np.stack([_render_task(env, *snaps[s]) for s in range(last - 9, last + 1)])
+            assert np.array_equal(got[last], want), last
+            assert all((got[last][i] != got[last][i + 1]).any() for i in range(9))        # consecutive frames differ
+        assert bool((big[nbytes:] == 0xA5).all())
+        frames, palette, delays = apng.read_apng(os.path.join(str(tmp_path), f"{env.time_str}_video_49.png"))
+        assert np.array_equal(frames, got[49]) and np.array_equal(palette, v.palette)
+        assert delays == [apng.delay_fraction(env.control_dt)] * 10
+        # the step count moved to 115: the window 120 .. 129 starts five steps later; the one already open at 80 .. 89 is
+        # not touched (ring unchanged over steps 115 .. 119)
+        env.step_count = 115
+        before = v.ring.clone()
+        snaps = []
+        for t in range(16):
+            env.step(actions[t])
+            snaps.append((env.state.clone(), env.progress_buf.clone()))
+            if t == 4:
+                torch.cuda.synchronize()
+                assert torch.equal(v.ring, before)
+        torch.cuda.synchronize()
+        v.drain()
+        assert sorted(got) == [9, 49, 129]
+        want = np.stack([_render_task(env, *snaps[s]) for s in range(5, 15)])
+        assert np.array_equal(got[129], want)
+    finally:
+        env.close()
+
+
+def _agent(use_graphs, tmp_path, every=40, frames=24, n=512):
+    from vine_robot_isaacgymenvs_amd import load_config
+    from vine_robot_isaacgymenvs_amd.learning.a2c_continuous import A2CAgent
+    from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
+    cfg = load_config(overrides=["num_envs=%d" % n, "minibatch_size=%d" % (4 * n), "seed=11"])
+    cfg["task"]["seed"] = 42
+    if every:
+        cfg["task"]["env"].update(CAPTURE_VIDEO=True, CAPTURE_VIDEO_EVERY=every, CAPTURE_VIDEO_FRAMES=frames,
+                                  CAPTURE_VIDEO_WIDTH=200, CAPTURE_VIDEO_HEIGHT=112, CAPTURE_VIDEO_VIEWS=4,
+                                  CAPTURE_VIDEO_DIR=str(tmp_path))
+    env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
+                                                  graphics_device_id=0, headless=True)
+    params = cfg["train"]["params"]
+    params["config"].update(write_files=False, print_stats=False, use_graphs=use_graphs)
+    torch.manual_seed(0)
+    agent = A2CAgent("t", params, vec_env=env)
+    agent.init_tensors()
+    agent.obs = agent.env_reset()["obs"]
+    return agent, env
+
+
+def test_schedule_fused_rollout_eager_and_graphed(tmp_path):
+    """The agent's rollout (16 fused steps) eager and graph-replayed from the same seed, windows of 24 frames every 40
+    steps (0 .. 23 and 80 .. 103 straddle rollouts, 40 .. 63 ends on a rollout's last step): the harvested frames are
+    byte-identical between the two, consecutive frames differ, and the last frame of the window that ends with a rollout
+    is vine_render of the state that rollout left."""
+    outs = []
+    for use_graphs in (False, True):
+        agent, env = _agent(use_graphs, tmp_path / ("graph" if use_graphs else "eager"))
+        try:
+            assert agent._can_fuse_rollout()
+            got = _collect(env)
+            agent.set_eval()
+            at_63 = None
+            with torch.no_grad():
+                for it in range(7):                                   # 112 steps
+                    agent.play_steps_rnn()
+                    env.video.drain()         # pace the loop to the writer: a 2 ms rollout outruns the encoder, and a
+                                              # harvest that finds the host buffer taken is (rightly) skipped
+                    if it == 3:                                       # steps 48 .. 63 just ran
+                        torch.cuda.synchronize()
+                        at_63 = _render_task(env)
+            torch.cuda.synchronize()
+            env.video.drain()
+            assert agent.graph_status["rollout"] == ("graph" if use_graphs else "off") or not use_graphs
+            assert sorted(got) == [23, 63, 103] and env.video.skipped == []
+            assert env.video.steps_done == 112 == env.step_count
+            for frames in got.values():
+                assert frames.shape == (24, 2 * 112, 2 * 200)
+                assert all((frames[i] != frames[i + 1]).any() for i in range(23))
+            assert np.array_equal(got[63][23], at_63)
+            assert len(glob.glob(os.path.join(env.log_dir, "*_video_*.png"))) == 3
+            outs.append(got)
+        finally:
+            env.close()
+    for last in (23, 63, 103):
+        assert np.array_equal(outs[0][last], outs[1][last]), last
+
+
+def test_off_is_free(tmp_path):
+    """CAPTURE_VIDEO false (the default): no ring, no draw launch -- the fused rollout step stays at three launches."""
+    agent, env = _agent(False, tmp_path, every=0)
+    try:
+        assert env.video is None and env.cfg["env"]["CAPTURE_VIDEO"] is False
+        agent.set_eval()
+        with torch.no_grad():
+            agent.play_steps_rnn()
+        assert agent.rollout_step_launches == 3
+        assert not any(t.name == "vine-video-writer" for t in __import__("threading").enumerate())
+    finally:
+        env.close()
+
+
+def _train(tmp_path, monkeypatch, name, capture):
+    from vine_robot_isaacgymenvs_amd import train
+    run = tmp_path / name
+    run.mkdir()
+    monkeypatch.chdir(run)
+    argv = ["num_envs=512", "minibatch_size=2048", "seed=5", "max_iterations=6", "headless=True",
+            "+train.params.config.print_stats=False"]
+    if capture:
+        argv += ["CAPTURE_VIDEO=True", "task.env.CAPTURE_VIDEO_EVERY=64", "task.env.CAPTURE_VIDEO_FRAMES=24",
+                 "task.env.CAPTURE_VIDEO_WIDTH=200", "task.env.CAPTURE_VIDEO_HEIGHT=112"]
+    train.main(argv)
+    torch.cuda.synchronize()
+    root = run / "runs" / "Vine5LinkMovingBase"
+    ckpt = sorted(glob.glob(str(root / "nn" / "last_*ep6*.pth")))
+    assert ckpt, os.listdir(str(root / "nn"))
+    events = glob.glob(str(root / "summaries" / "events.out.tfevents.*"))
+    return torch.load(ckpt[-1], map_location="cpu", weights_only=False), tfevents.read_scalars(events[0]), root
+
+
+def _same(a, b, path=""):
+    if isinstance(a, dict):
+        assert a.keys() == b.keys(), path
+        for k in a:
+            _same(a[k], b[k], path + "/" + str(k))
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), path
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, path + "/" + str(i))
+    elif torch.is_tensor(a):
+        assert torch.equal(a, b), path
+    else:
+        assert a == b or (a != a and b != b), path
+
+
+def test_capture_perturbs_nothing(tmp_path, monkeypatch):
+    """Two trainings through train.py's entry, six iterations, same seed, CAPTURE_VIDEO on and off: weights, optimiser
+    state and every logged scalar that is not a wall-clock figure are bit-identical; the run with capture leaves
+    readable videos of the configured size."""
+    off, off_scalars, _ = _train(tmp_path, monkeypatch, "off", False)
+    on, on_scalars, root = _train(tmp_path, monkeypatch, "on", True)
+    _same(on, off)
+    clock = ("performance/", "rewards/time", "episode_lengths/time")
+
+    def keep(rows):
+        return [(tag, value, step) for tag, value, step, _wall in rows if not tag.startswith(clock)]
+    assert keep(on_scalars) == keep(off_scalars) and len(keep(on_scalars)) > 20
+    videos = sorted(glob.glob(str(root / "*_video_*.png")))
+    assert [int(v.rsplit("_", 1)[1][:-4]) for v in videos] == [23, 87]        # 96 steps: the windows opened at steps 0 and 64 are complete
+    for v in videos:
+        frames, palette, delays = apng.read_apng(v)
+        assert frames.shape == (24, 112, 200) and palette.shape == (abi.VR_NUM_MATERIALS, 3) and len(delays) == 24
+        assert (frames == abi.VR_LINK_A).any() and (frames[0] != frames[-1]).any()
+    assert not glob.glob(str(tmp_path / "off" / "runs" / "Vine5LinkMovingBase" / "*_video_*"))
+
+
+def test_player_writes_a_video(tmp_path):
+    """PpoPlayerContinuous.run (test=True) steps through VecTask.step: the capture rides along."""
+    from vine_robot_isaacgymenvs_amd import load_config
+    from vine_robot_isaacgymenvs_amd.learning.player import PpoPlayerContinuous
+    from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
+    cfg = load_config(overrides=["num_envs=64"])
+    cfg["task"]["seed"] = 42
+    cfg["task"]["env"].update(CAPTURE_VIDEO=True, CAPTURE_VIDEO_EVERY=30, CAPTURE_VIDEO_FRAMES=12,
+                              CAPTURE_VIDEO_DIR=str(tmp_path))
+    env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
+                                                  graphics_device_id=0, headless=True)
+    try:
+        torch.manual_seed(0)
+        player = PpoPlayerContinuous(cfg["train"]["params"], vec_env=env)
+        player.run(n_steps=45)
+        videos = sorted(glob.glob(os.path.join(str(tmp_path), "*_video_*.png")))
+        assert [os.path.basename(v).rsplit("_", 1)[1] for v in videos] == ["11.png", "41.png"]
+        frames, _, _ = apng.read_apng(videos[1])
+        assert frames.shape == (12, 225, 400) and (frames[0] != frames[11]).any()
+    finally:
+        env.close()

@@ -302,6 +302,63 @@ class TrunkArgs(C.Structure):
                 [(k, C.c_void_p) for k in ("gz3", "gz2", "gz1", "part3", "part2", "part1")])
 
 
+# ---- include/vine_render.h (product library only)
+RENDER_ABI_VERSION = 1
+RENDER_LINE_PX = 2.5
+RENDER_TIP_RADIUS = 0.012
+RENDER_MAX_VIEWS = 64
+# VineRenderMaterial = palette indices = pixel values
+(VR_BACKGROUND, VR_RAIL, VR_LIMIT, VR_PROGRESS, VR_CART, VR_LINK_A, VR_LINK_B, VR_TIP, VR_TARGET, VR_SHELF, VR_STRIP,
+ VR_PIPE) = range(12)
+VR_NUM_MATERIALS = 12
+RENDER_MATERIAL_NAMES = ("background", "rail", "limit", "progress", "cart", "link_a", "link_b", "tip", "target", "shelf",
+                         "strip", "pipe")
+
+
+class VineRenderConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("num_views", C.c_int32),
+        ("grid_cols", C.c_int32),
+        ("num_frames", C.c_int32),
+        ("capture_every", C.c_int32),
+        ("centre_y", C.c_float),
+        ("centre_z", C.c_float),
+        ("metres_per_pixel", C.c_float),
+    ]
+
+    @property
+    def grid_rows(self):
+        return (self.num_views + self.grid_cols - 1) // self.grid_cols
+
+    @property
+    def frame_shape(self):
+        return (self.grid_rows * self.height, self.grid_cols * self.width)
+
+
+RENDER_PROTOTYPES = {
+    "vine_render_config_default": (C.c_int, [_P(VineRenderConfig)]),
+    "vine_render_config_size": (C.c_int, []),
+    "vine_render_frame_bytes": (C.c_int64, [_P(VineRenderConfig)]),
+    "vine_render_ring_bytes": (C.c_int64, [_P(VineRenderConfig)]),
+    "vine_render_palette": (C.c_int, [C.c_void_p, _P(C.c_int)]),
+    "vine_render": (C.c_int, [_H, _P(VineRenderConfig), _VP, _VP, _VP, _VP]),
+    "vine_render_scheduled": (C.c_int, [_H, _P(VineRenderConfig), _VP, _VP, _VP, _VP]),
+}
+
+
+def declare_render(lib):
+    for name, (restype, argtypes) in RENDER_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.vine_render_config_size() != C.sizeof(VineRenderConfig):
+        raise RuntimeError("VineRenderConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     for name, (restype, argtypes) in PPO_PROTOTYPES.items():
         fn = getattr(lib, name)

@@ -27,6 +27,8 @@
 
 #include "../../include/vine.h"
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
+#include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
+#include "vine_render_internal.h"
 
 #define NL VINE_NUM_LINKS
 #define ND VINE_NUM_DOFS
@@ -273,8 +275,6 @@ __device__ __forceinline__ void substep(const DevParams& P, Dyn& s, const float 
 // Culled pairs contribute exactly zero, so the result is bit-identical to the unculled evaluation.
 #define CONTACT_K 2000.0f
 #define CONTACT_C 2.0f
-#define LINK_Y0 (-0.0381f)
-#define LINK_Y1 0.0719f
 #define LINK_REACH 0.078f   // lateral half-extent 0.0719 + link_0's 5.75 mm axial overhang beyond its joints, rounded up
 // One link against the shelf: the link's joint position (py, pz) and velocity (pvy, pvz), sin / cos of its world angle,
 // its rate, the axial extent [z0, z1] of its rectangle.  Adds the force on the link (fy, fz), its moment about the
@@ -283,7 +283,7 @@ __device__ __forceinline__ bool shelf_link_contact(const DevParams& P, float z0,
                                                    float pvz, float sp, float cp, float om, float shelf_y, float shelf_z,
                                                    float& fy_tot, float& fz_tot, float& mom, float& strip_fy,
                                                    float& strip_fz) {
-    const float board[2][4] = {{-0.001f, 0.0f, 0.1995f, 0.005f}, {0.0f, 0.2f, 0.2f, 0.005f}};
+    const float board[2][4] = SHELF_BOARDS;
     const float dy = -sp, dz = cp, ly = cp, lz = sp;     // link axis d, lateral l; n = d(d)/d(phi) = (-cp, -sp) = -l
     // every shelf shape lies at y <= shelf_y + 0.2; board A / the strip around z = shelf_z, board B around shelf_z + 0.2
     const float ycut = shelf_y + 0.2f;
@@ -360,7 +360,7 @@ __device__ __forceinline__ float shelf_contact(const DevParams& P, const Dyn& s,
     for (int k = 0; k < NL; ++k) {
         const float sp = s.sn[k], cp = s.cs[k];              // sin/cos of the world link angle
         const float om = s.w[k];
-        const float z0 = (k == 0) ? -0.00575f : 0.0f, z1 = (k == 0) ? 0.09425f : P.L;
+        const float z0 = (k == 0) ? LINK0_Z0 : 0.0f, z1 = (k == 0) ? LINK0_Z1 : P.L;
         float fy_tot = 0.0f, fz_tot = 0.0f, mom = 0.0f;
         ny_[k] = -cp; nz_[k] = -sp;
         any |= shelf_link_contact(P, z0, z1, py, pz, pvy, pvz, sp, cp, om, shelf_y, shelf_z, fy_tot, fz_tot, mom, strip_fy,
@@ -391,15 +391,7 @@ __device__ __forceinline__ float shelf_contact(const DevParams& P, const Dyn& s,
 // (2) the link rectangle's exact axis-aligned box in the pipe frame against each wall's box; (3) the narrow phase of
 // the (link, wall) pairs that are left.  A vine reaching INTO the tube sits between the walls: level 2 is what keeps it
 // out of the narrow phase until it actually comes within a rounding margin of a wall.
-#define PIPE_LEN 0.34125f
-#define PIPE_WALL 0.00525f
-#define PIPE_OUTER 0.1554f
 #define PIPE_CULL_EPS 1.0e-5f      // the box tests use other (equivalent) expressions than the narrow phase: rounding margin
-struct PipePose { float y, z, ct, st, ccy, ccz; };      // origin, cos / sin of the tube's axis angle, centre of its box
-__device__ __forceinline__ PipePose pipe_pose(float pipe_y, float pipe_z, float ct, float st) {
-    const float hcy = 0.5f * PIPE_OUTER, hcz = 0.5f * PIPE_LEN;
-    return PipePose{pipe_y, pipe_z, ct, st, pipe_y + hcy * ct - hcz * st, pipe_z + hcy * st + hcz * ct};
-}
 __device__ __forceinline__ unsigned pipe_broad_phase(float z0, float z1, float py, float pz, float sp, float cp,
                                                      const PipePose& T);
 // nearbits: pipe_broad_phase of this link when the caller has it already (the four-lane kernel), PIPE_BROAD_HERE otherwise
@@ -488,7 +480,7 @@ __device__ __forceinline__ void pipe_contact(const DevParams& P, const Dyn& s, f
     for (int k = 0; k < NL; ++k) {
         const float sp = s.sn[k], cp = s.cs[k];
         const float om = s.w[k];
-        const float z0 = (k == 0) ? -0.00575f : 0.0f, z1 = (k == 0) ? 0.09425f : P.L;
+        const float z0 = (k == 0) ? LINK0_Z0 : 0.0f, z1 = (k == 0) ? LINK0_Z1 : P.L;
         float fy_tot = 0.0f, fz_tot = 0.0f, mom = 0.0f;
         ny_[k] = -cp; nz_[k] = -sp;
         any |= pipe_link_contact(P, z0, z1, py, pz, pvy, pvz, sp, cp, om, T, fy_tot, fz_tot, mom);
@@ -524,7 +516,7 @@ __device__ __forceinline__ void shelf_link_contact_coop(const DevParams& P, int 
                                                         float pvy, float pvz, float sp, float cp, float om, float shelf_y,
                                                         float shelf_z, float& fy_tot, float& fz_tot, float& mom,
                                                         float& strip_fy, float& strip_fz) {
-    const float board[2][4] = {{-0.001f, 0.0f, 0.1995f, 0.005f}, {0.0f, 0.2f, 0.2f, 0.005f}};
+    const float board[2][4] = SHELF_BOARDS;
     const float dy = -sp, dz = cp, ly = cp, lz = sp;
     const float ycut = shelf_y + 0.2f;
     const float a_lo = shelf_z - 0.005f, a_hi = shelf_z + 0.005f, b_lo = shelf_z + 0.195f, b_hi = shelf_z + 0.205f;
@@ -1555,7 +1547,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                     const float pvy = vy + L * (ivy - vyo), pvz = L * (ivz - vzo);
                     const float p4y = y + L * qbcast<3>(iy), p4z = P.z1 + L * qbcast<3>(iz);
                     const float pv4y = vy + L * qbcast<3>(ivy), pv4z = L * qbcast<3>(ivz);
-                    const float z0 = t == 0 ? -0.00575f : 0.0f, z1 = t == 0 ? 0.09425f : L;
+                    const float z0 = t == 0 ? LINK0_Z0 : 0.0f, z1 = t == 0 ? LINK0_Z1 : L;
                     float fy = 0.0f, fz = 0.0f, mom = 0.0f, f4y = 0.0f, f4z = 0.0f, mom4 = 0.0f;
                     float sfy = 0.0f, sfz = 0.0f, s4y = 0.0f, s4z = 0.0f;
                     // proximal links: by their own lanes (rarely anywhere near the obstacle); distal links (pipe: 3 and 4,
@@ -2707,6 +2699,22 @@ int vine_set_step_count(VineHandle* h, int64_t step_count) {
     HIP_TRY(hipMemcpy(h->counters, v, sizeof v, hipMemcpyHostToDevice));
     return VINE_OK;
 }
+
+// What the renderer (vine_render.hip, its own translation unit) needs to know of a handle.
+int vine_render_info(VineHandle* h, VineRenderInfo* out) {
+    if (!h || !out) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_render_info");
+    out->state = h->state;
+    out->counters = h->counters;
+    out->glog = h->P.glog;
+    out->n = h->P.n;
+    out->device = h->device;
+    out->max_len = h->P.max_len;
+    out->flags = h->P.flags;
+    out->L = h->P.L; out->z1 = h->P.z1; out->s0 = h->P.s0; out->c0 = h->P.c0;
+    out->soft_limit = h->P.soft_limit; out->success_dist = h->P.success_dist;
+    return VINE_OK;
+}
+void vine_set_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 
 #ifdef VSQ_TIMING
 int vine_debug_timing(unsigned long long* out) {

@@ -17,6 +17,7 @@ MI355X-first choices (none changes the arithmetic):
     torch.amp.GradScaler's semantics restated on the device (FlatAdam.enable_loss_scaling), not autocast; rollout
     inference runs in fp32 on the matrix cores (``_infer``: vine_mlp3_elu_f32 / vine_lstm_step_f32).
 """
+import contextlib
 import copy
 import os
 import time
@@ -356,6 +357,7 @@ class A2CAgent:
             os.makedirs(self.nn_dir, exist_ok=True)
             self.writer = ScalarLog(self.summaries_dir)
         self._rollout_graph = None
+        self._video_replayed = None
         if self.algo_observer is not None:
             self.algo_observer.after_init(self)
 
@@ -1042,9 +1044,14 @@ class A2CAgent:
             flat = [self._g_in[0], self._g_in[1]] + self._g_in[2] + self._g_in[3:5]
             backup = [t.clone() for t in flat]
             snap = self._snapshot_env()
+            # CAPTURE_VIDEO: the steps of the warm-up pass are rolled back and those of the capture pass are not
+            # executed, so neither counts towards the env's capture schedule
+            env_ = getattr(self.vec_env, "env", self.vec_env)
+            video_paused = getattr(env_, "video_paused", contextlib.nullcontext)
+            self._video_replayed = getattr(env_, "video_replayed", None)
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):     # warm-up outside capture (lazy inits of libraries, autotuning)
+            with torch.cuda.stream(side), video_paused():     # warm-up outside capture (lazy inits of libraries, autotuning)
                 self._load_live(self._g_in)
                 body()
             torch.cuda.current_stream(self.device).wait_stream(side)
@@ -1055,14 +1062,18 @@ class A2CAgent:
             self._rollout_graph = torch.cuda.CUDAGraph()
             self._load_live(self._g_in)
             # thread_local: RCCL's watchdog thread may touch the HIP runtime while this thread captures
-            with torch.cuda.graph(self._rollout_graph, capture_error_mode="thread_local"):
+            with torch.cuda.graph(self._rollout_graph, capture_error_mode="thread_local"), video_paused():
                 self._load_live(self._g_in)
                 body()
                 self._g_out = [self.obs, self.dones, self.rnn_states, self.current_rewards, self.current_lengths,
                                self.game_rewards.mean, self.game_rewards.current_size, self.game_lengths.mean,
                                self.game_lengths.current_size]
+        if self._video_replayed is not None:
+            self._video_replayed(self.horizon_length, before=True)
         with _Range("rollout_graph_replay"):
             self._rollout_graph.replay()
+        if self._video_replayed is not None:
+            self._video_replayed(self.horizon_length)
         self._graph_replayed = True
         # carry the outputs over to the static inputs of the next replay
         o = self._g_out
@@ -1777,6 +1788,10 @@ class A2CAgent:
                 dist.broadcast(flag, 0)
                 should_exit = bool(flag.item())
             if should_exit:
+                video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
+                if video is not None:            # CAPTURE_VIDEO: the last harvested window is on disk when train() returns
+                    torch.cuda.synchronize(self.device)
+                    video.drain()
                 return self.last_mean_rewards, epoch_num
 
     def write_stats(self, total_time, epoch_num, play_time, update_time, stats, curr_frames):

@@ -64,6 +64,10 @@ class PpoPlayerContinuous:
             self.states = [s * keep.view(1, -1, 1) for s in self.states]
             cur_r *= keep
             cur_l *= keep
+        video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
+        if video is not None:                    # CAPTURE_VIDEO: every harvested window is on disk when run() returns
+            torch.cuda.synchronize(self.device)
+            video.drain()
         g = max(float(games), 1.0)
         print("reward:", float(sum_r) / g, "steps:", float(sum_l) / g, "games:", int(games))
         return float(sum_r) / g, float(sum_l) / g

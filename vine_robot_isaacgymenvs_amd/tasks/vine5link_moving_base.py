@@ -144,8 +144,7 @@ class Vine5LinkMovingBase(VecTask):
         self.cfg["env"]["numActions"] = N_PRESSURE_ACTIONS + N_PRISMATIC_DOFS
         if self.cfg["env"].get("CREATE_PIPE", False):
             self.logger.info("CREATE_PIPE: the pipe mesh is simulated as its planar cross-section (two walls)")
-        if self.cfg["env"].get("CAPTURE_VIDEO", False):
-            self.logger.info("CAPTURE_VIDEO is accepted and ignored (no renderer on the target)")
+        self._video = None
 
         self._lib = None
         self._handle = None
@@ -172,6 +171,56 @@ class Vine5LinkMovingBase(VecTask):
             # replay overwrites the DOF state before every step without moving the bodies: the step kernel must keep
             # reading the tip / cart rigid-body states from memory, which it does with introspection on
             self.set_introspection(True)
+        if self.cfg["env"].get("CAPTURE_VIDEO", False):
+            if int(os.getenv("LOCAL_RANK", "0")) == 0:
+                self._setup_video()
+            else:           # every rank would write the same file names: rank 0 records its env, the others do not draw
+                self.logger.info("CAPTURE_VIDEO: recorded by rank 0 only")
+
+    # ------------------------------------------------------------------ CAPTURE_VIDEO (V5:205-221, 1169-1207)
+    def _setup_video(self):
+        """The camera of V5:206-221 as a ``VineRenderConfig`` (include/vine_render.h), the device frame ring and the
+        writer.  Frames are drawn by a launch behind every step; see utils/video.py for the harvest."""
+        import datetime
+        from ..utils import video
+        env = self.cfg["env"]
+        torch.cuda.synchronize(self.device)
+        tip_y = float(self._state[abi.VF_TIP_Y, self.index_to_view])         # cam_target, V5:206-207
+        rcfg = video.render_config(self._lib, env, tip_y, INIT_Z)
+        views = [(self.index_to_view + v) % self.num_envs for v in range(rcfg.num_views)]
+        self.log_dir = env.get("CAPTURE_VIDEO_DIR") or os.path.join("runs", self.cfg["name"])     # V5:140
+        self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")                      # V5:145
+        self._video = video.VideoCapture(self._lib, self._handle, rcfg, views, self.progress_buf, self.device,
+                                         self.log_dir, self.time_str, self.control_dt, self.logger)
+        self.logger.info(f"CAPTURE_VIDEO: {rcfg.num_frames} frames of {rcfg.num_views} view(s) at "
+                         f"{rcfg.width} x {rcfg.height} every {rcfg.capture_every} steps -> "
+                         f"{self.log_dir}/{self.time_str}_video_<num_steps>.png")
+
+    @property
+    def video(self):
+        """The ``VideoCapture`` of this env (``None`` unless ``CAPTURE_VIDEO``)."""
+        return self._video
+
+    def video_paused(self):
+        """Context manager: steps enqueued inside are not counted towards the capture (the warm-up and capture passes of
+        a hipGraph, whose effects are rolled back or not executed at all)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def paused():
+            if self._video is not None:
+                self._video.paused += 1
+            try:
+                yield
+            finally:
+                if self._video is not None:
+                    self._video.paused -= 1
+        return paused()
+
+    def video_replayed(self, n_steps, before=False):
+        """A captured graph holding ``n_steps`` steps (and their draws) is about to be / has been replayed."""
+        if self._video is not None:
+            (self._video.before if before else self._video.advance)(n_steps)
 
     # ------------------------------------------------------------------ MAT_FILE replay (V5:281-297, 947-982)
     def read_mat_file(self, filename):
@@ -220,6 +269,11 @@ class Vine5LinkMovingBase(VecTask):
         self._handle = h
 
     def close(self):
+        if self._video is not None:
+            torch.cuda.synchronize(self.device)
+            self._video.drain()
+            self._video.close()
+            self._video = None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -237,9 +291,14 @@ class Vine5LinkMovingBase(VecTask):
     def _native_step(self, actions, obs_out):
         if self.mat is not None:
             self.overwrite_with_mat()
+        if self._video is not None:
+            self._video.before(1)
         native.check(self._lib.vine_step(self._handle, actions.data_ptr(), obs_out.data_ptr(), self.rew_buf.data_ptr(),
                                          self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
                                          self.timeout_buf.data_ptr(), self._stream()), self._lib)
+        if self._video is not None:
+            self._video.enqueue(self._stream())
+            self._video.advance(1)
         self.num_steps += 1
 
     def rollout_step_blocks(self):
@@ -253,9 +312,14 @@ class Vine5LinkMovingBase(VecTask):
         ``_rollout_body_fused``); ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.RolloutArgs; the
         observation goes to ``obs_out`` and the buffers are re-bound exactly as ``step_into`` does."""
         import ctypes as C
+        if self._video is not None:
+            self._video.before(1)
         native.check(self._lib.vine_step_rollout(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
                                                  self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
                                                  self.timeout_buf.data_ptr(), self._stream()), self._lib)
+        if self._video is not None:
+            self._video.enqueue(self._stream())
+            self._video.advance(1)
         self.num_steps += 1
         self.obs_buf = obs_out
         self.obs_dict["obs"] = obs_out.to(self.rl_device)
@@ -405,6 +469,8 @@ class Vine5LinkMovingBase(VecTask):
     @step_count.setter
     def step_count(self, v):
         native.check(self._lib.vine_set_step_count(self._handle, int(v)), self._lib)
+        if self._video is not None:
+            self._video.set_steps(int(v))
 
     @property
     def state(self):
