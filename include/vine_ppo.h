@@ -223,16 +223,6 @@ int vine_lstm_step_backward_mfma(int64_t B, int64_t H, const float* g_out, int64
                                  void* dgates, int64_t dg_stride, float* dc_prev, float* bias_partial,
                                  const float* bias_partial_prev, void* stream);
 
-/* Weight gradient of a linear layer on the matrix cores (mixed precision): for each of `slices` equal row slices
- *   part[s][m][n] = sum over the rows k of slice s of dy[k][m] * x[k][n],   m < M, n < Nv
- * dy [rows, M] and x [rows, Np] bfloat16 (rows ldy / ldx elements apart, 16-B aligned), part [slices, M, Nv] fp32.
- * Np = the tile width actually read from x (32, 96 or a multiple of 128; columns Nv .. Np-1 must be readable, their
- * products are not stored).  The sum over the slices (vine_column_sums over part viewed as [slices, M * Nv]) is the
- * gradient dy^T x -- fixed summation order, no atomics.  Requires M % 64 == 0 and rows % (32 * slices) == 0;
- * VINE_ERR_UNSUPPORTED otherwise (callers fall back to a library GEMM). */
-int vine_weight_grad_mfma(int64_t rows, int64_t M, int64_t Np, int64_t Nv, const void* dy, int64_t ldy, const void* x,
-                          int64_t ldx, int64_t slices, float* part, void* stream);
-
 /* Weight gradient(s) dy^T [x1 | x2] in ONE pass over dy on the matrix cores, for each of `slices` equal row slices:
  *   part1[s][m][n] = sum_k dy[k][m] x1[k][n] (n < Nv1),   part2[s][m][n] = sum_k dy[k][m] x2[k][n] (n < Nv2)
  * dy [rows, M], x1 [rows, N1p] (N1p columns read, Nv1 <= N1p stored; N1p = 0: no first operand), x2 [rows, N2p] (Nv2 <= N2p
@@ -250,7 +240,7 @@ int vine_weight_grad_cat_mfma(int64_t rows, int64_t M, const void* dy, int64_t l
 /* The LSTM's two weight gradients with the recurrent operand formed on the fly from the ONE copy of the hidden states that
  * vine_lstm_seq_forward_mfma writes with c_bf16 bit 1: operand row k = seq * T + t of the second product is
  * (1 - done[k]) * h_{t-1} = slot t of sequence seq in h_all [rows / T, T + 1, ldh] (16-bit, unmasked; slot 0 = the
- * initial state).  x1 = the 96-column step-input block (Nv1 stored), 256 hidden units (Nv2 stored); NT = 22 | 21 as in
+ * initial state).  x1 = the 96-column step-input block (Nv1 stored), 256 hidden units (Nv2 stored); NT = 22 as in
  * vine_weight_grad_cat_mfma (the wide tile only); needs 32 % T == 0 and done 16-B aligned.  Same partial sums, bit for
  * bit, as vine_weight_grad_cat_mfma on the masked [rows, 256] tensor. */
 int vine_weight_grad_cat_seq_mfma(int64_t rows, int64_t M, const void* dy, int64_t ldy, const void* x1, int64_t ldx1,
@@ -400,7 +390,7 @@ int vine_ppo_loss(int64_t n, int32_t A, const float* mu, const float* logstd, co
  * the loss terms and statistics of vine_ppo_loss on them, and d loss / d x ([n, H], dx: fp32, or bfloat16 with dx_bf16 --
  * the operand type vine_lstm_seq_backward_mfma takes with g_bf16) -- what
  * vine_layernorm_heads_forward + vine_ppo_loss + vine_layernorm_heads_backward produce in three launches, with the
- * same arithmetic.  ln_partial [n / R, (2 + NH) H] with R = vine_ln_heads_loss_rows() rows per workgroup (128 by default;
+ * same arithmetic.  ln_partial [n / R, (2 + NH) H] with R = vine_ln_heads_loss_rows() rows per workgroup (128;
  * n % R == 0, n / R <= VINE_PPO_LOSS_BLOCKS): per-workgroup sums {d gamma | d beta | d W} (finish with vine_column_sums).  stats / grad_logstd / grad_mu_bias / grad_value_bias / scratch / kl_out / logstd_grad_accum /
  * mu_store / sigma_store: as in vine_ppo_loss. */
 int vine_ln_heads_loss(int64_t n, int64_t H, int32_t NH, const void* x, const float* gamma, const float* beta, float eps,

@@ -436,55 +436,6 @@ def test_lstm_sequence_kernels_equal_step_kernels(B, use_dones):
 
 
 @pytest.mark.gpu
-def test_weight_grad_mfma_matches_float64_product(monkeypatch):
-    """dy^T x on the matrix cores (transposed LDS reads, row slices + deterministic column sums) for every weight of the
-    default network, against the float64 product of the same bf16 operands; operands that are column blocks of a
-    wider padded buffer (the LSTM operand buffer) included."""
-    import time
-    dev = torch.device("cuda:0")
-    torch.manual_seed(11)
-    bf = fused.lp_dtype()
-    n = 32768
-    monkeypatch.setattr(fused, "WGRAD_MAX_OUT", 1 << 30)          # the kernel is opt-in (see fused.WGRAD_MAX_OUT)
-    xfull = (torch.randn(n, 96, device=dev) * 0.5).to(bf)
-    xfull[:, 90:] = float("nan")                       # pad columns are read but must never reach an output
-    cases = [("W1 [256,26]", 256, xfull[:, 64:90]), ("W2 [128,256]", 128, (torch.randn(n, 256, device=dev)).to(bf)),
-             ("W3 [64,128]", 64, torch.randn(n, 128, device=dev).to(bf)), ("w_ih [1024,90]", 1024, xfull[:, :90]),
-             ("w_hh [1024,256]", 1024, torch.randn(n, 256, device=dev).to(bf))]
-    for name, M, x in cases:
-        dy = (torch.randn(n, M, device=dev) * 0.1).to(bf)
-        assert fused._wgrad_plan(dy, x) is not None, name
-        out = fused.weight_grad(dy, x)
-        ref = dy.double().t() @ x.double()
-        err = float((out.double() - ref).abs().max()) / float(ref.abs().max())
-        assert out.shape == ref.shape and err < 2e-5, (name, err)
-        again = fused.weight_grad(dy, x)
-        assert torch.equal(out, again)                 # fixed summation order
-        res = []
-        for f in (lambda: fused.weight_grad(dy, x), lambda: fused.splitk_tn(dy, x)):
-            for _ in range(3):
-                f()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(30):
-                f()
-            torch.cuda.synchronize()
-            res.append((time.perf_counter() - t0) / 30 * 1e6)
-        print("weight gradient %-16s mfma %6.1f us   split-K bmm + column sums %6.1f us" % (name, res[0], res[1]))
-    # small / direct (one slice) and the fallback for unsupported operands
-    dy, x = torch.randn(256, 64, device=dev).to(bf), torch.randn(256, 128, device=dev).to(bf)
-    assert fused._wgrad_plan(dy, x) == (128, 1)
-    assert float((fused.weight_grad(dy, x).double() - dy.double().t() @ x.double()).abs().max()) < 1e-3
-    x26 = torch.randn(256, 26, device=dev).to(bf)                                   # unpadded 26-column rows
-    assert fused._wgrad_plan(dy, x26) is None
-    monkeypatch.setattr(fused, "WGRAD_MAX_OUT", 0)
-    assert fused._wgrad_plan(dy, x) is None                                         # default: off
-    assert float((fused.weight_grad(dy, x26).double() - dy.double().t() @ x26.double()).abs().max()) < 1e-3
-    lib = fused._lib()
-    assert lib.vine_weight_grad_mfma(256, 48, 128, 128, dy.data_ptr(), 64, x.data_ptr(), 128, 1, x.data_ptr(), None) == -2
-
-
-@pytest.mark.gpu
 @pytest.mark.parametrize("wide", [True, False])
 @pytest.mark.parametrize("n,width", [(32768, 92), (4096, 82)])
 def test_weight_grad_cat_matches_float64_products(n, width, wide, monkeypatch):
@@ -574,7 +525,7 @@ def test_hidden_states_stored_once(B, T):
     dG = (torch.randn(n, M, device=dev) * 0.1).to(bf)
     o1, o2, a1, a2 = (torch.empty(M, w_, device=dev) for w_ in (width, H, width, H))
     plan = fused._wgrad_cat_plan(dG, xfull[:, :width], hp2.view(n, H), o1, o2)
-    if plan is None or plan[6] not in (21, 22):      # (too few rows for the wide tile: the forward half was the test)
+    if plan is None or plan[6] != 22:      # (too few rows for the wide tile: the forward half was the test)
         assert not fused.weight_grad_cat(dG, xfull[:, :width], out1, a1, a2, seq=(dones, T))
         return
     assert fused.weight_grad_cat(dG, xfull[:, :width], hp2.view(n, H), o1, o2)
@@ -604,6 +555,9 @@ def test_weight_grad_cat_single_operand(M, N, stride, off):
     err = float((out.double() - ref).abs().max()) / float(ref.abs().max())
     assert torch.isfinite(out).all() and err < 2e-5, err
     assert torch.equal(fused.weight_grad(dy, x), out)                  # the default route of bf16 operands
+    # operands outside the kernel's family (unpadded 26-column rows) take the split-K fallback
+    dy, x26 = torch.randn(256, 64, device=dev).to(bf), torch.randn(256, 26, device=dev).to(bf)
+    assert float((fused.weight_grad(dy, x26).double() - dy.double().t() @ x26.double()).abs().max()) < 1e-3
 
 
 @pytest.mark.gpu

@@ -200,7 +200,6 @@ PPO_PROTOTYPES = {
                                           _I64, _VP, _VP, _VP, C.c_int32, _VP]),
     "vine_lstm_step_backward_mfma": (C.c_int, [_I64, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP,
                                                _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
-    "vine_weight_grad_mfma": (C.c_int, [_I64, _I64, _I64, _I64, _VP, _I64, _VP, _I64, _I64, _VP, _VP]),
     "vine_mlp3_elu_mfma": (C.c_int, [_I64, _VP, _I64, _VP, _I64, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _I64, _VP, _I64, _VP,
                                      _I64, _VP, _I64, _VP, _I64, C.c_float, _VP, _VP, _VP, _I64, _VP]),
     "vine_lstm_seq_backward_mlp3_mfma": (C.c_int, [_I64, _I64, _I64] + [_VP] * 9 + [_VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP,

@@ -2223,16 +2223,14 @@ __global__ __launch_bounds__(256) void lstm_bwd_mfma_kernel(
     }
 }
 
-// ---- Weight gradient on the matrix cores: part[s][m][n] = sum over the rows k of slice s of dy[k][m] * x[k][n]
+// ---- Weight gradients on the matrix cores: part[s][m][n] = sum over the rows k of slice s of dy[k][m] * x[k][n]
 // (dy [rows, M], x [rows, N] bf16, both with the reduction index as the SLOW dimension -- the layout the backward
 // kernels produce).  Both MFMA operands want 8 consecutive k per lane, i.e. a column of the row-major tiles: the
 // tiles are staged row-major in LDS ([32 rows][cols], pitch = cols * 2 + 32 B) and read with the gfx950 transposed
 // LDS read (ds_read_b64_tr_b16: a 16-lane group fetches a 4-row x 16-column block and gets it column-major).
 // The k <-> lane-group assignment of an MFMA is free as long as both operands agree: group g takes rows 4g .. 4g+3
 // and 16+4g .. 16+4g+3 of the stage, so that a 32-lane half always reads 8 consecutive rows, which the pitch spreads
-// over all 64 banks.  Workgroup = 4 waves along M: (64 MT) x (16 NT) outputs; stages of 32 rows, double-buffered in
-// LDS behind a register prefetch, one barrier per stage.  The slices are summed by the column-sum kernel
-// (deterministic, no atomics).
+// over all 64 banks.  The slices are summed by the column-sum kernel (deterministic, no atomics).
 typedef __attribute__((__vector_size__(4 * sizeof(lp16_hw)))) lp16_hw lp16x4_t;
 #define VINE_LDS __attribute__((address_space(3)))
 __device__ __forceinline__ lp16x8_t tr_read8(const lp16_t* p, int second_block_elems) {
@@ -2243,97 +2241,19 @@ __device__ __forceinline__ lp16x8_t tr_read8(const lp16_t* p, int second_block_e
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <int MT, int NT>
-__global__ __launch_bounds__(256) void wgrad_mfma_kernel(int stages, const lp16_t* __restrict__ dy, long long ldy,
-                                                         const lp16_t* __restrict__ x, long long ldx,
-                                                         float* __restrict__ part, int M, int Nv) {
-    constexpr int MTW = 64 * MT, NTW = 16 * NT;
-    constexpr int PA = MTW + 16, PB = NTW + 16;                 // bf16 elements per LDS row
-    constexpr int AC = MTW / 8, BC = NTW / 8;                   // 16-B pieces per row
-    constexpr int AP = 32 * AC, BP = 32 * BC;
-    constexpr int NA = (AP + 255) / 256, NB = (BP + 255) / 256;
-    __shared__ __attribute__((aligned(16))) lp16_t al[2][32 * PA];
-    __shared__ __attribute__((aligned(16))) lp16_t bl[2][32 * PB];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int m0 = blockIdx.x * MTW, n0 = blockIdx.y * NTW;
-    const long long k0 = (long long)blockIdx.z * stages * 32;
-    // up to two 16-B pieces of each tile per thread and stage (named scalars: indexed arrays end up in scratch)
-    const int pa0 = (int)threadIdx.x, pa1 = (int)threadIdx.x + 256;
-    const bool va0 = pa0 < AP, va1 = NA > 1 && pa1 < AP, vb0 = pa0 < BP, vb1 = NB > 1 && pa1 < BP;
-    const lp16_t* asrc0 = dy + (k0 + pa0 / AC) * ldy + m0 + 8 * (pa0 % AC);
-    const lp16_t* asrc1 = dy + (k0 + pa1 / AC) * ldy + m0 + 8 * (pa1 % AC);
-    const lp16_t* bsrc0 = x + (k0 + pa0 / BC) * ldx + n0 + 8 * (pa0 % BC);
-    const lp16_t* bsrc1 = x + (k0 + pa1 / BC) * ldx + n0 + 8 * (pa1 % BC);
-    const int aoff0 = (pa0 / AC) * PA + 8 * (pa0 % AC), aoff1 = (pa1 / AC) * PA + 8 * (pa1 % AC);
-    const int boff0 = (pa0 / BC) * PB + 8 * (pa0 % BC), boff1 = (pa1 / BC) * PB + 8 * (pa1 % BC);
-    uint4 wa0 = make_uint4(0, 0, 0, 0), wa1 = wa0, wb0 = wa0, wb1 = wa0;
-#define WG_LOAD(it)                                                                              \
-    if (va0) wa0 = *reinterpret_cast<const uint4*>(asrc0 + (long long)(it) * 32 * ldy);          \
-    if (va1) wa1 = *reinterpret_cast<const uint4*>(asrc1 + (long long)(it) * 32 * ldy);          \
-    if (vb0) wb0 = *reinterpret_cast<const uint4*>(bsrc0 + (long long)(it) * 32 * ldx);          \
-    if (vb1) wb1 = *reinterpret_cast<const uint4*>(bsrc1 + (long long)(it) * 32 * ldx)
-#define WG_STORE(buf)                                                                            \
-    if (va0) *reinterpret_cast<uint4*>(&al[buf][aoff0]) = wa0;                                   \
-    if (va1) *reinterpret_cast<uint4*>(&al[buf][aoff1]) = wa1;                                   \
-    if (vb0) *reinterpret_cast<uint4*>(&bl[buf][boff0]) = wb0;                                   \
-    if (vb1) *reinterpret_cast<uint4*>(&bl[buf][boff1]) = wb1
-    WG_LOAD(0);
-    WG_STORE(0);
-    __syncthreads();
-    f32x4_t acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
-    // transposed-read address of this lane inside a 16-column tile: row 4g + q, columns 4p .. 4p+3
-    const int g = lane >> 4, il = lane & 15;
-    const int ra = (4 * g + (il >> 2)) * PA + 4 * (il & 3) + wave * MT * 16;
-    const int rb = (4 * g + (il >> 2)) * PB + 4 * (il & 3);
-    for (int it = 0; it < stages; ++it) {
-        const bool more = it + 1 < stages;
-        if (more) { WG_LOAD(it + 1); }
-        const lp16_t* ab = al[it & 1];
-        const lp16_t* bb = bl[it & 1];
-        lp16x8_t af[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) af[mt] = tr_read8(ab + ra + 16 * mt, 16 * PA);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const lp16x8_t bf = tr_read8(bb + rb + 16 * nt, 16 * PB);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-                acc[mt][nt] = MFMA_LP16(af[mt], bf, acc[mt][nt]);
-        }
-        if (more) { WG_STORE((it + 1) & 1); }
-        __syncthreads();
-    }
-#undef WG_LOAD
-#undef WG_STORE
-    // D[m = 4g + r][n = il] of tile (mt, nt)
-    float* out = part + ((long long)blockIdx.z * M + m0 + (wave * MT) * 16 + 4 * g) * Nv + n0 + il;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            if (n0 + 16 * nt + il < Nv) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) out[(long long)(16 * mt + r) * Nv + 16 * nt] = acc[mt][nt][r];
-            }
-}
-
 // ---- Weight gradient(s) on the matrix cores, second generation: dy^T [x1 | x2] in ONE pass over dy,
 //   part1[s][m][n] = sum_k dy[k][m] x1[k][n]  (n < Nv1),   part2[s][m][n] = sum_k dy[k][m] x2[k][n]  (n < Nv2)
 // over the rows k of slice s; x1 may be empty (N1p = 0: a plain dy^T x2).  The LSTM's dW_ih and dW_hh come out of one
 // launch -- dy = dG [n, 4H], the largest tensor of the backward pass, x1 = the step-input block of the operand buffer
 // (92 + 4 pad columns), x2 = the masked hidden states -- and the three MLP weights use the same kernel.
-// What the first generation (wgrad_mfma_kernel, and a 128 x 352-tile version of this one) got wrong was the SPLIT: few,
-// large output tiles need many row slices to fill the chip, and every slice writes a full fp32 copy of the output
+// What the first generation (up to 128 x 128 outputs per workgroup, and a 128 x 352-tile version of this one) got wrong
+// was the SPLIT: few, large output tiles need many row slices to fill the chip, and every slice writes a full fp32 copy of the output
 // (32 slices x 1.4 MB = 46 MB for the LSTM) that the column-sum kernel reads back -- as much HBM traffic as the
 // operands.  Here the output tile is small, 64 x (16 NT) with NT <= 11, so that ~512 workgroups need only 8-64 slices:
 //   workgroup = 4 waves along M (16 rows each), every wave NT column tiles: NT MFMAs against 2 (1 + NT) transposed LDS
 //   reads per 32-row stage; stages double-buffered in LDS behind a register prefetch (one barrier per stage); 2+
 //   workgroups per CU hide each other's barriers.  Tiles are staged row-major and read column-wise with
-//   ds_read_b64_tr_b16 exactly as in wgrad_mfma_kernel; the LDS pitches are odd multiples of 32 B so that 8 consecutive
+//   ds_read_b64_tr_b16 (tr_read8 above); the LDS pitches are odd multiples of 32 B so that 8 consecutive
 //   rows tile all 64 banks.  Block -> (slice, tile) keeps the tiles of a slice on one XCD (they share the operand rows:
 //   blocks b and b + 8 share an L2).  Slices are summed by the column-sum kernel: fixed order, no atomics.
 // One problem of a grouped launch (several independent products in ONE kernel: every node of the replayed update graph
@@ -5548,10 +5468,9 @@ int vine_lstm_step_mfma(int64_t B, int64_t H, int64_t K, const void* A, int64_t 
                            (long long)done_next_stride, (long long)hp_stride);                                          \
     } while (0)
     const int ks = (int)(K / 32), ks1 = (int)(K1 / 32);
-    static const bool use64 = getenv("VINE_LSTM_MFMA_SLAB") == nullptr;       // resident-slab kernel for A/B runs
     // (measured at B = 8192: K = 352 two-source 28.9 us streamed vs 32.3 us slab; K = 256 + igates 35.5 vs 29.8: the
     //  streamed kernel only takes the K = 352 shapes the update and the rollout actually use)
-    if (use64 && (H & 63) == 0 && ks == 11 && (ks1 == 0 || ks1 == 3)) {
+    if ((H & 63) == 0 && ks == 11 && (ks1 == 0 || ks1 == 3)) {
         const dim3 grid64((unsigned)(B / 64), (unsigned)(H / 64));
 #define VINE_LSTM_MFMA64(KS, KS1)                                                                                       \
         hipLaunchKernelGGL((lstm_step_mfma64_kernel<KS, KS1>), grid64, block, 0, s, (long long)B, (int)H,               \
@@ -5627,13 +5546,12 @@ int vine_lstm_seq_forward_mfma(int64_t B, int64_t T, int64_t H, int64_t KX, cons
     const dim3 grid((unsigned)(B / SEQ_ROWS)), block(512);
     hipStream_t s = (hipStream_t)stream;
     const int ablate = seq_ablate();
-    static const bool wcache_on = [] { const char* e = getenv("VINE_SEQ_FWD_WCACHE"); return !(e && e[0] == '0'); }();      // A/B knob
 #define VINE_SEQ_FWD_T(KS1, RING, CT, HT)                                                                               \
     do {                                                                                                                \
         const size_t rows_ = 4 * SEQ_H * sizeof(float) + ((size_t)2 * SEQ_ROWS * (SEQ_H + LDS_SKEW) +                    \
                                                           (size_t)T * SEQ_ROWS * (32 * KS1 + LDS_SKEW)) * sizeof(lp16_t); \
         /* the LDS weight cache (SEQ_FWD_NC fragments per wave = 88 KB) when the operand rows leave room for it */        \
-        const bool cache_ = wcache_on && T > 1 && rows_ + (size_t)8 * SEQ_FWD_NC * 1024 <= 160 * 1024;                   \
+        const bool cache_ = T > 1 && rows_ + (size_t)8 * SEQ_FWD_NC * 1024 <= 160 * 1024;                                \
         const size_t lds_ = rows_ + (cache_ ? (size_t)8 * SEQ_FWD_NC * 1024 : 0);                                        \
         if (cache_) {                                                                                                   \
             if (!ensure_dyn_lds(reinterpret_cast<const void*>(&lstm_seq_fwd_kernel<KS1, RING, CT, HT, SEQ_FWD_NC>), lds_)) \
@@ -5761,15 +5679,15 @@ int vine_mlp3_elu_mfma_prep(int64_t n, void* x, int64_t ldx, const float* raw, i
     if (!ensure_dyn_lds(threads == 512 ? reinterpret_cast<const void*>(&mlp3_elu_mfma_kernel<256, 128, 64, 8>)
                                        : reinterpret_cast<const void*>(&mlp3_elu_mfma_kernel<256, 128, 64, 4>), lds))
         return VINE_ERR_DEVICE;
-#define VINE_MLP3(NW_)                                                                                                   \
+#define VINE_MLP3_LAUNCH(NW_)                                                                                            \
     hipLaunchKernelGGL((mlp3_elu_mfma_kernel<256, 128, 64, NW_>), dim3((unsigned)(n / (16 * NW_))), dim3(64 * NW_), lds,  \
                        (hipStream_t)stream, (long long)n, (lp16_t*)x, (long long)ldx, raw, (int)F_in, mean, var, eps, clip, \
                        (const lp16_t*)w1p, b1, (const lp16_t*)w2, (long long)ldw2, b2, (const lp16_t*)w3, (long long)ldw3, \
                        b3, alpha, (lp16_t*)act1, (lp16_t*)act2, (lp16_t*)out, (long long)out_stride, (int)ldw1, side,     \
                        side_blocks)
-    if (threads == 512) VINE_MLP3(8);
-    else VINE_MLP3(4);
-#undef VINE_MLP3
+    if (threads == 512) VINE_MLP3_LAUNCH(8);
+    else VINE_MLP3_LAUNCH(4);
+#undef VINE_MLP3_LAUNCH
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
@@ -5969,30 +5887,6 @@ int vine_lstm_step_backward_mfma(int64_t B, int64_t H, const float* g_out, int64
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
-int vine_weight_grad_mfma(int64_t rows, int64_t M, int64_t Np, int64_t Nv, const void* dy, int64_t ldy, const void* x,
-                          int64_t ldx, int64_t slices, float* part, void* stream) {
-    if (rows <= 0 || M <= 0 || Np <= 0 || Nv <= 0 || Nv > Np || slices <= 0 || !dy || !x || !part || ldy < M || ldx < Np ||
-        (ldy & 7) || (ldx & 7) || ((uintptr_t)dy & 15) || ((uintptr_t)x & 15))
-        return VINE_ERR_INVALID_ARG;
-    if ((M & 63) || rows % (slices * 32) || slices > 65535) return VINE_ERR_UNSUPPORTED;
-    const int mt = (M & 127) ? 1 : 2;
-    int nt;
-    if (Np == 32) nt = 2;
-    else if (Np == 96) nt = 6;
-    else if ((Np & 127) == 0) nt = 8;
-    else return VINE_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)(M / (64 * mt)), (unsigned)(Np / (16 * nt)), (unsigned)slices);
-    const int stages = (int)(rows / slices / 32);
-    hipStream_t s = (hipStream_t)stream;
-#define VINE_WGRAD(MT_, NT_)                                                                                          \
-    hipLaunchKernelGGL((wgrad_mfma_kernel<MT_, NT_>), grid, dim3(256), 0, s, stages, (const lp16_t*)dy, (long long)ldy, \
-                       (const lp16_t*)x, (long long)ldx, part, (int)M, (int)Nv)
-    if (mt == 2) { if (nt == 2) VINE_WGRAD(2, 2); else if (nt == 6) VINE_WGRAD(2, 6); else VINE_WGRAD(2, 8); }
-    else { if (nt == 2) VINE_WGRAD(1, 2); else if (nt == 6) VINE_WGRAD(1, 6); else VINE_WGRAD(1, 8); }
-#undef VINE_WGRAD
-    return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
-}
-
 int vine_weight_grad_group(int32_t nprob, const int64_t* rows, const int64_t* M, const void* const* dy, const int64_t* ldy,
                            const void* const* x1, const int64_t* ldx1, const int64_t* N1p, const int64_t* Nv1,
                            const void* const* x2, const int64_t* ldx2, const int64_t* N2p, const int64_t* Nv2, const int64_t* NT,
@@ -6029,25 +5923,19 @@ int vine_weight_grad_group(int32_t nprob, const int64_t* rows, const int64_t* M,
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
-// one (128 | 64) x 352 tile per workgroup over [x1 96 | x2 256]; seq: the "h once" form of the second operand
+// one 128 x 352 tile per workgroup (NT = 22) over [x1 96 | x2 256]; seq: the "h once" form of the second operand
 static int wgrad_cat_wide_launch(int64_t rows, int64_t M, const void* dy, int64_t ldy, const void* x1, int64_t ldx1,
-                                 int64_t Nv1, const void* x2, int64_t ldx2, int64_t Nv2, int64_t NT, int64_t slices,
+                                 int64_t Nv1, const void* x2, int64_t ldx2, int64_t Nv2, int64_t slices,
                                  float* part1, float* part2, const uint8_t* done, int64_t T, void* stream) {
-    const int bm = NT == 22 ? 128 : 64;
+    const int bm = 128;
     if ((M % bm) || (slices & 7) || rows % (slices * 64) || slices > 8192) return VINE_ERR_UNSUPPORTED;
     const int mtiles = (int)(M / bm), stages = (int)(rows / slices / 32);
-    const size_t lds = (size_t)2 * 32 * ((bm + 16) + (352 + 16)) * sizeof(lp16_t);      // 64 / 56 KiB
-#define VINE_WGW(MT_)                                                                                                     \
-    {                                                                                                                     \
-        if (!ensure_dyn_lds((const void*)wgrad_cat_wide_kernel<6, MT_>, lds)) return VINE_ERR_DEVICE;                     \
-        hipLaunchKernelGGL((wgrad_cat_wide_kernel<6, MT_>), dim3((unsigned)(mtiles * slices)), dim3(512), lds,            \
-                           (hipStream_t)stream, stages, mtiles, (int)slices, (const lp16_t*)dy, (long long)ldy,           \
-                           (const lp16_t*)x1, (long long)ldx1, (const lp16_t*)x2, (long long)ldx2, part1, (int)Nv1,       \
-                           part2, (int)Nv2, (int)M, done, done ? (int)T : (1 << 30));                                     \
-    }
-    if (NT == 22) VINE_WGW(2)
-    else VINE_WGW(1)
-#undef VINE_WGW
+    const size_t lds = (size_t)2 * 32 * ((bm + 16) + (352 + 16)) * sizeof(lp16_t);      // 64 KiB
+    if (!ensure_dyn_lds((const void*)wgrad_cat_wide_kernel<6, 2>, lds)) return VINE_ERR_DEVICE;
+    hipLaunchKernelGGL((wgrad_cat_wide_kernel<6, 2>), dim3((unsigned)(mtiles * slices)), dim3(512), lds, (hipStream_t)stream,
+                       stages, mtiles, (int)slices, (const lp16_t*)dy, (long long)ldy, (const lp16_t*)x1, (long long)ldx1,
+                       (const lp16_t*)x2, (long long)ldx2, part1, (int)Nv1, part2, (int)Nv2, (int)M, done,
+                       done ? (int)T : (1 << 30));
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
@@ -6058,8 +5946,8 @@ int vine_weight_grad_cat_seq_mfma(int64_t rows, int64_t M, const void* dy, int64
         ldx1 < 96 || ldh < 256 || ((ldy | ldx1 | ldh) & 7) || (((uintptr_t)dy | (uintptr_t)x1 | (uintptr_t)h_all) & 15) ||
         Nv1 <= 0 || Nv1 > 96 || Nv2 <= 0 || Nv2 > 256 || rows % T)
         return VINE_ERR_INVALID_ARG;
-    if ((NT != 22 && NT != 21) || (32 % T) || ((uintptr_t)done & 15) || rows / slices / 32 > 1024) return VINE_ERR_UNSUPPORTED;
-    return wgrad_cat_wide_launch(rows, M, dy, ldy, x1, ldx1, Nv1, h_all, ldh, Nv2, NT, slices, part1, part2, done, T, stream);
+    if (NT != 22 || (32 % T) || ((uintptr_t)done & 15) || rows / slices / 32 > 1024) return VINE_ERR_UNSUPPORTED;
+    return wgrad_cat_wide_launch(rows, M, dy, ldy, x1, ldx1, Nv1, h_all, ldh, Nv2, slices, part1, part2, done, T, stream);
 }
 
 int vine_weight_grad_cat_mfma(int64_t rows, int64_t M, const void* dy, int64_t ldy, const void* x1, int64_t ldx1, int64_t N1p,
@@ -6069,10 +5957,9 @@ int vine_weight_grad_cat_mfma(int64_t rows, int64_t M, const void* dy, int64_t l
         ((uintptr_t)dy & 15) || ((uintptr_t)x2 & 15) || N2p <= 0 || Nv2 <= 0 || Nv2 > N2p || N1p < 0 ||
         (N1p > 0 && (!x1 || !part1 || ldx1 < N1p || (ldx1 & 7) || ((uintptr_t)x1 & 15) || Nv1 <= 0 || Nv1 > N1p)))
         return VINE_ERR_INVALID_ARG;
-    if (NT == 22 || NT == 21) {
+    if (NT == 22) {
         if (N1p != 96 || N2p != 256) return VINE_ERR_UNSUPPORTED;
-        return wgrad_cat_wide_launch(rows, M, dy, ldy, x1, ldx1, Nv1, x2, ldx2, Nv2, NT, slices, part1, part2, nullptr, 1,
-                                     stream);
+        return wgrad_cat_wide_launch(rows, M, dy, ldy, x1, ldx1, Nv1, x2, ldx2, Nv2, slices, part1, part2, nullptr, 1, stream);
     }
     if ((NT != 11 && NT != 8 && NT != 2) || (M & 63) || (N1p & 15) || ((N1p + N2p) % (16 * NT)) || (slices & 7) ||
         rows % (slices * 32) || slices > 8192)
@@ -6404,15 +6291,9 @@ int vine_ln_heads_loss(int64_t n, int64_t H, int32_t NH, const void* x, const fl
         !returns || !old_mu || !old_sigma || !heads || !dx || !ln_partial || !stats || !grad_logstd || !scratch ||
         ((grad_mu_bias == nullptr) != (grad_value_bias == nullptr)) || ((mu_store == nullptr) != (sigma_store == nullptr)))
         return VINE_ERR_INVALID_ARG;
-    // rows per wave (4 per pass): 16 keeps the workgroup count -- and with it the serial tail of the last workgroup,
-    // which folds one row of loss sums per workgroup -- small (VINE_LHL_ROWS = 4 | 8 | 16 for experiments)
-    static int rw = 0;
-    if (!rw) {
-        const char* e = getenv("VINE_LHL_ROWS");
-        rw = e ? atoi(e) : 16;
-        if (rw != 4 && rw != 8 && rw != 16) rw = 16;
-    }
-    const int rows_wg = 8 * rw;
+    // 16 rows per wave (4 per pass, R = 4 passes): that keeps the workgroup count -- and with it the serial tail of the
+    // last workgroup, which folds one row of loss sums per workgroup -- small
+    const int rows_wg = vine_ln_heads_loss_rows();
     if (H != 256 || NH < 2 || NH > 5 || n % rows_wg || n / rows_wg > VINE_PPO_LOSS_BLOCKS) return VINE_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)(n / rows_wg)), block(512);
     hipStream_t s = (hipStream_t)stream;
@@ -6423,41 +6304,30 @@ int vine_ln_heads_loss(int64_t n, int64_t H, int32_t NH, const void* x, const fl
     if ((x16 && !(dx_bf16 & 1)) || (xT && (!x16 || n % xT))) return VINE_ERR_UNSUPPORTED;
     const int defer = (dx_bf16 >> 2) & 1;     // bit 2: leave the per-workgroup loss rows in `scratch` (vine_column_sums_batched_fin)
     dx_bf16 &= 3;
-#define VINE_LHL_T(K, R, DXT, XT)                                                                                         \
-    hipLaunchKernelGGL((ln_heads_loss_kernel<K, R, DXT, XT>), grid, block, 0, s, (long long)n, (const XT*)x, xT, gamma, beta, \
+#define VINE_LHL_T(K, DXT, XT)                                                                                            \
+    hipLaunchKernelGGL((ln_heads_loss_kernel<K, 4, DXT, XT>), grid, block, 0, s, (long long)n, (const XT*)x, xT, gamma, beta, \
                        eps, w, wb, logstd, actions, old_neglogp, advantages, old_values, returns, old_mu, old_sigma, e_clip,           \
                        (int)clip_value, critic_coef, entropy_coef, bounds_coef, soft_bound, heads, (DXT*)dx, ln_partial,   \
                        scratch, stats, grad_logstd, grad_mu_bias, grad_value_bias, kl_out, logstd_grad_accum, mu_store,    \
                        sigma_store, loss_scale, found_inf, ticket, defer)
-#define VINE_LHL(K, R)                                                                                                    \
-    {                                                                                                                     \
-        if (x16) VINE_LHL_T(K, R, lp16_t, lp16_t);                                                                        \
-        else if (dx_bf16) VINE_LHL_T(K, R, lp16_t, float);                                                                \
-        else VINE_LHL_T(K, R, float, float);                                                                              \
-    }
-#define VINE_LHL_R(K)                                                                                                     \
+#define VINE_LHL(K)                                                                                                       \
     do {                                                                                                                  \
-        if (rw == 4) VINE_LHL(K, 1)                                                                                       \
-        else if (rw == 8) VINE_LHL(K, 2)                                                                                  \
-        else VINE_LHL(K, 4)                                                                                               \
+        if (x16) VINE_LHL_T(K, lp16_t, lp16_t);                                                                           \
+        else if (dx_bf16) VINE_LHL_T(K, lp16_t, float);                                                                   \
+        else VINE_LHL_T(K, float, float);                                                                                 \
     } while (0)
     switch (NH) {
-        case 2: VINE_LHL_R(2); break;
-        case 3: VINE_LHL_R(3); break;
-        case 4: VINE_LHL_R(4); break;
-        default: VINE_LHL_R(5); break;
+        case 2: VINE_LHL(2); break;
+        case 3: VINE_LHL(3); break;
+        case 4: VINE_LHL(4); break;
+        default: VINE_LHL(5); break;
     }
-#undef VINE_LHL_R
 #undef VINE_LHL
 #undef VINE_LHL_T
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
-int vine_ln_heads_loss_rows(void) {
-    const char* e = getenv("VINE_LHL_ROWS");
-    const int rw = e ? atoi(e) : 16;
-    return 8 * ((rw == 8 || rw == 4) ? rw : 16);
-}
+int vine_ln_heads_loss_rows(void) { return 128; }
 
 static int policy_head_launch(int64_t N, int32_t A, int64_t H, const float* y, const float* w_mu, const float* b_mu,
                               const float* w_v, const float* b_v, const float* logstd, const float* value_mean,
@@ -6569,13 +6439,9 @@ int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, f
     const int threads = 256;
     // every workgroup ends with a returning atomic for the election of the one that advances the step counter and the
     // schedules.  On ONE ticket word these serialise at ~23 ns each: 400 workgroups spent longer queueing there than on their
-    // 4 KB of parameters.  Default: a two-level election (8 group words 128 B apart, then the common word) on the full grid;
-    // VINE_ADAM_TICKETS=1 = the single word, for which the grid is capped at 128 workgroups (VINE_ADAM_BLOCKS overrides)
-    static const bool two_level = [] { const char* e = getenv("VINE_ADAM_TICKETS"); return !e || atoi(e) != 1; }();
-    static const int max_blocks = [] { const char* e = getenv("VINE_ADAM_BLOCKS"); return e ? atoi(e) : (two_level ? 0 : 128); }();
-    int blocks = grid_for((n + 3) / 4, threads);
-    if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-    unsigned int* sub = two_level ? ticket_sub_of(ticket) : nullptr;
+    // 4 KB of parameters.  Hence a two-level election (8 group words 128 B apart, then the common word) on the full grid
+    const int blocks = grid_for((n + 3) / 4, threads);
+    unsigned int* sub = ticket_sub_of(ticket);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, (long long)n,
                        params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
                        (lp16_t*)lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, ticket, sub);

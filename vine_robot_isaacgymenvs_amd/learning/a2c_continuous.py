@@ -475,7 +475,7 @@ class A2CAgent:
                 and fused.linear_elu_mfma_ok(N, net.units[0], 32)):
             f["w1p"] = torch.zeros((net.units[0], 32), device=dev, dtype=op)
         # fp32 matrix-core kernels (vine_mlp3_elu_f32 / vine_lstm_step_f32): the default network at N % 512 == 0
-        f["f32_mfma"] = (op == torch.float32 and fused.ROLLOUT_F32_MFMA and net.rnn_concat_input and H == 256 and XW + H == 352
+        f["f32_mfma"] = (op == torch.float32 and net.rnn_concat_input and H == 256 and XW + H == 352
                          and XW - U == 32 and U == 64 and F_in <= 32 and tuple(net.units) == (256, 128, 64) and N % 512 == 0)
         f["f32_split"] = self.rollout_f32_terms if (f["f32_mfma"] and self.rollout_f32_terms in (6, 9)) else 0
         f["wt_f32"] = torch.empty(4 * H * (XW + H), device=dev) if (f["f32_mfma"] and not f["f32_split"]) else None
@@ -574,7 +574,7 @@ class A2CAgent:
         x0 = f["x0_sep"] if f["x0_sep"] is not None else xh[:, f["U"]:f["U"] + f["F"]]
         hp_ptr = (xh_next.data_ptr() + xh_next.element_size() * XW) if commit else None
         n_mlp = len(f["mlp"])
-        mlp3 = (bf and fused.MLP3 and f["w1p"] is not None and f["x0_sep"] is None and n_mlp == 3 and N % 64 == 0
+        mlp3 = (bf and f["w1p"] is not None and f["x0_sep"] is None and n_mlp == 3 and N % 64 == 0
                 and f["U"] == 64 and f["F"] <= 32 and obs.is_contiguous() and obs.dtype == torch.float32
                 and tuple(W.shape for W, _ in f["mlp"][1:]) == ((128, 256), (64, 128)) and f["mlp"][0][0].shape[0] == 256)
         f32k = bool(f["f32_mfma"]) and obs.is_contiguous() and obs.dtype == torch.float32 and n_mlp == 3
@@ -1189,7 +1189,7 @@ class A2CAgent:
         if norm_stats is not None:
             batch_dict["obs_norm_stats"] = norm_stats
         pack = None
-        if ext and fused.HEADS_LOSS and self.fused_mixed:
+        if ext and self.fused_mixed:
             # LayerNorm + heads + loss + their backward inside the trunk node (one launch instead of three)
             pack = fused.ppo_loss_pack(net.sigma, mb["actions"], mb["old_logp_actions"], mb["advantages"], mb["old_values"],
                                        mb["returns"], mb["mu"], mb["sigma"], self.e_clip, self.clip_value, self.critic_coef,
@@ -1197,7 +1197,7 @@ class A2CAgent:
                                        logstd_grad=net.sigma.grad, update_old=True, stats_out=stats_out, amp=self._amp)
             batch_dict["loss_pack"] = pack
         mu, value, logstd, _, heads = self.model.forward_raw(batch_dict)
-        if pack is not None and heads is not None and heads.grad_fn is not None and getattr(heads.grad_fn, "loss_fused", None):
+        if pack is not None and heads is not None and getattr(getattr(heads.grad_fn, "route", None), "loss_fused", None):
             torch.autograd.backward([heads], [heads.detach()])      # the gradient handed over is ignored by the node
             self._amp_covered = bool(pack.get("amp_covered", False))
             return pack["stats"], mu.detach(), logstd.detach()

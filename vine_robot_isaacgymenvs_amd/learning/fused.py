@@ -19,7 +19,10 @@ over the whole reduction.  Here:
 On a CPU tensor every op falls back to the plain PyTorch composition it replaces (used by the gloo tests and as the
 fp32 reference of the numerics tests); on a GPU tensor the HIP kernels are mandatory.
 """
+import ctypes as C
 import math
+import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -86,16 +89,79 @@ def _mm(a, b):
     return a.mm(b)
 
 
+# --------------------------------------------------------------------------- switches
+# Configuration choices (each has a config key or a bench extra behind it) and the A/B switches the tests patch to obtain
+# a reference; everything else about the route of an op follows from its arguments.
+SPLITK_ROWS = 1024      # rows of the reduction per slice of ``splitk_tn``
+WGRAD_CAT_WGS = 512     # workgroups a ``vine_weight_grad_cat_mfma`` launch aims for (2 per CU)
+WGRAD_GROUP_WGS = int(os.environ.get("VINE_WGRAD_GROUP_WGS", "256"))   # per problem of a grouped launch
+WGRAD_CAT_WIDE = os.environ.get("VINE_WGRAD_CAT_WIDE", "1") != "0"  # 128 x 352 tiles for the LSTM's [x | h] (A/B knob)
+# fp32 rollout inference with the products formed from bf16 pieces on the bf16 matrix cores (vine_lstm_step_f32_split,
+# vine_mlp3_elu_f32_split): 6 = without the three piece pairs below 2^-24 of a product (the default), 9 = all nine pairs,
+# 0 = the native fp32 matrix-core kernels (vine_lstm_step_f32, vine_mlp3_elu_f32).
+# Round 5, measured (VERDICT r4 item 7: "worse on any case: keep 9"; scripts/ubench/split_terms_error.py,
+# profiles/r05/split_terms_error.txt; asserted by test_*_f32_split_against_float64_torch): with ONE accumulator per tile the
+# 6- and 9-pair forms have the same error against float64 to four digits (the accumulation's 66 / 99 roundings dominate, not
+# the dropped pairs), 10-25 % below the native fp32 instruction's in rms but up to 1.19x (LSTM test inputs: 1.63x) ABOVE it
+# in max.  With TWO accumulators (ROLLOUT_F32_DUAL below) both forms are at most 0.60x (LSTM) / 0.45x (MLP) of the native
+# instruction's error on every input, max and rms, and 6 against 9 pairs differ by < 1 % of that error on rms and either
+# way on max: 6 pairs + two accumulators is the default (rollout 2.20 -> 1.93 ms), the 9-pair iteration rides in the bench
+# line as `extra_split9_rollout`.
+ROLLOUT_F32_SPLIT = int(os.environ.get("VINE_ROLLOUT_F32_SPLIT", "6"))
+# the one-gate-per-wave form of the LSTM kernel (four waves share 64 rows, operand pieces exchanged through LDS; bit 16 of
+# `terms`): "auto" = below 16384 rows, where it is faster (23.1 against 24.9 us at 4096 rows, 14.7 against 22.0 at 2048;
+# level at 16384: profiles/r04/rollout_kernels_round4.txt); "1" / "0" = always / never
+ROLLOUT_F32_NSPLIT = os.environ.get("VINE_LSTM_STEP_NSPLIT", "auto")
+# two accumulators per tile (bit 17 of the LSTM kernel's `terms`, bit 16 of the MLP kernel's): the hi x hi pair apart from
+# the smaller pairs -- the smaller pairs' sum is rounded at 2^-8 of the result's magnitude, which leaves one rounding per
+# k-block at full magnitude (11 in the LSTM step instead of 66-99).  On (the default) it makes the one-gate-per-wave kernel
+# the LSTM kernel at every size (the only one that has the second accumulator).
+ROLLOUT_F32_DUAL = os.environ.get("VINE_ROLLOUT_F32_DUAL", os.environ.get("VINE_LSTM_STEP_DUAL", "1")) != "0"
+# the fp32 rollout MLP with the same piece products (vine_mlp3_elu_f32_split: four waves share the rows and split the units);
+# 0 = the native fp32 matrix-core kernel (vine_mlp3_elu_f32).  VINE_MLP3_F32_SPLIT_RT: row tiles per workgroup (0: from N)
+MLP3_F32_SPLIT = os.environ.get("VINE_MLP3_F32_SPLIT", "1") != "0"
+MLP3_F32_SPLIT_RT = int(os.environ.get("VINE_MLP3_F32_SPLIT_RT", "0"))
+MLP3_PREP = os.environ.get("VINE_MLP3_PREP", "1") != "0"      # the step's operand preparation rides in the MLP launch (A/B knob)
+COPY_SCATTER = os.environ.get("VINE_COPY_SCATTER", "1") != "0"  # coalesced-load / scattered-store forms of tiles and transposes
+RIDES = [0]      # forward passes whose operand preparation rode in the MLP launch (tests look at it)
+# LSTM backward + MLP backward as two phases of one launch (same rows per workgroup); 0: two launches (A/B knob)
+BWD_PHASES = os.environ.get("VINE_BWD_PHASES", "1") != "0"
+# LSTM forward + LayerNorm / heads / loss + LSTM backward + MLP backward as four phases of one launch; 0: separate launches
+TRUNK_PHASES = os.environ.get("VINE_TRUNK_PHASES", "1") != "0"
+PHASE_LAUNCHES = [0]      # vine_trunk_phases launches (tests look at it)
+# the hidden states of the update's LSTM stored ONCE (16-bit, unmasked) instead of fp32 for the LayerNorm + masked 16-bit
+# for the recurrent weight gradient; 0: both copies (A/B knob)
+H_ONCE = os.environ.get("VINE_H_ONCE", "1") != "0"
+
+
+def rollout_f32_nsplit(rows):
+    """Bits 16-17 of vine_lstm_step_f32_split's `terms` for a batch of `rows`: 1 = one gate per wave, 3 = with two accumulators."""
+    if ROLLOUT_F32_NSPLIT == "0":
+        return 0
+    if ROLLOUT_F32_DUAL:
+        return 3
+    return 1 if (ROLLOUT_F32_NSPLIT == "1" or rows < 16384) else 0
+
+
+def _carray(ctype, values):
+    """ctypes array argument of the batched launches (one entry per job)."""
+    return (ctype * len(values))(*values)
+
+
 # --------------------------------------------------------------------------- split-K weight gradient
-import os as _os
-SPLITK_ROWS = int(_os.environ.get("VINE_SPLITK_ROWS", "1024"))      # rows of the reduction per slice (experiments)
+def _splitk_slices(K):
+    """Slices of a K-row reduction: halved while both halves keep SPLITK_ROWS rows, 64 at most."""
+    s = 1
+    while K % (s * 2) == 0 and K // (s * 2) >= SPLITK_ROWS and s < 64:
+        s *= 2
+    return s
+
+
 def splitk_tn(dy, x, out=None, batch=None):
     """``dy^T @ x`` for tall-skinny operands: dy [K, M], x [K, N] -> [M, N] (written into ``out`` when given).
     ``batch``: defer the sum over the slices to a ``ColumnSumBatch`` (the result exists after its ``flush``)."""
     K = dy.shape[0]
-    s = 1
-    while K % (s * 2) == 0 and K // (s * 2) >= SPLITK_ROWS and s < 64:
-        s *= 2
+    s = _splitk_slices(K)
     if s == 1 or not dy.is_cuda:
         if batch is not None:
             batch.bypassed = True       # this gradient does not pass the overflow-checked column-sum launch
@@ -114,46 +180,10 @@ def splitk_tn(dy, x, out=None, batch=None):
 def _splitk_parts(dy, x):
     """The slices of ``splitk_tn`` before their sum: (s, part [s, M, N]) or (1, dy^T x [M, N])."""
     K = dy.shape[0]
-    s = 1
-    while K % (s * 2) == 0 and K // (s * 2) >= SPLITK_ROWS and s < 64:
-        s *= 2
+    s = _splitk_slices(K)
     if s == 1 or not dy.is_cuda:
         return 1, dy.t().mm(x)
     return s, torch.bmm(dy.unflatten(0, (s, K // s)).transpose(1, 2), x.unflatten(0, (s, K // s)))
-
-
-WGRAD_WGS = int(_os.environ.get("VINE_WGRAD_WGS", "256"))      # workgroups a weight-gradient launch aims for
-# largest M * Np the matrix-core weight-gradient kernel (vine_weight_grad_mfma) takes.  0 = off, the default: measured
-# inside the whole update (MI355X, n = 32768) the library split-K product + column sums wins at every weight of the
-# default network -- update 15.3 ms without the kernel, 16.0 ms with it for the four small weights, 17.8 ms for all
-# five (w_hh [1024, 256] alone: 93 us against 38 us).  With one workgroup per CU and 32-row stages the kernel is bound
-# by memory latency, not by the matrix cores; it stays as a tested building block (transposed LDS reads) behind this
-# knob.
-WGRAD_MAX_OUT = int(_os.environ.get("VINE_WGRAD_MAX_OUT", "0"))
-
-
-def _wgrad_plan(dy, x):
-    """(Np, slices) when ``vine_weight_grad_mfma`` covers dy^T x for these operands, else None.  Np: x's columns
-    rounded up to a tile width of the kernel; the extra columns must lie inside x's own rows (a column block of a
-    wider, padded buffer) -- they are read, their products are not stored."""
-    if not (dy.is_cuda and dy.dtype == lp_dtype() and x.dtype == lp_dtype() and dy.dim() == 2 and x.dim() == 2):
-        return None
-    n, M = dy.shape
-    N = x.shape[1]
-    if x.shape[0] != n or M % 64 or n % 256 or dy.stride(1) != 1 or x.stride(1) != 1:
-        return None
-    Np = 32 if N <= 32 else (96 if 64 < N <= 96 else ((N + 127) // 128 * 128 if N > 96 else 0))
-    if not Np or dy.stride(0) % 8 or x.stride(0) % 8 or dy.data_ptr() % 16 or x.data_ptr() % 16 or dy.stride(0) < M:
-        return None
-    if Np != N and (x.storage_offset() % x.stride(0)) + Np > x.stride(0):
-        return None
-    if x.stride(0) < Np or M * Np > WGRAD_MAX_OUT:
-        return None
-    wgs = (M // (128 if M % 128 == 0 else 64)) * (Np // (Np if Np <= 96 else 128))
-    s = 1
-    while wgs * s < WGRAD_WGS and n // (2 * s) >= 256 and n % (2 * s * 32) == 0:
-        s *= 2
-    return Np, s
 
 
 def weight_grad(dy, x, out=None, batch=None):
@@ -163,86 +193,7 @@ def weight_grad(dy, x, out=None, batch=None):
         o = out if out is not None else torch.empty((dy.shape[1], x.shape[1]), device=dy.device, dtype=torch.float32)
         if o.is_contiguous() and weight_grad_cat(dy, None, x, None, o, batch=batch):
             return o
-    plan = _wgrad_plan(dy, x)
-    if plan is None:
-        return splitk_tn(dy, x, out=out, batch=batch)
-    Np, s = plan
-    n, M = dy.shape
-    N = x.shape[1]
-    if out is None:
-        out = torch.empty((M, N), device=dy.device, dtype=torch.float32)
-    direct = s == 1 and out.is_contiguous()
-    part = out.view(1, M, N) if direct else torch.empty((s, M, N), device=dy.device, dtype=torch.float32)
-    _check(_lib().vine_weight_grad_mfma(n, M, Np, N, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), s,
-                                        part.data_ptr(), _stream(dy)), "vine_weight_grad_mfma")
-    if direct:
-        if batch is not None:
-            batch.bypassed = True
-        return out
-    return column_sums(part, out, batch=batch)
-
-
-HEADS_LOSS = _os.environ.get("VINE_HEADS_LOSS", "1") != "0"    # LayerNorm + heads + loss + backward in one launch (A/B knob)
-ROLLOUT_F32_MFMA = _os.environ.get("VINE_ROLLOUT_F32_MFMA", "1") != "0"   # fp32 matrix-core rollout kernels (A/B knob)
-# fp32 rollout inference with the products formed from bf16 pieces on the bf16 matrix cores (vine_lstm_step_f32_split,
-# vine_mlp3_elu_f32_split): 6 = without the three piece pairs below 2^-24 of a product (the default), 9 = all nine pairs,
-# 0 = the native fp32 matrix-core kernels (vine_lstm_step_f32, vine_mlp3_elu_f32).
-# Round 5, measured (VERDICT r4 item 7: "worse on any case: keep 9"; scripts/ubench/split_terms_error.py,
-# profiles/r05/split_terms_error.txt; asserted by test_*_f32_split_against_float64_torch): with ONE accumulator per tile the
-# 6- and 9-pair forms have the same error against float64 to four digits (the accumulation's 66 / 99 roundings dominate, not
-# the dropped pairs), 10-25 % below the native fp32 instruction's in rms but up to 1.19x (LSTM test inputs: 1.63x) ABOVE it
-# in max.  With TWO accumulators (ROLLOUT_F32_DUAL below) both forms are at most 0.60x (LSTM) / 0.45x (MLP) of the native
-# instruction's error on every input, max and rms, and 6 against 9 pairs differ by < 1 % of that error on rms and either
-# way on max: 6 pairs + two accumulators is the default (rollout 2.20 -> 1.93 ms), the 9-pair iteration rides in the bench
-# line as `extra_split9_rollout`.
-ROLLOUT_F32_SPLIT = int(_os.environ.get("VINE_ROLLOUT_F32_SPLIT", "6"))
-# the one-gate-per-wave form of the LSTM kernel (four waves share 64 rows, operand pieces exchanged through LDS; bit 16 of
-# `terms`): "auto" = below 16384 rows, where it is faster (23.1 against 24.9 us at 4096 rows, 14.7 against 22.0 at 2048;
-# level at 16384: profiles/r04/rollout_kernels_round4.txt); "1" / "0" = always / never
-ROLLOUT_F32_NSPLIT = _os.environ.get("VINE_LSTM_STEP_NSPLIT", "auto")
-# two accumulators per tile (bit 17 of the LSTM kernel's `terms`, bit 16 of the MLP kernel's): the hi x hi pair apart from
-# the smaller pairs -- the smaller pairs' sum is rounded at 2^-8 of the result's magnitude, which leaves one rounding per
-# k-block at full magnitude (11 in the LSTM step instead of 66-99).  On (the default) it makes the one-gate-per-wave kernel
-# the LSTM kernel at every size (the only one that has the second accumulator).
-ROLLOUT_F32_DUAL = _os.environ.get("VINE_ROLLOUT_F32_DUAL", _os.environ.get("VINE_LSTM_STEP_DUAL", "1")) != "0"
-
-
-def rollout_f32_nsplit(rows):
-    """Bits 16-17 of vine_lstm_step_f32_split's `terms` for a batch of `rows`: 1 = one gate per wave, 3 = with two accumulators."""
-    if ROLLOUT_F32_NSPLIT == "0":
-        return 0
-    if ROLLOUT_F32_DUAL:
-        return 3
-    return 1 if (ROLLOUT_F32_NSPLIT == "1" or rows < 16384) else 0
-
-
-# the fp32 rollout MLP with the same piece products (vine_mlp3_elu_f32_split: four waves share the rows and split the units);
-# 0 = the native fp32 matrix-core kernel (vine_mlp3_elu_f32).  VINE_MLP3_F32_SPLIT_RT: row tiles per workgroup (0: from N)
-MLP3_F32_SPLIT = _os.environ.get("VINE_MLP3_F32_SPLIT", "1") != "0"
-MLP3_F32_SPLIT_RT = int(_os.environ.get("VINE_MLP3_F32_SPLIT_RT", "0"))
-MLP3 = _os.environ.get("VINE_MLP3", "1") != "0"                # the three MLP layers in one launch (A/B knob)
-MLP3_PREP = _os.environ.get("VINE_MLP3_PREP", "1") != "0"      # the step's operand preparation rides in that launch (A/B knob)
-COPY_SCATTER = _os.environ.get("VINE_COPY_SCATTER", "1") != "0"  # coalesced-load / scattered-store forms of tiles and transposes
-RIDES = [0]      # forward passes whose operand preparation rode in the MLP launch (tests look at it)
-# LSTM backward + MLP backward as two phases of one launch (same rows per workgroup); 0: two launches (A/B knob)
-BWD_PHASES = _os.environ.get("VINE_BWD_PHASES", "1") != "0"
-# LSTM forward + LayerNorm / heads / loss + LSTM backward + MLP backward as four phases of one launch; 0: separate launches
-TRUNK_PHASES = _os.environ.get("VINE_TRUNK_PHASES", "1") != "0"
-PHASE_LAUNCHES = [0]      # vine_trunk_phases launches (tests look at it)
-WGRAD_SIDE = _os.environ.get("VINE_WGRAD_SIDE", "0") == "1"      # MLP weight gradients on a parallel branch (experiment)
-_SIDE_STREAMS = {}
-
-
-def _side_stream(dev):
-    key = (dev.type, dev.index)
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _SIDE_STREAMS[key]
-WGRAD_CAT = _os.environ.get("VINE_WGRAD_CAT", "1") != "0"      # second-generation weight-gradient kernel (A/B knob)
-WGRAD_CAT_WGS = int(_os.environ.get("VINE_WGRAD_CAT_WGS", "512"))   # workgroups a launch aims for (2 per CU)
-WGRAD_WIDE_BM = int(_os.environ.get("VINE_WGRAD_WIDE_BM", "128"))   # 128 | 64 rows of dy^T per workgroup tile (A/B knob)
-WGRAD_GROUP_WGS = int(_os.environ.get("VINE_WGRAD_GROUP_WGS", "256"))   # per problem of a grouped launch
-WGRAD_CAT_WIDE = _os.environ.get("VINE_WGRAD_CAT_WIDE", "1") != "0"  # 128 x 352 tiles for the LSTM's [x | h] (A/B knob)
+    return splitk_tn(dy, x, out=out, batch=batch)
 
 
 def _cat_operand(x, n):
@@ -260,7 +211,7 @@ def _cat_operand(x, n):
 
 def _wgrad_cat_plan(dy, x1, x2, out1, out2, allow_wide=True, wgs=None):
     """Arguments of ``vine_weight_grad_cat_mfma`` for ``dy^T @ [x1 | x2]`` -> (n, M, N1p, Nv1, N2p, Nv2, NT, S) or None."""
-    if not (WGRAD_CAT and dy.is_cuda and dy.dtype == lp_dtype() and dy.dim() == 2 and dy.stride(1) == 1
+    if not (dy.is_cuda and dy.dtype == lp_dtype() and dy.dim() == 2 and dy.stride(1) == 1
             and dy.stride(0) % 8 == 0 and dy.data_ptr() % 16 == 0 and out2.is_contiguous()
             and (out1 is None or out1.is_contiguous())):
         return None
@@ -274,8 +225,8 @@ def _wgrad_cat_plan(dy, x1, x2, out1, out2, allow_wide=True, wgs=None):
     if not NT:
         return None
     wide = allow_wide and WGRAD_CAT_WIDE and o1[0] == 96 and o2[0] == 256 and M % 128 == 0
-    if wide:        # one 128 x 352 (or 64 x 352) tile per workgroup, one workgroup per CU
-        NT, tiles, target = (22, M // 128, 256) if WGRAD_WIDE_BM == 128 else (21, M // 64, 256)
+    if wide:        # one 128 x 352 tile per workgroup, one workgroup per CU
+        NT, tiles, target = 22, M // 128, 256
     else:
         tiles, target = (M // 64) * (Nt // (16 * NT)), (wgs or WGRAD_CAT_WGS)
     S = 8
@@ -312,7 +263,7 @@ def weight_grad_cat(dy, x1, x2, out1, out2, batch=None, seq=None):
     if plan is None:
         return False
     n, M, N1p, Nv1, N2p, Nv2, NT, S = plan
-    if seq is not None and (NT not in (21, 22) or x1 is None or not h_once_ok(seq[1]) or seq[0].data_ptr() % 16
+    if seq is not None and (NT != 22 or x1 is None or not h_once_ok(seq[1]) or seq[0].data_ptr() % 16
                             or n // S // 32 > 1024 or x2.shape[0] != n // seq[1] * (seq[1] + 1) or not x2.is_contiguous()):
         return False
     part2 = torch.empty((S, M, Nv2), device=dy.device, dtype=torch.float32)
@@ -361,16 +312,14 @@ class WeightGradGroup:
     def flush(self):
         if not self.jobs:
             return
-        import ctypes as C
         k = len(self.jobs)
-        I64, VP = C.c_int64 * k, C.c_void_p * k
-        col = lambda f: [f(j) for j in self.jobs]
-        zeros, nulls = I64(*([0] * k)), VP(*([None] * k))
+        i64 = lambda f: _carray(C.c_int64, [f(j) for j in self.jobs])
+        ptr = lambda f: _carray(C.c_void_p, [f(j) for j in self.jobs])
+        zeros, nulls = _carray(C.c_int64, [0] * k), _carray(C.c_void_p, [None] * k)
         _check(_lib().vine_weight_grad_group(
-            k, I64(*col(lambda j: j[0])), I64(*col(lambda j: j[1])), VP(*col(lambda j: j[2].data_ptr())),
-            I64(*col(lambda j: j[2].stride(0))), nulls, zeros, zeros, zeros, VP(*col(lambda j: j[3].data_ptr())),
-            I64(*col(lambda j: j[3].stride(0))), I64(*col(lambda j: j[4])), I64(*col(lambda j: j[5])),
-            I64(*col(lambda j: j[6])), I64(*col(lambda j: j[7])), nulls, VP(*col(lambda j: j[8].data_ptr())),
+            k, i64(lambda j: j[0]), i64(lambda j: j[1]), ptr(lambda j: j[2].data_ptr()), i64(lambda j: j[2].stride(0)),
+            nulls, zeros, zeros, zeros, ptr(lambda j: j[3].data_ptr()), i64(lambda j: j[3].stride(0)), i64(lambda j: j[4]),
+            i64(lambda j: j[5]), i64(lambda j: j[6]), i64(lambda j: j[7]), nulls, ptr(lambda j: j[8].data_ptr()),
             _stream(self.jobs[0][2])), "vine_weight_grad_group")
         self.jobs = []
 
@@ -466,21 +415,9 @@ def _lstm_state_buffers(x, w_hh, h0, c0, dones, T, need_grad, prep=None, copy_c0
     return out, c_all, gates, hp
 
 
-# saved cell states and the hidden-state gradient of the persistent LSTM kernels as bfloat16 (backward-only data; the
-# recurrence, the returned state and every parameter gradient stay fp32); 0: fp32 (A/B knob)
-LSTM_LP = _os.environ.get("VINE_LSTM_LP", "1") != "0"
-LSTM_SEQ = _os.environ.get("VINE_LSTM_SEQ", "1") != "0"      # 0: one launch per time step (the round-1 kernels), for A/B runs
-# the hidden states of the update's LSTM stored ONCE (16-bit, unmasked) instead of fp32 for the LayerNorm + masked 16-bit
-# for the recurrent weight gradient; 0: both copies (A/B knob)
-H_ONCE = _os.environ.get("VINE_H_ONCE", "1") != "0"
-# the loss kernel's serial last step deferred into the column-sum launch that ends the backward pass; 0: inside the loss
-# kernel (ticket + last workgroup), as its stand-alone callers get it (A/B knob)
-LOSS_DEFER = _os.environ.get("VINE_LOSS_DEFER", "1") != "0"
-
-
 def lstm_seq_ok(B, H, T, wpad):
     """Shapes the persistent sequence kernels (vine_lstm_seq_forward_mfma / _backward_mfma) cover."""
-    return LSTM_SEQ and B % 32 == 0 and H == 256 and 1 <= T <= 8 and wpad in (32, 64, 96, 128)
+    return B % 32 == 0 and H == 256 and 1 <= T <= 8 and wpad in (32, 64, 96, 128)
 
 
 def _lstm_forward_steps(lib, x, ig, w_hh, bias, h0, c0, dones, T, need_grad, wcat=None, buffers=None, c0_direct=None,
@@ -663,17 +600,13 @@ class ColumnSumBatch:
         return out
 
     def flush(self, ref):
-        import ctypes as C
         lib, st = _lib(), _stream(ref)
+        i64, ptr = (lambda v: _carray(C.c_int64, v)), (lambda v: _carray(C.c_void_p, v))
         for k in range(0, len(self.jobs), 16):
-            js = self.jobs[k:k + 16]
-            n = len(js)
-            cols = list(zip(*js))
-            i64 = lambda v: (C.c_int64 * n)(*v)
-            ptr = lambda v: (C.c_void_p * n)(*v)
+            cols = list(zip(*self.jobs[k:k + 16]))
             fin = self.fin if k + 16 >= len(self.jobs) else None      # (with the last launch)
-            _check(lib.vine_column_sums_batched_fin(n, i64(cols[0]), i64(cols[1]), ptr(cols[2]), i64(cols[3]), ptr(cols[4]),
-                                                    i64(cols[5]), ptr(cols[6]), (C.c_int32 * n)(*cols[7]),
+            _check(lib.vine_column_sums_batched_fin(len(cols[0]), i64(cols[0]), i64(cols[1]), ptr(cols[2]), i64(cols[3]),
+                                                    ptr(cols[4]), i64(cols[5]), ptr(cols[6]), _carray(C.c_int32, cols[7]),
                                                     self.found_inf.data_ptr() if self.found_inf is not None else None,
                                                     C.byref(fin) if fin is not None else None, st),
                    "vine_column_sums_batched_fin")
@@ -747,33 +680,25 @@ class CopyBatch:
         """(njobs, the ten ctypes arrays of vine_copy_batched) for a launch that carries these moves as a side job
         (``vine_mlp3_elu_mfma_prep``), or None when they do not fit one launch; the batch stays filled (``keep`` holds the
         tensors) until ``clear``."""
-        import ctypes as C
-        n = len(self.jobs)
-        if n == 0 or n > 24:
+        if not 0 < len(self.jobs) <= 24:
             return None
-        cols = list(zip(*self.jobs))
-        i32 = lambda v: (C.c_int32 * n)(*v)
-        i64 = lambda v: (C.c_int64 * n)(*v)
-        ptr = lambda v: (C.c_void_p * n)(*v)
-        return (n, i32(cols[0]), i32(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(cols[4]), i64(cols[5]), i64(cols[6]),
+        return self._pack(self.jobs)
+
+    @staticmethod
+    def _pack(jobs):
+        """(njobs, op, element size, src, src2, dst, rows, cols, src stride, dst stride, aux) as ``vine_copy_batched`` takes them."""
+        cols = list(zip(*jobs))
+        i32, i64, ptr = (lambda v: _carray(C.c_int32, v)), (lambda v: _carray(C.c_int64, v)), (lambda v: _carray(C.c_void_p, v))
+        return (len(jobs), i32(cols[0]), i32(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(cols[4]), i64(cols[5]), i64(cols[6]),
                 i64(cols[7]), i64(cols[8]), i64(cols[9]))
 
     def clear(self):
         self.jobs, self.keep = [], []
 
     def flush(self, ref):
-        import ctypes as C
         lib, st = _lib(), _stream(ref)
         for k in range(0, len(self.jobs), 24):
-            js = self.jobs[k:k + 24]
-            n = len(js)
-            cols = list(zip(*js))
-            i32 = lambda v: (C.c_int32 * n)(*v)
-            i64 = lambda v: (C.c_int64 * n)(*v)
-            ptr = lambda v: (C.c_void_p * n)(*v)
-            _check(lib.vine_copy_batched(n, i32(cols[0]), i32(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(cols[4]),
-                                         i64(cols[5]), i64(cols[6]), i64(cols[7]), i64(cols[8]), i64(cols[9]), st),
-                   "vine_copy_batched")
+            _check(lib.vine_copy_batched(*self._pack(self.jobs[k:k + 24]), st), "vine_copy_batched")
         self.jobs, self.keep = [], []
 
 
@@ -849,11 +774,43 @@ def lstm_sequence(x, w_ih, w_hh, b_ih, b_hh, h0, c0, dones, T):
 
 
 # --------------------------------------------------------------------------- whole actor-critic trunk
-def _heads_loss_route(n, H, NH, loss_pack, head_bias_external, lib):
-    """Does the trunk run LayerNorm + heads + loss + their backward as the one ``vine_ln_heads_loss`` launch?"""
-    rows = lib.vine_ln_heads_loss_rows()
-    return (H == 256 and 2 <= NH <= 5 and loss_pack is not None and HEADS_LOSS and n % rows == 0 and n // rows <= 1024
+def _heads_loss_route(n, H, NH, loss_pack, head_bias_external, rows):
+    """Does the trunk run LayerNorm + heads + loss + their backward as the one ``vine_ln_heads_loss`` launch?
+    ``rows`` = ``vine_ln_heads_loss_rows()``, the rows per workgroup of that kernel."""
+    return (H == 256 and 2 <= NH <= 5 and loss_pack is not None and n % rows == 0 and n // rows <= 1024
             and bool(head_bias_external))
+
+
+def _padded_w1(prep, W1, F_in):
+    """Layer 1's operand weight with zero columns up to K = 32 (the moves join the CopyBatch ``prep``)."""
+    w1p = torch.empty((W1.shape[0], 32), device=W1.device, dtype=W1.dtype)
+    prep.add(CopyBatch.COPY, w1p[:, :F_in], W1)
+    prep.add(CopyBatch.ZERO, w1p[:, F_in:])
+    return w1p
+
+
+def _loss_finalize(lpk, blocks, NH, n):
+    """The loss kernel's serial last step (fold of its ``blocks`` per-workgroup loss rows -> statistics, KL slot,
+    log-sigma and head-bias gradients) as the job a ``ColumnSumBatch`` carries in its last launch."""
+    from ..abi import LossFinalize
+    return LossFinalize(lpk["scratch"].data_ptr(), blocks, NH - 1, n, lpk["logstd"].data_ptr(), lpk["scal"][2],
+                        lpk["scal"][3], lpk["scal"][4], lpk["stats"].data_ptr(), lpk["grad_logstd"].data_ptr(),
+                        lpk["head_bias_grads"][0].data_ptr(), lpk["head_bias_grads"][1].data_ptr(), lpk["extra"][0],
+                        lpk["extra"][1], _amp_ptrs(lpk.get("amp"))[0])
+
+
+def _lstm_grad_buffers(n, B, H, dev):
+    """Outputs of the persistent LSTM backward inside a phased launch: dG [n, 4H] (16-bit) and the bias-gradient
+    partial sums (one row per 32 sequences)."""
+    return (torch.empty((n, 4 * H), device=dev, dtype=lp_dtype()),
+            torch.empty((B // 32, 4 * H), device=dev, dtype=torch.float32))
+
+
+def _mlp3_grad_buffers(n, rows_wg, dev):
+    """Outputs of the one-launch MLP backward: pre-activation gradients of layers 1, 2, 3 (16-bit) and their bias
+    partial sums, one row per workgroup of ``rows_wg`` rows."""
+    return ([torch.empty((n, c), device=dev, dtype=lp_dtype()) for c in (256, 128, 64)],
+            [torch.empty((n // rows_wg, c), device=dev, dtype=torch.float32) for c in (256, 128, 64)])
 
 
 class _Trunk(torch.autograd.Function):
@@ -868,7 +825,11 @@ class _Trunk(torch.autograd.Function):
       * both heads share one forward GEMM, one input-gradient GEMM and one weight-gradient GEMM.
     Argument order: obs_n, h0, c0, dones, T, concat, n_mlp, op_weights (None, or the bfloat16 copies of
     W_1..W_L, w_ih, w_hh for the mixed-precision update), then the parameters
-    (W_1, b_1, ..., W_L, b_L, w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta, ln_eps, mu_w, mu_b, v_w, v_b)."""
+    (W_1, b_1, ..., W_L, b_L, w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta, ln_eps, mu_w, mu_b, v_w, v_b).
+    Which kernels run is decided ONCE, at the top of ``forward``, from the arguments and the module's switches: the
+    route ``ctx.route``.  Three of its entries can still be overturned further down -- ``ride`` by the moves the prepared
+    batch turns out to hold, ``ride`` / ``phases`` / ``bwd_phases`` by a kernel that answers VINE_ERR_UNSUPPORTED -- and
+    then record what actually ran.  It also carries what forward hands to backward outside ``saved_tensors``."""
 
     @staticmethod
     def forward(ctx, obs_n, h0, c0, dones, T, concat, n_mlp, op_weights, head_bias_external, norm, loss_pack, *params):
@@ -886,20 +847,74 @@ class _Trunk(torch.autograd.Function):
         U = mlp[-1][0].shape[0]
         H = w_hh.shape[1]
         B = n // T
+        A_ = mu_w.shape[0]
+        NH = A_ + v_w.shape[0]
         width = U + (F_in if concat else 0)
         # rows padded to 64 B so that every row (and the column block the ELU kernels address) is 16-B aligned
         wpad = (width + 15) // 16 * 16
+
+        # ---- the route
+        r = ctx.route = SimpleNamespace(T=T, concat=concat, n_mlp=n_mlp, U=U, A=A_, mixed=mixed, has_dones=dones is not None,
+                                        head_bias_external=head_bias_external, loss_pack=loss_pack)
         # layer 1 on the matrix cores: its operand is the observation block of the LSTM operand buffer plus the zero
         # pad columns behind it (K = 32); all three layers in one launch when the shapes are the default network's
-        l1_mfma = mixed and concat and wpad - U == 32 and linear_elu_mfma_ok(n, Wop[0].shape[0], 32)
-        mlp3 = (mixed and MLP3 and l1_mfma and n_mlp == 3 and n % 64 == 0 and U == 64
-                and tuple(W.shape[0] for W in Wop) == (256, 128, 64) and Wop[1].shape[1] == 256 and Wop[2].shape[1] == 128)
+        r.l1_mfma = mixed and concat and wpad - U == 32 and linear_elu_mfma_ok(n, Wop[0].shape[0], 32)
+        r.mlp3 = (mixed and r.l1_mfma and n_mlp == 3 and n % 64 == 0 and U == 64
+                  and tuple(W.shape[0] for W in Wop) == (256, 128, 64) and Wop[1].shape[1] == 256 and Wop[2].shape[1] == 128)
         # ``norm`` = (running mean, running var, eps): obs_n holds RAW observations and the one-launch MLP normalises
         # them itself; every other route normalises here first (vine_normalize_obs, same arithmetic)
+        r.raw = norm is not None and r.mlp3 and obs_n.dtype == torch.float32 and F_in <= 32
+        r.seq = mixed and lstm_seq_ok(B, H, T, wpad)      # persistent sequence kernels (one launch per direction)
+        r.no_proj = r.seq or (mixed and B % 64 == 0 and H == 256 and wpad % 32 == 0 and wpad <= 128)
+        # the one-launch MLP opens the forward pass: the operands derived from the parameters alone are first read by the
+        # launches behind it, so they ride in ITS launch (vine_mlp3_elu_mfma_prep) instead of one of their own; it then
+        # pads W1 itself on the way into LDS.  Any operand built from the minibatch keeps the own launch
+        r.ride = (MLP3_PREP and r.mlp3 and r.raw and Wop[0].is_contiguous() and Wop[0].shape[1] == F_in
+                  and F_in % 2 == 0)
+        c0_direct = c0 if (mixed and c0.dtype == torch.float32 and c0.is_contiguous()) else None
+        r.has_c0 = c0_direct is not None     # the caller's own c0 buffer is read again in backward (saved below)
+        # persistent kernels: the saved cell states (backward-only) and the gradient w.r.t. the hidden states travel
+        # as bfloat16; c_T, the state handed back, stays fp32 in its own buffer (``c_last``)
+        r.lp = r.seq and c0_direct is not None
+        h0_direct = h0 if (r.seq and h0.dtype == torch.float32 and h0.is_contiguous()) else None
+        lhl_rows = lib.vine_ln_heads_loss_rows()
+        r.heads_loss = _heads_loss_route(n, H, NH, loss_pack, head_bias_external, lhl_rows)
+        # the hidden states once, 16-bit: when their only readers are the fused LayerNorm + heads + loss kernel and
+        # the weight-gradient kernel (which both take them that way)
+        r.h_once = r.lp and h0_direct is not None and dones is not None and h_once_ok(T) and r.heads_loss
+        r.fuse_heads = H == 256 and 2 <= NH <= 5      # (without a loss pack) LayerNorm + both heads in one kernel
+        r.slots = [_grad_slot(p) if isinstance(p, torch.Tensor) else None for p in params]
+        r.pshapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in params]
+        r.all_slots = all(sl is not None for sl, p in zip(r.slots, params) if isinstance(p, torch.Tensor))
+        # the loss kernel's serial last step rides in the column-sum launch that ends this node's backward pass, when
+        # there is one; else it runs inside the loss kernel (ticket + last workgroup), as its stand-alone callers get it
+        r.defer = r.heads_loss and mixed and any(ctx.needs_input_grad) and r.all_slots
+        # transposed operand weights of the matrix-core backward kernels: entry 0 = the MLP block of w_ih (the LSTM's
+        # input gradient and the last ELU's backward are one kernel), entry i = layer i's
+        wt_ok = ([mixed and n % 64 == 0 and U % 64 == 0 and 4 * H in (512, 1024)]
+                 + [mixed and linear_bwd_mfma_ok(n, Wop[i].shape[1], Wop[i].shape[0]) for i in range(1, n_mlp)])
+        # the whole MLP backward in one launch (vine_mlp3_bwd_elu_mfma: layers 2, 3 transposed are [256, 128], [128, 64])
+        r.mlp3b = (mixed and n_mlp == 3 and all(wt_ok) and n % 64 == 0 and U == 64 and 4 * H == 1024
+                   and tuple(W.shape for W in Wop[1:]) == ((128, 256), (64, 128)) and Wop[0].shape[0] == 256)
+        # Round 4: LSTM forward -> LayerNorm + heads + loss -> LSTM backward -> MLP backward as four phases of ONE launch
+        # (vine_trunk_phases: same 128 rows per workgroup in all four).  The update's default configuration only; everything
+        # the backward pass of this node would compute up to the weight gradients is then done in forward.
+        r.phases = (TRUNK_PHASES and mixed and r.seq and r.h_once and r.lp and r.mlp3 and r.no_proj and T == 4 and wpad == 96
+                    and H == 256 and NH == 3 and dones is not None and c0_direct is not None and h0_direct is not None
+                    and r.heads_loss and any(ctx.needs_input_grad) and r.all_slots and all(wt_ok)
+                    and tuple(W.shape for W in Wop[1:]) == ((128, 256), (64, 128)) and B % 32 == 0 and n // 128 <= 1024)
+        # LSTM backward + MLP backward as two phases of one launch (vine_lstm_seq_backward_mlp3_mfma), when the gradient
+        # it starts from and the saved cell states are 16-bit (heads_loss and lp) and the MLP phase has 128-row workgroups
+        r.bwd_phases = (BWD_PHASES and r.mlp3b and r.seq and T == 4 and r.lp and r.heads_loss and n % 128 == 0
+                        and n >= 32768 and B % 32 == 0)
+        # filled in below by the launches that produce them (A2CAgent reads ``loss_fused``: did this node run the loss?)
+        r.loss_fin = r.loss_fused = r.phases_done = None
+
+        # ---- operands
         raw = None
         if norm is not None:
             obs_c = obs_n.contiguous()
-            if mlp3 and obs_c.dtype == torch.float32 and F_in <= 32:
+            if r.raw:
                 raw = obs_c
             else:
                 y = torch.empty_like(obs_c)
@@ -908,14 +923,11 @@ class _Trunk(torch.autograd.Function):
                 obs_n = y
         xfull = torch.empty((n, wpad), device=dev, dtype=op)
         xcat = xfull[:, :width]
-        A_ = mu_w.shape[0]
-        w_heads = torch.empty((A_ + v_w.shape[0], H), device=dev, dtype=torch.float32)
-        b_heads = torch.empty(A_ + v_w.shape[0], device=dev, dtype=torch.float32)
+        w_heads = torch.empty((NH, H), device=dev, dtype=torch.float32)
+        b_heads = torch.empty(NH, device=dev, dtype=torch.float32)
         bias = torch.empty(4 * H, device=dev, dtype=torch.float32)
-        seq = mixed and lstm_seq_ok(B, H, T, wpad)      # persistent sequence kernels (one launch per direction)
-        no_proj = seq or (mixed and B % 64 == 0 and H == 256 and wpad % 32 == 0 and wpad <= 128)
         wcat, wts, w_hh_t = None, [None] * n_mlp, None
-        wtile = w_hh_tiled = None
+        wtile = w_hh_tiled = w1p = c_last = lstm_buffers = side = None
         if mixed:
             # every operand derived from the parameters or the observations, in ONE launch: bf16 cast of the
             # observations (layer-1 operand and the LSTM operand's obs block), zero pad columns, [w_ih | 0 | w_hh],
@@ -927,43 +939,33 @@ class _Trunk(torch.autograd.Function):
                     prep.add(CopyBatch.CAST_BF16, xfull[:, U:width], obs_c)
                 if wpad > width:
                     prep.add(CopyBatch.ZERO, xfull[:, width:])
-            # the one-launch MLP opens the forward pass: the operands below are derived from the parameters alone and first
-            # read by the launches behind it, so they ride in ITS launch (vine_mlp3_elu_mfma_prep) instead of one of their
-            # own; it then pads W1 itself on the way into LDS.  Any operand built from the minibatch keeps the own launch
-            ride = (MLP3_PREP and mlp3 and raw is not None and Wop[0].is_contiguous() and Wop[0].shape[1] == F_in
-                    and F_in % 2 == 0)
-            if l1_mfma and ride:
-                x0 = xfull[:, U:width]
-                w1p = None
-            elif l1_mfma:
+            if r.l1_mfma:
                 x0 = xfull[:, U:width]                        # strided view; also the operand of layer 1's weight gradient
-                w1p = torch.empty((Wop[0].shape[0], 32), device=dev, dtype=op)
-                prep.add(CopyBatch.COPY, w1p[:, :F_in], Wop[0])
-                prep.add(CopyBatch.ZERO, w1p[:, F_in:])
+                if not r.ride:
+                    w1p = _padded_w1(prep, Wop[0], F_in)
             else:
                 x0 = torch.empty((n, F_in), device=dev, dtype=op)
                 prep.add(CopyBatch.CAST_BF16, x0, obs_c)
-            if seq:
+            if r.seq:
                 # persistent sequence kernels: fragment-ordered weight copies instead of [w_ih | 0 | w_hh] / w_hh^T
                 wtile = torch.empty(4 * H * (wpad + H), device=dev, dtype=op)
                 w_hh_tiled = torch.empty(4 * H * H, device=dev, dtype=op)
                 prep.add_lstm_tiles(w_ih_op, w_hh_op, wpad, wtile, w_hh_tiled)
-            elif no_proj:
+            elif r.no_proj:
                 wcat = torch.empty((4 * H, wpad + H), device=dev, dtype=op)
                 prep.add(CopyBatch.COPY, wcat[:, :width], w_ih_op)
                 if wpad > width:
                     prep.add(CopyBatch.ZERO, wcat[:, width:wpad])
                 prep.add(CopyBatch.COPY, wcat[:, wpad:], w_hh_op)
             for i in range(1, n_mlp):
-                if linear_bwd_mfma_ok(n, Wop[i].shape[1], Wop[i].shape[0]):
+                if wt_ok[i]:
                     wts[i] = torch.empty((Wop[i].shape[1], Wop[i].shape[0]), device=dev, dtype=op)
                     prep.add(CopyBatch.TRANSPOSE, wts[i], Wop[i])
-            # transposed MLP block of w_ih: the LSTM's input gradient and the last ELU's backward are one kernel
-            if n % 64 == 0 and U % 64 == 0 and 4 * H in (512, 1024):
+            if wt_ok[0]:
                 wts[0] = torch.empty((U, 4 * H), device=dev, dtype=op)
                 prep.add(CopyBatch.TRANSPOSE, wts[0], w_ih_op[:, :U])
             # transposed recurrent weight: the backward step forms dG_{t+1} w_hh inside its own kernel
-            if not seq and lstm_bwd_mfma_ok(B, H):
+            if not r.seq and lstm_bwd_mfma_ok(B, H):
                 w_hh_t = torch.empty((H, 4 * H), device=dev, dtype=op)
                 prep.add(CopyBatch.TRANSPOSE, w_hh_t, w_hh_op)
             prep.add(CopyBatch.COPY, w_heads[:A_], mu_w)
@@ -971,42 +973,30 @@ class _Trunk(torch.autograd.Function):
             prep.add(CopyBatch.COPY, b_heads[:A_], mu_b)
             prep.add(CopyBatch.COPY, b_heads[A_:], v_b)
             prep.add(CopyBatch.ADD, bias, b_ih, b_hh)
-            c0_direct = c0 if (c0.dtype == torch.float32 and c0.is_contiguous()) else None
-            # persistent kernels: the saved cell states (backward-only) and the gradient w.r.t. the hidden states travel
-            # as bfloat16 (LSTM_LP); c_T, the state handed back, stays fp32 in its own buffer
-            lp = seq and LSTM_LP and c0_direct is not None
-            c_last = torch.empty((B, H), device=dev, dtype=torch.float32) if lp else None
-            h0_direct = h0 if (seq and h0.dtype == torch.float32 and h0.is_contiguous()) else None
-            # the hidden states once, 16-bit: when their only readers are the fused LayerNorm + heads + loss kernel and
-            # the weight-gradient kernel (which both take them that way)
-            h_once = (lp and h0_direct is not None and dones is not None and h_once_ok(T)
-                      and _heads_loss_route(n, H, A_ + v_w.shape[0], loss_pack, head_bias_external, lib))
+            c_last = torch.empty((B, H), device=dev, dtype=torch.float32) if r.lp else None
             n_param_jobs = len(prep.jobs)
             lstm_buffers = _lstm_state_buffers(xfull, w_hh_op, h0, c0, dones, T, True, prep=prep,
-                                               copy_c0=c0_direct is None, c_dtype=lp_dtype() if lp else torch.float32,
-                                               mask_h0=h0_direct is None, h_once=h_once)
-            side = prep.packed() if (ride and len(prep.jobs) == n_param_jobs) else None
-            if ride and side is None:      # (minibatch-derived moves, or too many for one launch: the own launch after all)
-                w1p = torch.empty((Wop[0].shape[0], 32), device=dev, dtype=op)
-                prep.add(CopyBatch.COPY, w1p[:, :F_in], Wop[0])
-                prep.add(CopyBatch.ZERO, w1p[:, F_in:])
-            if side is None:
+                                               copy_c0=c0_direct is None, c_dtype=lp_dtype() if r.lp else torch.float32,
+                                               mask_h0=h0_direct is None, h_once=r.h_once)
+            side = prep.packed() if (r.ride and len(prep.jobs) == n_param_jobs) else None
+            if r.ride and side is None:    # (minibatch-derived moves, or too many for one launch: the own launch after all)
+                r.ride = False
+                w1p = _padded_w1(prep, Wop[0], F_in)
+            if not r.ride:
                 prep.flush(obs_n)
         else:
-            lstm_buffers = None
-            c0_direct = None
-            side = None
-            lp, c_last, h0_direct, h_once = False, None, None, False
             x0 = obs_n.contiguous()
             torch.cat([mu_w, v_w], 0, out=w_heads)
             torch.cat([mu_b, v_b], 0, out=b_heads)
             torch.add(b_ih, b_hh, out=bias)
+
+        # ---- MLP
         acts = []
         x = x0
-        if mlp3:
+        if r.mlp3:
             # the whole MLP in one launch, activations carried in registers (vine_mlp3_elu_mfma)
             acts = [torch.empty((n, 256), device=dev, dtype=op), torch.empty((n, 128), device=dev, dtype=op)]
-            if side is not None:
+            if r.ride:
                 rc = lib.vine_mlp3_elu_mfma_prep(n, xfull.data_ptr() + 2 * U, xfull.stride(0), raw.data_ptr(), F_in,
                                                  norm[0].data_ptr(), norm[1].data_ptr(), float(norm[2]), 5.0,
                                                  Wop[0].data_ptr(), F_in, mlp[0][1].data_ptr(), 256, Wop[1].data_ptr(),
@@ -1014,16 +1004,14 @@ class _Trunk(torch.autograd.Function):
                                                  Wop[2].stride(0), mlp[2][1].data_ptr(), 64, 1.0, acts[0].data_ptr(),
                                                  acts[1].data_ptr(), xfull.data_ptr(), xfull.stride(0), *side, st)
                 if rc == -2:       # VINE_ERR_UNSUPPORTED (a move the side job does not cover, or too small a launch to carry
-                    side = None    # them): nothing has run -- the moves get their own launch after all
-                    w1p = torch.empty((Wop[0].shape[0], 32), device=dev, dtype=op)
-                    prep.add(CopyBatch.COPY, w1p[:, :F_in], Wop[0])
-                    prep.add(CopyBatch.ZERO, w1p[:, F_in:])
+                    r.ride = False      # them): nothing has run -- the moves get their own launch after all
+                    w1p = _padded_w1(prep, Wop[0], F_in)
                     prep.flush(obs_n)
                 else:
                     _check(rc, "vine_mlp3_elu_mfma_prep")
                     prep.clear()
                     RIDES[0] += 1
-            if side is None:
+            if not r.ride:
                 _check(lib.vine_mlp3_elu_mfma(n, xfull.data_ptr() + 2 * U, xfull.stride(0),
                                               raw.data_ptr() if raw is not None else None, F_in,
                                               norm[0].data_ptr() if raw is not None else None,
@@ -1033,12 +1021,12 @@ class _Trunk(torch.autograd.Function):
                                               mlp[1][1].data_ptr(), 128, Wop[2].data_ptr(), Wop[2].stride(0),
                                               mlp[2][1].data_ptr(), 64, 1.0, acts[0].data_ptr(), acts[1].data_ptr(),
                                               xfull.data_ptr(), xfull.stride(0), st), "vine_mlp3_elu_mfma")
-        for i, (W, b) in enumerate(mlp if not mlp3 else ()):
+        for i, (W, b) in enumerate(mlp if not r.mlp3 else ()):
             last = i == n_mlp - 1
             if mixed:
                 C_, K_ = Wop[i].shape
                 a = xcat if last else torch.empty((n, C_), device=dev, dtype=op)
-                if i == 0 and l1_mfma:
+                if i == 0 and r.l1_mfma:
                     _check(lib.vine_linear_elu_mfma(n, C_, 32, xfull.data_ptr() + 2 * U, xfull.stride(0), w1p.data_ptr(), 32,
                                                     b.data_ptr(), 1.0, a.data_ptr(), a.stride(0), st),
                            "vine_linear_elu_mfma")
@@ -1061,37 +1049,17 @@ class _Trunk(torch.autograd.Function):
                 x = a
         if concat and not mixed:
             xcat[:, U:].copy_(obs_n)
-        NH_ = mu_w.shape[0] + v_w.shape[0]
-        slots_early = [_grad_slot(p) if isinstance(p, torch.Tensor) else None for p in params]
-        # Round 4: LSTM forward -> LayerNorm + heads + loss -> LSTM backward -> MLP backward as four phases of ONE launch
-        # (vine_trunk_phases: same 128 rows per workgroup in all four).  The update's default configuration only; everything
-        # the backward pass of this node would compute up to the weight gradients is then done HERE, in forward.
-        phases = (TRUNK_PHASES and mixed and seq and h_once and lp and mlp3 and no_proj and T == 4 and wpad == 96 and H == 256
-                  and NH_ == 3 and dones is not None and c0_direct is not None and h0_direct is not None
-                  and _heads_loss_route(n, H, NH_, loss_pack, head_bias_external, lib) and LOSS_DEFER
-                  and lib.vine_ln_heads_loss_rows() == 128 and any(ctx.needs_input_grad)
-                  and all(sl is not None for sl, p in zip(slots_early, params) if isinstance(p, torch.Tensor))
-                  and all(w is not None for w in wts) and w_hh_tiled is not None
-                  and tuple(wts[i].shape for i in (1, 2)) == ((256, 128), (128, 64)) and B % 32 == 0 and n // 128 <= 1024)
-        ctx.phases_done = None
-        if _os.environ.get("VINE_DEBUG_PHASES") and not phases:
-            print("trunk phases off:", dict(mixed=mixed, seq=seq, h_once=h_once, lp=lp, mlp3=mlp3, no_proj=no_proj, T=T, wpad=wpad,
-                  H=H, NH=NH_, dones=dones is not None, c0=c0_direct is not None, h0=h0_direct is not None,
-                  route=_heads_loss_route(n, H, NH_, loss_pack, head_bias_external, lib), rows=lib.vine_ln_heads_loss_rows(),
-                  grad=any(ctx.needs_input_grad), slots=[sl is not None for sl in slots_early], wts=[w is not None for w in wts],
-                  tiled=w_hh_tiled is not None, B=B, n=n), flush=True)
-        if phases:
-            from ..abi import LossFinalize, TrunkArgs
+
+        # ---- LSTM, LayerNorm, heads (and, with a loss pack, the loss and the first half of the backward pass)
+        if r.phases:
+            from ..abi import TrunkArgs
             out, c_all, gates, hp = lstm_buffers
             lpk = loss_pack
-            heads = torch.empty((n, NH_), device=dev, dtype=torch.float32)
+            heads = torch.empty((n, NH), device=dev, dtype=torch.float32)
             d_out = torch.empty((n, H), device=dev, dtype=lp_dtype())
-            ln_part = torch.empty((n // 128, (2 + NH_) * H), device=dev, dtype=torch.float32)
-            dG = torch.empty((n, 4 * H), device=dev, dtype=lp_dtype())
-            bias_partial = torch.empty((B // 32, 4 * H), device=dev, dtype=torch.float32)
-            gzs = [torch.empty((n, c), device=dev, dtype=lp_dtype()) for c in (256, 128, 64)]       # layers 1, 2, 3
-            parts = [torch.empty((n // 128, c), device=dev, dtype=torch.float32) for c in (256, 128, 64)]
-            amp_ = _amp_ptrs(lpk.get("amp"))
+            ln_part = torch.empty((n // 128, (2 + NH) * H), device=dev, dtype=torch.float32)
+            dG, bias_partial = _lstm_grad_buffers(n, B, H, dev)
+            gzs, parts = _mlp3_grad_buffers(n, 128, dev)
             ta = TrunkArgs()
             ta.B, ta.T = B, T
             ta.x, ta.ldx, ta.w_tiled, ta.bias = xfull.data_ptr(), xfull.stride(0), wtile.data_ptr(), bias.data_ptr()
@@ -1107,38 +1075,28 @@ class _Trunk(torch.autograd.Function):
             ta.stats, ta.grad_logstd = lpk["stats"].data_ptr(), lpk["grad_logstd"].data_ptr()
             ta.grad_mu_bias, ta.grad_value_bias = lpk["head_bias_grads"][0].data_ptr(), lpk["head_bias_grads"][1].data_ptr()
             ta.kl_out, ta.logstd_grad_accum, ta.mu_store, ta.sigma_store = lpk["extra"]
-            ta.loss_scale, ta.found_inf = amp_
+            ta.loss_scale, ta.found_inf = _amp_ptrs(lpk.get("amp"))
             ta.w_hh_tiled, ta.dgates, ta.bias_partial = w_hh_tiled.data_ptr(), dG.data_ptr(), bias_partial.data_ptr()
             ta.wt0, ta.ldw0, ta.wt1, ta.ldw1 = wts[0].data_ptr(), wts[0].stride(0), wts[2].data_ptr(), wts[2].stride(0)
             ta.wt2, ta.ldw2 = wts[1].data_ptr(), wts[1].stride(0)
             ta.a3, ta.a3_stride, ta.a2, ta.a1 = xcat.data_ptr(), xcat.stride(0), acts[1].data_ptr(), acts[0].data_ptr()
             ta.gz3, ta.gz2, ta.gz1 = gzs[2].data_ptr(), gzs[1].data_ptr(), gzs[0].data_ptr()
             ta.part3, ta.part2, ta.part1 = parts[2].data_ptr(), parts[1].data_ptr(), parts[0].data_ptr()
-            import ctypes as C_
-            rc = lib.vine_trunk_phases(C_.byref(ta), st)
-            if rc == -2:
-                phases = False
-                if _os.environ.get("VINE_DEBUG_PHASES"):
-                    print("vine_trunk_phases: unsupported shapes", B, T, xfull.stride(0), flush=True)
+            rc = lib.vine_trunk_phases(C.byref(ta), st)
+            if rc == -2:       # VINE_ERR_UNSUPPORTED: nothing has run -- the separate launches below
+                r.phases = False
             else:
                 _check(rc, "vine_trunk_phases")
-                ctx.loss_fin = LossFinalize(lpk["scratch"].data_ptr(), n // 128, NH_ - 1, n, lpk["logstd"].data_ptr(),
-                                            lpk["scal"][2], lpk["scal"][3], lpk["scal"][4], lpk["stats"].data_ptr(),
-                                            lpk["grad_logstd"].data_ptr(), lpk["head_bias_grads"][0].data_ptr(),
-                                            lpk["head_bias_grads"][1].data_ptr(), lpk["extra"][0], lpk["extra"][1], amp_[0])
-                ctx.loss_fused = (d_out, ln_part)
-                ctx.loss_pack = loss_pack
-                ctx.h_once = h_once
-                ctx.phases_done = (dG, bias_partial, gzs, parts)
+                r.loss_fin = _loss_finalize(lpk, n // 128, NH, n)
+                r.loss_fused = (d_out, ln_part)
+                r.phases_done = (dG, bias_partial, gzs, parts)
                 PHASE_LAUNCHES[0] += 1
-        if phases:
-            pass
-        elif no_proj:
+        if not r.phases and r.no_proj:
             # no input projection: the step kernel multiplies [x_t | h_{t-1}] by [w_ih | 0 | w_hh] in one product
             out, c_all, gates, hp = _lstm_forward_steps(lib, xfull, None, w_hh_op, bias, h0, c0, dones, T, True, wcat=wcat,
                                                         buffers=lstm_buffers, c0_direct=c0_direct, wtile=wtile,
-                                                        c_last=c_last, h0_direct=h0_direct if mixed else None)
-        else:
+                                                        c_last=c_last, h0_direct=h0_direct)
+        elif not r.phases:
             ig = _mm(xcat, w_ih_op.t())
             out, c_all, gates, hp = _lstm_forward_steps(lib, xcat, ig, w_hh_op, bias, h0, c0, dones, T, True,
                                                         buffers=lstm_buffers, c0_direct=c0_direct)
@@ -1147,48 +1105,30 @@ class _Trunk(torch.autograd.Function):
         # the probability ratio directly)
         mean = torch.empty(n, device=dev, dtype=torch.float32)
         rstd = torch.empty(n, device=dev, dtype=torch.float32)
-        NH = w_heads.shape[0]
-        fuse_heads = H == 256 and 2 <= NH <= 5
-        if not phases:
-            ctx.loss_fused = None
-        ctx.loss_pack = loss_pack       # (its "amp" entry: loss scale / overflow flag of the device-side GradScaler)
-        lhl_rows = lib.vine_ln_heads_loss_rows()
-        ctx.h_once = h_once
-        if phases:
+        if r.phases:
             y = out.new_empty(0)        # (LayerNorm + heads + loss ran as the second phase of vine_trunk_phases)
-        elif _heads_loss_route(n, H, NH, loss_pack, head_bias_external, lib):
+        elif r.heads_loss:
             # LayerNorm + heads + PPO loss + their backward in ONE launch: the gradient w.r.t. the LSTM output is
             # known before this node's backward runs (which ignores the gradient it is handed for `heads`)
             y = out.new_empty(0)
             heads = torch.empty((n, NH), device=dev, dtype=torch.float32)
-            d_out = torch.empty((n, H), device=dev, dtype=lp_dtype() if lp else torch.float32)
+            d_out = torch.empty((n, H), device=dev, dtype=lp_dtype() if r.lp else torch.float32)
             ln_part = torch.empty((n // lhl_rows, (2 + NH) * H), device=dev, dtype=torch.float32)
             lpk = loss_pack
-            # the kernel's serial last step (fold of the per-workgroup loss rows -> statistics, KL slot, log-sigma and
-            # head-bias gradients) rides in the column-sum launch that ends this node's backward pass, when there is one
-            slots_now = [_grad_slot(p) if isinstance(p, torch.Tensor) else None for p in params]
-            defer = (LOSS_DEFER and mixed and any(ctx.needs_input_grad)
-                     and all(sl is not None for sl, p in zip(slots_now, params) if isinstance(p, torch.Tensor)))
-            ctx.loss_fin = None
-            if defer:
-                from ..abi import LossFinalize
-                amp_ = _amp_ptrs(lpk.get("amp"))
-                ctx.loss_fin = LossFinalize(lpk["scratch"].data_ptr(), n // lhl_rows, NH - 1, n, lpk["logstd"].data_ptr(),
-                                            lpk["scal"][2], lpk["scal"][3], lpk["scal"][4], lpk["stats"].data_ptr(),
-                                            lpk["grad_logstd"].data_ptr(), lpk["head_bias_grads"][0].data_ptr(),
-                                            lpk["head_bias_grads"][1].data_ptr(), lpk["extra"][0], lpk["extra"][1], amp_[0])
+            if r.defer:
+                r.loss_fin = _loss_finalize(lpk, n // lhl_rows, NH, n)
             _check(lib.vine_ln_heads_loss(n, H, NH, out.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), float(ln_eps),
                                           w_heads.data_ptr(), b_heads.data_ptr(), lpk["logstd"].data_ptr(),
                                           *[t.data_ptr() for t in lpk["args"]], *lpk["scal"], heads.data_ptr(),
-                                          d_out.data_ptr(), int(lp) | ((2 | (T << 8)) if h_once else 0) | (4 if defer else 0),
-                                          ln_part.data_ptr(),
-                                          lpk["stats"].data_ptr(),
+                                          d_out.data_ptr(),
+                                          int(r.lp) | ((2 | (T << 8)) if r.h_once else 0) | (4 if r.defer else 0),
+                                          ln_part.data_ptr(), lpk["stats"].data_ptr(),
                                           lpk["grad_logstd"].data_ptr(), lpk["head_bias_grads"][0].data_ptr(),
                                           lpk["head_bias_grads"][1].data_ptr(), lpk["scratch"].data_ptr(), *lpk["extra"],
                                           *_amp_ptrs(lpk.get("amp")), st),
                    "vine_ln_heads_loss")
-            ctx.loss_fused = (d_out, ln_part)
-        elif fuse_heads:      # LayerNorm + both heads in one kernel; LN(x) is never written
+            r.loss_fused = (d_out, ln_part)
+        elif r.fuse_heads:      # LayerNorm + both heads in one kernel; LN(x) is never written
             y = out.new_empty(0)
             heads = torch.empty((n, NH), device=dev, dtype=torch.float32)
             _check(lib.vine_layernorm_heads_forward(n, H, NH, out.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(),
@@ -1201,21 +1141,13 @@ class _Trunk(torch.autograd.Function):
                                               y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), st),
                    "vine_layernorm_forward")
             heads = torch.addmm(b_heads, y, w_heads.t())          # [n, A + 1] = [mu | value]
-        ctx.meta = (T, concat, n_mlp, U, float(ln_eps), mu_w.shape[0], dones is not None, mixed, head_bias_external)
-        ctx.slots = [_grad_slot(p) if isinstance(p, torch.Tensor) else None for p in params]
-        ctx.pshapes = [tuple(p.shape) if isinstance(p, torch.Tensor) else None for p in params]
-        ctx.fuse_heads = fuse_heads
-        ctx.wts = wts
-        ctx.w_hh_t = w_hh_t
-        ctx.w_hh_tiled = w_hh_tiled
-        ctx.has_c0 = c0_direct is not None   # the caller's own c0 buffer is read again in backward (saved below)
-        ctx.has_clast = c_last is not None
+        r.wts, r.w_hh_t, r.w_hh_tiled = wts, w_hh_t, w_hh_tiled
         ctx.save_for_backward(x0, xcat, hp, out, c_all, gates, y, mean, rstd, w_heads, w_ih_op, w_hh_op, ln_g, ln_b,
                               dones if dones is not None else obs_n.new_empty(0), *acts, *Wop,
                               *([c_last] if c_last is not None else []),
                               *([c0_direct] if c0_direct is not None else []))
         # final LSTM state as views (no copies): the update discards it, other callers may clone
-        hT = out.view(B, T + 1, H)[:, T] if h_once else out.view(B, T, H)[:, T - 1]      # (h_once: 16-bit)
+        hT = out.view(B, T + 1, H)[:, T] if r.h_once else out.view(B, T, H)[:, T - 1]      # (h_once: 16-bit)
         cT = c_last if c_last is not None else c_all[T]
         ctx.mark_non_differentiable(hT, cT)
         ctx.set_materialize_grads(False)       # no zero-filled [B, H] gradients for the two state outputs
@@ -1225,14 +1157,17 @@ class _Trunk(torch.autograd.Function):
     def backward(ctx, g_heads, _gh, _gc):
         from ..abi import PPO_PARTIAL_BLOCKS
         lib = _lib()
-        T, concat, n_mlp, U, ln_eps, A, has_dones, mixed, head_bias_external = ctx.meta
+        r = ctx.route
+        T, n_mlp, U, A, mixed, wts = r.T, r.n_mlp, r.U, r.A, r.mixed, r.wts
         saved = ctx.saved_tensors
         x0, xcat, hp, out, c_all, gates, y, mean, rstd, w_heads, w_ih, w_hh, ln_g, ln_b, dones = saved[:15]
         acts = list(saved[15:15 + n_mlp - 1])
         weights = list(saved[15 + n_mlp - 1:15 + 2 * n_mlp - 1])
-        c0_direct = saved[-1] if ctx.has_c0 else None
-        c_last = saved[-2 if ctx.has_c0 else -1] if ctx.has_clast else None
-        slots = ctx.slots
+        c0_direct = saved[-1] if r.has_c0 else None
+        c_last = saved[-2 if r.has_c0 else -1] if r.lp else None
+        if not r.has_dones:
+            dones = None
+        slots = r.slots
         n, H = xcat.shape[0], out.shape[1]      # (with h_once ``out`` has T + 1 rows per sequence)
         dev = out.device
         st = _stream(out)
@@ -1243,38 +1178,34 @@ class _Trunk(torch.autograd.Function):
             if slots[idx] is not None:
                 write(slots[idx])
             else:
-                grads[idx] = torch.empty(ctx.pshapes[idx], device=dev, dtype=torch.float32)
+                grads[idx] = torch.empty(r.pshapes[idx], device=dev, dtype=torch.float32)
                 write(grads[idx])
 
         base = 2 * n_mlp
         # with the optimiser's gradient slots in place all column sums are deferred into one launch at the end
-        amp = ctx.loss_pack.get("amp") if ctx.loss_pack is not None else None
-        batch = (ColumnSumBatch(found_inf=amp[1] if (mixed and amp is not None) else None)
-                 if all(sl is not None for k, sl in enumerate(slots) if ctx.pshapes[k] is not None) else None)
-        if getattr(ctx, "loss_fin", None) is not None:
+        amp = r.loss_pack.get("amp") if r.loss_pack is not None else None
+        batch = ColumnSumBatch(found_inf=amp[1] if (mixed and amp is not None) else None) if r.all_slots else None
+        if r.loss_fin is not None:
             assert batch is not None, "the loss finalize was deferred to a column-sum launch that does not exist"
-            batch.fin = ctx.loss_fin
-            ctx.loss_fin = None
+            batch.fin, r.loss_fin = r.loss_fin, None
         if amp is not None:
             # do ALL parameter gradients of this backward pass end in the overflow-checked column-sum launch?  (else the
             # optimiser checks the gradient block itself before it steps: FlatAdam.step)
-            ctx.loss_pack["amp_covered"] = bool(mixed and batch is not None)
+            r.loss_pack["amp_covered"] = bool(mixed and batch is not None)
         NH = w_heads.shape[0]
-        if ctx.loss_fused is not None:
-            d_out, part = ctx.loss_fused             # computed in forward by the fused LayerNorm + heads + loss kernel
-            ctx.loss_fused = None
+        # ---- heads + LayerNorm
+        if r.loss_fused is not None:      # computed in forward by the fused LayerNorm + heads + loss kernel
+            (d_out, part), r.loss_fused = r.loss_fused, None
         else:
             g_heads = g_heads.contiguous()
             d_out = torch.empty_like(out)
             part = None
-        if part is not None:
-            pass
-        elif not head_bias_external:      # else: the loss kernel has already added them into the two bias gradients
-            gb = g_heads.sum(0)
-            deliver(base + 8, lambda o: o.copy_(gb[:A]))
-            deliver(base + 10, lambda o: o.copy_(gb[A:]))
-        if ctx.fuse_heads:
-            # ---- heads + LayerNorm in one kernel: dy = g W is never stored; partial sums of {d gamma | d beta | d W}
+            if not r.head_bias_external:      # else: the loss kernel has already added them into the two bias gradients
+                gb = g_heads.sum(0)
+                deliver(base + 8, lambda o: o.copy_(gb[:A]))
+                deliver(base + 10, lambda o: o.copy_(gb[A:]))
+        if r.fuse_heads:
+            # heads + LayerNorm in one kernel: dy = g W is never stored; partial sums of {d gamma | d beta | d W}
             if part is None:
                 part = torch.empty((PPO_PARTIAL_BLOCKS, (2 + NH) * H), device=dev, dtype=torch.float32)
                 _check(lib.vine_layernorm_heads_backward(n, H, NH, g_heads.data_ptr(), out.data_ptr(), mean.data_ptr(),
@@ -1288,12 +1219,12 @@ class _Trunk(torch.autograd.Function):
                 deliver(base + 7, lambda o: column_sums(w_part[:, :A * H], o))
                 deliver(base + 9, lambda o: column_sums(w_part[:, A * H:], o))
         else:
-            # ---- heads: one weight-gradient GEMM, one input-gradient GEMM
+            # heads: one weight-gradient GEMM, one input-gradient GEMM
             s_heads, wpart = _splitk_parts(g_heads, y)                 # [s, A+1, H] slices of the weight gradient
             deliver(base + 7, lambda o: column_sums(wpart[:, :A], o) if s_heads > 1 else o.copy_(wpart[:A]))
             deliver(base + 9, lambda o: column_sums(wpart[:, A:], o) if s_heads > 1 else o.copy_(wpart[A:]))
             dy = g_heads.mm(w_heads)
-            # ---- LayerNorm
+            # LayerNorm
             ln_part = torch.empty((PPO_PARTIAL_BLOCKS, 2 * H), device=dev, dtype=torch.float32)
             _check(lib.vine_layernorm_backward(n, H, dy.data_ptr(), out.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                                ln_g.data_ptr(), d_out.data_ptr(), ln_part.data_ptr(), st),
@@ -1305,48 +1236,32 @@ class _Trunk(torch.autograd.Function):
             deliver(base + 4, lambda o: column_sums(ln_part[:, :H], o))
             deliver(base + 5, lambda o: column_sums(ln_part[:, H:], o))
         # ---- LSTM (+ the MLP backward chain as a second phase of the same launch, round 4: vine_lstm_seq_backward_mlp3_mfma)
-        mlp3b = (mixed and MLP3 and n_mlp == 3 and all(w is not None for w in ctx.wts) and n % 64 == 0 and U == 64
-                 and 4 * H == 1024 and tuple(ctx.wts[i].shape for i in (1, 2)) == ((256, 128), (128, 64))
-                 and acts[0].shape[1] == 256 and acts[1].shape[1] == 128)
-        gzs = parts = None
-        B_ = n // T
-        if getattr(ctx, "phases_done", None) is not None:      # vine_trunk_phases ran the LSTM / MLP backward in forward
-            dG, bias_partial, gzs, parts = ctx.phases_done
-            ctx.phases_done = None
-        elif (BWD_PHASES and mlp3b and ctx.w_hh_tiled is not None and T == 4 and c_last is not None and c0_direct is not None
-                and d_out.dtype == lp_dtype() and c_all.dtype == lp_dtype() and n % 128 == 0 and n >= 32768 and B_ % 32 == 0
-                and d_out.is_contiguous() and gates.is_contiguous() and c_all.is_contiguous()):
-            dG = torch.empty((n, 4 * H), device=dev, dtype=lp_dtype())
-            bias_partial = torch.empty((B_ // 32, 4 * H), device=dev, dtype=torch.float32)
-            gzs = [torch.empty((n, c), device=dev, dtype=lp_dtype()) for c in (256, 128, 64)]       # layers 1, 2, 3
-            parts = [torch.empty((n // 128, c), device=dev, dtype=torch.float32) for c in (256, 128, 64)]
+        if r.phases:      # vine_trunk_phases ran the LSTM / MLP backward in forward
+            (dG, bias_partial, gzs, parts), r.phases_done = r.phases_done, None
+        elif r.bwd_phases:
+            dG, bias_partial = _lstm_grad_buffers(n, n // T, H, dev)
+            gzs, parts = _mlp3_grad_buffers(n, 128, dev)
             rc = lib.vine_lstm_seq_backward_mlp3_mfma(
-                B_, T, H, d_out.data_ptr(), ctx.w_hh_tiled.data_ptr(), gates.data_ptr(), c_all.data_ptr(),
-                c0_direct.data_ptr(), dones.data_ptr() if has_dones else None, dG.data_ptr(), bias_partial.data_ptr(),
-                c_last.data_ptr(), ctx.wts[0].data_ptr(), ctx.wts[0].stride(0), ctx.wts[2].data_ptr(), ctx.wts[2].stride(0),
-                ctx.wts[1].data_ptr(), ctx.wts[1].stride(0), xcat.data_ptr(), xcat.stride(0), acts[1].data_ptr(),
+                n // T, T, H, d_out.data_ptr(), r.w_hh_tiled.data_ptr(), gates.data_ptr(), c_all.data_ptr(),
+                c0_direct.data_ptr(), dones.data_ptr() if dones is not None else None, dG.data_ptr(), bias_partial.data_ptr(),
+                c_last.data_ptr(), wts[0].data_ptr(), wts[0].stride(0), wts[2].data_ptr(), wts[2].stride(0),
+                wts[1].data_ptr(), wts[1].stride(0), xcat.data_ptr(), xcat.stride(0), acts[1].data_ptr(),
                 acts[0].data_ptr(), 1.0, gzs[2].data_ptr(), gzs[1].data_ptr(), gzs[0].data_ptr(), parts[2].data_ptr(),
                 parts[1].data_ptr(), parts[0].data_ptr(), st)
-            if rc == -2:
-                gzs = parts = None
+            if rc == -2:      # VINE_ERR_UNSUPPORTED: nothing has run -- two launches after all
+                r.bwd_phases = False
             else:
                 _check(rc, "vine_lstm_seq_backward_mlp3_mfma")
-        if gzs is None:
-            dG, bias_partial = _lstm_backward_steps(lib, d_out, w_hh, c_all, gates, dones if has_dones else None, T,
-                                                    w_hh_t=ctx.w_hh_t, c0_direct=c0_direct, w_hh_tiled=ctx.w_hh_tiled,
-                                                    c_last=c_last)
+        mlp_done = r.phases or r.bwd_phases      # the MLP backward chain has run with the LSTM backward
+        if not mlp_done:
+            dG, bias_partial = _lstm_backward_steps(lib, d_out, w_hh, c_all, gates, dones, T, w_hh_t=r.w_hh_t,
+                                                    c0_direct=c0_direct, w_hh_tiled=r.w_hh_tiled, c_last=c_last)
         fused2 = False
-        ctx.wgrad_fork = None
-        if WGRAD_SIDE and gzs is not None:
-            cur = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-            side.wait_stream(cur)            # (fork: everything the MLP weight gradients read is complete on `cur`)
-            ctx.wgrad_fork = (side, cur)
-        if ctx.h_once and mixed and slots[base + 0] is not None and slots[base + 1] is not None:
+        if r.h_once and mixed and slots[base + 0] is not None and slots[base + 1] is not None:
             # ``out`` is the one 16-bit copy of the hidden states (slot 0 = h0): the kernel shifts and masks
             fused2 = weight_grad_cat(dG, xcat, out, slots[base + 0], slots[base + 1], batch=batch, seq=(dones, T))
-        if ctx.h_once and not fused2:
-            hp = masked_previous_hidden(out, dones if has_dones else None, T)
+        if r.h_once and not fused2:
+            hp = masked_previous_hidden(out, dones, T)
         if not fused2 and mixed and slots[base + 0] is not None and slots[base + 1] is not None:
             # dW_ih and dW_hh from one pass over dG (the largest tensor of the backward pass)
             fused2 = weight_grad_cat(dG, xcat, hp.view(n, H), slots[base + 0], slots[base + 1], batch=batch)
@@ -1358,87 +1273,73 @@ class _Trunk(torch.autograd.Function):
         else:
             deliver(base + 2, lambda o: _sum_rows(bias_partial, dG.float(), out=o))
             deliver(base + 3, lambda o: o.copy_(slots[base + 2] if slots[base + 2] is not None else grads[base + 2]))
-        gz = part = g = None
+        # ---- MLP.  gz = gradient w.r.t. layer i's pre-activation, part = the bias partial sums its kernel emits
         wgroup = WeightGradGroup()
-        if mlp3b:
+
+        def deliver_layer(i, gz, part):
+            x_in = acts[i - 1] if i > 0 else x0
+            deliver(2 * i, lambda o: wgroup.add(gz, x_in, o, batch) or weight_grad(gz, x_in, out=o, batch=batch))
+            deliver(2 * i + 1, lambda o: column_sums(part, o, batch=batch))
+
+        if r.mlp3b:
             # the whole MLP backward in one launch (vine_mlp3_bwd_elu_mfma): LSTM input gradient (MLP columns) x ELU' ->
             # gz3 -> gz2 -> gz1 carried in registers, bias partial sums per workgroup
-            if gzs is None:      # (else: it ran as the second phase of the LSTM backward launch above)
-                rows_wg = 128 if (n % 128 == 0 and n >= 32768) else 64
-                gzs = [torch.empty((n, c), device=dev, dtype=lp_dtype()) for c in (256, 128, 64)]       # layers 1, 2, 3
-                parts = [torch.empty((n // rows_wg, c), device=dev, dtype=torch.float32) for c in (256, 128, 64)]
-                _check(lib.vine_mlp3_bwd_elu_mfma(n, dG.data_ptr(), dG.stride(0), 4 * H, ctx.wts[0].data_ptr(),
-                                                  ctx.wts[0].stride(0), ctx.wts[2].data_ptr(), ctx.wts[2].stride(0),
-                                                  ctx.wts[1].data_ptr(), ctx.wts[1].stride(0), xcat.data_ptr(), xcat.stride(0),
+            if not mlp_done:
+                gzs, parts = _mlp3_grad_buffers(n, 128 if (n % 128 == 0 and n >= 32768) else 64, dev)
+                _check(lib.vine_mlp3_bwd_elu_mfma(n, dG.data_ptr(), dG.stride(0), 4 * H, wts[0].data_ptr(),
+                                                  wts[0].stride(0), wts[2].data_ptr(), wts[2].stride(0),
+                                                  wts[1].data_ptr(), wts[1].stride(0), xcat.data_ptr(), xcat.stride(0),
                                                   acts[1].data_ptr(), acts[0].data_ptr(), 64, 128, 256, 1.0,
                                                   gzs[2].data_ptr(), gzs[1].data_ptr(), gzs[0].data_ptr(),
                                                   parts[2].data_ptr(), parts[1].data_ptr(), parts[0].data_ptr(), st),
                        "vine_mlp3_bwd_elu_mfma")
             del dG
             for i in range(n_mlp):
-                x_in = acts[i - 1] if i > 0 else x0
-                deliver(2 * i, lambda o, gz=gzs[i], x_in=x_in: wgroup.add(gz, x_in, o, batch) or weight_grad(gz, x_in, out=o, batch=batch))
-                deliver(2 * i + 1, lambda o, part=parts[i]: column_sums(part, o, batch=batch))
-            n_mlp_loop = 0
+                deliver_layer(i, gzs[i], parts[i])
         else:
-            n_mlp_loop = n_mlp
-        if mlp3b:
-            pass
-        elif mixed and ctx.wts[0] is not None:
-            # LSTM input gradient (MLP columns only) x ELU' of the last MLP layer + its bias partial sums: one
-            # matrix-core kernel streaming the 4H-long reduction in k chunks
-            gz = torch.empty((n, U), device=dev, dtype=lp_dtype())
-            part = torch.empty((n // 64, U), device=dev, dtype=torch.float32)
-            _check(lib.vine_linear_bwd_elu_mfma(n, U, 4 * H, dG.data_ptr(), dG.stride(0), ctx.wts[0].data_ptr(),
-                                                ctx.wts[0].stride(0), xcat.data_ptr(), xcat.stride(0), 1.0,
-                                                gz.data_ptr(), U, part.data_ptr(), st), "vine_linear_bwd_elu_mfma")
-        else:
-            g = _mm(dG, w_ih[:, :U] if concat else w_ih)    # only the MLP columns of the LSTM input need a gradient
-        if not mlp3b:
-            del dG
-        # ---- MLP, last layer first: ELU' from the stored OUTPUT, bias gradient from the kernels' partial sums.
-        # gz = gradient w.r.t. layer i's pre-activation.  In mixed precision the step from layer i to layer i-1
-        # (input-gradient GEMM + ELU backward + bias partial sums) is one matrix-core kernel.
-        for i in reversed(range(n_mlp_loop)):
-            if gz is None:
-                a = xcat if i == n_mlp - 1 else acts[i]
-                C_ = g.shape[1]
-                part = torch.empty((PPO_PARTIAL_BLOCKS, C_), device=dev, dtype=torch.float32)
-                gz = torch.empty((n, C_), device=dev, dtype=lp_dtype()) if mixed else g     # fp32: in place
-                _check(lib.vine_elu_backward(n, C_, g.data_ptr(), C_, a.data_ptr(), a.stride(0), 1.0, gz.data_ptr(), C_,
-                                             part.data_ptr(), int(mixed), int(mixed), st), "vine_elu_backward")
-            x_in = acts[i - 1] if i > 0 else x0
-            deliver(2 * i, lambda o, gz=gz, x_in=x_in: wgroup.add(gz, x_in, o, batch) or weight_grad(gz, x_in, out=o, batch=batch))
-            deliver(2 * i + 1, lambda o, part=part: column_sums(part, o, batch=batch))
-            if i == 0:
-                break
-            C_in = weights[i].shape[1]
-            if mixed and ctx.wts[i] is not None:
-                wt = ctx.wts[i]                                                    # [C_in, C_i] bf16, made in forward
-                gz_next = torch.empty((n, C_in), device=dev, dtype=lp_dtype())
-                part = torch.empty((n // 64, C_in), device=dev, dtype=torch.float32)
-                _check(lib.vine_linear_bwd_elu_mfma(n, C_in, gz.shape[1], gz.data_ptr(), gz.stride(0), wt.data_ptr(),
-                                                    wt.stride(0), acts[i - 1].data_ptr(), acts[i - 1].stride(0), 1.0,
-                                                    gz_next.data_ptr(), C_in, part.data_ptr(), st),
-                       "vine_linear_bwd_elu_mfma")
-                gz = gz_next
+            gz = g = None
+            if mixed and wts[0] is not None:
+                # LSTM input gradient (MLP columns only) x ELU' of the last MLP layer + its bias partial sums: one
+                # matrix-core kernel streaming the 4H-long reduction in k chunks
+                gz = torch.empty((n, U), device=dev, dtype=lp_dtype())
+                part = torch.empty((n // 64, U), device=dev, dtype=torch.float32)
+                _check(lib.vine_linear_bwd_elu_mfma(n, U, 4 * H, dG.data_ptr(), dG.stride(0), wts[0].data_ptr(),
+                                                    wts[0].stride(0), xcat.data_ptr(), xcat.stride(0), 1.0,
+                                                    gz.data_ptr(), U, part.data_ptr(), st), "vine_linear_bwd_elu_mfma")
             else:
-                g = _mm(gz, weights[i])
-                gz = None
-        # the MLP weight gradients: one launch, all operands exist by now.  WGRAD_SIDE (round 4 experiment): on a side stream --
-        # a parallel branch of the captured graph -- beside the LSTM weight-gradient kernel issued above: that kernel holds
-        # 8 waves x 196 VGPRs and 64 KB of LDS per CU, which leaves room for exactly one 4-wave workgroup of this one
-        if WGRAD_SIDE and getattr(ctx, "wgrad_fork", None) is not None:
-            side, cur = ctx.wgrad_fork
-            with torch.cuda.stream(side):
-                wgroup.flush()
-            cur.wait_stream(side)
-            ctx.wgrad_fork = None
-        else:
-            wgroup.flush()
+                g = _mm(dG, w_ih[:, :U] if r.concat else w_ih)    # only the MLP columns of the LSTM input need a gradient
+            del dG
+            # last layer first: ELU' from the stored OUTPUT, bias gradient from the kernels' partial sums.  In mixed
+            # precision the step from layer i to layer i-1 (input-gradient GEMM + ELU backward + bias partial sums) is
+            # one matrix-core kernel.
+            for i in reversed(range(n_mlp)):
+                if gz is None:
+                    a = xcat if i == n_mlp - 1 else acts[i]
+                    C_ = g.shape[1]
+                    part = torch.empty((PPO_PARTIAL_BLOCKS, C_), device=dev, dtype=torch.float32)
+                    gz = torch.empty((n, C_), device=dev, dtype=lp_dtype()) if mixed else g     # fp32: in place
+                    _check(lib.vine_elu_backward(n, C_, g.data_ptr(), C_, a.data_ptr(), a.stride(0), 1.0, gz.data_ptr(), C_,
+                                                 part.data_ptr(), int(mixed), int(mixed), st), "vine_elu_backward")
+                deliver_layer(i, gz, part)
+                if i == 0:
+                    break
+                C_in = weights[i].shape[1]
+                if mixed and wts[i] is not None:
+                    wt = wts[i]                                                    # [C_in, C_i] bf16, made in forward
+                    gz_next = torch.empty((n, C_in), device=dev, dtype=lp_dtype())
+                    part = torch.empty((n // 64, C_in), device=dev, dtype=torch.float32)
+                    _check(lib.vine_linear_bwd_elu_mfma(n, C_in, gz.shape[1], gz.data_ptr(), gz.stride(0), wt.data_ptr(),
+                                                        wt.stride(0), acts[i - 1].data_ptr(), acts[i - 1].stride(0), 1.0,
+                                                        gz_next.data_ptr(), C_in, part.data_ptr(), st),
+                           "vine_linear_bwd_elu_mfma")
+                    gz = gz_next
+                else:
+                    g = _mm(gz, weights[i])
+                    gz = None
+        wgroup.flush()      # the MLP weight gradients: one launch, all operands exist by now
         if batch is not None:
             if batch.bypassed and amp is not None:
-                ctx.loss_pack["amp_covered"] = False     # (coverage is per delivery, not per batch)
+                r.loss_pack["amp_covered"] = False     # (coverage is per delivery, not per batch)
             batch.flush(out)
         return (None, None, None, None, None, None, None, None, None, None, None, *grads)
 
