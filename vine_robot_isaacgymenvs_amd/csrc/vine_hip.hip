@@ -24,6 +24,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "../../include/vine.h"
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
@@ -276,6 +277,80 @@ __device__ __forceinline__ void substep(const DevParams& P, Dyn& s, const float 
 #define CONTACT_K 2000.0f
 #define CONTACT_C 2.0f
 #define LINK_REACH 0.078f   // lateral half-extent 0.0719 + link_0's 5.75 mm axial overhang beyond its joints, rounded up
+// ---- narrow-phase primitives, stated once: the whole-link forms (one lane per link) and the cooperative forms (a link's
+// points and the obstacle's corners split over a quad) below call the same three tests.
+// A point of a link rectangle, r = (ry, rz) from the link's joint, world position (wy, wz), against the shelf board on its
+// side of z = shelf_z + 0.1 (bsel: board B).  Adds the penalty force on the link and its moment about the joint.
+// (Operands by reference on purpose: with copies the compiler fuses the multiply-adds of the penalty force in another
+// pattern than it does for the callers' own values -- 44 v_mul + 88 v_add/v_sub become 88 v_fma in a one-lane shelf kernel --
+// and the last bit of a contact force would move.)
+__device__ __forceinline__ void shelf_point_contact(const bool& bsel, const float& wy, const float& wz, const float& ry,
+                                                    const float& rz, const float& pvy, const float& pvz, const float& om,
+                                                    const float& shelf_y, const float& shelf_z, float& fy_tot, float& fz_tot,
+                                                    float& mom) {
+    const float board[2][4] = SHELF_BOARDS;
+    const float ddy = wy - (shelf_y + (bsel ? board[1][0] : board[0][0]));
+    const float ddz = wz - (shelf_z + (bsel ? board[1][1] : board[0][1]));
+    const float ey = (bsel ? board[1][2] : board[0][2]) - fabsf(ddy), ez = board[0][3] - fabsf(ddz);
+    if (ey > 0.0f && ez > 0.0f) {
+        const float vy = pvy - om * rz, vz = pvz + om * ry;
+        float fy = 0.0f, fz = 0.0f;
+        if (ey < ez) {
+            const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
+            fy = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vy, 0.0f);
+        } else {
+            const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
+            fz = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vz, 0.0f);
+        }
+        fy_tot += fy; fz_tot += fz;
+        mom += -rz * fy + ry * fz;          // F . (z n_k + y d_k) = r x F about joint k
+    }
+}
+// The same point, at (pyl, pzl) in the pipe frame (ct, st: the frame's rotation), against the tube wall on its side of the
+// tube's axis (w1: the far wall).
+__device__ __forceinline__ void pipe_point_contact(bool w1, float pyl, float pzl, float ry, float rz, float pvy, float pvz,
+                                                   float om, float ct, float st, float& fy_tot, float& fz_tot, float& mom) {
+    const float wall_lo[2] = {0.0f, PIPE_OUTER - PIPE_WALL};
+    const float cw = w1 ? (wall_lo[1] + 0.5f * PIPE_WALL) : (wall_lo[0] + 0.5f * PIPE_WALL);
+    const float ddy = pyl - cw, ddz = pzl - 0.5f * PIPE_LEN;
+    const float ey = 0.5f * PIPE_WALL - fabsf(ddy), ez = 0.5f * PIPE_LEN - fabsf(ddz);
+    if (ey > 0.0f && ez > 0.0f) {
+        const float vy = pvy - om * rz, vz = pvz + om * ry;
+        const float vyl = vy * ct + vz * st, vzl = -vy * st + vz * ct;
+        float fyl = 0.0f, fzl = 0.0f;
+        if (ey < ez) {
+            const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
+            fyl = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vyl, 0.0f);
+        } else {
+            const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
+            fzl = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vzl, 0.0f);
+        }
+        const float fy = fyl * ct - fzl * st, fz = fyl * st + fzl * ct;
+        fy_tot += fy; fz_tot += fz;
+        mom += -rz * fy + ry * fz;
+    }
+}
+// A corner of an obstacle (a front corner of the shelf's strip, a corner of a tube wall), r = (ry, rz) from the link's
+// joint, against the link rectangle [z0, z1] x [LINK_Y0, LINK_Y1]: pushed out through the nearest side.  Adds the force on
+// the link, its moment, and the reaction on the obstacle (the shelf's strip reports it; the tube's is not read).
+__device__ __forceinline__ void corner_link_contact(float ry, float rz, float z0, float z1, float sp, float cp, float pvy,
+                                                    float pvz, float om, float& fy_tot, float& fz_tot, float& mom,
+                                                    float& react_y, float& react_z) {
+    const float dy = -sp, dz = cp, ly = cp, lz = sp;
+    const float zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
+    if (zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1) {
+        float dep = zl - z0, ny = -dy, nz = -dz;
+        if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
+        if (yl - LINK_Y0 < dep) { dep = yl - LINK_Y0; ny = -ly; nz = -lz; }
+        if (LINK_Y1 - yl < dep) { dep = LINK_Y1 - yl; ny = ly; nz = lz; }
+        const float vy = pvy - om * rz, vz = pvz + om * ry;
+        const float f = fmaxf(CONTACT_K * dep + CONTACT_C * (vy * ny + vz * nz), 0.0f);
+        react_y += f * ny; react_z += f * nz;
+        const float fy = -f * ny, fz = -f * nz;
+        fy_tot += fy; fz_tot += fz;
+        mom += -rz * fy + ry * fz;
+    }
+}
 // One link against the shelf: the link's joint position (py, pz) and velocity (pvy, pvz), sin / cos of its world angle,
 // its rate, the axial extent [z0, z1] of its rectangle.  Adds the force on the link (fy, fz), its moment about the
 // link's joint (mom) and the reaction on the `shelf_link` strip (sfy, sfz); returns whether any narrow phase ran.
@@ -283,7 +358,6 @@ __device__ __forceinline__ bool shelf_link_contact(const DevParams& P, float z0,
                                                    float pvz, float sp, float cp, float om, float shelf_y, float shelf_z,
                                                    float& fy_tot, float& fz_tot, float& mom, float& strip_fy,
                                                    float& strip_fz) {
-    const float board[2][4] = SHELF_BOARDS;
     const float dy = -sp, dz = cp, ly = cp, lz = sp;     // link axis d, lateral l; n = d(d)/d(phi) = (-cp, -sp) = -l
     // every shelf shape lies at y <= shelf_y + 0.2; board A / the strip around z = shelf_z, board B around shelf_z + 0.2
     const float ycut = shelf_y + 0.2f;
@@ -306,24 +380,8 @@ __device__ __forceinline__ bool shelf_link_contact(const DevParams& P, float z0,
                 const float ry = zl * dy + yl * ly, rz = zl * dz + yl * lz;
                 const float wy = py + ry, wz = pz + rz;
                 const bool bsel = wz - shelf_z > 0.1f;
-                if (bsel ? near_b : near_a) {
-                    const float ddy = wy - (shelf_y + (bsel ? board[1][0] : board[0][0]));
-                    const float ddz = wz - (shelf_z + (bsel ? board[1][1] : board[0][1]));
-                    const float ey = (bsel ? board[1][2] : board[0][2]) - fabsf(ddy), ez = board[0][3] - fabsf(ddz);
-                    if (ey > 0.0f && ez > 0.0f) {
-                        const float vy = pvy - om * rz, vz = pvz + om * ry;
-                        float fy = 0.0f, fz = 0.0f;
-                        if (ey < ez) {
-                            const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
-                            fy = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vy, 0.0f);
-                        } else {
-                            const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
-                            fz = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vz, 0.0f);
-                        }
-                        fy_tot += fy; fz_tot += fz;
-                        mom += -rz * fy + ry * fz;          // F . (z n_k + y d_k) = r x F about joint k
-                    }
-                }
+                if (bsel ? near_b : near_a)
+                    shelf_point_contact(bsel, wy, wz, ry, rz, pvy, pvz, om, shelf_y, shelf_z, fy_tot, fz_tot, mom);
             }
         }
     }
@@ -331,20 +389,7 @@ __device__ __forceinline__ bool shelf_link_contact(const DevParams& P, float z0,
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const float wy = shelf_y + 0.2f, wz = shelf_z + (e ? 0.005f : -0.005f);
-            const float ry = wy - py, rz = wz - pz;
-            const float zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
-            if (zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1) {
-                float dep = zl - z0, ny = -dy, nz = -dz;
-                if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
-                if (yl - LINK_Y0 < dep) { dep = yl - LINK_Y0; ny = -ly; nz = -lz; }
-                if (LINK_Y1 - yl < dep) { dep = LINK_Y1 - yl; ny = ly; nz = lz; }
-                const float vy = pvy - om * rz, vz = pvz + om * ry;
-                const float f = fmaxf(CONTACT_K * dep + CONTACT_C * (vy * ny + vz * nz), 0.0f);
-                strip_fy += f * ny; strip_fz += f * nz;
-                const float fy = -f * ny, fz = -f * nz;
-                fy_tot += fy; fz_tot += fz;
-                mom += -rz * fy + ry * fz;
-            }
+            corner_link_contact(wy - py, wz - pz, z0, z1, sp, cp, pvy, pvz, om, fy_tot, fz_tot, mom, strip_fy, strip_fz);
         }
     }
     return near_a || near_b;
@@ -392,19 +437,43 @@ __device__ __forceinline__ float shelf_contact(const DevParams& P, const Dyn& s,
 // the (link, wall) pairs that are left.  A vine reaching INTO the tube sits between the walls: level 2 is what keeps it
 // out of the narrow phase until it actually comes within a rounding margin of a wall.
 #define PIPE_CULL_EPS 1.0e-5f      // the box tests use other (equivalent) expressions than the narrow phase: rounding margin
+// The broad phase of one (link, tube) pair, levels 1 and 2: bit 0 / bit 1 = the link's box reaches wall 0 / wall 1.  The
+// four-lane kernel evaluates it ONCE per link, on the lane that owns the link (link 4: on every lane), and broadcasts the
+// bits to the lanes that share the link's narrow phase (~45 instructions x 3 links per substep otherwise).
 __device__ __forceinline__ unsigned pipe_broad_phase(float z0, float z1, float py, float pz, float sp, float cp,
-                                                     const PipePose& T);
-// nearbits: pipe_broad_phase of this link when the caller has it already (the four-lane kernel), PIPE_BROAD_HERE otherwise
-#define PIPE_BROAD_HERE 0xffffffffu
+                                                     const PipePose& T) {
+    const float pipe_y = T.y, pipe_z = T.z, ct = T.ct, st = T.st;
+    const float dy = -sp, dz = cp;
+    // radius of the tube's bounding circle + the link's (half-length 0.05, lateral reach 0.0719 about the axis midpoint)
+    const float rsum = 0.18748f + 0.0877f + 1.0e-4f;       // hypot(0.0777, 0.170625) + hypot(0.05, 0.0719)
+    const float my = py + 0.04425f * dy - T.ccy, mz = pz + 0.04425f * dz - T.ccz;     // axis midpoint - tube centre
+    if (!(my * my + mz * mz < rsum * rsum)) return 0u;
+    // level 2: the rectangle's box in the pipe frame.  Local axis / lateral directions, local joint position.
+    const float dly = dy * ct + dz * st, dlz = -dy * st + dz * ct;          // d in the pipe frame; l = (dlz, -dly)
+    const float gy0 = py - pipe_y, gz0 = pz - pipe_z;
+    const float jy = gy0 * ct + gz0 * st, jz = -gy0 * st + gz0 * ct;
+    const float ay0 = z0 * dly, ay1 = z1 * dly, by0 = LINK_Y0 * dlz, by1 = LINK_Y1 * dlz;
+    const float az0 = z0 * dlz, az1 = z1 * dlz, bz0 = LINK_Y0 * -dly, bz1 = LINK_Y1 * -dly;
+    const float ymin = jy + fminf(ay0, ay1) + fminf(by0, by1) - PIPE_CULL_EPS;
+    const float ymax = jy + fmaxf(ay0, ay1) + fmaxf(by0, by1) + PIPE_CULL_EPS;
+    const float zmin = jz + fminf(az0, az1) + fminf(bz0, bz1) - PIPE_CULL_EPS;
+    const float zmax = jz + fmaxf(az0, az1) + fmaxf(bz0, bz1) + PIPE_CULL_EPS;
+    const bool zin = zmin < PIPE_LEN && zmax > 0.0f;
+    const bool near0 = zin && ymin < PIPE_WALL && ymax > 0.0f;
+    const bool near1 = zin && ymin < PIPE_OUTER && ymax > PIPE_OUTER - PIPE_WALL;
+    // bits 2, 3: the box reaches the tube's end z = 0 / z = PIPE_LEN.  A wall's corners lie on those two lines, and a corner
+    // inside the link's rectangle lies inside the rectangle's box: a link deep inside the tube (a trained vine's links 3 and
+    // 4, most of the time) cannot contain any corner, and its corner tests -- a third of a cooperative link's narrow phase --
+    // are skipped.  Exact: the box carries the same rounding margin as above.
+    return (near0 ? 1u : 0u) | (near1 ? 2u : 0u) | (zmin < 0.0f ? 4u : 0u) | (zmax > PIPE_LEN ? 8u : 0u);
+}
+// nearbits: pipe_broad_phase of this link
 __device__ __forceinline__ bool pipe_link_contact(const DevParams& P, float z0, float z1, float py, float pz, float pvy,
                                                   float pvz, float sp, float cp, float om, const PipePose& T, float& fy_tot,
-                                                  float& fz_tot, float& mom, unsigned nearbits = PIPE_BROAD_HERE) {
+                                                  float& fz_tot, float& mom, unsigned nearbits) {
     const float wall_lo[2] = {0.0f, PIPE_OUTER - PIPE_WALL};
     const float pipe_y = T.y, pipe_z = T.z, ct = T.ct, st = T.st;
     const float dy = -sp, dz = cp, ly = cp, lz = sp;
-    // broad phase (pipe_broad_phase below): (1) bounding circles of the link and of the tube, (2) the rectangle's box in the
-    // pipe frame against each wall's box
-    if (nearbits == PIPE_BROAD_HERE) nearbits = pipe_broad_phase(z0, z1, py, pz, sp, cp, T);
     const bool near0 = (nearbits & 1u) != 0, near1 = (nearbits & 2u) != 0;
     if (!(near0 || near1)) return false;
 #pragma unroll
@@ -419,31 +488,11 @@ __device__ __forceinline__ bool pipe_link_contact(const DevParams& P, float z0, 
             // the walls are disjoint in the pipe frame's y ((0, 0.00525) and (0.15015, 0.1554)): a point can be inside
             // the one on its side of the tube's axis only, so ONE test body per point instead of one per (point, wall) --
             // same arithmetic for the wall that is tested, half the worst-case instruction stream of a wave
-            {
-                const bool w1 = pyl > 0.5f * PIPE_OUTER;
-                const float cw = w1 ? (wall_lo[1] + 0.5f * PIPE_WALL) : (wall_lo[0] + 0.5f * PIPE_WALL);
-                if (w1 ? near1 : near0) {
-                    const float ddy = pyl - cw, ddz = pzl - 0.5f * PIPE_LEN;
-                    const float ey = 0.5f * PIPE_WALL - fabsf(ddy), ez = 0.5f * PIPE_LEN - fabsf(ddz);
-                    if (ey > 0.0f && ez > 0.0f) {
-                        const float vy = pvy - om * rz, vz = pvz + om * ry;
-                        const float vyl = vy * ct + vz * st, vzl = -vy * st + vz * ct;
-                        float fyl = 0.0f, fzl = 0.0f;
-                        if (ey < ez) {
-                            const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
-                            fyl = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vyl, 0.0f);
-                        } else {
-                            const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
-                            fzl = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vzl, 0.0f);
-                        }
-                        const float fy = fyl * ct - fzl * st, fz = fyl * st + fzl * ct;
-                        fy_tot += fy; fz_tot += fz;
-                        mom += -rz * fy + ry * fz;
-                    }
-                }
-            }
+            const bool w1 = pyl > 0.5f * PIPE_OUTER;
+            if (w1 ? near1 : near0) pipe_point_contact(w1, pyl, pzl, ry, rz, pvy, pvz, om, ct, st, fy_tot, fz_tot, mom);
         }
     }
+    float tube_fy = 0.0f, tube_fz = 0.0f;      // (the reaction on the tube: not read)
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
         if (w == 0 ? near0 : near1) {
@@ -452,18 +501,7 @@ __device__ __forceinline__ bool pipe_link_contact(const DevParams& P, float z0, 
                 if (!(nearbits & ((cidx & 2) ? 8u : 4u))) continue;      // this end of the tube is outside the link's box
                 const float pyl = wall_lo[w] + ((cidx & 1) ? PIPE_WALL : 0.0f), pzl = (cidx & 2) ? PIPE_LEN : 0.0f;
                 const float ry = pipe_y + pyl * ct - pzl * st - py, rz = pipe_z + pyl * st + pzl * ct - pz;
-                const float zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
-                if (zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1) {
-                    float dep = zl - z0, ny = -dy, nz = -dz;
-                    if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
-                    if (yl - LINK_Y0 < dep) { dep = yl - LINK_Y0; ny = -ly; nz = -lz; }
-                    if (LINK_Y1 - yl < dep) { dep = LINK_Y1 - yl; ny = ly; nz = lz; }
-                    const float vy = pvy - om * rz, vz = pvz + om * ry;
-                    const float f = fmaxf(CONTACT_K * dep + CONTACT_C * (vy * ny + vz * nz), 0.0f);
-                    const float fy = -f * ny, fz = -f * nz;
-                    fy_tot += fy; fz_tot += fz;
-                    mom += -rz * fy + ry * fz;
-                }
+                corner_link_contact(ry, rz, z0, z1, sp, cp, pvy, pvz, om, fy_tot, fz_tot, mom, tube_fy, tube_fz);
             }
         }
     }
@@ -483,7 +521,8 @@ __device__ __forceinline__ void pipe_contact(const DevParams& P, const Dyn& s, f
         const float z0 = (k == 0) ? LINK0_Z0 : 0.0f, z1 = (k == 0) ? LINK0_Z1 : P.L;
         float fy_tot = 0.0f, fz_tot = 0.0f, mom = 0.0f;
         ny_[k] = -cp; nz_[k] = -sp;
-        any |= pipe_link_contact(P, z0, z1, py, pz, pvy, pvz, sp, cp, om, T, fy_tot, fz_tot, mom);
+        any |= pipe_link_contact(P, z0, z1, py, pz, pvy, pvz, sp, cp, om, T, fy_tot, fz_tot, mom,
+                                 pipe_broad_phase(z0, z1, py, pz, sp, cp, T));
         Fy[k] = fy_tot; Fz[k] = fz_tot; mom_[k] = mom;
         py += P.L * (-sp); pz += P.L * cp;
         pvy += P.L * om * (-cp); pvz += P.L * om * (-sp);
@@ -516,7 +555,6 @@ __device__ __forceinline__ void shelf_link_contact_coop(const DevParams& P, int 
                                                         float pvy, float pvz, float sp, float cp, float om, float shelf_y,
                                                         float shelf_z, float& fy_tot, float& fz_tot, float& mom,
                                                         float& strip_fy, float& strip_fz) {
-    const float board[2][4] = SHELF_BOARDS;
     const float dy = -sp, dz = cp, ly = cp, lz = sp;
     const float ycut = shelf_y + 0.2f;
     const float a_lo = shelf_z - 0.005f, a_hi = shelf_z + 0.005f, b_lo = shelf_z + 0.195f, b_hi = shelf_z + 0.205f;
@@ -533,74 +571,14 @@ __device__ __forceinline__ void shelf_link_contact_coop(const DevParams& P, int 
         coop_point(t, slot, z0, z1, yl, zl, valid);
         const float ry = zl * dy + yl * ly, rz = zl * dz + yl * lz;
         const float wy = py + ry, wz = pz + rz;
-        {   // one test body per point: the board on the point's side of z = shelf_z + 0.1 (see shelf_link_contact)
-            const bool bsel = wz - shelf_z > 0.1f;
-            const float ddy = wy - (shelf_y + (bsel ? board[1][0] : board[0][0]));
-            const float ddz = wz - (shelf_z + (bsel ? board[1][1] : board[0][1]));
-            const float ey = (bsel ? board[1][2] : board[0][2]) - fabsf(ddy), ez = board[0][3] - fabsf(ddz);
-            if (valid && (bsel ? near_b : near_a) && ey > 0.0f && ez > 0.0f) {
-                const float vy = pvy - om * rz, vz = pvz + om * ry;
-                float fy = 0.0f, fz = 0.0f;
-                if (ey < ez) {
-                    const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
-                    fy = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vy, 0.0f);
-                } else {
-                    const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
-                    fz = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vz, 0.0f);
-                }
-                fy_tot += fy; fz_tot += fz;
-                mom += -rz * fy + ry * fz;
-            }
-        }
+        const bool bsel = wz - shelf_z > 0.1f;
+        if (valid && (bsel ? near_b : near_a))
+            shelf_point_contact(bsel, wy, wz, ry, rz, pvy, pvz, om, shelf_y, shelf_z, fy_tot, fz_tot, mom);
     }
     if (near_a && t < 2) {                                   // strip corner t
         const float wy = shelf_y + 0.2f, wz = shelf_z + (t ? 0.005f : -0.005f);
-        const float ry = wy - py, rz = wz - pz;
-        const float zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
-        if (zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1) {
-            float dep = zl - z0, ny = -dy, nz = -dz;
-            if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
-            if (yl - LINK_Y0 < dep) { dep = yl - LINK_Y0; ny = -ly; nz = -lz; }
-            if (LINK_Y1 - yl < dep) { dep = LINK_Y1 - yl; ny = ly; nz = lz; }
-            const float vy = pvy - om * rz, vz = pvz + om * ry;
-            const float f = fmaxf(CONTACT_K * dep + CONTACT_C * (vy * ny + vz * nz), 0.0f);
-            strip_fy += f * ny; strip_fz += f * nz;
-            const float fy = -f * ny, fz = -f * nz;
-            fy_tot += fy; fz_tot += fz;
-            mom += -rz * fy + ry * fz;
-        }
+        corner_link_contact(wy - py, wz - pz, z0, z1, sp, cp, pvy, pvz, om, fy_tot, fz_tot, mom, strip_fy, strip_fz);
     }
-}
-// The broad phase of one (link, tube) pair -- levels 1 and 2 of pipe_link_contact, the same expressions -- as bit 0 / bit 1 =
-// the link's box reaches wall 0 / wall 1.  Round 5: the four-lane kernel evaluates it ONCE per link, on the lane that owns
-// the link (link 4: on every lane), and broadcasts the two bits to the lanes that share the link's narrow phase; the
-// cooperative form used to repeat it on all four lanes for each of its links (~45 instructions x 3 links per substep).
-__device__ __forceinline__ unsigned pipe_broad_phase(float z0, float z1, float py, float pz, float sp, float cp,
-                                                     const PipePose& T) {
-    const float pipe_y = T.y, pipe_z = T.z, ct = T.ct, st = T.st;
-    const float dy = -sp, dz = cp;
-    // radius of the tube's bounding circle + the link's (half-length 0.05, lateral reach 0.0719 about the axis midpoint)
-    const float rsum = 0.18748f + 0.0877f + 1.0e-4f;       // hypot(0.0777, 0.170625) + hypot(0.05, 0.0719)
-    const float my = py + 0.04425f * dy - T.ccy, mz = pz + 0.04425f * dz - T.ccz;     // axis midpoint - tube centre
-    if (!(my * my + mz * mz < rsum * rsum)) return 0u;
-    // level 2: the rectangle's box in the pipe frame.  Local axis / lateral directions, local joint position.
-    const float dly = dy * ct + dz * st, dlz = -dy * st + dz * ct;          // d in the pipe frame; l = (dlz, -dly)
-    const float gy0 = py - pipe_y, gz0 = pz - pipe_z;
-    const float jy = gy0 * ct + gz0 * st, jz = -gy0 * st + gz0 * ct;
-    const float ay0 = z0 * dly, ay1 = z1 * dly, by0 = LINK_Y0 * dlz, by1 = LINK_Y1 * dlz;
-    const float az0 = z0 * dlz, az1 = z1 * dlz, bz0 = LINK_Y0 * -dly, bz1 = LINK_Y1 * -dly;
-    const float ymin = jy + fminf(ay0, ay1) + fminf(by0, by1) - PIPE_CULL_EPS;
-    const float ymax = jy + fmaxf(ay0, ay1) + fmaxf(by0, by1) + PIPE_CULL_EPS;
-    const float zmin = jz + fminf(az0, az1) + fminf(bz0, bz1) - PIPE_CULL_EPS;
-    const float zmax = jz + fmaxf(az0, az1) + fmaxf(bz0, bz1) + PIPE_CULL_EPS;
-    const bool zin = zmin < PIPE_LEN && zmax > 0.0f;
-    const bool near0 = zin && ymin < PIPE_WALL && ymax > 0.0f;
-    const bool near1 = zin && ymin < PIPE_OUTER && ymax > PIPE_OUTER - PIPE_WALL;
-    // bits 2, 3: the box reaches the tube's end z = 0 / z = PIPE_LEN.  A wall's corners lie on those two lines, and a corner
-    // inside the link's rectangle lies inside the rectangle's box: a link deep inside the tube (a trained vine's links 3 and
-    // 4, most of the time) cannot contain any corner, and its corner tests -- a third of a cooperative link's narrow phase --
-    // are skipped.  Exact: the box carries the same rounding margin as above.
-    return (near0 ? 1u : 0u) | (near1 ? 2u : 0u) | (zmin < 0.0f ? 4u : 0u) | (zmax > PIPE_LEN ? 8u : 0u);
 }
 __device__ __forceinline__ void pipe_link_contact_coop(const DevParams& P, int t, float z0, float z1, float py, float pz,
                                                        float pvy, float pvz, float sp, float cp, float om, const PipePose& T,
@@ -618,51 +596,218 @@ __device__ __forceinline__ void pipe_link_contact_coop(const DevParams& P, int t
         const float ry = zl * dy + yl * ly, rz = zl * dz + yl * lz;
         const float gy = py + ry - pipe_y, gz = pz + rz - pipe_z;
         const float pyl = gy * ct + gz * st, pzl = -gy * st + gz * ct;
-        {   // one test body per point: the wall on the point's side of the tube's axis (see pipe_link_contact)
-            const bool w1 = pyl > 0.5f * PIPE_OUTER;
-            const float cw = w1 ? (wall_lo[1] + 0.5f * PIPE_WALL) : (wall_lo[0] + 0.5f * PIPE_WALL);
-            const float ddy = pyl - cw, ddz = pzl - 0.5f * PIPE_LEN;
-            const float ey = 0.5f * PIPE_WALL - fabsf(ddy), ez = 0.5f * PIPE_LEN - fabsf(ddz);
-            if (valid && (w1 ? near1 : near0) && ey > 0.0f && ez > 0.0f) {
-                const float vy = pvy - om * rz, vz = pvz + om * ry;
-                const float vyl = vy * ct + vz * st, vzl = -vy * st + vz * ct;
-                float fyl = 0.0f, fzl = 0.0f;
-                if (ey < ez) {
-                    const float sg = (ddy > 0.0f) ? 1.0f : -1.0f;
-                    fyl = sg * fmaxf(CONTACT_K * ey - CONTACT_C * sg * vyl, 0.0f);
-                } else {
-                    const float sg = (ddz > 0.0f) ? 1.0f : -1.0f;
-                    fzl = sg * fmaxf(CONTACT_K * ez - CONTACT_C * sg * vzl, 0.0f);
-                }
-                const float fy = fyl * ct - fzl * st, fz = fyl * st + fzl * ct;
-                fy_tot += fy; fz_tot += fz;
-                mom += -rz * fy + ry * fz;
-            }
-        }
+        const bool w1 = pyl > 0.5f * PIPE_OUTER;      // the wall on the point's side of the tube's axis (see pipe_link_contact)
+        if (valid && (w1 ? near1 : near0)) pipe_point_contact(w1, pyl, pzl, ry, rz, pvy, pvz, om, ct, st, fy_tot, fz_tot, mom);
     }
+    float tube_fy = 0.0f, tube_fz = 0.0f;      // (the reaction on the tube: not read)
     const bool my_end = (nearbits & ((t & 2) ? 8u : 4u)) != 0;      // can this lane's corner (end t >> 1 of the tube) lie in the link's box?
 #pragma unroll
     for (int w = 0; w < 2; ++w) {
         if ((w == 0 ? near0 : near1) && my_end) {            // corner t of wall w
             const float pyl = wall_lo[w] + ((t & 1) ? PIPE_WALL : 0.0f), pzl = (t & 2) ? PIPE_LEN : 0.0f;
             const float ry = pipe_y + pyl * ct - pzl * st - py, rz = pipe_z + pyl * st + pzl * ct - pz;
-            const float zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
-            if (zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1) {
-                float dep = zl - z0, ny = -dy, nz = -dz;
-                if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
-                if (yl - LINK_Y0 < dep) { dep = yl - LINK_Y0; ny = -ly; nz = -lz; }
-                if (LINK_Y1 - yl < dep) { dep = LINK_Y1 - yl; ny = ly; nz = lz; }
-                const float vy = pvy - om * rz, vz = pvz + om * ry;
-                const float f = fmaxf(CONTACT_K * dep + CONTACT_C * (vy * ny + vz * nz), 0.0f);
-                const float fy = -f * ny, fz = -f * nz;
-                fy_tot += fy; fz_tot += fz;
-                mom += -rz * fy + ry * fz;
-            }
+            corner_link_contact(ry, rz, z0, z1, sp, cp, pvy, pvz, om, fy_tot, fz_tot, mom, tube_fy, tube_fz);
         }
     }
 }
 
 __device__ __forceinline__ float clampf(float v, float lim) { return fminf(fmaxf(v, -lim), lim); }
+
+// ================================================================================================================
+// The task, stated once: what Vine5LinkMovingBase computes around the physics, as per-lane arithmetic on values the caller
+// holds in registers.  vine_step_kernel (one lane per env) and vine_step_quad_kernel (four lanes per env, everything here
+// replicated on the quad) both call these; what differs between the kernels -- where the loads, the random draws and the
+// stores sit, who holds which joint, the solver -- stays in the kernels.  No memory access and no cross-lane operation in
+// here.  (oracle/vine_oracle.c restates the task independently and shares nothing with this section.)
+
+// VecTask.step's clamp (vec_task.py:333) and the first half of pre_physics_step (V5:922-934): the action, with its noise
+// deviates n0, n1, becomes the command (new_rail, new_fpam).
+template <bool RANDOMIZE>
+__device__ __forceinline__ void task_new_command(const DevParams& P, float2 act, float n0, float n1, float& new_rail,
+                                                 float& new_fpam) {
+    float a0 = clampf(act.x, P.clip_act), a1 = clampf(act.y, P.clip_act);
+    if (RANDOMIZE && P.act_noise != 0.0f) {
+        a0 += P.act_noise * n0;
+        a1 += P.act_noise * n1;
+    }
+    new_rail = a0 * P.rail_scale;
+    new_fpam = (a1 + 1.0f) * 0.5f * P.fpam_span + P.fpam_min;   // /2 == *0.5 exactly
+}
+// The second half (V5:935-945): the command in effect (u_rail, u_fpam) is the one the delay FIFO held for this step (delay > 0;
+// the caller loads it and stores the new one in its place) or the new one; then the two force flags and the FPAM smoothing.
+__device__ __forceinline__ void task_command_in_effect(const DevParams& P, float new_rail, float new_fpam, float fifo_rail,
+                                                       float fifo_fpam, float& smoothed, float& u_rail, float& u_fpam) {
+    u_rail = new_rail; u_fpam = new_fpam;
+    if (P.delay > 0) { u_rail = fifo_rail; u_fpam = fifo_fpam; }
+    if (P.flags & VINE_FLAG_FORCE_U_FPAM) u_fpam = 0.0f;
+    if (P.flags & VINE_FLAG_FORCE_U_RAIL_VELOCITY) u_rail = 0.0f;
+    const float alpha = (u_fpam > smoothed) ? P.alpha_inf : P.alpha_def;
+    smoothed = alpha * smoothed + (1.0f - alpha) * u_fpam;
+}
+
+// The 20 dynamics-scaling factors of control iteration `it` (V5:1053-1055; K, C, b, B of joints 0..4 at [0, 5, 10, 15) + j)
+// from three Philox calls: 16-bit uniforms, two per 32-bit word.
+template <bool RANDOMIZE>
+__device__ __forceinline__ void task_dyn_scales(const DevParams& P, unsigned env, unsigned long long step, int it,
+                                                float (&sc)[20]) {
+    if (RANDOMIZE && P.dyn_span != 0.0f) {
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            unsigned r[4];
+            rng4(P, env, step, RNG_DYN_SCALE, (unsigned)(it * 3 + g), r);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (g * 8 + k < 20) {
+                    const float u = (float)((r[k >> 1] >> (16 * (k & 1))) & 0xffffu) * (1.0f / 65536.0f);
+                    sc[g * 8 + k] = P.dyn_min + P.dyn_span * u;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 20; ++k) sc[k] = RANDOMIZE ? P.dyn_min : 1.0f;
+    }
+}
+
+// FPAM torque model of one joint (V5:1028-1066): its constants K, C, bb, B with their scaling factors, the joint's relative
+// angle and rate, the FPAM command.  eff: the held effort, cj: the joint's damping coefficient in the solve.
+__device__ __forceinline__ void task_joint_torque(const DevParams& P, float K, float C, float bb, float B, float sK, float sC,
+                                                  float sb, float sB, float qj, float qdj, float u_used, bool held,
+                                                  float& eff, float& cj) {
+    float t = K * sK * qj;
+    const float cv = C * sC;
+    if (held) t += cv * qdj;
+    t += bb * sb;
+    t += B * sB * u_used;
+    eff = (P.eff_lim > 0.0f) ? clampf(-t, P.eff_lim) : -t;
+    cj = P.damping + (held ? 0.0f : cv);
+}
+
+// Rail controller (V5:1069-1098): the force on the cart, bang-bang with an acceleration term far from the commanded
+// velocity and PD near it; updates its two memories.
+__device__ __forceinline__ float task_rail_force(const DevParams& P, float u_rail, float cart_vy, float& pcv, float& pce) {
+    const float err = u_rail - cart_vy;
+    const float fmax = P.rail_acc * 0.5f;
+    float minmax = (err > 0.0f) ? fmax : -fmax;
+    const float accel = (cart_vy - pcv) * P.inv_dt;
+    const float accel_target = (err > 0.0f) ? P.rail_acc : -P.rail_acc;
+    minmax += 0.30f * (accel_target - accel);
+    const float pid = P.p_gain * err + P.d_gain * (err - pce);
+    pce = err;
+    pcv = cart_vy;
+    return (fabsf(err) > 0.1f) ? minmax : pid;
+}
+
+// reset_idx (V5:774-839, 887-914): the new episode's joint positions qn (cart first), target and obstacle depths, from a
+// `reset_values` row (when given) or from the three Philox word quadruples RNG_RESET 0..2 of the env.
+__device__ __forceinline__ void task_reset_pose(const DevParams& P, const float* __restrict__ row, const unsigned (&r0)[4],
+                                                const unsigned (&r1)[4], const unsigned (&r2)[4], float (&qn)[ND], float& ty,
+                                                float& tz, float& depth, float& pdepth) {
+    const float ten = 0.17453292519943295f;  // math.radians(10)
+    if (row) {
+#pragma unroll
+        for (int k = 0; k < NL; ++k) qn[k + 1] = row[k];
+        qn[0] = row[5]; pdepth = row[6]; ty = row[7]; tz = row[8]; depth = row[9];
+    } else {
+        qn[1] = -ten + (2.0f * ten) * u01(r0[0]);
+        qn[2] = -ten + (2.0f * ten) * u01(r0[1]);
+        qn[3] = -ten + (2.0f * ten) * u01(r0[2]);
+        qn[4] = -ten + (2.0f * ten) * u01(r0[3]);
+        qn[5] = -ten + (2.0f * ten) * u01(r1[0]);
+        qn[0] = P.cart_min + P.cart_span * u01(r1[1]);
+        pdepth = P.depth_min + P.depth_span * u01(r1[2]);
+        ty = P.ty_min + P.ty_span * u01(r1[3]);
+        tz = P.tz_min + P.tz_span * u01(r2[0]);
+        depth = P.depth_min + P.depth_span * u01(r2[1]);
+    }
+    if (!(P.flags & VINE_FLAG_RANDOMIZE_DOF_INIT)) {
+#pragma unroll
+        for (int i = 0; i < ND; ++i) qn[i] = 0.0f;
+    }
+    if (!(P.flags & VINE_FLAG_RANDOMIZE_TARGETS)) { ty = P.ty_max; tz = P.tz_fixed; }
+}
+
+// Obstacle poses of a new episode (V5:818-885): the shelf hangs off the target at `depth`; the pipe's mouth is `pdepth`
+// from the target along an axis whose angle is a cubic of the target's height.
+struct ObstaclePoses {
+    float shelf_y, shelf_z, pipe_y, pipe_z, pipe_angle;
+};
+__device__ __forceinline__ ObstaclePoses task_obstacle_poses(bool shelf, bool pipe, float ty, float tz, float depth,
+                                                             float pdepth) {
+    ObstaclePoses o = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (shelf) {
+        o.shelf_y = ty + (-0.2f + depth);
+        o.shelf_z = tz - 0.01f;
+    }
+    if (pipe) {
+        const float R = 0.0735f;             // PIPE_RADIUS = 0.07 * 1.05 (V5:88)
+        const float ez = 1.0f - tz;
+        const float deg = ((13199.0f * ez - 12276.0f) * ez + 4045.0f) * ez - 447.0f;
+        const float tp = deg * 0.017453292519943295f;
+        float stp, ctp;
+        sincosf(tp, &stp, &ctp);
+        o.pipe_y = ty + pdepth * ctp + R * stp;
+        o.pipe_z = tz + pdepth * stp - R * ctp;
+        o.pipe_angle = tp;
+    }
+    return o;
+}
+
+// The last 16 columns of the two scalable observation layouts (V5:1369-1390) behind the NOBS - 16 joint columns the caller
+// has written, then the scaling of the whole row.
+template <int NOBS, int CAP>
+__device__ __forceinline__ void task_obs_tail_and_scale(const DevParams& P, float (&o)[CAP], float tip_y, float tip_z,
+                                                        float fd_tip_y, float fd_tip_z, float ty, float tz, float smoothed,
+                                                        float prev_u_rail, float obj_depth, float obj_angle) {
+    int k = NOBS - 16;
+    o[k++] = 0.0f; o[k++] = tip_y; o[k++] = tip_z;
+    o[k++] = 0.0f; o[k++] = fd_tip_y; o[k++] = fd_tip_z;
+    o[k++] = 0.0f; o[k++] = ty; o[k++] = tz;
+    o[k++] = 0.0f; o[k++] = 0.0f; o[k++] = 0.0f;
+    o[k++] = smoothed; o[k++] = prev_u_rail; o[k++] = obj_depth; o[k++] = obj_angle;
+#pragma unroll
+    for (int i = 0; i < NOBS; ++i) o[i] = o[i] * P.inv_obs_scale[i];
+}
+
+// compute_reward (V5:1218-1331) + compute_reward_jit (V5:1470-1537), compute_reset_jit (V5:1540-1558) and the time-out flag
+// of VecTask.step's epilogue (vec_task.py:366-380).  contact_sum: the shelf strip's force summed over the control
+// iterations (SHELF).  rst comes in as 0 and leaves as the reset request.
+template <bool SHELF>
+__device__ __forceinline__ void task_reward_and_reset(const DevParams& P, float tip_y, float tip_z, float tip_vy, float tip_vz,
+                                                      float ty, float tz, float cart_y, float u_rail, float u_fpam,
+                                                      float prev_u_rail, float smoothed, float contact_sum, long long prog,
+                                                      float (&rm)[VINE_NUM_REWARDS], float& total, float& cmean,
+                                                      long long& rst, unsigned char& to) {
+    const float dy = tip_y - ty, dz = tip_z - tz;
+    const float dist = sqrtf(dy * dy + dz * dz);
+    const bool reached = dist < P.success_dist;
+    const bool limit_hit = (cart_y > P.soft_limit) || (cart_y < -P.soft_limit);
+    const bool tip_limit_hit = tip_y < ty;
+    cmean = SHELF ? contact_sum / (float)P.cfi : 0.0f;      // V5:1242-1248
+    const float vnorm = sqrtf(tip_vy * tip_vy + tip_vz * tip_vz);
+    rm[0] = -dist;
+    rm[1] = -1.0f;
+    rm[2] = reached ? 1000.0f : 0.0f;
+    rm[3] = -(reached ? vnorm : 0.0f);
+    rm[4] = vnorm;
+    rm[5] = -fabsf(u_rail);
+    rm[6] = -fabsf(u_fpam);
+    rm[7] = -fabsf(u_rail - prev_u_rail);
+    rm[8] = -fabsf(u_fpam - smoothed);
+    rm[9] = limit_hit ? -100.0f : 0.0f;
+    rm[10] = -fabsf(cart_y);
+    rm[11] = tip_limit_hit ? -100.0f : 0.0f;
+    rm[12] = -((cmean > 0.0f) ? cmean : 0.0f);
+    total = 0.0f;
+#pragma unroll
+    for (int i = 0; i < VINE_NUM_REWARDS; ++i) total += rm[i] * P.rw[i];
+    if (prog >= (long long)P.max_len - 1) rst = 1;
+    if (reached && (P.flags & VINE_FLAG_USE_TARGET_REACHED_RESET)) rst = 1;
+    if (tip_limit_hit && (P.flags & VINE_FLAG_USE_TIP_LIMIT_HIT_RESET)) rst = 1;
+    if (limit_hit) rst = 1;
+    if (SHELF && cmean > 0.0f && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) rst = 1;
+    to = (prog >= (long long)P.max_len - 1) && (rst != 0);
+}
 
 #define ST(f) st[(size_t)(f) * n + e]
 
@@ -671,34 +816,14 @@ __device__ __forceinline__ float clampf(float v, float lim) { return fminf(fmaxf
 __device__ __forceinline__ void reset_env(const DevParams& P, float* __restrict__ st, int n, int e,
                                           unsigned long long step, const float* __restrict__ reset_values,
                                           float (&qn)[ND], float& ty, float& tz) {
-    const float ten = 0.17453292519943295f;  // math.radians(10)
-    float depth, pdepth;
-    if (reset_values) {
-        const float* v = reset_values + (size_t)e * 10;
-#pragma unroll
-        for (int k = 0; k < NL; ++k) qn[k + 1] = v[k];
-        qn[0] = v[5]; pdepth = v[6]; ty = v[7]; tz = v[8]; depth = v[9];
-    } else {
-        unsigned r0[4], r1[4], r2[4];
+    unsigned r0[4] = {0u, 0u, 0u, 0u}, r1[4] = {0u, 0u, 0u, 0u}, r2[4] = {0u, 0u, 0u, 0u};
+    if (!reset_values) {
         rng4(P, (unsigned)e, step, RNG_RESET, 0, r0);
         rng4(P, (unsigned)e, step, RNG_RESET, 1, r1);
         rng4(P, (unsigned)e, step, RNG_RESET, 2, r2);
-        qn[1] = -ten + (2.0f * ten) * u01(r0[0]);
-        qn[2] = -ten + (2.0f * ten) * u01(r0[1]);
-        qn[3] = -ten + (2.0f * ten) * u01(r0[2]);
-        qn[4] = -ten + (2.0f * ten) * u01(r0[3]);
-        qn[5] = -ten + (2.0f * ten) * u01(r1[0]);
-        qn[0] = P.cart_min + P.cart_span * u01(r1[1]);
-        ty = P.ty_min + P.ty_span * u01(r1[3]);
-        tz = P.tz_min + P.tz_span * u01(r2[0]);
-        depth = P.depth_min + P.depth_span * u01(r2[1]);
-        pdepth = P.depth_min + P.depth_span * u01(r1[2]);
     }
-    if (!(P.flags & VINE_FLAG_RANDOMIZE_DOF_INIT)) {
-#pragma unroll
-        for (int i = 0; i < ND; ++i) qn[i] = 0.0f;
-    }
-    if (!(P.flags & VINE_FLAG_RANDOMIZE_TARGETS)) { ty = P.ty_max; tz = P.tz_fixed; }
+    float depth, pdepth;
+    task_reset_pose(P, reset_values ? reset_values + (size_t)e * 10 : nullptr, r0, r1, r2, qn, ty, tz, depth, pdepth);
 #pragma unroll
     for (int i = 0; i < ND; ++i) {
         ST(VF_Q0 + i) = qn[i];
@@ -707,22 +832,38 @@ __device__ __forceinline__ void reset_env(const DevParams& P, float* __restrict_
     }
     ST(VF_TARGET_Y) = ty;
     ST(VF_TARGET_Z) = tz;
-    if (P.flags & VINE_FLAG_CREATE_SHELF) {
-        ST(VF_SHELF_Y) = ty + (-0.2f + depth);
-        ST(VF_SHELF_Z) = tz - 0.01f;
+    const bool shelf = (P.flags & VINE_FLAG_CREATE_SHELF) != 0, pipe = (P.flags & VINE_FLAG_CREATE_PIPE) != 0;
+    const ObstaclePoses o = task_obstacle_poses(shelf, pipe, ty, tz, depth, pdepth);
+    if (shelf) {
+        ST(VF_SHELF_Y) = o.shelf_y;
+        ST(VF_SHELF_Z) = o.shelf_z;
         ST(VF_OBJ_DEPTH) = depth;
     }
-    if (P.flags & VINE_FLAG_CREATE_PIPE) {   // V5:841-885
-        const float R = 0.0735f;             // PIPE_RADIUS = 0.07 * 1.05 (V5:88)
-        const float ez = 1.0f - tz;
-        const float deg = ((13199.0f * ez - 12276.0f) * ez + 4045.0f) * ez - 447.0f;
-        const float tp = deg * 0.017453292519943295f;
-        float stp, ctp;
-        sincosf(tp, &stp, &ctp);
-        ST(VF_PIPE_Y) = ty + pdepth * ctp + R * stp;
-        ST(VF_PIPE_Z) = tz + pdepth * stp - R * ctp;
+    if (pipe) {   // V5:841-885
+        ST(VF_PIPE_Y) = o.pipe_y;
+        ST(VF_PIPE_Z) = o.pipe_z;
         ST(VF_OBJ_DEPTH) = pdepth;
-        ST(VF_OBJ_ANGLE) = tp;
+        ST(VF_OBJ_ANGLE) = o.pipe_angle;
+    }
+}
+
+// The persistent fields both step kernels store at the end of every step (the tip / cart body states, which the four-lane
+// kernel stores lazily, are the caller's), and the attribute / dashboard views behind VINE_FLAG_INTROSPECT.
+template <bool SHELF>
+__device__ __forceinline__ void store_step_state(const DevParams& P, float* __restrict__ st, int n, int e, float smoothed,
+                                                 float pcv, float pce, float agg, float contact, float tip_vy, float tip_vz,
+                                                 float prev_tip_y, float prev_tip_z, float u_fpam, float u_rail,
+                                                 float prev_u_rail, float rail_force, float cmean) {
+    ST(VF_SMOOTHED_U) = smoothed;
+    ST(VF_PREV_CART_VEL) = pcv; ST(VF_PREV_CART_VEL_ERR) = pce;
+    ST(VF_AGG_REW) = agg;
+    if (SHELF) ST(VF_CONTACT) = contact;
+    if (P.flags & VINE_FLAG_INTROSPECT) {
+        ST(VF_TIP_VY) = tip_vy; ST(VF_TIP_VZ) = tip_vz;
+        ST(VF_PREV_TIP_Y) = prev_tip_y; ST(VF_PREV_TIP_Z) = prev_tip_z;
+        ST(VF_U_FPAM) = u_fpam; ST(VF_U_RAIL) = u_rail; ST(VF_PREV_U_RAIL) = prev_u_rail;
+        ST(VF_RAIL_FORCE) = rail_force;
+        if (SHELF) ST(VF_CONTACT_MEAN) = cmean;
     }
 }
 
@@ -766,35 +907,26 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long step = step_of(P, counters);
     if (e < n) {
-        // ---- VecTask.step: clamp actions (vec_task.py:333) ----
+        // ---- VecTask.step: clamp actions (vec_task.py:333); pre_physics_step (V5:922-945) ----
         const float2 act = reinterpret_cast<const float2*>(actions)[e];
-        float a0 = clampf(act.x, P.clip_act), a1 = clampf(act.y, P.clip_act);
-        // ---- pre_physics_step (V5:922-945) ----
+        float n0 = 0.0f, n1 = 0.0f;
         if (RANDOMIZE && P.act_noise != 0.0f) {
             unsigned r[4];
-            float n0, n1;
             rng4(P, (unsigned)e, step, RNG_ACTION_NOISE, 0, r);
             normal2(r[0], r[1], n0, n1);
-            a0 += P.act_noise * n0;
-            a1 += P.act_noise * n1;
         }
-        float new_rail = a0 * P.rail_scale;
-        float new_fpam = (a1 + 1.0f) * 0.5f * P.fpam_span + P.fpam_min;   // /2 == *0.5 exactly
-        float u_rail = new_rail, u_fpam = new_fpam;
+        float new_rail, new_fpam, fifo_rail = 0.0f, fifo_fpam = 0.0f;
+        task_new_command<RANDOMIZE>(P, act, n0, n1, new_rail, new_fpam);
         if (P.delay > 0) {
-            int slot = (int)(step % (unsigned long long)P.delay);
-            u_rail = ST(VF_FIFO0 + 2 * slot);
-            u_fpam = ST(VF_FIFO0 + 2 * slot + 1);
+            const int slot = (int)(step % (unsigned long long)P.delay);
+            fifo_rail = ST(VF_FIFO0 + 2 * slot);
+            fifo_fpam = ST(VF_FIFO0 + 2 * slot + 1);
             ST(VF_FIFO0 + 2 * slot) = new_rail;
             ST(VF_FIFO0 + 2 * slot + 1) = new_fpam;
         }
-        if (P.flags & VINE_FLAG_FORCE_U_FPAM) u_fpam = 0.0f;
-        if (P.flags & VINE_FLAG_FORCE_U_RAIL_VELOCITY) u_rail = 0.0f;
         float smoothed = ST(VF_SMOOTHED_U);
-        {
-            float alpha = (u_fpam > smoothed) ? P.alpha_inf : P.alpha_def;
-            smoothed = alpha * smoothed + (1.0f - alpha) * u_fpam;
-        }
+        float u_rail, u_fpam;
+        task_command_in_effect(P, new_rail, new_fpam, fifo_rail, fifo_fpam, smoothed, u_rail, u_fpam);
         float q[ND], qd[ND], prev_q[ND];
 #pragma unroll
         for (int i = 0; i < ND; ++i) {
@@ -835,54 +967,17 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
         // ---- control_freq_inv x [refresh, actuation (V5:1028-1106), simulate] (vec_task.py:338-356) ----
         for (int it = 0; it < P.cfi; ++it) {
             float sc[20];
-            if (RANDOMIZE && P.dyn_span != 0.0f) {
-                // 20 factors from 3 Philox calls: 16-bit uniforms, two per 32-bit word
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    unsigned r[4];
-                    rng4(P, (unsigned)e, step, RNG_DYN_SCALE, (unsigned)(it * 3 + g), r);
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        if (g * 8 + k < 20) {
-                            const float u = (float)((r[k >> 1] >> (16 * (k & 1))) & 0xffffu) * (1.0f / 65536.0f);
-                            sc[g * 8 + k] = P.dyn_min + P.dyn_span * u;
-                        }
-                    }
-                }
-            } else if (RANDOMIZE) {
-#pragma unroll
-                for (int k = 0; k < 20; ++k) sc[k] = P.dyn_min;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 20; ++k) sc[k] = 1.0f;
-            }
+            task_dyn_scales<RANDOMIZE>(P, (unsigned)e, step, it, sc);
             float eff[ND], cj[ND], hc[ND];
             cj[0] = P.damping;
 #pragma unroll
             for (int j = 0; j < NL; ++j) {
-                float qj = (j == 0) ? s.th[0] : s.th[j] - s.th[j - 1];
-                float qdj = (j == 0) ? s.w[0] : s.w[j] - s.w[j - 1];
-                float t = P.K[j] * sc[j] * qj;
-                float cv = P.C[j] * sc[5 + j];
-                if (held) t += cv * qdj;
-                t += P.bb[j] * sc[10 + j];
-                t += P.B[j] * sc[15 + j] * u_used;
-                eff[j + 1] = (P.eff_lim > 0.0f) ? clampf(-t, P.eff_lim) : -t;
-                cj[j + 1] = P.damping + (held ? 0.0f : cv);
+                const float qj = (j == 0) ? s.th[0] : s.th[j] - s.th[j - 1];
+                const float qdj = (j == 0) ? s.w[0] : s.w[j] - s.w[j - 1];
+                task_joint_torque(P, P.K[j], P.C[j], P.bb[j], P.B[j], sc[j], sc[5 + j], sc[10 + j], sc[15 + j], qj, qdj, u_used,
+                                  held, eff[j + 1], cj[j + 1]);
             }
-            {
-                float err = u_rail - cart_vy;
-                float fmax = P.rail_acc * 0.5f;
-                float minmax = (err > 0.0f) ? fmax : -fmax;
-                float accel = (cart_vy - pcv) * P.inv_dt;
-                float accel_target = (err > 0.0f) ? P.rail_acc : -P.rail_acc;
-                minmax += 0.30f * (accel_target - accel);
-                float pid = P.p_gain * err + P.d_gain * (err - pce);
-                eff[0] = (fabsf(err) > 0.1f) ? minmax : pid;
-                pce = err;
-                pcv = cart_vy;
-                rail_force = eff[0];
-            }
+            eff[0] = rail_force = task_rail_force(P, u_rail, cart_vy, pcv, pce);
 #pragma unroll
             for (int i = 0; i < ND; ++i) hc[i] = P.hsub * cj[i];
             float qa[ND] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -1009,13 +1104,8 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
                 o[k++] = q[0];
                 o[k++] = (q[0] - prev_q[0]) * P.inv_cdt;
             }
-            o[k++] = 0.0f; o[k++] = tip[0]; o[k++] = tip[1];
-            o[k++] = 0.0f; o[k++] = fd_tip_y; o[k++] = fd_tip_z;
-            o[k++] = 0.0f; o[k++] = ty; o[k++] = tz;
-            o[k++] = 0.0f; o[k++] = 0.0f; o[k++] = 0.0f;
-            o[k++] = smoothed; o[k++] = prev_u_rail; o[k++] = obj_depth; o[k++] = obj_angle;
-#pragma unroll
-            for (int i = 0; i < NOBS; ++i) o[i] = o[i] * P.inv_obs_scale[i];
+            task_obs_tail_and_scale<NOBS>(P, o, tip[0], tip[1], fd_tip_y, fd_tip_z, ty, tz, smoothed, prev_u_rail, obj_depth,
+                                          obj_angle);
         }
         if (RANDOMIZE && P.obs_noise != 0.0f) {
 #pragma unroll
@@ -1030,40 +1120,12 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
                     if (i + j < NOBS) o[i + j] += P.obs_noise * nn[j];
             }
         }
-        // compute_reward (V5:1218-1331) + compute_reward_jit (V5:1470-1537)
-        const float dy = tip[0] - ty, dz = tip[1] - tz;
-        const float dist = sqrtf(dy * dy + dz * dz);
-        const bool reached = dist < P.success_dist;
-        const bool limit_hit = (cart_y > P.soft_limit) || (cart_y < -P.soft_limit);
-        const bool tip_limit_hit = tip[0] < ty;
-        const float cmean = SHELF ? contact_sum / (float)P.cfi : 0.0f;      // V5:1242-1248
-        const float vnorm = sqrtf(tip[2] * tip[2] + tip[3] * tip[3]);
-        float rm[VINE_NUM_REWARDS];
-        rm[0] = -dist;
-        rm[1] = -1.0f;
-        rm[2] = reached ? 1000.0f : 0.0f;
-        rm[3] = -(reached ? vnorm : 0.0f);
-        rm[4] = vnorm;
-        rm[5] = -fabsf(u_rail);
-        rm[6] = -fabsf(u_fpam);
-        rm[7] = -fabsf(u_rail - prev_u_rail);
-        rm[8] = -fabsf(u_fpam - smoothed);
-        rm[9] = limit_hit ? -100.0f : 0.0f;
-        rm[10] = -fabsf(cart_y);
-        rm[11] = tip_limit_hit ? -100.0f : 0.0f;
-        rm[12] = -((cmean > 0.0f) ? cmean : 0.0f);
-        float total = 0.0f;
-#pragma unroll
-        for (int i = 0; i < VINE_NUM_REWARDS; ++i) total += rm[i] * P.rw[i];
+        // compute_reward, compute_reset, the time-out flag of VecTask.step's epilogue
+        float rm[VINE_NUM_REWARDS], total, cmean;
+        unsigned char to;
+        task_reward_and_reset<SHELF>(P, tip[0], tip[1], tip[2], tip[3], ty, tz, cart_y, u_rail, u_fpam, prev_u_rail, smoothed,
+                                     contact_sum, prog, rm, total, cmean, rst, to);
         agg += total;
-        // compute_reset_jit (V5:1540-1558)
-        if (prog >= (long long)P.max_len - 1) rst = 1;
-        if (reached && (P.flags & VINE_FLAG_USE_TARGET_REACHED_RESET)) rst = 1;
-        if (tip_limit_hit && (P.flags & VINE_FLAG_USE_TIP_LIMIT_HIT_RESET)) rst = 1;
-        if (limit_hit) rst = 1;
-        if (SHELF && cmean > 0.0f && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) rst = 1;
-        // ---- VecTask.step epilogue (vec_task.py:366-380) ----
-        const unsigned char to = (prog >= (long long)P.max_len - 1) && (rst != 0);
         float* orow = obs + (size_t)e * NOBS;
         if (NOBS % 4 == 0) {
 #pragma unroll
@@ -1086,17 +1148,8 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
         // persistent state
         ST(VF_TIP_Y) = tip[0]; ST(VF_TIP_Z) = tip[1];
         ST(VF_CART_Y) = cart_y; ST(VF_CART_VY) = cart_vy;
-        ST(VF_SMOOTHED_U) = smoothed;
-        ST(VF_PREV_CART_VEL) = pcv; ST(VF_PREV_CART_VEL_ERR) = pce;
-        ST(VF_AGG_REW) = agg;
-        if (SHELF) ST(VF_CONTACT) = contact;
-        if (introspect) {
-            ST(VF_TIP_VY) = tip[2]; ST(VF_TIP_VZ) = tip[3];
-            ST(VF_PREV_TIP_Y) = prev_tip_y; ST(VF_PREV_TIP_Z) = prev_tip_z;
-            ST(VF_U_FPAM) = u_fpam; ST(VF_U_RAIL) = u_rail; ST(VF_PREV_U_RAIL) = prev_u_rail;
-            ST(VF_RAIL_FORCE) = rail_force;
-            if (SHELF) ST(VF_CONTACT_MEAN) = cmean;
-        }
+        store_step_state<SHELF>(P, st, n, e, smoothed, pcv, pce, agg, contact, tip[2], tip[3], prev_tip_y, prev_tip_z, u_fpam,
+                                u_rail, prev_u_rail, rail_force, cmean);
     }
     step_arrive(counters);
 }
@@ -1328,22 +1381,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         }
         // dynamics-scaling factors: lane i draws the 20 factors of control iteration i (V5:1053-1055)
         float scl[20];
-        if (RANDOMIZE && P.dyn_span != 0.0f) {
-#pragma unroll
-            for (int g = 0; g < 3; ++g) {
-                unsigned r[4];
-                rng4(P, (unsigned)e, step, RNG_DYN_SCALE, (unsigned)(t * 3 + g), r);
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (g * 8 + k < 20) {
-                        const float u = (float)((r[k >> 1] >> (16 * (k & 1))) & 0xffffu) * (1.0f / 65536.0f);
-                        scl[g * 8 + k] = P.dyn_min + P.dyn_span * u;
-                    }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 20; ++k) scl[k] = RANDOMIZE ? P.dyn_min : 1.0f;
-        }
+        task_dyn_scales<RANDOMIZE>(P, (unsigned)e, step, t, scl);
 #ifdef VSQ_TIMING
         if ((threadIdx.x & 63) == 0) vsq_t[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 3] = wall_clock64();
 #endif
@@ -1396,27 +1434,12 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
             }
         }
         // ---- VecTask.step: clamp actions (vec_task.py:333); pre_physics_step (V5:922-945), replicated on the quad
-        float a0 = clampf(act.x, P.clip_act), a1 = clampf(act.y, P.clip_act);
-        if (RANDOMIZE && P.act_noise != 0.0f) {
-            a0 += P.act_noise * an0;
-            a1 += P.act_noise * an1;
-        }
-        const float new_rail = a0 * P.rail_scale;
-        const float new_fpam = (a1 + 1.0f) * 0.5f * P.fpam_span + P.fpam_min;
-        float u_rail = new_rail, u_fpam = new_fpam;
-        if (P.delay > 0) {
-            u_rail = fifo_rail;
-            u_fpam = fifo_fpam;
-            if (t == 0) {
-                ST(VF_FIFO0 + 2 * fifo_slot) = new_rail;
-                ST(VF_FIFO0 + 2 * fifo_slot + 1) = new_fpam;
-            }
-        }
-        if (P.flags & VINE_FLAG_FORCE_U_FPAM) u_fpam = 0.0f;
-        if (P.flags & VINE_FLAG_FORCE_U_RAIL_VELOCITY) u_rail = 0.0f;
-        {
-            const float alpha = (u_fpam > smoothed) ? P.alpha_inf : P.alpha_def;
-            smoothed = alpha * smoothed + (1.0f - alpha) * u_fpam;
+        float new_rail, new_fpam, u_rail, u_fpam;
+        task_new_command<RANDOMIZE>(P, act, an0, an1, new_rail, new_fpam);
+        task_command_in_effect(P, new_rail, new_fpam, fifo_rail, fifo_fpam, smoothed, u_rail, u_fpam);
+        if (P.delay > 0 && t == 0) {
+            ST(VF_FIFO0 + 2 * fifo_slot) = new_rail;
+            ST(VF_FIFO0 + 2 * fifo_slot + 1) = new_fpam;
         }
         const float prev_q_own = q_own, prev_q5 = q5, prev_y = y;
         const bool introspect = (P.flags & VINE_FLAG_INTROSPECT) != 0;
@@ -1494,43 +1517,20 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         auto quad_simulate = [&](float sK, float sC, float sb, float sB, float sK4, float sC4, float sb4, float sB4) {
             // FPAM torque model of joint t (own) and joint 4 (replicated)
             const float qj = th - pick(t > 0, qprev(th), 0.0f), qdj = w - pick(t > 0, qprev(w), 0.0f);
-            float tq = K_t * sK * qj;
-            const float cv = C_t * sC;
-            if (held) tq += cv * qdj;
-            tq += bb_t * sb;
-            tq += B_t * sB * u_used;
-            const float eff_t = (P.eff_lim > 0.0f) ? clampf(-tq, P.eff_lim) : -tq, cj_t = P.damping + (held ? 0.0f : cv);
+            float eff_t, cj_t, eff4, cj4;
+            task_joint_torque(P, K_t, C_t, bb_t, B_t, sK, sC, sb, sB, qj, qdj, u_used, held, eff_t, cj_t);
             const float q5r = th4 - qbcast<3>(th), qd5r = w4 - qbcast<3>(w);
-            float tq4 = P.K[4] * sK4 * q5r;
-            const float cv4 = P.C[4] * sC4;
-            if (held) tq4 += cv4 * qd5r;
-            tq4 += P.bb[4] * sb4;
-            tq4 += P.B[4] * sB4 * u_used;
-            const float eff4 = (P.eff_lim > 0.0f) ? clampf(-tq4, P.eff_lim) : -tq4, cj4 = P.damping + (held ? 0.0f : cv4);
-            float eff0;
-            {   // rail controller (V5:1069-1098), replicated
-                const float err = u_rail - cart_vy;
-                const float fmax = P.rail_acc * 0.5f;
-                float minmax = (err > 0.0f) ? fmax : -fmax;
-                const float accel = (cart_vy - pcv) * P.inv_dt;
-                const float accel_target = (err > 0.0f) ? P.rail_acc : -P.rail_acc;
-                minmax += 0.30f * (accel_target - accel);
-                const float pid = P.p_gain * err + P.d_gain * (err - pce);
-                eff0 = (fabsf(err) > 0.1f) ? minmax : pid;
-                pce = err;
-                pcv = cart_vy;
-                rail_force = eff0;
-            }
+            task_joint_torque(P, P.K[4], P.C[4], P.bb[4], P.B[4], sK4, sC4, sb4, sB4, q5r, qd5r, u_used, held, eff4, cj4);
+            const float eff0 = rail_force = task_rail_force(P, u_rail, cart_vy, pcv, pce);      // (replicated)
             // constants of this simulate: implicit damping folded into the matrix (tridiagonal in the absolute angles)
             const float cj0 = P.damping;
-            const float hc_t = h * cj_t, hc4 = h * cj4, hc0 = h * cj0;
+            const float hc_t = h * cj_t, hc4 = h * cj4;
             const float hc_n = pick(t == 3, hc4, qnext(hc_t));                 // damping of the joint BEYOND link t
             float nbase[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) nbase[k] = t == k ? hc_t + hc_n : (t == k + 1 ? -hc_t : (t == k - 1 ? -hc_n : 0.0f));
             const float nb4 = t == 3 ? -hc4 : 0.0f;
             const float adiag4 = a44 + hc4;
-            (void)hc0;
             if (SHELF) contact_sum += contact;            // vec_task.py:348-351: force left by the previous simulate
             float csum = 0.0f;
             for (int ss = 0; ss < P.substeps; ++ss) {
@@ -1559,7 +1559,10 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                     // (measured at 16384 envs: the split pays for the pipe -- a reaching vine has links 3 and 4 INSIDE the tube:
                     // default-config training rollout 5.06 -> 4.66 ms -- while the shelf is touched by link 4 almost alone:
                     // there link 3 stays with its own lane (random policy 85 us; with link 3 split as well 95 us))
-                    float cs3y = 0.0f, cs3z = 0.0f, cms3 = 0.0f, s3y = 0.0f, s3z = 0.0f;      // link 3's shelf share (cooperative form)
+                    float s3y = 0.0f, s3z = 0.0f;                      // link 3's shelf share (cooperative form)
+#if VSQ_SHELF_COOP_FROM <= 3
+                    float cs3y = 0.0f, cs3z = 0.0f, cms3 = 0.0f;
+#endif
                     if (SHELF) {
 #if VSQ_SHELF_COOP_FROM <= 3
                         if (t < 3) shelf_link_contact(P, z0, z1, py, pz, pvy, pvz, sn, cs, w, shelf_y, shelf_z, fy, fz, mom, sfy, sfz);
@@ -1569,7 +1572,12 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
 #endif
                         shelf_link_contact_coop(P, t, 0.0f, L, p4y, p4z, pv4y, pv4z, sn4, cs4, w4, shelf_y, shelf_z, c4y, c4z, cm4, s4y, s4z);
                     }
-                    float c2y = 0.0f, c2z = 0.0f, cm2 = 0.0f, c1y = 0.0f, c1z = 0.0f, cm1 = 0.0f;
+#if VSQ_PIPE_COOP_FROM <= 2
+                    float c2y = 0.0f, c2z = 0.0f, cm2 = 0.0f;
+#endif
+#if VSQ_PIPE_COOP_FROM <= 1
+                    float c1y = 0.0f, c1z = 0.0f, cm1 = 0.0f;
+#endif
                     if (PIPE) {
                         // broad phase: link t's on lane t (z0 = 0, z1 = L for t >= 1), link 4's on every lane; two bits per
                         // link, broadcast over the quad to the lanes that share a cooperative link's narrow phase
@@ -1742,57 +1750,39 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         long long prog = prog_in + 1;
         const bool was_reset = rst != 0;
         if (rst != 0) {      // reset_idx (V5:774-839, 887-914): a quad-uniform branch
-            const float ten = 0.17453292519943295f;
-            float qn1_4[4], qn5, qn0, depth, pdepth;
+            unsigned r0[4] = {0u, 0u, 0u, 0u}, r1[4] = {0u, 0u, 0u, 0u}, r2[4] = {0u, 0u, 0u, 0u};
+            float qn[ND], depth, pdepth;
             if (reset_values) {
-                const float* v = reset_values + (size_t)e * 10;
-                qn1_4[0] = v[0]; qn1_4[1] = v[1]; qn1_4[2] = v[2]; qn1_4[3] = v[3];
-                qn5 = v[4]; qn0 = v[5]; pdepth = v[6]; ty = v[7]; tz = v[8]; depth = v[9];
+                task_reset_pose(P, reset_values + (size_t)e * 10, r0, r1, r2, qn, ty, tz, depth, pdepth);
             } else {
-                // lanes 0..2 draw one Philox word quadruple each; the ten uniforms are then broadcast
+                // lanes 0..2 draw one Philox word quadruple each; the words are then broadcast
                 unsigned r[4];
                 rng4(P, (unsigned)e, step, RNG_RESET, (unsigned)(t < 3 ? t : 0), r);
-                qn1_4[0] = -ten + (2.0f * ten) * u01(qbcast_u<0>(r[0]));
-                qn1_4[1] = -ten + (2.0f * ten) * u01(qbcast_u<0>(r[1]));
-                qn1_4[2] = -ten + (2.0f * ten) * u01(qbcast_u<0>(r[2]));
-                qn1_4[3] = -ten + (2.0f * ten) * u01(qbcast_u<0>(r[3]));
-                qn5 = -ten + (2.0f * ten) * u01(qbcast_u<1>(r[0]));
-                qn0 = P.cart_min + P.cart_span * u01(qbcast_u<1>(r[1]));
-                pdepth = P.depth_min + P.depth_span * u01(qbcast_u<1>(r[2]));
-                ty = P.ty_min + P.ty_span * u01(qbcast_u<1>(r[3]));
-                tz = P.tz_min + P.tz_span * u01(qbcast_u<2>(r[0]));
-                depth = P.depth_min + P.depth_span * u01(qbcast_u<2>(r[1]));
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { r0[i] = qbcast_u<0>(r[i]); r1[i] = qbcast_u<1>(r[i]); r2[i] = qbcast_u<2>(r[i]); }
+                task_reset_pose(P, nullptr, r0, r1, r2, qn, ty, tz, depth, pdepth);
             }
-            if (!(P.flags & VINE_FLAG_RANDOMIZE_DOF_INIT)) {
-                qn1_4[0] = qn1_4[1] = qn1_4[2] = qn1_4[3] = 0.0f; qn5 = 0.0f; qn0 = 0.0f;
-            }
-            if (!(P.flags & VINE_FLAG_RANDOMIZE_TARGETS)) { ty = P.ty_max; tz = P.tz_fixed; }
-            (void)depth; (void)pdepth;
+            // obstacle poses of the new episode; the observation row shows the new episode's depth / angle
+            const ObstaclePoses op = task_obstacle_poses(SHELF, PIPE, ty, tz, depth, pdepth);
             if (SHELF) obj_depth = depth;
-            if (SHELF && t == 0) {             // obstacle poses of the new episode (reset_env's arithmetic, V5:818-885)
-                ST(VF_SHELF_Y) = ty + (-0.2f + depth);
-                ST(VF_SHELF_Z) = tz - 0.01f;
+            if (SHELF && t == 0) {
+                ST(VF_SHELF_Y) = op.shelf_y;
+                ST(VF_SHELF_Z) = op.shelf_z;
                 ST(VF_OBJ_DEPTH) = depth;
             }
             if (PIPE) {
-                const float R = 0.0735f;             // PIPE_RADIUS = 0.07 * 1.05 (V5:88)
-                const float ez = 1.0f - tz;
-                const float deg = ((13199.0f * ez - 12276.0f) * ez + 4045.0f) * ez - 447.0f;
-                const float tp = deg * 0.017453292519943295f;
-                float stp, ctp;
-                sincosf(tp, &stp, &ctp);
-                obj_depth = pdepth; obj_angle = tp;      // (what the observation row shows: the new episode's)
+                obj_depth = pdepth; obj_angle = op.pipe_angle;
                 if (t == 0) {
-                    ST(VF_PIPE_Y) = ty + pdepth * ctp + R * stp;
-                    ST(VF_PIPE_Z) = tz + pdepth * stp - R * ctp;
+                    ST(VF_PIPE_Y) = op.pipe_y;
+                    ST(VF_PIPE_Z) = op.pipe_z;
                     ST(VF_OBJ_DEPTH) = pdepth;
-                    ST(VF_OBJ_ANGLE) = tp;
+                    ST(VF_OBJ_ANGLE) = op.pipe_angle;
                 }
             }
             rst = 0;
             prog = 0;
-            q_own = sel4(t, qn1_4[0], qn1_4[1], qn1_4[2], qn1_4[3]);
-            q5 = qn5; q0 = qn0;
+            q_own = sel4(t, qn[1], qn[2], qn[3], qn[4]);
+            q5 = qn[5]; q0 = qn[0];
             qd_own = 0.0f; qd5 = 0.0f; qd0 = 0.0f;
             prev_qo = q_own; prev_q5v = q5; prev_q0 = q0;
             ST(VF_Q0 + 1 + t) = q_own; ST(VF_QD0 + 1 + t) = 0.0f; ST(VF_PREV_Q0 + 1 + t) = q_own;
@@ -1848,13 +1838,8 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                 o[k++] = q0;
                 o[k++] = (q0 - prev_q0) * P.inv_cdt;
             }
-            o[k++] = 0.0f; o[k++] = tip_y; o[k++] = tip_z;
-            o[k++] = 0.0f; o[k++] = fd_tip_y; o[k++] = fd_tip_z;
-            o[k++] = 0.0f; o[k++] = ty; o[k++] = tz;
-            o[k++] = 0.0f; o[k++] = 0.0f; o[k++] = 0.0f;
-            o[k++] = smoothed; o[k++] = prev_u_rail; o[k++] = obj_depth; o[k++] = obj_angle;
-#pragma unroll
-            for (int i = 0; i < NOBS; ++i) o[i] = o[i] * P.inv_obs_scale[i];
+            task_obs_tail_and_scale<NOBS>(P, o, tip_y, tip_z, fd_tip_y, fd_tip_z, ty, tz, smoothed, prev_u_rail, obj_depth,
+                                          obj_angle);
 #pragma unroll
             for (int i = NOBS; i < 32; ++i) o[i] = 0.0f;
         }
@@ -1885,37 +1870,11 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         if ((threadIdx.x & 63) == 0) vsq_t[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 6] = wall_clock64();
 #endif
         // ---- compute_reward (V5:1218-1331, 1470-1537), compute_reset (V5:1540-1558): replicated, lane 0 stores
-        const float dy = tip_y - ty, dz = tip_z - tz;
-        const float dist = sqrtf(dy * dy + dz * dz);
-        const bool reached = dist < P.success_dist;
-        const bool limit_hit = (cart_y > P.soft_limit) || (cart_y < -P.soft_limit);
-        const bool tip_limit_hit = tip_y < ty;
-        const float vnorm = sqrtf(tip_vy * tip_vy + tip_vz * tip_vz);
-        const float cmean = SHELF ? contact_sum / (float)P.cfi : 0.0f;      // V5:1242-1248
-        float rm[VINE_NUM_REWARDS];
-        rm[0] = -dist;
-        rm[1] = -1.0f;
-        rm[2] = reached ? 1000.0f : 0.0f;
-        rm[3] = -(reached ? vnorm : 0.0f);
-        rm[4] = vnorm;
-        rm[5] = -fabsf(u_rail);
-        rm[6] = -fabsf(u_fpam);
-        rm[7] = -fabsf(u_rail - prev_u_rail);
-        rm[8] = -fabsf(u_fpam - smoothed);
-        rm[9] = limit_hit ? -100.0f : 0.0f;
-        rm[10] = -fabsf(cart_y);
-        rm[11] = tip_limit_hit ? -100.0f : 0.0f;
-        rm[12] = -((cmean > 0.0f) ? cmean : 0.0f);
-        float total = 0.0f;
-#pragma unroll
-        for (int i = 0; i < VINE_NUM_REWARDS; ++i) total += rm[i] * P.rw[i];
+        float rm[VINE_NUM_REWARDS], total, cmean;
+        unsigned char to;
+        task_reward_and_reset<SHELF>(P, tip_y, tip_z, tip_vy, tip_vz, ty, tz, cart_y, u_rail, u_fpam, prev_u_rail, smoothed,
+                                     contact_sum, prog, rm, total, cmean, rst, to);
         agg += total;
-        if (prog >= (long long)P.max_len - 1) rst = 1;
-        if (reached && (P.flags & VINE_FLAG_USE_TARGET_REACHED_RESET)) rst = 1;
-        if (tip_limit_hit && (P.flags & VINE_FLAG_USE_TIP_LIMIT_HIT_RESET)) rst = 1;
-        if (limit_hit) rst = 1;
-        if (SHELF && cmean > 0.0f && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) rst = 1;
-        const unsigned char to = (prog >= (long long)P.max_len - 1) && (rst != 0);
         if (t == 0) {
             rew[e] = total;
             reset[e] = rst;
@@ -1929,17 +1888,8 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                 ST(VF_TIP_Y) = tip_y; ST(VF_TIP_Z) = tip_z;
                 ST(VF_CART_Y) = cart_y; ST(VF_CART_VY) = cart_vy;
             }
-            ST(VF_SMOOTHED_U) = smoothed;
-            ST(VF_PREV_CART_VEL) = pcv; ST(VF_PREV_CART_VEL_ERR) = pce;
-            ST(VF_AGG_REW) = agg;
-            if (SHELF) ST(VF_CONTACT) = contact;
-            if (introspect) {
-                ST(VF_TIP_VY) = tip_vy; ST(VF_TIP_VZ) = tip_vz;
-                ST(VF_PREV_TIP_Y) = prev_tip_y; ST(VF_PREV_TIP_Z) = prev_tip_z;
-                ST(VF_U_FPAM) = u_fpam; ST(VF_U_RAIL) = u_rail; ST(VF_PREV_U_RAIL) = prev_u_rail;
-                ST(VF_RAIL_FORCE) = rail_force;
-                if (SHELF) ST(VF_CONTACT_MEAN) = cmean;
-            }
+            store_step_state<SHELF>(P, st, n, e, smoothed, pcv, pce, agg, contact, tip_vy, tip_vz, prev_tip_y, prev_tip_z, u_fpam,
+                                    u_rail, prev_u_rail, rail_force, cmean);
         }
         if (ROLL) {
             // ---- vine_rollout_post's bookkeeping (play_steps_rnn; common_agent.py:293-306): shaped reward with the time-out
@@ -2275,6 +2225,92 @@ struct DeviceGuard {
         if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
     }
 };
+
+#ifndef VSQ_THREADS
+#define VSQ_THREADS 256      // threads per workgroup of the four-lane step kernel (A/B: 64 / 128)
+#endif
+
+// ---- the step launch: which kernel, which instantiation, what has to happen first.  vine_step and vine_step_rollout
+// share all of it.
+int obstacle_mask(const VineHandle* h) {      // the kernels' OBST: bit 0 shelf, bit 1 pipe
+    return ((h->P.flags & VINE_FLAG_CREATE_SHELF) ? 1 : 0) | ((h->P.flags & VINE_FLAG_CREATE_PIPE) ? 2 : 0);
+}
+
+// Four lanes per env (vine_step_quad_kernel) where the chip would otherwise be three quarters empty, for the
+// configurations that kernel covers.  Measured (profiles/r02/step_kernels.txt): 4096 envs 30.7 -> 23.6 us, 16384 envs
+// 32.5 -> 30.2 us, 32768 envs 35.3 -> 43.4 us: up to 16384 envs the quad kernel, beyond one lane per env.
+bool use_quad_kernel(const VineHandle* h) {
+    const bool quad_ok = h->P.cfi == 4 && (h->P.flags & VINE_FLAG_IMPLICIT_JOINT_DAMPING) && h->P.kq == 0.0f &&
+                         h->P.cad == 0.0f && (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO ||
+                                              h->P.obs_type == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO);
+    return quad_ok && (h->step_kernel == 2 || (h->step_kernel == 0 && h->P.n <= 16384));
+}
+
+// log2 of the step launch's grid: the workgroups the kernel needs, rounded up to a power of two (see step_of(); the
+// workgroups past the last env find no live lane and only report their arrival)
+int step_grid_log2(const VineHandle* h) {
+    const long long blocks = use_quad_kernel(h) ? ((long long)h->P.n * 4 + VSQ_THREADS - 1) / VSQ_THREADS
+                                                : ((long long)h->P.n + VINE_STEP_THREADS - 1) / VINE_STEP_THREADS;
+    int l = 0;
+    while ((1ll << l) < blocks) ++l;
+    return l;
+}
+
+// What precedes a step launch: the step count re-based on the grid size if the kernel choice changed since the counters
+// were last normalised (it cannot with the present switches, all of which are fixed at creation), and the lazily stored
+// body states refreshed if introspection was switched on since the last step.
+int prepare_step_launch(VineHandle* h, const int64_t* progress, hipStream_t s) {
+    if (step_grid_log2(h) != h->P.glog) {
+        const int64_t now = vine_get_step_count(h);
+        if (now < 0) return fail(VINE_ERR_DEVICE, "step count unreadable");
+        h->P.glog = step_grid_log2(h);
+        const int rc = vine_set_step_count(h, now);
+        if (rc != VINE_OK) return rc;
+    }
+    if (h->refresh_body) {
+        h->refresh_body = false;
+        hipLaunchKernelGGL(vine_refresh_body_kernel, dim3((h->P.n + 255) / 256), dim3(256), 0, s, h->P, h->state,
+                           (const long long*)progress);
+    }
+    return VINE_OK;
+}
+
+// The one map from a configuration to a step-kernel instantiation: calls f(OBS_TYPE, RANDOMIZE, OBST) with the handle's
+// observation layout, randomisation switch and obstacle mask as std::integral_constant values.
+template <class F>
+void with_step_instantiation(const VineHandle* h, F&& f) {
+    const bool rnd = (h->P.flags & VINE_FLAG_VINE_RANDOMIZE) != 0;
+    const int obst = obstacle_mask(h);
+    auto with_obst = [&](auto ot, auto rn) {
+        if (obst == 0) f(ot, rn, std::integral_constant<int, 0>{});
+        else if (obst == 1) f(ot, rn, std::integral_constant<int, 1>{});
+        else if (obst == 2) f(ot, rn, std::integral_constant<int, 2>{});
+        else f(ot, rn, std::integral_constant<int, 3>{});
+    };
+    auto with_rnd = [&](auto ot) {
+        if (rnd) with_obst(ot, std::true_type{});
+        else with_obst(ot, std::false_type{});
+    };
+    if (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO) with_rnd(std::integral_constant<int, VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO>{});
+    else if (h->P.obs_type == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO) with_rnd(std::integral_constant<int, VINE_OBS_TIP_AND_CART_AND_OBJ_INFO>{});
+    else if (h->P.obs_type == VINE_OBS_POS_ONLY) with_rnd(std::integral_constant<int, VINE_OBS_POS_ONLY>{});
+    else with_rnd(std::integral_constant<int, VINE_OBS_POS_AND_VEL>{});    // the 26-column family, resolved inside the kernel
+}
+
+// The four-lane kernel, plain (ROLL = false) or with the rollout's policy head and bookkeeping around the step.
+template <bool ROLL>
+void launch_quad_step(VineHandle* h, const float* actions, float* obs, float* rew, int64_t* reset, int64_t* progress,
+                      uint8_t* timeouts, const RollArgs& R, hipStream_t s) {
+    with_step_instantiation(h, [&](auto ot, auto rn, auto ob) {
+        constexpr int OT = decltype(ot)::value;
+        // (use_quad_kernel admits the two scalable layouts only; the kernel is not instantiated for the others)
+        if constexpr (OT == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO || OT == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO)
+            hipLaunchKernelGGL((vine_step_quad_kernel<OT, decltype(rn)::value, decltype(ob)::value, ROLL>), dim3(1 << h->P.glog),
+                               dim3(VSQ_THREADS), 0, s, h->P, h->state, actions, obs, rew, (long long*)reset,
+                               (long long*)progress, (unsigned char*)timeouts, h->reward_matrix, h->reset_values, h->counters,
+                               R);
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -2357,11 +2393,6 @@ int vine_num_obs(const VineConfig* c) {
     return fail(VINE_ERR_INVALID_ARG, "unknown observation type");
 }
 
-#ifndef VSQ_THREADS
-#define VSQ_THREADS 256      // threads per workgroup of the four-lane step kernel (A/B: 64 / 128)
-#endif
-static int step_grid_log2(const VineHandle* h);
-
 int vine_create(const VineConfig* cfg, int device_id, float* state_storage, VineHandle** out) {
     int rc = validate(cfg);
     if (rc) return rc;
@@ -2416,28 +2447,6 @@ void vine_destroy(VineHandle* h) {
     delete h;
 }
 
-// Four lanes per env (vine_step_quad_kernel) where the chip would otherwise be three quarters empty, for the
-// configurations that kernel covers.  Measured (profiles/r02/step_kernels.txt): 4096 envs 30.7 -> 23.6 us, 16384 envs
-// 32.5 -> 30.2 us, 32768 envs 35.3 -> 43.4 us: up to 16384 envs the quad kernel, beyond one lane per env.
-static bool use_quad_kernel(const VineHandle* h) {
-    const int obst = ((h->P.flags & VINE_FLAG_CREATE_SHELF) ? 1 : 0) | ((h->P.flags & VINE_FLAG_CREATE_PIPE) ? 2 : 0);
-    (void)obst;      // (obstacles are covered since round 3: lane t evaluates link t's contacts)
-    const bool quad_ok = h->P.cfi == 4 && (h->P.flags & VINE_FLAG_IMPLICIT_JOINT_DAMPING) && h->P.kq == 0.0f &&
-                         h->P.cad == 0.0f && (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO ||
-                                              h->P.obs_type == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO);
-    return quad_ok && (h->step_kernel == 2 || (h->step_kernel == 0 && h->P.n <= 16384));
-}
-
-// log2 of the step launch's grid: the workgroups the kernel needs, rounded up to a power of two (see step_of(); the
-// workgroups past the last env find no live lane and only report their arrival)
-static int step_grid_log2(const VineHandle* h) {
-    const long long blocks = use_quad_kernel(h) ? ((long long)h->P.n * 4 + VSQ_THREADS - 1) / VSQ_THREADS
-                                                : ((long long)h->P.n + VINE_STEP_THREADS - 1) / VINE_STEP_THREADS;
-    int l = 0;
-    while ((1ll << l) < blocks) ++l;
-    return l;
-}
-
 const char* vine_step_kernel_name(VineHandle* h) {
     if (!h) return "";
     return use_quad_kernel(h) ? "vine_step_quad_kernel" : "vine_step_kernel";
@@ -2448,73 +2457,19 @@ int vine_step(VineHandle* h, const float* actions, float* obs, float* rew, int64
     if (!h || !actions || !obs || !rew || !reset || !progress || !timeouts)
         return fail(VINE_ERR_INVALID_ARG, "null argument to vine_step");
     DeviceGuard guard(h->device);
-    const int threads = VINE_STEP_THREADS;
     hipStream_t s = (hipStream_t)stream;
-    if (step_grid_log2(h) != h->P.glog) {
-        // (the kernel choice changed since the counters were last normalised -- it cannot with the present switches, all of
-        // which are fixed at creation: re-base the step count on the new grid size)
-        const int64_t now = vine_get_step_count(h);
-        if (now < 0) return fail(VINE_ERR_DEVICE, "step count unreadable");
-        h->P.glog = step_grid_log2(h);
-        const int rc = vine_set_step_count(h, now);
-        if (rc != VINE_OK) return rc;
-    }
-    const int blocks = 1 << h->P.glog;
-    const bool rnd = (h->P.flags & VINE_FLAG_VINE_RANDOMIZE) != 0;
-    const int obst = ((h->P.flags & VINE_FLAG_CREATE_SHELF) ? 1 : 0) | ((h->P.flags & VINE_FLAG_CREATE_PIPE) ? 2 : 0);
-    if (h->refresh_body) {
-        h->refresh_body = false;
-        hipLaunchKernelGGL(vine_refresh_body_kernel, dim3((h->P.n + 255) / 256), dim3(256), 0, s, h->P, h->state,
-                           (const long long*)progress);
-    }
+    const int rc = prepare_step_launch(h, progress, s);
+    if (rc != VINE_OK) return rc;
     if (use_quad_kernel(h)) {
-        const int qblocks = 1 << h->P.glog;
-#define LAUNCH_QUAD_O(OT, RND, OB)                                                                                         \
-    hipLaunchKernelGGL((vine_step_quad_kernel<OT, RND, OB, false>), dim3(qblocks), dim3(VSQ_THREADS), 0, s, h->P, h->state, actions, obs, rew, \
-                       (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,              \
-                       h->reset_values, h->counters, RollArgs{})
-#define LAUNCH_QUAD(OT, RND)                        \
-    do {                                            \
-        if (obst == 0) LAUNCH_QUAD_O(OT, RND, 0);   \
-        else if (obst == 1) LAUNCH_QUAD_O(OT, RND, 1); \
-        else if (obst == 2) LAUNCH_QUAD_O(OT, RND, 2); \
-        else LAUNCH_QUAD_O(OT, RND, 3);             \
-    } while (0)
-        if (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO) {
-            if (rnd) LAUNCH_QUAD(VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO, true);
-            else LAUNCH_QUAD(VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO, false);
-        } else {
-            if (rnd) LAUNCH_QUAD(VINE_OBS_TIP_AND_CART_AND_OBJ_INFO, true);
-            else LAUNCH_QUAD(VINE_OBS_TIP_AND_CART_AND_OBJ_INFO, false);
-        }
-#undef LAUNCH_QUAD
-#undef LAUNCH_QUAD_O
-        HIP_TRY(hipGetLastError());
-        return VINE_OK;
+        launch_quad_step<false>(h, actions, obs, rew, reset, progress, timeouts, RollArgs{}, s);
+    } else {
+        with_step_instantiation(h, [&](auto ot, auto rn, auto ob) {
+            hipLaunchKernelGGL((vine_step_kernel<decltype(ot)::value, decltype(rn)::value, decltype(ob)::value>),
+                               dim3(1 << h->P.glog), dim3(VINE_STEP_THREADS), 0, s, h->P, h->state, actions, obs, rew,
+                               (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,
+                               h->reset_values, h->counters);
+        });
     }
-#define LAUNCH(OT, RND, SH)                                                                                      \
-    hipLaunchKernelGGL((vine_step_kernel<OT, RND, SH>), dim3(blocks), dim3(threads), 0, s, h->P, h->state, actions, \
-                       obs, rew, (long long*)reset, (long long*)progress, (unsigned char*)timeouts,                 \
-                       h->reward_matrix, h->reset_values, h->counters)
-#define LAUNCH_RND(OT, RND)                  \
-    do {                                     \
-        if (obst == 0) LAUNCH(OT, RND, 0);   \
-        else if (obst == 1) LAUNCH(OT, RND, 1); \
-        else if (obst == 2) LAUNCH(OT, RND, 2); \
-        else LAUNCH(OT, RND, 3);             \
-    } while (0)
-#define LAUNCH_OT(OT)                        \
-    do {                                     \
-        if (rnd) LAUNCH_RND(OT, true);       \
-        else LAUNCH_RND(OT, false);          \
-    } while (0)
-    if (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO) LAUNCH_OT(VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO);
-    else if (h->P.obs_type == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO) LAUNCH_OT(VINE_OBS_TIP_AND_CART_AND_OBJ_INFO);
-    else if (h->P.obs_type == VINE_OBS_POS_ONLY) LAUNCH_OT(VINE_OBS_POS_ONLY);
-    else LAUNCH_OT(VINE_OBS_POS_AND_VEL);    // the 26-column family, resolved inside the kernel
-#undef LAUNCH_OT
-#undef LAUNCH_RND
-#undef LAUNCH
     HIP_TRY(hipGetLastError());
     return VINE_OK;
 }
@@ -2572,18 +2527,8 @@ int vine_step_rollout(VineHandle* h, const VineRolloutArgs* a, float* obs, float
     if (!use_quad_kernel(h)) return fail(VINE_ERR_UNSUPPORTED, "vine_step_rollout needs the four-lanes-per-env step kernel");
     DeviceGuard guard(h->device);
     hipStream_t s = (hipStream_t)stream;
-    if (step_grid_log2(h) != h->P.glog) {
-        const int64_t now = vine_get_step_count(h);
-        if (now < 0) return fail(VINE_ERR_DEVICE, "step count unreadable");
-        h->P.glog = step_grid_log2(h);
-        const int rc = vine_set_step_count(h, now);
-        if (rc != VINE_OK) return rc;
-    }
-    if (h->refresh_body) {
-        h->refresh_body = false;
-        hipLaunchKernelGGL(vine_refresh_body_kernel, dim3((h->P.n + 255) / 256), dim3(256), 0, s, h->P, h->state,
-                           (const long long*)progress);
-    }
+    const int rc = prepare_step_launch(h, progress, s);
+    if (rc != VINE_OK) return rc;
     RollArgs R;
     R.y = a->y; R.hw = a->hw; R.hc = a->hc; R.logstd = a->logstd; R.vmean = a->value_mean; R.vvar = a->value_var;
     R.ln_eps = a->ln_eps; R.veps = a->value_eps; R.seed_lo = (unsigned)a->seed; R.seed_hi = (unsigned)(a->seed >> 32);
@@ -2592,29 +2537,7 @@ int vine_step_rollout(VineHandle* h, const VineRolloutArgs* a, float* obs, float
     R.gamma_b = a->gamma_bootstrap; R.shaped = a->shaped_out; R.dones = a->dones_out; R.cur_r = a->cur_rewards;
     R.cur_l = a->cur_lengths; R.h_state = a->h_state; R.c_state = a->c_state; R.h_op = a->h_op; R.h_op_stride = a->h_op_stride;
     R.partial = a->partial;
-    const int qblocks = 1 << h->P.glog;
-    const bool rnd = (h->P.flags & VINE_FLAG_VINE_RANDOMIZE) != 0;
-    const int obst = ((h->P.flags & VINE_FLAG_CREATE_SHELF) ? 1 : 0) | ((h->P.flags & VINE_FLAG_CREATE_PIPE) ? 2 : 0);
-#define LAUNCH_ROLL_O(OT, RND, OB)                                                                                         \
-    hipLaunchKernelGGL((vine_step_quad_kernel<OT, RND, OB, true>), dim3(qblocks), dim3(VSQ_THREADS), 0, s, h->P, h->state, (const float*)nullptr, obs, rew, \
-                       (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,              \
-                       h->reset_values, h->counters, R)
-#define LAUNCH_ROLL(OT, RND)                        \
-    do {                                            \
-        if (obst == 0) LAUNCH_ROLL_O(OT, RND, 0);   \
-        else if (obst == 1) LAUNCH_ROLL_O(OT, RND, 1); \
-        else if (obst == 2) LAUNCH_ROLL_O(OT, RND, 2); \
-        else LAUNCH_ROLL_O(OT, RND, 3);             \
-    } while (0)
-    if (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO) {
-        if (rnd) LAUNCH_ROLL(VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO, true);
-        else LAUNCH_ROLL(VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO, false);
-    } else {
-        if (rnd) LAUNCH_ROLL(VINE_OBS_TIP_AND_CART_AND_OBJ_INFO, true);
-        else LAUNCH_ROLL(VINE_OBS_TIP_AND_CART_AND_OBJ_INFO, false);
-    }
-#undef LAUNCH_ROLL
-#undef LAUNCH_ROLL_O
+    launch_quad_step<true>(h, nullptr, obs, rew, reset, progress, timeouts, R, s);
     HIP_TRY(hipGetLastError());
     return VINE_OK;
 }
