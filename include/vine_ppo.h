@@ -631,6 +631,57 @@ int32_t vine_step_rollout_args_size(void);      /* sizeof(VineRolloutArgs): chec
 int vine_rollout_head_prep(const float* ln_gamma, const float* ln_beta, const float* w_mu, const float* b_mu, const float* w_v,
                            const float* b_v, float* hw, float* hc, void* stream);
 
+/* One EVALUATION step in one launch: the policy head's mean -> vine_step -> per-episode task statistics, for the player
+ * (`test=True`).  The third mode of the four-lanes-per-env step kernel, under a kernel name of its own
+ * (vine_step_eval_kernel); vine_step and vine_step_rollout run the instantiations they ran before.
+ *   Prologue: the two-pass LayerNorm of the env's LSTM output row and the two mu products of vine_rollout_head_prep's hw / hc
+ *   (rows 0 and 1; no value head).  deterministic != 0: action = mu.  Otherwise action = mu + exp(logstd) eps, eps from
+ *   Philox keyed by (seed, env, the handle's own step count, a purpose word of its own): no counter outside the handle.
+ *   The env clamps the action to clip_actions as it clamps any action.  mu_out / action_out [N, 2] (unclamped), dones_out [N]
+ *   u8: nullable.
+ *   Step: obs, rew, reset, progress, timeouts and the state block exactly as vine_step writes them.
+ *   Epilogue: episode [VINE_EVAL_EPISODE_FIELDS][N] fp32 (in/out, struct of arrays) holds each env's running
+ *     {return: sum of the raw rewards, length: steps, min_dist: smallest tip-to-target distance,
+ *      first_reach: 1-based step at which dist < success_dist first held, 0 = not yet};
+ *   the caller starts it at (0, 0, +inf, 0).  When the step requests a reset the episode is added to the workgroup's row of
+ *   totals [vine_step_eval_rows(h)][VINE_EVAL_NUM_TOTALS] float64 (in/out; the caller zeroes it), the accumulators return
+ *   to (0, 0, +inf, 0) and the env's rows of h_state / c_state [N, 256] (and of h_op, nullable, row stride h_op_stride
+ *   floats) are cleared.  END_* count the armed reset reasons that held at the last step (not exclusive): END_TIP_LIMIT
+ *   only with USE_TIP_LIMIT_HIT_RESET, END_CONTACT only with a shelf and USE_NONZERO_CONTACT_FORCE_RESET.
+ *   A step's finished episodes (at most 64 per workgroup) are summed in fp32 in a fixed order and added to row `blockIdx`
+ *   by that workgroup alone, only when it finished one: no atomics, bit-reproducible, and the workgroups past the last env
+ *   (the grid is a power of two) touch no memory.
+ * Returns VINE_ERR_UNSUPPORTED when the handle's configuration does not run the four-lane kernel. */
+#define VINE_EVAL_EPISODE_FIELDS 4
+#define VINE_EVAL_EP_RETURN 0
+#define VINE_EVAL_EP_LENGTH 1
+#define VINE_EVAL_EP_MIN_DIST 2
+#define VINE_EVAL_EP_FIRST_REACH 3
+#define VINE_EVAL_NUM_TOTALS 12
+#define VINE_EVAL_EPISODES 0
+#define VINE_EVAL_RETURN_SUM 1
+#define VINE_EVAL_LENGTH_SUM 2
+#define VINE_EVAL_REACHED_EVER 3
+#define VINE_EVAL_REACHED_AT_END 4
+#define VINE_EVAL_FIRST_REACH_SUM 5
+#define VINE_EVAL_FINAL_DIST_SUM 6
+#define VINE_EVAL_MIN_DIST_SUM 7
+#define VINE_EVAL_END_TIMEOUT 8
+#define VINE_EVAL_END_RAIL_LIMIT 9
+#define VINE_EVAL_END_TIP_LIMIT 10
+#define VINE_EVAL_END_CONTACT 11
+typedef struct VineEvalArgs {
+    const float* y; const float* hw; const float* hc; const float* logstd;
+    float ln_eps; int32_t deterministic; uint64_t seed;
+    float* mu_out; float* action_out; uint8_t* dones_out;      /* all nullable */
+    float* h_state; float* c_state; float* h_op; int64_t h_op_stride;
+    float* episode; double* totals;
+} VineEvalArgs;
+int vine_step_eval(struct VineHandle* h, const VineEvalArgs* args, float* obs, float* rew, int64_t* reset, int64_t* progress,
+                   uint8_t* timeouts, void* stream);
+int32_t vine_step_eval_rows(struct VineHandle* h);      /* rows of `totals` = the launch's grid; 0: four-lane kernel not in use */
+int32_t vine_step_eval_args_size(void);                 /* sizeof(VineEvalArgs): checked against the ctypes mirror */
+
 
 #ifdef __cplusplus
 }

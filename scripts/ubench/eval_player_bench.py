@@ -1,0 +1,86 @@
+"""The player's two paths at 16384 envs, free space and the task default (pipe): env-steps/s of ``run(2048)`` by the host clock
+(``run`` ends in the device->host copy of the totals, a synchronise follows), stock and device path alternated three times
+after one warm-up run each (the device path's warm-up also captures its graph).  Raw lines go to
+profiles/eval_player/player_paths.txt.
+
+  python scripts/ubench/eval_player_bench.py                       # both configurations, both paths
+  python scripts/ubench/eval_player_bench.py --trace-device pipe   # device path only, short: a workload for a kernel trace
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+from vine_robot_isaacgymenvs_amd import load_config  # noqa: E402
+from vine_robot_isaacgymenvs_amd.learning.player import PpoPlayerContinuous  # noqa: E402
+from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map  # noqa: E402
+
+CONFIGS = {"free": ["task.env.CREATE_PIPE=False"], "pipe": []}
+
+
+def make(name, n, device_rollout):
+    cfg = load_config(overrides=["num_envs=%d" % n] + CONFIGS[name])
+    cfg["task"]["seed"] = 42
+    env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
+                                                  graphics_device_id=0, headless=True)
+    params = cfg["train"]["params"]
+    params["config"]["player"] = {"device_rollout": device_rollout}
+    torch.manual_seed(0)
+    return PpoPlayerContinuous(params, vec_env=env), env
+
+
+def timed_run(player, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with contextlib.redirect_stdout(io.StringIO()):
+        player.run(n_steps=steps)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--steps", type=int, default=2048)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--trace-device", choices=sorted(CONFIGS), default=None)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_player", "player_paths.txt"))
+    args = ap.parse_args()
+    if args.trace_device:
+        player, env = make(args.trace_device, args.envs, True)
+        timed_run(player, 64)
+        dt = timed_run(player, 512)
+        assert player.device_path is True
+        print(json.dumps({"config": args.trace_device, "envs": args.envs, "steps": 512, "env_steps_per_s": args.envs * 512 / dt}))
+        env.close()
+        return
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    lines = []
+    for name in CONFIGS:
+        players = {path: make(name, args.envs, path == "device") for path in ("stock", "device")}
+        for path, (player, _) in players.items():
+            timed_run(player, 64 if path == "device" else 16)           # warm-up (device: the graph capture too)
+            assert player.device_path is (path == "device")
+        for rnd in range(args.rounds):
+            for path, (player, _) in players.items():
+                dt = timed_run(player, args.steps)
+                rec = {"config": name, "path": path, "round": rnd, "envs": args.envs, "steps": args.steps, "seconds": round(dt, 6),
+                       "env_steps_per_s": round(args.envs * args.steps / dt, 1), "report": player.report}
+                lines.append(json.dumps(rec))
+                print(lines[-1], flush=True)
+        for _, env in players.values():
+            env.close()
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -256,6 +256,9 @@ PPO_PROTOTYPES = {
     "vine_step_rollout_blocks": (C.c_int32, [_VP]),
     "vine_step_rollout_args_size": (C.c_int32, []),
     "vine_rollout_head_prep": (C.c_int, [_VP] * 9),
+    "vine_step_eval": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "vine_step_eval_rows": (C.c_int32, [_VP]),
+    "vine_step_eval_args_size": (C.c_int32, []),
     "vine_rollout_finalize": (C.c_int, [_VP, C.c_float, _VP, _VP, C.c_int32, _VP]),
     "vine_rollout_post_defer": (C.c_int, [_I64, _I64] + [_VP] * 4 + [C.c_float] * 3 + [_VP] * 6 + [_VP, _I64, C.c_int32, _VP, _VP]),
     "vine_gae": (C.c_int, [C.c_int32, _I64, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP]),
@@ -282,6 +285,22 @@ class RolloutArgs(C.Structure):
                 [("reward_shift", C.c_float), ("reward_scale", C.c_float), ("gamma_bootstrap", C.c_float), ("reserved", C.c_int32)] +
                 [(k, C.c_void_p) for k in ("shaped_out", "dones_out", "cur_rewards", "cur_lengths", "h_state", "c_state", "h_op")] +
                 [("h_op_stride", C.c_int64), ("partial", C.c_void_p)])
+
+
+# vine_step_eval (include/vine_ppo.h): fields of the per-env episode accumulators, columns of the per-workgroup totals
+EVAL_EPISODE_FIELDS = 4
+(EVAL_EP_RETURN, EVAL_EP_LENGTH, EVAL_EP_MIN_DIST, EVAL_EP_FIRST_REACH) = range(4)
+EVAL_NUM_TOTALS = 12
+(EVAL_EPISODES, EVAL_RETURN_SUM, EVAL_LENGTH_SUM, EVAL_REACHED_EVER, EVAL_REACHED_AT_END, EVAL_FIRST_REACH_SUM,
+ EVAL_FINAL_DIST_SUM, EVAL_MIN_DIST_SUM, EVAL_END_TIMEOUT, EVAL_END_RAIL_LIMIT, EVAL_END_TIP_LIMIT, EVAL_END_CONTACT) = range(12)
+
+
+class EvalArgs(C.Structure):
+    """VineEvalArgs of include/vine_ppo.h (vine_step_eval)."""
+    _fields_ = ([(k, C.c_void_p) for k in ("y", "hw", "hc", "logstd")] +
+                [("ln_eps", C.c_float), ("deterministic", C.c_int32), ("seed", C.c_uint64)] +
+                [(k, C.c_void_p) for k in ("mu_out", "action_out", "dones_out", "h_state", "c_state", "h_op")] +
+                [("h_op_stride", C.c_int64), ("episode", C.c_void_p), ("totals", C.c_void_p)])
 
 
 class TrunkArgs(C.Structure):

@@ -771,13 +771,19 @@ __device__ __forceinline__ void task_obs_tail_and_scale(const DevParams& P, floa
 
 // compute_reward (V5:1218-1331) + compute_reward_jit (V5:1470-1537), compute_reset_jit (V5:1540-1558) and the time-out flag
 // of VecTask.step's epilogue (vec_task.py:366-380).  contact_sum: the shelf strip's force summed over the control
-// iterations (SHELF).  rst comes in as 0 and leaves as the reset request.
+// iterations (SHELF).  rst comes in as 0 and leaves as the reset request.  ends: the tests the reward and the reset are
+// built from, for a caller that accounts for episodes (vine_step_eval); the overload without it drops them, and the
+// stores into a local nobody reads cost its callers nothing.
+struct TaskEnds {
+    float dist;                                        // tip to target
+    bool reached, limit_hit, tip_limit_hit, contact;   // dist < success_dist; rail soft limit; tip below the target's y; cmean > 0
+};
 template <bool SHELF>
 __device__ __forceinline__ void task_reward_and_reset(const DevParams& P, float tip_y, float tip_z, float tip_vy, float tip_vz,
                                                       float ty, float tz, float cart_y, float u_rail, float u_fpam,
                                                       float prev_u_rail, float smoothed, float contact_sum, long long prog,
                                                       float (&rm)[VINE_NUM_REWARDS], float& total, float& cmean,
-                                                      long long& rst, unsigned char& to) {
+                                                      long long& rst, unsigned char& to, TaskEnds& ends) {
     const float dy = tip_y - ty, dz = tip_z - tz;
     const float dist = sqrtf(dy * dy + dz * dz);
     const bool reached = dist < P.success_dist;
@@ -807,6 +813,19 @@ __device__ __forceinline__ void task_reward_and_reset(const DevParams& P, float 
     if (limit_hit) rst = 1;
     if (SHELF && cmean > 0.0f && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) rst = 1;
     to = (prog >= (long long)P.max_len - 1) && (rst != 0);
+    ends.dist = dist;
+    ends.reached = reached; ends.limit_hit = limit_hit; ends.tip_limit_hit = tip_limit_hit;
+    ends.contact = SHELF && cmean > 0.0f;
+}
+template <bool SHELF>
+__device__ __forceinline__ void task_reward_and_reset(const DevParams& P, float tip_y, float tip_z, float tip_vy, float tip_vz,
+                                                      float ty, float tz, float cart_y, float u_rail, float u_fpam,
+                                                      float prev_u_rail, float smoothed, float contact_sum, long long prog,
+                                                      float (&rm)[VINE_NUM_REWARDS], float& total, float& cmean,
+                                                      long long& rst, unsigned char& to) {
+    TaskEnds ends;
+    task_reward_and_reset<SHELF>(P, tip_y, tip_z, tip_vy, tip_vz, ty, tz, cart_y, u_rail, u_fpam, prev_u_rail, smoothed,
+                                 contact_sum, prog, rm, total, cmean, rst, to, ends);
 }
 
 #define ST(f) st[(size_t)(f) * n + e]
@@ -1243,7 +1262,7 @@ __device__ __forceinline__ float quad_scan_incl(float v, int t) {
 __device__ unsigned long long vsq_t[1024 * 8];      // (debug build: 8 time stamps per wave, scripts/ubench/step_phases.py)
 #endif
 // ROLL (round 5, vine_step_rollout): the rollout step's policy head in front of the step and its bookkeeping behind it, in
-// this launch -- see include/vine.h.  The plain step (ROLL = false) is a separate instantiation and is not touched.
+// this launch -- see include/vine_ppo.h.  The plain step (MODE = STEP_PLAIN) is a separate instantiation and is not touched.
 struct RollArgs {
     const float* y; const float* hw; const float* hc; const float* logstd;
     const double* vmean; const double* vvar;
@@ -1255,7 +1274,23 @@ struct RollArgs {
     float* h_state; float* c_state; float* h_op; long long h_op_stride;
     float* partial;
 };
-template <int OBS_TYPE, bool RANDOMIZE, int OBST, bool ROLL = false>   // OBST bit 0: shelf, bit 1: pipe
+// EVAL (vine_step_eval, include/vine_ppo.h): the player's step.  The deterministic (or sampled) action of the policy head in
+// front of the step, per-episode task statistics behind it.  MODE selects plain / ROLL / EVAL at compile time: three separate
+// instantiations, the plain and the rollout ones with the argument list and the code of the two-mode kernel before it
+// (checked on the compiler's resource report), the last kernel argument being the mode's own struct (RollArgs, unused in
+// the plain step, or EvalArgs).  The modes' blocks are `if constexpr`: each names members of its own struct only.
+struct EvalArgs {
+    const float* y; const float* hw; const float* hc; const float* logstd;
+    float ln_eps; int deterministic; unsigned seed_lo, seed_hi;
+    float* mu_out; float* action_out; unsigned char* dones;
+    float* h_state; float* c_state; float* h_op; long long h_op_stride;
+    float* episode; double* totals;
+};
+enum { STEP_PLAIN = 0, STEP_ROLL = 1, STEP_EVAL = 2 };
+template <int MODE> struct StepModeArgs { using type = RollArgs; };
+template <> struct StepModeArgs<STEP_EVAL> { using type = EvalArgs; };
+#define RNG_EVAL_ACTION 0x4556414cu      // Philox purpose word of the evaluation step's action noise ("EVAL")
+template <int OBS_TYPE, bool RANDOMIZE, int OBST, int MODE = STEP_PLAIN>   // OBST bit 0: shelf, bit 1: pipe
 __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, float* __restrict__ st,
                                                              const float* __restrict__ actions, float* __restrict__ obs,
                                                              float* __restrict__ rew, long long* __restrict__ reset,
@@ -1263,7 +1298,9 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                                                              unsigned char* __restrict__ timeouts,
                                                              float* __restrict__ reward_matrix,
                                                              const float* __restrict__ reset_values,
-                                                             unsigned long long* __restrict__ counters, const RollArgs R) {
+                                                             unsigned long long* __restrict__ counters,
+                                                             const typename StepModeArgs<MODE>::type R) {
+    constexpr bool ROLL = MODE == STEP_ROLL, EVAL = MODE == STEP_EVAL;
     static_assert(OBS_TYPE == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO || OBS_TYPE == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO, "");
     constexpr int NOBS = OBS_TYPE == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO ? 28 : 18;
     constexpr bool SHELF = (OBST & 1) != 0, PIPE = (OBST & 2) != 0, CONTACT = OBST != 0;
@@ -1275,6 +1312,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
 #endif
     const unsigned long long step = step_of(P, counters);
     float roll_sr = 0.0f, roll_sl = 0.0f, roll_cnt = 0.0f;      // (ROLL) this lane's finished-episode totals
+    float ev_tot[EVAL ? VINE_EVAL_NUM_TOTALS : 1] = {};         // (EVAL) this lane's finished episode, as a row of the totals
     if (e < n) {
         // ---- everything the step needs from memory is requested FIRST, in one batch, and waited for once (behind the
         // pure-ALU random-number work below).  The prologue used to be four dependent stages -- per-lane constants fetched
@@ -1282,15 +1320,15 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         // select that needs it: ~45 scalar loads, each with its own wait), the action load, the action-noise Philox, then
         // the state loads, with the body-state fields behind `if (progress == 0)` -- and took 6 of the kernel's 24 us.
         float2 act = make_float2(0.0f, 0.0f);
-        float4 yq[ROLL ? 16 : 1];      // ROLL: this lane's 64 units {16 i + 4 t .. + 3 : i < 16} of the env's LSTM output row
+        float4 yq[ROLL || EVAL ? 16 : 1];      // ROLL / EVAL: this lane's 64 units {16 i + 4 t .. + 3 : i < 16} of the env's LSTM output row
         float roll_cr = 0.0f, roll_cl = 0.0f;
-        if (ROLL) {
+        if constexpr (ROLL || EVAL) {
             // (interleaved: the four lanes of a quad read 64 contiguous bytes per load -- 16 lines per wave instruction; with
             // 64 consecutive units per lane every lane of the wave sat on its own line)
             const float4* yr = reinterpret_cast<const float4*>(R.y + (size_t)e * 256) + t;
 #pragma unroll
             for (int i = 0; i < 16; ++i) yq[i] = yr[4 * i];
-            roll_cr = R.cur_r[e]; roll_cl = R.cur_l[e];
+            if constexpr (ROLL) { roll_cr = R.cur_r[e]; roll_cl = R.cur_l[e]; }
         } else {
             act = reinterpret_cast<const float2*>(actions)[e];
         }
@@ -1386,7 +1424,43 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         if ((threadIdx.x & 63) == 0) vsq_t[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 3] = wall_clock64();
 #endif
         float roll_value = 0.0f;
-        if (ROLL) {
+        if constexpr (EVAL) {
+            // ---- the policy head's mean only (the ROLL head below without the value row): two-pass LayerNorm of the row, the
+            // two centred dot products with gamma_u w_k[u]; the action is the mean, or the mean plus noise keyed by the
+            // handle's own step count (nothing outside the handle counts evaluation steps)
+            float s1 = 0.0f;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s1 += (yq[i].x + yq[i].y) + (yq[i].z + yq[i].w);
+            const float mean = quad_sum(s1) * (1.0f / 256.0f);
+            float q2 = 0.0f, d0 = 0.0f, d1 = 0.0f;
+            const float4* hw0 = reinterpret_cast<const float4*>(R.hw) + t;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float4 w0 = hw0[4 * i], w1 = hw0[64 + 4 * i];
+                const float c0 = yq[i].x - mean, c1 = yq[i].y - mean, c2 = yq[i].z - mean, c3 = yq[i].w - mean;
+                q2 += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
+                d0 += (c0 * w0.x + c1 * w0.y) + (c2 * w0.z + c3 * w0.w);
+                d1 += (c0 * w1.x + c1 * w1.y) + (c2 * w1.z + c3 * w1.w);
+            }
+            const float rstd = rsqrtf(quad_sum(q2) * (1.0f / 256.0f) + R.ln_eps);
+            const float m0 = rstd * quad_sum(d0) + R.hc[0], m1 = rstd * quad_sum(d1) + R.hc[1];
+            act = make_float2(m0, m1);
+            if (!R.deterministic) {
+                unsigned r[4];
+                philox4x32_10((unsigned)e, (unsigned)step, RNG_EVAL_ACTION, (unsigned)(step >> 32), R.seed_lo, R.seed_hi, r);
+                const float u1 = 1.0f - (float)(r[0] >> 8) * (1.0f / 16777216.0f);
+                const float u2 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
+                const float rad = sqrtf(-2.0f * __logf(u1));
+                float sn_, cs_;
+                __sincosf(6.283185307179586f * u2, &sn_, &cs_);
+                act = make_float2(m0 + __expf(R.logstd[0]) * (rad * cs_), m1 + __expf(R.logstd[1]) * (rad * sn_));
+            }
+            if (t == 0) {
+                if (R.mu_out) reinterpret_cast<float2*>(R.mu_out)[e] = make_float2(m0, m1);
+                if (R.action_out) reinterpret_cast<float2*>(R.action_out)[e] = act;
+            }
+        }
+        if constexpr (ROLL) {
             // ---- policy head (vine_policy_head's formulas, ppo_kernels.hip): LayerNorm of the row (two passes: mean, then
             // centred second moment and the three centred dot products with gamma_u w_k[u]), mu / value, sampling
             float s1 = 0.0f;
@@ -1822,6 +1896,13 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         }
         // ---- compute_observations (V5:1339-1390): the row is assembled replicated, then lane t keeps, perturbs, clamps
         // and stores columns [4t, 4t+4) and [16+4t, 16+4t+4)
+        // (EVAL) the env's running episode: requested here, behind the simulation (four registers that are not held across
+        // it), and waited for in the epilogue, behind the observation and the reward
+        float ev_ret = 0.0f, ev_len = 0.0f, ev_min = 0.0f, ev_first = 0.0f;
+        if constexpr (EVAL) {
+            ev_ret = R.episode[e]; ev_len = R.episode[(size_t)n + e];
+            ev_min = R.episode[(size_t)2 * n + e]; ev_first = R.episode[(size_t)3 * n + e];
+        }
         float o[32];
         {
             const float fd_tip_y = (tip_y - prev_tip_y) * P.inv_cdt, fd_tip_z = (tip_z - prev_tip_z) * P.inv_cdt;
@@ -1872,8 +1953,9 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         // ---- compute_reward (V5:1218-1331, 1470-1537), compute_reset (V5:1540-1558): replicated, lane 0 stores
         float rm[VINE_NUM_REWARDS], total, cmean;
         unsigned char to;
+        TaskEnds ends;
         task_reward_and_reset<SHELF>(P, tip_y, tip_z, tip_vy, tip_vz, ty, tz, cart_y, u_rail, u_fpam, prev_u_rail, smoothed,
-                                     contact_sum, prog, rm, total, cmean, rst, to);
+                                     contact_sum, prog, rm, total, cmean, rst, to, ends);
         agg += total;
         if (t == 0) {
             rew[e] = total;
@@ -1891,7 +1973,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
             store_step_state<SHELF>(P, st, n, e, smoothed, pcv, pce, agg, contact, tip_vy, tip_vz, prev_tip_y, prev_tip_z, u_fpam,
                                     u_rail, prev_u_rail, rail_force, cmean);
         }
-        if (ROLL) {
+        if constexpr (ROLL) {
             // ---- vine_rollout_post's bookkeeping (play_steps_rnn; common_agent.py:293-306): shaped reward with the time-out
             // bootstrap, done flag, episode accumulators; the LSTM-state rows of a finished env are cleared by its four lanes
             const bool done = rst != 0;
@@ -1918,8 +2000,77 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                 }
             }
         }
+        if constexpr (EVAL) {
+            // ---- episode accounting: the env's running {return, length, smallest distance, step of the first reach}; an
+            // episode that ends in this step becomes the lane's row of totals and the accumulators start over.  The
+            // LSTM-state rows of a finished env are cleared by its four lanes, as ROLL clears them.
+            const bool done = rst != 0;
+            const float er = ev_ret + total, el = ev_len + 1.0f, emin = fminf(ev_min, ends.dist);
+            const float efirst = (ev_first == 0.0f && ends.reached) ? el : ev_first;
+            if (t == 0) {
+                if (R.dones) R.dones[e] = done ? 1 : 0;
+                R.episode[e] = done ? 0.0f : er;
+                R.episode[(size_t)n + e] = done ? 0.0f : el;
+                R.episode[(size_t)2 * n + e] = done ? __builtin_huge_valf() : emin;
+                R.episode[(size_t)3 * n + e] = done ? 0.0f : efirst;
+                if (done) {
+                    ev_tot[VINE_EVAL_EPISODES] = 1.0f;
+                    ev_tot[VINE_EVAL_RETURN_SUM] = er;
+                    ev_tot[VINE_EVAL_LENGTH_SUM] = el;
+                    ev_tot[VINE_EVAL_REACHED_EVER] = efirst != 0.0f ? 1.0f : 0.0f;
+                    ev_tot[VINE_EVAL_REACHED_AT_END] = ends.reached ? 1.0f : 0.0f;
+                    ev_tot[VINE_EVAL_FIRST_REACH_SUM] = efirst;
+                    ev_tot[VINE_EVAL_FINAL_DIST_SUM] = ends.dist;
+                    ev_tot[VINE_EVAL_MIN_DIST_SUM] = emin;
+                    ev_tot[VINE_EVAL_END_TIMEOUT] = to ? 1.0f : 0.0f;
+                    ev_tot[VINE_EVAL_END_RAIL_LIMIT] = ends.limit_hit ? 1.0f : 0.0f;
+                    ev_tot[VINE_EVAL_END_TIP_LIMIT] =
+                        (ends.tip_limit_hit && (P.flags & VINE_FLAG_USE_TIP_LIMIT_HIT_RESET)) ? 1.0f : 0.0f;
+                    ev_tot[VINE_EVAL_END_CONTACT] =
+                        (ends.contact && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) ? 1.0f : 0.0f;
+                }
+            }
+            if (done) {
+                const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                float4* hr = reinterpret_cast<float4*>(R.h_state + (size_t)e * 256) + t;
+                float4* cr4 = reinterpret_cast<float4*>(R.c_state + (size_t)e * 256) + t;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) { hr[4 * i] = z; cr4[4 * i] = z; }
+                if (R.h_op) {
+                    float4* orow = reinterpret_cast<float4*>(R.h_op + (size_t)e * R.h_op_stride) + t;
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) orow[4 * i] = z;
+                }
+            }
+        }
     }
-    if (ROLL) {
+    if constexpr (EVAL) {
+        // the workgroup's finished episodes of this step, summed in fp32 in a fixed order (wave shuffles, then LDS: no
+        // atomics), then added to the workgroup's own float64 row.  A wave without a finished episode contributes zeros
+        // without shuffling; a workgroup without one (every workgroup past the last env among them) touches no memory.
+        __shared__ float ev_red[4][VINE_EVAL_NUM_TOTALS];
+        if (__any(ev_tot[VINE_EVAL_EPISODES] != 0.0f)) {
+#pragma unroll
+            for (int k = 0; k < VINE_EVAL_NUM_TOTALS; ++k) {
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) ev_tot[k] += __shfl_xor(ev_tot[k], off, 64);
+            }
+        }
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < VINE_EVAL_NUM_TOTALS; ++k) ev_red[threadIdx.x >> 6][k] = ev_tot[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < VINE_EVAL_NUM_TOTALS) {
+            const float cnt = (ev_red[0][VINE_EVAL_EPISODES] + ev_red[1][VINE_EVAL_EPISODES]) +
+                              (ev_red[2][VINE_EVAL_EPISODES] + ev_red[3][VINE_EVAL_EPISODES]);
+            if (cnt != 0.0f) {
+                const float v = (ev_red[0][threadIdx.x] + ev_red[1][threadIdx.x]) + (ev_red[2][threadIdx.x] + ev_red[3][threadIdx.x]);
+                R.totals[(size_t)blockIdx.x * VINE_EVAL_NUM_TOTALS + threadIdx.x] += (double)v;
+            }
+        }
+    }
+    if constexpr (ROLL) {
         // one {sum of finished returns, sum of finished lengths, count} row per workgroup, fixed order (no atomics)
         __shared__ float roll_red[4][3];
         float v3[3] = {roll_sr, roll_sl, roll_cnt};
@@ -2297,15 +2448,15 @@ void with_step_instantiation(const VineHandle* h, F&& f) {
     else with_rnd(std::integral_constant<int, VINE_OBS_POS_AND_VEL>{});    // the 26-column family, resolved inside the kernel
 }
 
-// The four-lane kernel, plain (ROLL = false) or with the rollout's policy head and bookkeeping around the step.
-template <bool ROLL>
+// The four-lane kernel: plain, with the rollout's policy head and bookkeeping around the step, or with the player's.
+template <int MODE>
 void launch_quad_step(VineHandle* h, const float* actions, float* obs, float* rew, int64_t* reset, int64_t* progress,
-                      uint8_t* timeouts, const RollArgs& R, hipStream_t s) {
+                      uint8_t* timeouts, const typename StepModeArgs<MODE>::type& R, hipStream_t s) {
     with_step_instantiation(h, [&](auto ot, auto rn, auto ob) {
         constexpr int OT = decltype(ot)::value;
         // (use_quad_kernel admits the two scalable layouts only; the kernel is not instantiated for the others)
         if constexpr (OT == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO || OT == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO)
-            hipLaunchKernelGGL((vine_step_quad_kernel<OT, decltype(rn)::value, decltype(ob)::value, ROLL>), dim3(1 << h->P.glog),
+            hipLaunchKernelGGL((vine_step_quad_kernel<OT, decltype(rn)::value, decltype(ob)::value, MODE>), dim3(1 << h->P.glog),
                                dim3(VSQ_THREADS), 0, s, h->P, h->state, actions, obs, rew, (long long*)reset,
                                (long long*)progress, (unsigned char*)timeouts, h->reward_matrix, h->reset_values, h->counters,
                                R);
@@ -2461,7 +2612,7 @@ int vine_step(VineHandle* h, const float* actions, float* obs, float* rew, int64
     const int rc = prepare_step_launch(h, progress, s);
     if (rc != VINE_OK) return rc;
     if (use_quad_kernel(h)) {
-        launch_quad_step<false>(h, actions, obs, rew, reset, progress, timeouts, RollArgs{}, s);
+        launch_quad_step<STEP_PLAIN>(h, actions, obs, rew, reset, progress, timeouts, RollArgs{}, s);
     } else {
         with_step_instantiation(h, [&](auto ot, auto rn, auto ob) {
             hipLaunchKernelGGL((vine_step_kernel<decltype(ot)::value, decltype(rn)::value, decltype(ob)::value>),
@@ -2537,11 +2688,41 @@ int vine_step_rollout(VineHandle* h, const VineRolloutArgs* a, float* obs, float
     R.gamma_b = a->gamma_bootstrap; R.shaped = a->shaped_out; R.dones = a->dones_out; R.cur_r = a->cur_rewards;
     R.cur_l = a->cur_lengths; R.h_state = a->h_state; R.c_state = a->c_state; R.h_op = a->h_op; R.h_op_stride = a->h_op_stride;
     R.partial = a->partial;
-    launch_quad_step<true>(h, nullptr, obs, rew, reset, progress, timeouts, R, s);
+    launch_quad_step<STEP_ROLL>(h, nullptr, obs, rew, reset, progress, timeouts, R, s);
     HIP_TRY(hipGetLastError());
     return VINE_OK;
 }
 
+// ---- vine_step_eval: the policy head's mean + step + per-episode task statistics in one launch (include/vine_ppo.h)
+int32_t vine_step_eval_args_size(void) { return (int32_t)sizeof(VineEvalArgs); }
+
+int32_t vine_step_eval_rows(VineHandle* h) {
+    if (!h || !use_quad_kernel(h)) return 0;
+    return (int32_t)(1 << step_grid_log2(h));      // the launch's grid: workgroup b adds to row b
+}
+
+int vine_step_eval(VineHandle* h, const VineEvalArgs* a, float* obs, float* rew, int64_t* reset, int64_t* progress,
+                   uint8_t* timeouts, void* stream) {
+    if (!h || !a || !obs || !rew || !reset || !progress || !timeouts || !a->y || !a->hw || !a->hc || !a->logstd || !a->h_state ||
+        !a->c_state || !a->episode || !a->totals || (a->h_op && a->h_op_stride < 256))
+        return fail(VINE_ERR_INVALID_ARG, "null or inconsistent argument to vine_step_eval");
+    if (((uintptr_t)a->y | (uintptr_t)a->hw | (uintptr_t)a->h_state | (uintptr_t)a->c_state | (uintptr_t)a->h_op) & 15 ||
+        ((uintptr_t)a->mu_out | (uintptr_t)a->action_out | (uintptr_t)a->totals) & 7 || (a->h_op && (a->h_op_stride & 3)))
+        return fail(VINE_ERR_INVALID_ARG, "vine_step_eval: misaligned row pointer");
+    if (!use_quad_kernel(h)) return fail(VINE_ERR_UNSUPPORTED, "vine_step_eval needs the four-lanes-per-env step kernel");
+    DeviceGuard guard(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = prepare_step_launch(h, progress, s);
+    if (rc != VINE_OK) return rc;
+    EvalArgs E;
+    E.y = a->y; E.hw = a->hw; E.hc = a->hc; E.logstd = a->logstd; E.ln_eps = a->ln_eps; E.deterministic = a->deterministic;
+    E.seed_lo = (unsigned)a->seed; E.seed_hi = (unsigned)(a->seed >> 32); E.mu_out = a->mu_out; E.action_out = a->action_out;
+    E.dones = a->dones_out; E.h_state = a->h_state; E.c_state = a->c_state; E.h_op = a->h_op; E.h_op_stride = a->h_op_stride;
+    E.episode = a->episode; E.totals = a->totals;
+    launch_quad_step<STEP_EVAL>(h, nullptr, obs, rew, reset, progress, timeouts, E, s);
+    HIP_TRY(hipGetLastError());
+    return VINE_OK;
+}
 
 int vine_reset_idx(VineHandle* h, const int64_t* env_ids, int64_t n, float* rew, int64_t* reset, int64_t* progress,
                    void* stream) {

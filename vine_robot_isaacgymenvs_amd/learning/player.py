@@ -1,11 +1,59 @@
 """Inference player (``test=True`` of train.py:166-171; deployment consumer
-isaacgymenvs/vine_robot_test_model.py:143-177): loads a checkpoint and runs the deterministic policy."""
+isaacgymenvs/vine_robot_test_model.py:143-177): loads a checkpoint and runs the deterministic policy.
+
+Two paths.  The stock path evaluates the stock model through PyTorch and steps through ``VecTask.step``; it serves every
+configuration.  The device path (the default network on the four-lanes-per-env step kernel, see ``_device_eligible``) is
+three hand-written launches per step -- the trainer's split MLP and LSTM step (``FastInferenceMixin``) and
+``vine_step_eval`` (include/vine_ppo.h), which applies the policy head, steps the env and accounts for episodes --
+replayed as one hipGraph of ``player.graph_steps`` steps.  It reports per-episode task statistics (``eval_report``)."""
+import contextlib
+import math
+
+import numpy as np
 import torch
 
+from .. import abi
+from .fast_inference import FastInferenceMixin
 from .network import ModelA2CContinuousLogStd
 
+REPORT_KEYS = ("episodes", "return_mean", "length_mean", "reached_ever_rate", "reached_at_end_rate", "steps_to_reach_mean",
+               "final_dist_mean", "min_dist_mean", "end_timeout_rate", "end_rail_limit_rate", "end_tip_limit_rate",
+               "end_contact_rate")
 
-class PpoPlayerContinuous:
+
+def eval_report(totals_rows):
+    """The evaluation report from ``vine_step_eval``'s per-workgroup totals ([rows, abi.EVAL_NUM_TOTALS]): the rows are
+    folded in float64; a mean over zero episodes (or zero reaching episodes) is ``nan``."""
+    t = np.asarray(totals_rows, dtype=np.float64).reshape(-1, abi.EVAL_NUM_TOTALS).sum(axis=0)
+    games, reached = t[abi.EVAL_EPISODES], t[abi.EVAL_REACHED_EVER]
+
+    def per(x, n):
+        return float(x) / float(n) if n > 0 else math.nan
+
+    return {"episodes": int(round(games)),
+            "return_mean": per(t[abi.EVAL_RETURN_SUM], games),
+            "length_mean": per(t[abi.EVAL_LENGTH_SUM], games),
+            "reached_ever_rate": per(reached, games),
+            "reached_at_end_rate": per(t[abi.EVAL_REACHED_AT_END], games),
+            "steps_to_reach_mean": per(t[abi.EVAL_FIRST_REACH_SUM], reached),
+            "final_dist_mean": per(t[abi.EVAL_FINAL_DIST_SUM], games),
+            "min_dist_mean": per(t[abi.EVAL_MIN_DIST_SUM], games),
+            "end_timeout_rate": per(t[abi.EVAL_END_TIMEOUT], games),
+            "end_rail_limit_rate": per(t[abi.EVAL_END_RAIL_LIMIT], games),
+            "end_tip_limit_rate": per(t[abi.EVAL_END_TIP_LIMIT], games),
+            "end_contact_rate": per(t[abi.EVAL_END_CONTACT], games)}
+
+
+def format_report(report):
+    """One line per quantity of ``eval_report`` (the stock path's report holds the first three only)."""
+    lines = ["episodes: %d" % report["episodes"]]
+    for k in REPORT_KEYS[1:]:
+        if k in report:
+            lines.append("%s: %.6g" % (k, report[k]))
+    return "\n".join("  " + line for line in lines)
+
+
+class PpoPlayerContinuous(FastInferenceMixin):
     def __init__(self, params, vec_env=None):
         self.config = config = params["config"]
         self.vec_env = vec_env
@@ -17,12 +65,27 @@ class PpoPlayerContinuous:
         info = self.vec_env.get_env_info()
         self.device = torch.device(config.get("device", "cuda:0"))
         self.actions_num = info["action_space"].shape[0]
-        self.model = ModelA2CContinuousLogStd(params["network"], self.actions_num, tuple(info["observation_space"].shape),
-                                              config.get("normalize_value", False), config["normalize_input"]).to(self.device)
+        self.obs_shape = tuple(info["observation_space"].shape)
+        self.normalize_input = config["normalize_input"]
+        self.model = ModelA2CContinuousLogStd(params["network"], self.actions_num, self.obs_shape,
+                                              config.get("normalize_value", False), self.normalize_input).to(self.device)
         self.model.eval()
-        self.is_deterministic = config.get("player", {}).get("deterministic", True)
-        self.max_steps = config.get("player", {}).get("max_steps", 27000)
+        pcfg = config.get("player", None) or {}
+        self.is_deterministic = pcfg.get("deterministic", True)
+        self.max_steps = pcfg.get("max_steps", 27000)
+        self.device_rollout = pcfg.get("device_rollout", True) is not False
+        self.graph_steps = int(pcfg.get("graph_steps", 16))      # steps per captured graph (0: eager)
+        if self.graph_steps < 0 or self.graph_steps % 2:
+            # the observation and the LSTM operand each alternate between two buffers: a graph must end where it began
+            raise ValueError("player.graph_steps must be 0 or a positive even number")
+        seed = config.get("seed", None)
+        self.eval_seed = int(seed) if seed is not None and int(seed) >= 0 else 0    # Philox key of sampled actions
         self.states = None
+        self.report = None           # filled by run()
+        self.device_path = None      # which path the last run() took
+        self._fast = None
+        self._dev = None
+        self._eval_graph = None
 
     def restore(self, fn):
         ckpt = torch.load(fn, map_location=self.device, weights_only=False)
@@ -41,8 +104,25 @@ class PpoPlayerContinuous:
         return torch.clamp(action, -1.0, 1.0)
 
     def run(self, n_steps=None):
-        """Plays ``n_steps`` env steps (default: max_steps); returns mean episode return and length."""
+        """Plays ``n_steps`` env steps (default: max_steps); returns mean episode return and length and leaves the
+        report in ``self.report``."""
         n_steps = n_steps or self.max_steps
+        self.device_path = self._device_eligible()
+        if self.device_path:
+            return self._run_device(n_steps)
+        return self._run_stock(n_steps)
+
+    def _finish(self, mean_r, mean_l, games):
+        video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
+        if video is not None:                    # CAPTURE_VIDEO: every harvested window is on disk when run() returns
+            torch.cuda.synchronize(self.device)
+            video.drain()
+        print("reward:", mean_r, "steps:", mean_l, "games:", games)
+        print(format_report(self.report))
+        return mean_r, mean_l
+
+    # ------------------------------------------------------------------ stock path
+    def _run_stock(self, n_steps):
         obs = self.vec_env.reset()["obs"].to(self.device)
         n = obs.shape[0]
         cur_r = torch.zeros(n, device=self.device)
@@ -64,10 +144,129 @@ class PpoPlayerContinuous:
             self.states = [s * keep.view(1, -1, 1) for s in self.states]
             cur_r *= keep
             cur_l *= keep
-        video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
-        if video is not None:                    # CAPTURE_VIDEO: every harvested window is on disk when run() returns
-            torch.cuda.synchronize(self.device)
-            video.drain()
         g = max(float(games), 1.0)
-        print("reward:", float(sum_r) / g, "steps:", float(sum_l) / g, "games:", int(games))
-        return float(sum_r) / g, float(sum_l) / g
+        mean_r, mean_l = float(sum_r) / g, float(sum_l) / g
+        played = int(games) > 0
+        self.report = {"episodes": int(games), "return_mean": mean_r if played else math.nan,
+                       "length_mean": mean_l if played else math.nan}
+        return self._finish(mean_r, mean_l, int(games))
+
+    # ------------------------------------------------------------------ device path
+    def _device_eligible(self):
+        """The device path serves the default network (256-128-64 MLP, LSTM 256 with LayerNorm, 2 actions) at a multiple
+        of 512 envs on the four-lanes-per-env step kernel; everything else stays on the stock path."""
+        env = getattr(self.vec_env, "env", self.vec_env)
+        if not (self.device_rollout and self.device.type == "cuda" and hasattr(env, "eval_step_rows")
+                and hasattr(env, "timeout_buf") and env.rew_buf.is_cuda and env.rew_buf.device == self.device
+                and self.actions_num == 2 and float(getattr(env, "clip_actions", 1.0)) <= 1.0
+                and int(env.num_envs) % 512 == 0 and self.normalize_input):
+            return False
+        if env.eval_step_rows() <= 0:            # (0 with a MAT_FILE too)
+            return False
+        if self._fast is None:
+            from . import fused
+            self.num_actors = int(env.num_envs)
+            self.fused_rollout, self.rollout_lp16, self._pending_fin = True, False, None
+            self.rollout_f32_terms = int(self.config.get("rollout_f32_terms", fused.ROLLOUT_F32_SPLIT))
+            self.rnn_states = [s.contiguous() for s in self.model.get_default_rnn_state(self.num_actors, self.device)]
+            self._setup_fast_inference()
+        f = self._fast
+        return bool(f is not None and f["f32_mfma"] and f.get("mlp_wt_split") is not None and f["ln_in_head"])
+
+    def _device_buffers(self, env):
+        if self._dev is None:
+            N, dev = self.num_actors, self.device
+            rows = env.eval_step_rows()
+            self._dev = {"obs_ring": [torch.zeros((N,) + self.obs_shape, device=dev) for _ in range(2)], "slot": 0,
+                         "episode": torch.zeros((abi.EVAL_EPISODE_FIELDS, N), device=dev),
+                         "totals": torch.zeros((rows, abi.EVAL_NUM_TOTALS), device=dev, dtype=torch.float64),
+                         "mu": torch.zeros((N, 2), device=dev), "action": torch.zeros((N, 2), device=dev),
+                         "dones": torch.zeros(N, device=dev, dtype=torch.uint8),
+                         "hw": torch.empty(3 * 256, device=dev), "hc": torch.empty(3, device=dev)}
+        return self._dev
+
+    def _device_step(self):
+        """One step: the split MLP, the split LSTM step, ``vine_step_eval``."""
+        env = getattr(self.vec_env, "env", self.vec_env)
+        d, f, net = self._dev, self._fast, self.model.a2c_network
+        y = self._infer(d["obs_ring"][d["slot"]])
+        a = abi.EvalArgs()
+        a.y, a.hw, a.hc, a.logstd = y.data_ptr(), d["hw"].data_ptr(), d["hc"].data_ptr(), net.sigma.data_ptr()
+        a.ln_eps, a.deterministic, a.seed = float(net.layer_norm.eps), int(bool(self.is_deterministic)), self.eval_seed
+        a.mu_out, a.action_out, a.dones_out = d["mu"].data_ptr(), d["action"].data_ptr(), d["dones"].data_ptr()
+        a.h_state, a.c_state = self.rnn_states[0].data_ptr(), self.rnn_states[1].data_ptr()
+        # the operand copy of h that the NEXT step reads (the buffer _infer just switched to)
+        a.h_op = f["xh2"][f["cur"]].data_ptr() + 4 * f["XW"]
+        a.h_op_stride = f["XW"] + f["H"]
+        a.episode, a.totals = d["episode"].data_ptr(), d["totals"].data_ptr()
+        d["slot"] ^= 1
+        env.step_eval_into(a, d["obs_ring"][d["slot"]])
+
+    def _capture(self, env):
+        """``graph_steps`` steps as one graph, as the trainer captures its rollout: a warm-up pass on a side stream whose
+        effects are rolled back (env state, step count -- the key of sampled actions --, LSTM state, accounting), then the
+        capture pass, which executes nothing."""
+        d, f = self._dev, self._fast
+        live = [env.state, env.reset_buf, env.progress_buf, env.rew_buf, env.timeout_buf, self.rnn_states[0], self.rnn_states[1],
+                f["xh2"][0], f["xh2"][1], d["obs_ring"][0], d["obs_ring"][1], d["episode"], d["totals"], d["mu"], d["action"],
+                d["dones"]]
+        backup = [t.clone() for t in live]
+        step, num_steps, rng = env.step_count, env.num_steps, torch.cuda.get_rng_state(self.device)
+        video_paused = getattr(env, "video_paused", contextlib.nullcontext)
+
+        def body():
+            for _ in range(self.graph_steps):
+                self._device_step()
+
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side), video_paused():
+            body()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        for t, b in zip(live, backup):
+            t.copy_(b)
+        env.step_count = step
+        torch.cuda.set_rng_state(rng, self.device)
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"), video_paused():
+            body()
+        env.num_steps = num_steps
+        return graph
+
+    @torch.no_grad()
+    def _run_device(self, n_steps):
+        from . import fused
+        env = getattr(self.vec_env, "env", self.vec_env)
+        d, f, net = self._device_buffers(env), self._fast, self.model.a2c_network
+        obs = self.vec_env.reset()["obs"]
+        d["slot"] = 0
+        d["obs_ring"][0].copy_(obs)
+        for s in self.rnn_states:
+            s.zero_()
+        d["episode"].zero_()
+        d["episode"][abi.EVAL_EP_MIN_DIST].fill_(math.inf)
+        d["totals"].zero_()
+        # operand copies of the weights (restore() may have changed them since the last run) and of h
+        self._infer_begin()
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        fused._check(fused._lib().vine_rollout_head_prep(net.layer_norm.weight.data_ptr(), net.layer_norm.bias.data_ptr(),
+                                                         net.mu.weight.data_ptr(), net.mu.bias.data_ptr(),
+                                                         net.value.weight.data_ptr(), net.value.bias.data_ptr(),
+                                                         d["hw"].data_ptr(), d["hc"].data_ptr(), st), "vine_rollout_head_prep")
+        # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph)
+        graphed = self.graph_steps > 0 and n_steps >= self.graph_steps and getattr(env, "video", None) is None
+        done = 0
+        if graphed:
+            if self._eval_graph is None:
+                self._eval_graph = self._capture(env)
+            for _ in range(n_steps // self.graph_steps):
+                self._eval_graph.replay()
+                env.num_steps += self.graph_steps
+            done = n_steps // self.graph_steps * self.graph_steps
+        for _ in range(n_steps - done):
+            self._device_step()
+        totals = d["totals"].cpu().numpy()           # the only device -> host copy; synchronises
+        self.report = eval_report(totals)
+        return self._finish(self.report["return_mean"], self.report["length_mean"], self.report["episodes"])

@@ -326,6 +326,31 @@ class Vine5LinkMovingBase(VecTask):
         self.extras["time_outs"] = self.timeout_buf.to(self.rl_device)
         return obs_out
 
+    def eval_step_rows(self):
+        """Rows of the per-workgroup float64 totals ``step_eval_into`` adds to (0: this configuration does not run the
+        four-lanes-per-env kernel, the evaluation step is not available)."""
+        return 0 if self.mat is not None else int(self._lib.vine_step_eval_rows(self._handle))
+
+    def step_eval_into(self, args, obs_out):
+        """One EVALUATION step in one launch (``vine_step_eval``, include/vine_ppo.h): the policy head's mean on the LSTM
+        output rows in front of the step, per-episode task statistics behind it -- an extension for the player's device
+        path; ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.EvalArgs; the observation goes to ``obs_out``
+        and the buffers are re-bound exactly as ``step_into`` does."""
+        import ctypes as C
+        if self._video is not None:
+            self._video.before(1)
+        native.check(self._lib.vine_step_eval(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
+                                              self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
+                                              self.timeout_buf.data_ptr(), self._stream()), self._lib)
+        if self._video is not None:
+            self._video.enqueue(self._stream())
+            self._video.advance(1)
+        self.num_steps += 1
+        self.obs_buf = obs_out
+        self.obs_dict["obs"] = obs_out.to(self.rl_device)
+        self.extras["time_outs"] = self.timeout_buf.to(self.rl_device)
+        return obs_out
+
     def reset_idx(self, env_ids):
         """V5:774-839 for callers outside the step (reset_done, V5:715-718)."""
         ids = torch.as_tensor(env_ids, device=self.device).to(torch.long).contiguous()
