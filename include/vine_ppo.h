@@ -601,7 +601,7 @@ int vine_adaptive_lr(float* lr, const float* kl, float kl_scale, float kl_thresh
  * (reward shaping + time-out bootstrap, done flags, episode accumulators, LSTM-state rows of finished envs cleared) -- the
  * four-lanes-per-env step kernel does in its prologue and epilogue: the sampled action never leaves the registers, the
  * value is still there when the bootstrap needs it, and two of the five launches of a rollout step (and their ~1.5 us
- * boundaries) are gone.  Same formulas and the same Philox keys as the separate kernels (include/vine_ppo.h); the LayerNorm
+ * boundaries) are gone.  Same formulas and the same Philox keys as the separate kernels (csrc/vine_policy_head.h); the LayerNorm
  * is two-pass (mean, then centred moments) over 64 units per lane.  A == 2 actions, H == 256.
  *   y [N, 256] fp32: LSTM output rows;  hw [3][256], hc [3]: vine_rollout_head_prep's products gamma_u w_k[u] (k = mu_0, mu_1,
  *   value) and constants sum_u beta_u w_k[u] + b_k;  logstd [2];  value_mean / value_var: float64 scalars of the value
@@ -610,7 +610,11 @@ int vine_adaptive_lr(float* lr, const float* kl, float kl_scale, float kl_thresh
  *   reward_shift / reward_scale / gamma_bootstrap, shaped_out [N], dones_out [N] u8, cur_rewards / cur_lengths [N] in/out,
  *   h_state / c_state [N, 256] (rows of finished envs cleared), h_op (nullable; fp32, row stride h_op_stride floats): the
  *   operand copy of h the next inference step reads, partial [vine_step_rollout_blocks(h)][3]: per-workgroup {sum of finished
- *   returns, sum of finished lengths, count} for vine_rollout_finalize / the fold that rides in the next MLP launch.
+ *   returns, sum of finished lengths, count} for vine_rollout_finalize / the fold that rides in the next MLP launch.  Exactly
+ *   the workgroups that own an env, ceil(4 N / 256) of them, write a row each (every step, zeros included); the launch's grid
+ *   is that count rounded up to a power of two, and the workgroups beyond it write nothing.
+ * The head's formulas, the Philox key layouts of the action noise and the bookkeeping are stated once, for this kernel,
+ * vine_policy_head and vine_rollout_post alike, in csrc/vine_policy_head.h.
  * Returns VINE_ERR_UNSUPPORTED when the handle's configuration does not run the four-lane kernel. */
 typedef struct VineRolloutArgs {
     const float* y; const float* hw; const float* hc; const float* logstd;

@@ -2009,6 +2009,153 @@ def test_rollout_step_in_one_launch_matches_the_three_launches(overrides):
     ea.close(); eb.close()
 
 
+def _head_call(lib, form, N, A, H, y, p, out, st):
+    """vine_policy_head (value statistics as two floats) or vine_policy_head_rms (the normaliser's float64 statistics)."""
+    ln = (p["gamma"].data_ptr(), p["beta"].data_ptr(), 1e-5) if p["gamma"] is not None else (None, None, 0.0)
+    tail = (12345, p["counter"].data_ptr(), out["mu"].data_ptr(), out["sigma"].data_ptr(), out["value"].data_ptr(),
+            out["action"].data_ptr(), out["nlp"].data_ptr()) + ln + (st,)
+    head = (N, A, H, y.data_ptr(), p["w_mu"].data_ptr(), p["b_mu"].data_ptr(), p["w_v"].data_ptr(), p["b_v"].data_ptr(),
+            p["logstd"].data_ptr())
+    if form == "rms":
+        return lib.vine_policy_head_rms(*head, p["vmean64"].data_ptr(), p["vvar64"].data_ptr(), 1e-5, *tail)
+    return lib.vine_policy_head(*head, p["vmean32"].data_ptr(), p["vstd32"].data_ptr(), 1, *tail)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,with_ln,A", [(256, True, 2), (512, False, 3)])
+def test_wave_per_env_policy_head_against_float64_torch(H, with_ln, A):
+    """policy_head_kernel (one wave per env: taken when N % 16 != 0, or without LayerNorm / H != 256) at N = 20 against a
+    float64 restatement, for both forms of the value un-normalisation.  H = 512: the strided unit loop runs twice; A = 3: the
+    second Philox draw serves one component.  mu to rtol = atol = 2e-6 (what test_eval_step holds mu to); the value to the
+    same bound on the raw head carried through clamp(v) * std + mean: atol 2e-6 (std + |mean|), rtol 2e-6; sigma equals
+    exp(logstd); neglogp against the stock model's formula at test_fused_rollout's 2e-4.  With H = 256 the first 16 envs also
+    go through policy_head16_kernel (16 lanes per env) with the same seed and counter: same Philox keys, so the implied noise
+    (action - mu) / sigma agrees to the 1e-4 of the one-launch / three-launch comparison, and neglogp -- a function of the
+    noise and logstd alone, from the one head_tail -- bit for bit (it does on the parent too: profiles/policy_head_once)."""
+    import math
+    from vine_robot_isaacgymenvs_amd.learning.network import ModelA2CContinuousLogStd
+    lib = fused._lib()
+    dev = torch.device("cuda:0")
+    N = 20
+    st = torch.cuda.current_stream().cuda_stream
+    g = torch.Generator(device=dev).manual_seed(7)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
+    p = dict(gamma=1.0 + 0.1 * rnd(H) if with_ln else None, beta=0.1 * rnd(H) if with_ln else None,
+             w_mu=0.1 * rnd(A, H), b_mu=0.1 * rnd(A), w_v=0.1 * rnd(1, H), b_v=0.1 * rnd(1),
+             logstd=torch.tensor([-0.3, 0.2, -1.1][:A], device=dev),
+             vmean64=torch.tensor([0.37], device=dev, dtype=torch.float64), vvar64=torch.tensor([2.3], device=dev, dtype=torch.float64),
+             counter=torch.tensor([3], device=dev, dtype=torch.int64))
+    p["vmean32"] = p["vmean64"].float()
+    p["vstd32"] = torch.sqrt(p["vvar64"].float() + 1e-5)
+    y = rnd(N, H)
+
+    def outputs(n):
+        return dict(mu=torch.empty(n, A, device=dev), sigma=torch.empty(n, A, device=dev), value=torch.empty(n, 1, device=dev),
+                    action=torch.empty(n, A, device=dev), nlp=torch.empty(n, device=dev))
+    # ---- the float64 restatement (computed once, shared by the two forms)
+    x = y.double()
+    if with_ln:
+        x = (x - x.mean(1, keepdim=True)) / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + 1e-5)
+        x = x * p["gamma"].double() + p["beta"].double()
+    mu_ref = x @ p["w_mu"].double().t() + p["b_mu"].double()
+    v_ref = (x @ p["w_v"].double().t() + p["b_v"].double()).clamp(-5.0, 5.0)
+    stats = {"rms": (float(p["vmean64"].float()), math.sqrt(float(p["vvar64"].float()) + float(np.float32(1e-5)))),
+             "two_floats": (float(p["vmean32"]), float(p["vstd32"]))}
+    outs = {}
+    for form, (vm, vs) in stats.items():
+        o = outs[form] = outputs(N)
+        assert _head_call(lib, form, N, A, H, y, p, o, st) == 0
+        torch.cuda.synchronize()
+        print(form, "max |mu - ref| %.3e  max |value - ref| %.3e  max |sigma - exp(logstd)| %.3e"
+              % (float((o["mu"].double() - mu_ref).abs().max()), float((o["value"].double() - (v_ref * vs + vm)).abs().max()),
+                 float((o["sigma"] - torch.exp(p["logstd"])).abs().max())))
+        torch.testing.assert_close(o["mu"].double(), mu_ref, rtol=2e-6, atol=2e-6, msg=form + " mu")
+        torch.testing.assert_close(o["value"].double(), v_ref * vs + vm, rtol=2e-6, atol=2e-6 * (vs + abs(vm)), msg=form + " value")
+        assert torch.equal(o["sigma"], torch.exp(p["logstd"]).expand(N, A)), form
+        nlp = ModelA2CContinuousLogStd.neglogp(o["action"], o["mu"], o["sigma"], torch.log(o["sigma"]))
+        assert torch.allclose(nlp, o["nlp"], atol=2e-4), form
+    # the sampling does not depend on the form of the value statistics
+    assert torch.equal(outs["rms"]["action"], outs["two_floats"]["action"]) and torch.equal(outs["rms"]["nlp"], outs["two_floats"]["nlp"])
+    if H == 256 and with_ln:
+        o, o16 = outs["rms"], outputs(16)
+        assert _head_call(lib, "rms", 16, A, H, y[:16].contiguous(), p, o16, st) == 0
+        torch.cuda.synchronize()
+        noise, noise16 = (o["action"] - o["mu"]) / o["sigma"], (o16["action"] - o16["mu"]) / o16["sigma"]
+        print("16 lanes per env: max |noise diff| %.3e  neglogp bit-equal: %s"
+              % (float((noise[:16] - noise16).abs().max()), torch.equal(o["nlp"][:16], o16["nlp"])))
+        torch.testing.assert_close(noise[:16], noise16, rtol=1e-4, atol=1e-4)
+        torch.testing.assert_close(o["mu"][:16], o16["mu"], rtol=2e-6, atol=2e-6)
+        assert torch.equal(o["nlp"][:16], o16["nlp"])
+
+
+@pytest.mark.gpu
+def test_rollout_step_writes_only_the_documented_partial_rows():
+    """vine_step_rollout at 300 envs: 1200 lanes = 4.69 workgroups, so 5 workgroups own envs (the last one partly filled) in
+    a grid of 8.  ``partial`` is documented as [vine_step_rollout_blocks()][3] = 5 rows: here it is a view of exactly 15 floats
+    in front of a sentinel tail, which stays intact; after every step the 5 rows add up to the step's finished episodes
+    (count and lengths exactly; returns within (terms + 1) 2^-24 sum |term|: one fp32 rounding per env's return and the
+    first-order bound of an fp32 sum of that many terms in any order)."""
+    from vine_robot_isaacgymenvs_amd import abi, load_config
+    from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
+    lib = fused._lib()
+    dev = torch.device("cuda:0")
+    N, H, A = 300, 256, 2
+    st = torch.cuda.current_stream().cuda_stream
+    cfg = load_config(overrides=["num_envs=%d" % N, "task.env.CREATE_PIPE=False", "task.env.maxEpisodeLength=3"])
+    cfg["task"]["seed"] = 42
+    env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
+                                                   graphics_device_id=0, headless=True)
+    assert env.rollout_step_blocks() == 5
+    g = torch.Generator(device=dev).manual_seed(1)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g)
+    gamma, beta = 1.0 + 0.1 * rnd(H), 0.1 * rnd(H)
+    w_mu, b_mu, w_v, b_v = 0.1 * rnd(A, H), 0.1 * rnd(A), 0.1 * rnd(1, H), 0.1 * rnd(1)
+    logstd = torch.tensor([-0.3, 0.2], device=dev)
+    vmean = torch.tensor([0.37], device=dev, dtype=torch.float64)
+    vvar = torch.tensor([2.3], device=dev, dtype=torch.float64)
+    counter = torch.tensor([3], device=dev, dtype=torch.int64)
+    hw, hc = torch.empty(3 * H, device=dev), torch.empty(3, device=dev)
+    assert lib.vine_rollout_head_prep(gamma.data_ptr(), beta.data_ptr(), w_mu.data_ptr(), b_mu.data_ptr(), w_v.data_ptr(),
+                                      b_v.data_ptr(), hw.data_ptr(), hc.data_ptr(), st) == 0
+    s = dict(mu=torch.empty(N, A, device=dev), sigma=torch.empty(N, A, device=dev), value=torch.empty(N, 1, device=dev),
+             action=torch.empty(N, A, device=dev), nlp=torch.empty(N, device=dev), shaped=torch.empty(N, 1, device=dev),
+             dones=torch.empty(N, device=dev, dtype=torch.uint8), cur_r=torch.zeros(N, 1, device=dev),
+             cur_l=torch.zeros(N, device=dev), h=torch.ones(1, N, H, device=dev), c=torch.ones(1, N, H, device=dev),
+             hop=torch.ones(N, 352, device=dev), obs=torch.empty(N, env.num_obs, device=dev))
+    SENTINEL = -12345.0
+    scratch = torch.full((64,), SENTINEL, device=dev)      # rows 5 .. 7 of the grid would land in [15, 24): inside the tensor
+    partial = scratch[:15]
+    n_done = n_done_last = 0
+    for step in range(4):
+        y = rnd(N, H)
+        cur_r, cur_l = s["cur_r"].double().view(N).clone(), s["cur_l"].double().clone()
+        ra = abi.RolloutArgs()
+        ra.y, ra.hw, ra.hc, ra.logstd = y.data_ptr(), hw.data_ptr(), hc.data_ptr(), logstd.data_ptr()
+        ra.value_mean, ra.value_var, ra.ln_eps, ra.value_eps = vmean.data_ptr(), vvar.data_ptr(), 1e-5, 1e-5
+        ra.seed, ra.counter = 12345, counter.data_ptr()
+        ra.mu_out, ra.sigma_out, ra.value_out = s["mu"].data_ptr(), s["sigma"].data_ptr(), s["value"].data_ptr()
+        ra.action_out, ra.neglogp_out = s["action"].data_ptr(), s["nlp"].data_ptr()
+        ra.reward_shift, ra.reward_scale, ra.gamma_bootstrap = 0.0, 0.01, 0.99
+        ra.shaped_out, ra.dones_out = s["shaped"].data_ptr(), s["dones"].data_ptr()
+        ra.cur_rewards, ra.cur_lengths = s["cur_r"].data_ptr(), s["cur_l"].data_ptr()
+        ra.h_state, ra.c_state, ra.h_op, ra.h_op_stride = s["h"].data_ptr(), s["c"].data_ptr(), s["hop"].data_ptr() + 4 * 96, 352
+        ra.partial = partial.data_ptr()
+        env.step_rollout_into(ra, s["obs"])
+        torch.cuda.synchronize()
+        assert torch.equal(scratch[15:], torch.full((49,), SENTINEL, device=dev)), "step %d: a row past the documented 5" % step
+        done = env.reset_buf != 0
+        assert torch.equal(s["dones"], done.to(torch.uint8))
+        fin_r, fin_l = (cur_r + env.rew_buf.double().view(N))[done], (cur_l + 1.0)[done]
+        rows = partial.view(5, 3).double().sum(0)
+        assert float(rows[2]) == float(done.sum()) and float(rows[1]) == float(fin_l.sum()), step
+        assert abs(float(rows[0]) - float(fin_r.sum())) <= (int(done.sum()) + 1) * 2.0 ** -24 * float(fin_r.abs().sum()) + 1e-30, step
+        n_done += int(done.sum())
+        n_done_last += int(done[256:].sum())
+        counter += 1
+    assert n_done >= N and n_done_last >= N - 256      # every env finished (time-outs), the partly filled workgroup's too
+    env.close()
+
+
 # --------------------------------------------------------------------------- GradScaler semantics on the device
 @pytest.mark.gpu
 def test_adam_amp_is_gradscaler_step_and_update():

@@ -8,6 +8,7 @@
 
 #include "../../include/vine.h"
 #include "../../include/vine_ppo.h"
+#include "vine_policy_head.h"      // Philox, the head's lane tail and the rollout bookkeeping, shared with vine_hip.hip
 
 namespace {
 
@@ -4131,19 +4132,6 @@ __global__ void adaptive_lr_kernel(float* lr, const float* kl, float kl_scale, f
     *lr = out;
 }
 
-__device__ __forceinline__ void philox4(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                        unsigned (&o)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-
 // One wave handles envs e = wave_id, wave_id + n_waves, ...; lane l owns hidden units 4l..4l+3 (H == 256) or a
 // strided subset (general H): partial dot products in registers, butterfly reduction across the 64 lanes.
 #define HEAD_MAX_A 8
@@ -4163,9 +4151,7 @@ __global__ __launch_bounds__(256) void policy_head_kernel(long long N, int A, in
     const long long n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
     const unsigned long long ctr = (unsigned long long)counter[0];
     for (long long e = wave; e < N; e += n_waves) {
-        float acc[HEAD_MAX_A + 1];
-#pragma unroll
-        for (int k = 0; k <= HEAD_MAX_A; ++k) acc[k] = 0.0f;
+        float acc[HEAD_MAX_A + 1] = {};
         // ln_gamma != NULL (H == 256 only): y is the raw LSTM output and the LayerNorm in front of the heads is applied
         // here (same arithmetic as layernorm_fwd_kernel: two-pass mean / biased variance over the 256 units)
         float ln_mean = 0.0f, ln_rstd = 1.0f;
@@ -4193,41 +4179,11 @@ __global__ __launch_bounds__(256) void policy_head_kernel(long long N, int A, in
             acc[HEAD_MAX_A] += yy.x * w.x + yy.y * w.y + yy.z * w.z + yy.w * w.w;
         }
 #pragma unroll
-        for (int k = 0; k <= HEAD_MAX_A; ++k) {
-            if (k < A || k == HEAD_MAX_A) {
-                acc[k] = wave_sum(acc[k]);
-            }
-        }
-        if (lane == 0) {
-            float v = acc[HEAD_MAX_A] + b_v[0];
-            if (normalize_value == 2) {      // RunningMeanStd's own float64 statistics: mean.float(), sqrt(var.float() + eps)
-                const float vm = (float)reinterpret_cast<const double*>(vmean)[0];
-                const float vs = sqrtf((float)reinterpret_cast<const double*>(vstd)[0] + value_eps);
-                v = fminf(fmaxf(v, -5.0f), 5.0f) * vs + vm;
-            } else if (normalize_value) v = fminf(fmaxf(v, -5.0f), 5.0f) * vstd[0] + vmean[0];
-            value_out[e] = v;
-            float nlp = 0.9189385332046727f * A;
-            unsigned r[4];
-            for (int k = 0; k < A; k += 2) {
-                philox4((unsigned)e, (unsigned)ctr, 0x504f4c59u | 0u, (unsigned)(k >> 1), seed_lo, seed_hi, r);
-                const float u1 = 1.0f - (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-                const float u2 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
-                const float rad = sqrtf(-2.0f * __logf(u1));
-                float sn, cs;
-                __sincosf(6.283185307179586f * u2, &sn, &cs);
-                const float eps2[2] = {rad * cs, rad * sn};
-                for (int q = 0; q < 2 && k + q < A; ++q) {
-                    const int kk = k + q;
-                    const float m = acc[kk] + b_mu[kk], ls = logstd[kk], sg = __expf(ls);
-                    const float a = m + sg * eps2[q];
-                    mu_out[e * A + kk] = m;
-                    sigma_out[e * A + kk] = sg;
-                    action_out[e * A + kk] = a;
-                    nlp += 0.5f * eps2[q] * eps2[q] + ls;
-                }
-            }
-            neglogp_out[e] = nlp;
-        }
+        for (int k = 0; k <= HEAD_MAX_A; ++k)
+            if (k < A || k == HEAD_MAX_A) acc[k] = wave_sum(acc[k]);
+        if (lane == 0)
+            head_tail<HEAD_MAX_A>(e, A, acc, b_mu, b_v, logstd, vmean, vstd, normalize_value, value_eps, seed_lo, seed_hi, ctr,
+                                  mu_out, sigma_out, value_out, action_out, neglogp_out);
     }
 }
 
@@ -4266,9 +4222,7 @@ __global__ __launch_bounds__(256) void policy_head16_kernel(long long N, int A, 
             q += xa[j][u] * xa[j][u];
         }
     const float rstd = rsqrtf(row_allsum16(q) * (1.0f / H) + ln_eps);
-    float acc[HEAD_MAX_A + 1];
-#pragma unroll
-    for (int k = 0; k <= HEAD_MAX_A; ++k) acc[k] = 0.0f;
+    float acc[HEAD_MAX_A + 1] = {};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = 4 * (cl + 16 * j);
@@ -4288,36 +4242,9 @@ __global__ __launch_bounds__(256) void policy_head16_kernel(long long N, int A, 
 #pragma unroll
     for (int k = 0; k <= HEAD_MAX_A; ++k)
         if (k < A || k == HEAD_MAX_A) acc[k] = row_allsum16(acc[k]);
-    if (cl == 0) {
-        float v = acc[HEAD_MAX_A] + b_v[0];
-        if (normalize_value == 2) {          // RunningMeanStd's own float64 statistics: mean.float(), sqrt(var.float() + eps)
-            const float vm = (float)reinterpret_cast<const double*>(vmean)[0];
-            const float vs = sqrtf((float)reinterpret_cast<const double*>(vstd)[0] + value_eps);
-            v = fminf(fmaxf(v, -5.0f), 5.0f) * vs + vm;
-        } else if (normalize_value) v = fminf(fmaxf(v, -5.0f), 5.0f) * vstd[0] + vmean[0];
-        value_out[e] = v;
-        float nlp = 0.9189385332046727f * A;
-        unsigned r[4];
-        for (int k = 0; k < A; k += 2) {
-            philox4((unsigned)e, (unsigned)ctr, 0x504f4c59u | 0u, (unsigned)(k >> 1), seed_lo, seed_hi, r);
-            const float u1 = 1.0f - (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-            const float u2 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
-            const float rad = sqrtf(-2.0f * __logf(u1));
-            float sn, cs;
-            __sincosf(6.283185307179586f * u2, &sn, &cs);
-            const float eps2[2] = {rad * cs, rad * sn};
-            for (int qq = 0; qq < 2 && k + qq < A; ++qq) {
-                const int kk = k + qq;
-                const float m = acc[kk] + b_mu[kk], ls = logstd[kk], sg = __expf(ls);
-                const float a = m + sg * eps2[qq];
-                mu_out[e * A + kk] = m;
-                sigma_out[e * A + kk] = sg;
-                action_out[e * A + kk] = a;
-                nlp += 0.5f * eps2[qq] * eps2[qq] + ls;
-            }
-        }
-        neglogp_out[e] = nlp;
-    }
+    if (cl == 0)
+        head_tail<HEAD_MAX_A>(e, A, acc, b_mu, b_v, logstd, vmean, vstd, normalize_value, value_eps, seed_lo, seed_hi, ctr, mu_out,
+                              sigma_out, value_out, action_out, neglogp_out);
 }
 
 #define ROLLOUT_POST_BLOCKS 1024
@@ -4338,18 +4265,11 @@ __global__ __launch_bounds__(256) void rollout_post_kernel(
         const int k = (int)(idx & 15);
         const bool done = reset[e] != 0;
         if (k == 0) {
-            const float r = rew[e];
-            float s = (r + shift) * scale;
-            if (gamma_b != 0.0f && timeouts[e]) s += gamma_b * values[e];
-            shaped[e] = s;
+            float cr = cur_r[e], cl = cur_l[e], fin_r, fin_l;
+            shaped[e] = rollout_book(rew[e], done, timeouts + e, values + e, shift, scale, gamma_b, cr, cl, fin_r, fin_l);
             dones[e] = done ? 1 : 0;
-            const float cr = cur_r[e] + r, cl = cur_l[e] + 1.0f;
-            if (done) {
-                sr += cr; sl += cl; cnt += 1.0f;
-                cur_r[e] = 0.0f; cur_l[e] = 0.0f;
-            } else {
-                cur_r[e] = cr; cur_l[e] = cl;
-            }
+            cur_r[e] = cr; cur_l[e] = cl;
+            if (done) { sr += fin_r; sl += fin_l; cnt += 1.0f; }
         }
         if (done) {
             const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -4363,14 +4283,9 @@ __global__ __launch_bounds__(256) void rollout_post_kernel(
             }
         }
     }
-    sr = wave_sum(sr); sl = wave_sum(sl); cnt = wave_sum(cnt);
     __shared__ float red[4][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[wave][0] = sr; red[wave][1] = sl; red[wave][2] = cnt; }
-    __syncthreads();
-    if (threadIdx.x < 3)
-        partial[blockIdx.x * 3 + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    const float v3[3] = {wave_sum(sr), wave_sum(sl), wave_sum(cnt)};
+    store_block_row3(red, v3, partial + blockIdx.x * 3);
 }
 
 // rl_games AverageMeter.update for both meters from the step's (sum, count) -- the per-workgroup rows of the kernel

@@ -29,6 +29,7 @@
 #include "../../include/vine.h"
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
 #include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
+#include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
 #include "vine_render_internal.h"
 
 #define NL VINE_NUM_LINKS
@@ -76,18 +77,7 @@ struct DevParams {
 
 enum { RNG_RESET = 1, RNG_ACTION_NOISE = 2, RNG_DYN_SCALE = 3, RNG_OBS_NOISE = 4 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// (philox4x32_10 and u01: vine_policy_head.h)
 __device__ __forceinline__ void rng4(const DevParams& P, unsigned env, unsigned long long step, unsigned purpose,
                                      unsigned idx, unsigned out[4]) {
     // env: local index; the key is the GLOBAL env id (VineConfig.env_id_offset), so a shard draws what the whole batch does
@@ -107,7 +97,6 @@ __device__ __forceinline__ void step_arrive(unsigned long long* counters) {
     __builtin_amdgcn_s_barrier();      // every wave of the workgroup has read the counters long ago; no fence: nothing is published
     if (threadIdx.x == 0) (void)__hip_atomic_fetch_add(&counters[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ void normal2(unsigned a, unsigned b, float& n0, float& n1) {
     // Box-Muller on the hardware's log2 / sin / cos (v_log_f32, v_sin_f32, v_cos_f32 take the angle in revolutions, i.e.
     // u2 itself): ~10 instructions instead of the ~250 of logf + sinf + cosf with their range reductions; the step draws
@@ -1190,18 +1179,11 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
 // differ by round-off only (another elimination order).  Covers the configurations the rollout actually runs at that
 // size -- no obstacle, implicit joint damping, no joint stiffness / link damping, the two scalable observation
 // layouts; everything else takes the one-lane kernel.
-template <int CTRL>
-__device__ __forceinline__ float qperm(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
+// (qperm<CTRL>, the DPP quad_perm read, and quad_sum: vine_policy_head.h)
 template <int K>
 __device__ __forceinline__ float qbcast(float v) { return qperm<K * 0x55>(v); }            // lane K of the quad
 __device__ __forceinline__ float qprev(float v) { return qperm<0x93>(v); }                 // lane t reads lane t - 1
 __device__ __forceinline__ float qnext(float v) { return qperm<0x39>(v); }                 // lane t reads lane t + 1
-__device__ __forceinline__ float quad_sum(float v) {
-    const float s = v + qperm<0xB1>(v);                                                    // xor 1
-    return s + qperm<0x4E>(s);                                                             // xor 2
-}
 // NOTE on selects: a DPP read must execute with the whole quad active -- a source lane that EXEC has switched off
 // delivers 0 -- and `c ? dpp(x) : y` is a branch around the DPP (C++ evaluates only the chosen operand, and the
 // compiler may not speculate a convergent operation).  Every cross-lane value is therefore produced unconditionally
@@ -1246,6 +1228,12 @@ __device__ __forceinline__ void fmac_bcast(float& acc, float src, float b) {
     }
 }
 
+// sum over the wave on every lane, as an xor butterfly (the order of the ROLL / EVAL folds and of the head's preparation)
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
 // inclusive prefix sum over the quad (lane t: v_0 + ... + v_t): two DPP steps
 __device__ __forceinline__ float quad_scan_incl(float v, int t) {
     const float s = v + pick(t > 0, qprev(v), 0.0f);
@@ -1289,7 +1277,6 @@ struct EvalArgs {
 enum { STEP_PLAIN = 0, STEP_ROLL = 1, STEP_EVAL = 2 };
 template <int MODE> struct StepModeArgs { using type = RollArgs; };
 template <> struct StepModeArgs<STEP_EVAL> { using type = EvalArgs; };
-#define RNG_EVAL_ACTION 0x4556414cu      // Philox purpose word of the evaluation step's action noise ("EVAL")
 template <int OBS_TYPE, bool RANDOMIZE, int OBST, int MODE = STEP_PLAIN>   // OBST bit 0: shelf, bit 1: pipe
 __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, float* __restrict__ st,
                                                              const float* __restrict__ actions, float* __restrict__ obs,
@@ -1425,35 +1412,18 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
 #endif
         float roll_value = 0.0f;
         if constexpr (EVAL) {
-            // ---- the policy head's mean only (the ROLL head below without the value row): two-pass LayerNorm of the row, the
-            // two centred dot products with gamma_u w_k[u]; the action is the mean, or the mean plus noise keyed by the
-            // handle's own step count (nothing outside the handle counts evaluation steps)
-            float s1 = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s1 += (yq[i].x + yq[i].y) + (yq[i].z + yq[i].w);
-            const float mean = quad_sum(s1) * (1.0f / 256.0f);
-            float q2 = 0.0f, d0 = 0.0f, d1 = 0.0f;
-            const float4* hw0 = reinterpret_cast<const float4*>(R.hw) + t;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float4 w0 = hw0[4 * i], w1 = hw0[64 + 4 * i];
-                const float c0 = yq[i].x - mean, c1 = yq[i].y - mean, c2 = yq[i].z - mean, c3 = yq[i].w - mean;
-                q2 += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
-                d0 += (c0 * w0.x + c1 * w0.y) + (c2 * w0.z + c3 * w0.w);
-                d1 += (c0 * w1.x + c1 * w1.y) + (c2 * w1.z + c3 * w1.w);
-            }
-            const float rstd = rsqrtf(quad_sum(q2) * (1.0f / 256.0f) + R.ln_eps);
-            const float m0 = rstd * quad_sum(d0) + R.hc[0], m1 = rstd * quad_sum(d1) + R.hc[1];
+            // ---- the policy head's mean only (the ROLL head below without the value row); the action is the mean, or the
+            // mean plus noise keyed by the handle's own step count (nothing outside the handle counts evaluation steps)
+            float hd[2];
+            quad_ln_heads<2>(yq, R.hw, t, R.ln_eps, R.hc, hd);
+            const float m0 = hd[0], m1 = hd[1];
             act = make_float2(m0, m1);
             if (!R.deterministic) {
                 unsigned r[4];
-                philox4x32_10((unsigned)e, (unsigned)step, RNG_EVAL_ACTION, (unsigned)(step >> 32), R.seed_lo, R.seed_hi, r);
-                const float u1 = 1.0f - (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-                const float u2 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
-                const float rad = sqrtf(-2.0f * __logf(u1));
-                float sn_, cs_;
-                __sincosf(6.283185307179586f * u2, &sn_, &cs_);
-                act = make_float2(m0 + __expf(R.logstd[0]) * (rad * cs_), m1 + __expf(R.logstd[1]) * (rad * sn_));
+                rng_eval_action((unsigned)e, step, R.seed_lo, R.seed_hi, r);
+                float e0, e1;
+                action_noise_pair(r[0], r[1], e0, e1);
+                act = make_float2(m0 + __expf(R.logstd[0]) * e0, m1 + __expf(R.logstd[1]) * e1);
             }
             if (t == 0) {
                 if (R.mu_out) reinterpret_cast<float2*>(R.mu_out)[e] = make_float2(m0, m1);
@@ -1461,45 +1431,24 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
             }
         }
         if constexpr (ROLL) {
-            // ---- policy head (vine_policy_head's formulas, ppo_kernels.hip): LayerNorm of the row (two passes: mean, then
-            // centred second moment and the three centred dot products with gamma_u w_k[u]), mu / value, sampling
-            float s1 = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) s1 += (yq[i].x + yq[i].y) + (yq[i].z + yq[i].w);
-            const float mean = quad_sum(s1) * (1.0f / 256.0f);
-            float q2 = 0.0f, d0 = 0.0f, d1 = 0.0f, d2 = 0.0f;
-            const float4* hw0 = reinterpret_cast<const float4*>(R.hw) + t;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float4 w0 = hw0[4 * i], w1 = hw0[64 + 4 * i], w2 = hw0[128 + 4 * i];
-                const float c0 = yq[i].x - mean, c1 = yq[i].y - mean, c2 = yq[i].z - mean, c3 = yq[i].w - mean;
-                q2 += (c0 * c0 + c1 * c1) + (c2 * c2 + c3 * c3);
-                d0 += (c0 * w0.x + c1 * w0.y) + (c2 * w0.z + c3 * w0.w);
-                d1 += (c0 * w1.x + c1 * w1.y) + (c2 * w1.z + c3 * w1.w);
-                d2 += (c0 * w2.x + c1 * w2.y) + (c2 * w2.z + c3 * w2.w);
-            }
-            const float rstd = rsqrtf(quad_sum(q2) * (1.0f / 256.0f) + R.ln_eps);
-            const float m0 = rstd * quad_sum(d0) + R.hc[0], m1 = rstd * quad_sum(d1) + R.hc[1];
-            float v = rstd * quad_sum(d2) + R.hc[2];
-            if (R.vmean) {      // RunningMeanStd's own float64 statistics: mean.float(), sqrt(var.float() + eps)
-                const float vm = (float)R.vmean[0], vs = sqrtf((float)R.vvar[0] + R.veps);
-                v = fminf(fmaxf(v, -5.0f), 5.0f) * vs + vm;
-            }
+            // ---- policy head (vine_policy_head's formulas for A == 2, vine_policy_head.h): LayerNorm of the row, mu / value,
+            // sampling
+            float hd[3];
+            quad_ln_heads<3>(yq, R.hw, t, R.ln_eps, R.hc, hd);
+            const float m0 = hd[0], m1 = hd[1];
+            float v = hd[2];
+            if (R.vmean) v = unnormalize_value(v, R.vmean, R.vvar, R.veps);
             roll_value = v;
             unsigned r[4];
-            philox4x32_10((unsigned)e, (unsigned)(unsigned long long)R.counter[0], 0x504f4c59u, 0u, R.seed_lo, R.seed_hi, r);
-            const float u1 = 1.0f - (float)(r[0] >> 8) * (1.0f / 16777216.0f);
-            const float u2 = (float)(r[1] >> 8) * (1.0f / 16777216.0f);
-            const float rad = sqrtf(-2.0f * __logf(u1));
-            float sn_, cs_;
-            __sincosf(6.283185307179586f * u2, &sn_, &cs_);
-            const float e0 = rad * cs_, e1 = rad * sn_;
+            rng_policy_action((unsigned)e, (unsigned long long)R.counter[0], 0u, R.seed_lo, R.seed_hi, r);
+            float e0, e1;
+            action_noise_pair(r[0], r[1], e0, e1);
             const float ls0 = R.logstd[0], ls1 = R.logstd[1], sg0 = __expf(ls0), sg1 = __expf(ls1);
             act = make_float2(m0 + sg0 * e0, m1 + sg1 * e1);
             if (t == 0) {
-                float nlp = 0.9189385332046727f * 2.0f;
-                nlp += 0.5f * e0 * e0 + ls0;
-                nlp += 0.5f * e1 * e1 + ls1;
+                float nlp = gauss_neglogp_const(2);
+                nlp += gauss_neglogp(e0, ls0);
+                nlp += gauss_neglogp(e1, ls1);
                 reinterpret_cast<float2*>(R.mu_out)[e] = make_float2(m0, m1);
                 reinterpret_cast<float2*>(R.sigma_out)[e] = make_float2(sg0, sg1);
                 reinterpret_cast<float2*>(R.action_out)[e] = act;
@@ -1974,31 +1923,18 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                                     u_rail, prev_u_rail, rail_force, cmean);
         }
         if constexpr (ROLL) {
-            // ---- vine_rollout_post's bookkeeping (play_steps_rnn; common_agent.py:293-306): shaped reward with the time-out
-            // bootstrap, done flag, episode accumulators; the LSTM-state rows of a finished env are cleared by its four lanes
+            // ---- vine_rollout_post's bookkeeping (rollout_book): shaped reward with the time-out bootstrap, done flag,
+            // episode accumulators; the LSTM-state rows of a finished env are cleared by its four lanes
             const bool done = rst != 0;
-            const float cr = roll_cr + total, cl = roll_cl + 1.0f;
             if (t == 0) {
-                float sh = (total + R.shift) * R.scale;
-                if (R.gamma_b != 0.0f && to) sh += R.gamma_b * roll_value;
-                R.shaped[e] = sh;
+                float fin_r, fin_l;
+                R.shaped[e] = rollout_book(total, done, &to, &roll_value, R.shift, R.scale, R.gamma_b, roll_cr, roll_cl, fin_r, fin_l);
                 R.dones[e] = done ? 1 : 0;
-                R.cur_r[e] = done ? 0.0f : cr;
-                R.cur_l[e] = done ? 0.0f : cl;
-                if (done) { roll_sr = cr; roll_sl = cl; roll_cnt = 1.0f; }
+                R.cur_r[e] = roll_cr;
+                R.cur_l[e] = roll_cl;
+                if (done) { roll_sr = fin_r; roll_sl = fin_l; roll_cnt = 1.0f; }
             }
-            if (done) {
-                const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                float4* hr = reinterpret_cast<float4*>(R.h_state + (size_t)e * 256) + t;
-                float4* cr4 = reinterpret_cast<float4*>(R.c_state + (size_t)e * 256) + t;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { hr[4 * i] = z; cr4[4 * i] = z; }
-                if (R.h_op) {
-                    float4* orow = reinterpret_cast<float4*>(R.h_op + (size_t)e * R.h_op_stride) + t;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) orow[4 * i] = z;
-                }
-            }
+            if (done) quad_clear_lstm_rows(R.h_state, R.c_state, R.h_op, R.h_op_stride, e, t);
         }
         if constexpr (EVAL) {
             // ---- episode accounting: the env's running {return, length, smallest distance, step of the first reach}; an
@@ -2030,18 +1966,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
                         (ends.contact && (P.flags & VINE_FLAG_USE_NONZERO_CONTACT_FORCE_RESET)) ? 1.0f : 0.0f;
                 }
             }
-            if (done) {
-                const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                float4* hr = reinterpret_cast<float4*>(R.h_state + (size_t)e * 256) + t;
-                float4* cr4 = reinterpret_cast<float4*>(R.c_state + (size_t)e * 256) + t;
-#pragma unroll
-                for (int i = 0; i < 16; ++i) { hr[4 * i] = z; cr4[4 * i] = z; }
-                if (R.h_op) {
-                    float4* orow = reinterpret_cast<float4*>(R.h_op + (size_t)e * R.h_op_stride) + t;
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) orow[4 * i] = z;
-                }
-            }
+            if (done) quad_clear_lstm_rows(R.h_state, R.c_state, R.h_op, R.h_op_stride, e, t);
         }
     }
     if constexpr (EVAL) {
@@ -2051,10 +1976,7 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         __shared__ float ev_red[4][VINE_EVAL_NUM_TOTALS];
         if (__any(ev_tot[VINE_EVAL_EPISODES] != 0.0f)) {
 #pragma unroll
-            for (int k = 0; k < VINE_EVAL_NUM_TOTALS; ++k) {
-#pragma unroll
-                for (int off = 32; off >= 1; off >>= 1) ev_tot[k] += __shfl_xor(ev_tot[k], off, 64);
-            }
+            for (int k = 0; k < VINE_EVAL_NUM_TOTALS; ++k) ev_tot[k] = wave_sum_xor(ev_tot[k]);
         }
         if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -2071,19 +1993,13 @@ __global__ __launch_bounds__(256) void vine_step_quad_kernel(const DevParams P, 
         }
     }
     if constexpr (ROLL) {
-        // one {sum of finished returns, sum of finished lengths, count} row per workgroup, fixed order (no atomics)
-        __shared__ float roll_red[4][3];
-        float v3[3] = {roll_sr, roll_sl, roll_cnt};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) v3[k] += __shfl_xor(v3[k], off, 64);
+        // one {sum of finished returns, sum of finished lengths, count} row per workgroup THAT OWNS AN ENV, fixed order (no
+        // atomics): `partial` has vine_step_rollout_blocks() rows, the power-of-two grid may have more workgroups
+        if ((int)(blockIdx.x * blockDim.x) < 4 * n) {
+            __shared__ float roll_red[4][3];
+            const float v3[3] = {wave_sum_xor(roll_sr), wave_sum_xor(roll_sl), wave_sum_xor(roll_cnt)};
+            store_block_row3(roll_red, v3, R.partial + blockIdx.x * 3);
         }
-        if ((threadIdx.x & 63) == 0) { roll_red[threadIdx.x >> 6][0] = v3[0]; roll_red[threadIdx.x >> 6][1] = v3[1]; roll_red[threadIdx.x >> 6][2] = v3[2]; }
-        __syncthreads();
-        if (threadIdx.x < 3)
-            R.partial[blockIdx.x * 3 + threadIdx.x] = (roll_red[0][threadIdx.x] + roll_red[1][threadIdx.x]) +
-                                                      (roll_red[2][threadIdx.x] + roll_red[3][threadIdx.x]);
     }
 #ifdef VSQ_TIMING
     if ((threadIdx.x & 63) == 0) vsq_t[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + 7] = wall_clock64();
@@ -2639,10 +2555,7 @@ __global__ __launch_bounds__(256) void rollout_head_prep_kernel(const float* __r
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         hw[k * 256 + u] = g * w[k];
-        float v = b * w[k];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        part[k] = v;
+        part[k] = wave_sum_xor(b * w[k]);
     }
     if ((u & 63) == 0) { red[0][u >> 6] = part[0]; red[1][u >> 6] = part[1]; red[2][u >> 6] = part[2]; }
     __syncthreads();
@@ -2662,7 +2575,8 @@ int32_t vine_step_rollout_args_size(void) { return (int32_t)sizeof(VineRolloutAr
 
 int32_t vine_step_rollout_blocks(VineHandle* h) {
     if (!h || !use_quad_kernel(h)) return 0;
-    return (int32_t)(((long long)h->P.n * 4 + VSQ_THREADS - 1) / VSQ_THREADS);      // the workgroups that own envs
+    // the workgroups that own envs: the rows of `partial` (include/vine_ppo.h); the ROLL epilogue applies the same test
+    return (int32_t)(((long long)h->P.n * 4 + VSQ_THREADS - 1) / VSQ_THREADS);
 }
 
 int vine_step_rollout(VineHandle* h, const VineRolloutArgs* a, float* obs, float* rew, int64_t* reset, int64_t* progress,

@@ -545,10 +545,7 @@ class A2CAgent(FastInferenceMixin):
                 self._roll_head = (torch.empty(3 * H, device=self.device), torch.empty(3, device=self.device))
                 self._roll_args = []
             hw, hc = self._roll_head
-            fused._check(lib.vine_rollout_head_prep(net.layer_norm.weight.data_ptr(), net.layer_norm.bias.data_ptr(),
-                                                    net.mu.weight.data_ptr(), net.mu.bias.data_ptr(), net.value.weight.data_ptr(),
-                                                    net.value.bias.data_ptr(), hw.data_ptr(), hc.data_ptr(), st),
-                         "vine_rollout_head_prep")
+            self._head_prep(hw, hc)
             self._roll_args.clear()
         self.rollout_step_launches = 3 if step_fused else (5 if defer_fin else 6)
         for n in range(self.horizon_length):
@@ -573,9 +570,9 @@ class A2CAgent(FastInferenceMixin):
             last = n + 1 == self.horizon_length
             if step_fused:
                 ra = abi.RolloutArgs()
-                ra.y, ra.hw, ra.hc, ra.logstd = y.data_ptr(), hw.data_ptr(), hc.data_ptr(), net.sigma.data_ptr()
+                self._fill_head_args(ra, y, hw, hc)
                 ra.value_mean, ra.value_var = vms.running_mean.data_ptr(), vms.running_var.data_ptr()
-                ra.ln_eps, ra.value_eps = float(net.layer_norm.eps), float(vms.epsilon)
+                ra.value_eps = float(vms.epsilon)
                 ra.seed, ra.counter = int(self.head_seed), self.roll_counter.data_ptr()
                 ra.mu_out, ra.sigma_out, ra.value_out = buf["mus"][n].data_ptr(), buf["sigmas"][n].data_ptr(), buf["values"][n].data_ptr()
                 ra.action_out, ra.neglogp_out = buf["actions"][n].data_ptr(), buf["neglogpacs"][n].data_ptr()
@@ -583,10 +580,6 @@ class A2CAgent(FastInferenceMixin):
                 ra.shaped_out = buf["rewards"][n].data_ptr()
                 ra.dones_out = (self.dones if last else buf["dones"][n + 1]).data_ptr()
                 ra.cur_rewards, ra.cur_lengths = self.current_rewards.data_ptr(), self.current_lengths.data_ptr()
-                ra.h_state, ra.c_state = self.rnn_states[0].data_ptr(), self.rnn_states[1].data_ptr()
-                # the operand copy of h that the NEXT step reads (the buffer _infer just switched to)
-                ra.h_op = self._fast["xh2"][self._fast["cur"]].data_ptr() + 4 * self._fast["XW"]
-                ra.h_op_stride = h_op_stride
                 ra.partial = self._post_scratch.data_ptr()
                 self._roll_args.append(ra)          # (the launch copies the struct; kept for the record only)
                 obs = env.step_rollout_into(ra, self._obs_last if last else buf["obses"][n + 1])
@@ -605,8 +598,7 @@ class A2CAgent(FastInferenceMixin):
                 obs_d, rewards, dones, infos = self.vec_env.step(buf["actions"][n])
                 obs = obs_d["obs"]
                 dones_dst = self.dones
-            h_op_ptr = ((self._fast["xh2"][self._fast["cur"]].data_ptr()
-                         + self._fast["xh2"][0].element_size() * self._fast["XW"]) if fast else None)
+            h_op_ptr = self._h_op_next() if fast else None
             if defer_fin:
                 # per-env pass only; the one-workgroup fold of its episode sums (meters, rollout counter) rides in the next
                 # inference's MLP launch -- always one more follows: the next step's, or the last-values forward below
@@ -625,7 +617,6 @@ class A2CAgent(FastInferenceMixin):
                 buf["rewards"][n].data_ptr(), dones_dst.data_ptr(), self.current_rewards.data_ptr(),
                 self.current_lengths.data_ptr(), self.rnn_states[0].data_ptr(), self.rnn_states[1].data_ptr(),
                 self.meter.data_ptr(), float(self.games_to_track), self.roll_counter.data_ptr(),
-                # the operand copy of h that the NEXT step reads (the buffer _infer just switched to)
                 h_op_ptr, h_op_stride, h_op_bf16, self._post_scratch.data_ptr(), st), "vine_rollout_post")
         self.obs = obs
         y = self._infer(obs, commit=False) if fast else trunk(obs)[0]

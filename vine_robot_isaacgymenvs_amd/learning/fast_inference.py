@@ -236,3 +236,30 @@ class FastInferenceMixin:
                                                 net.layer_norm.bias.data_ptr(), float(net.layer_norm.eps), y.data_ptr(),
                                                 None, None, st), "vine_layernorm_forward")
         return y
+
+    # ---- the policy head inside the step launch (vine_step_rollout / vine_step_eval): its operands, marshalled once
+    def _head_prep(self, hw, hc):
+        """``hw`` [3, 256] = gamma_u w_k[u] and ``hc`` [3] = beta . w_k + b_k for k = mu_0, mu_1, value: the LayerNorm folded
+        into the head's rows (once per rollout / evaluation run: the update changed the weights)."""
+        net = self.model.a2c_network
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        fused._check(fused._lib().vine_rollout_head_prep(net.layer_norm.weight.data_ptr(), net.layer_norm.bias.data_ptr(),
+                                                         net.mu.weight.data_ptr(), net.mu.bias.data_ptr(),
+                                                         net.value.weight.data_ptr(), net.value.bias.data_ptr(),
+                                                         hw.data_ptr(), hc.data_ptr(), st), "vine_rollout_head_prep")
+
+    def _h_op_next(self):
+        """Address of the operand copy of h that the NEXT step reads (in the buffer ``_infer`` just switched to): what a
+        kernel that clears the LSTM state of finished envs has to clear with it."""
+        f = self._fast
+        xh = f["xh2"][f["cur"]]
+        return xh.data_ptr() + xh.element_size() * f["XW"]
+
+    def _fill_head_args(self, args, y, hw, hc):
+        """The fields that ``abi.RolloutArgs`` and ``abi.EvalArgs`` share: the LSTM output rows ``y`` of this step, the
+        head's operands, and the LSTM-state rows that the step clears for finished envs."""
+        f, net = self._fast, self.model.a2c_network
+        args.y, args.hw, args.hc, args.logstd = y.data_ptr(), hw.data_ptr(), hc.data_ptr(), net.sigma.data_ptr()
+        args.ln_eps = float(net.layer_norm.eps)
+        args.h_state, args.c_state = self.rnn_states[0].data_ptr(), self.rnn_states[1].data_ptr()
+        args.h_op, args.h_op_stride = self._h_op_next(), f["XW"] + f["H"]

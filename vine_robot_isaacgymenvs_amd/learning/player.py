@@ -188,16 +188,12 @@ class PpoPlayerContinuous(FastInferenceMixin):
     def _device_step(self):
         """One step: the split MLP, the split LSTM step, ``vine_step_eval``."""
         env = getattr(self.vec_env, "env", self.vec_env)
-        d, f, net = self._dev, self._fast, self.model.a2c_network
+        d = self._dev
         y = self._infer(d["obs_ring"][d["slot"]])
         a = abi.EvalArgs()
-        a.y, a.hw, a.hc, a.logstd = y.data_ptr(), d["hw"].data_ptr(), d["hc"].data_ptr(), net.sigma.data_ptr()
-        a.ln_eps, a.deterministic, a.seed = float(net.layer_norm.eps), int(bool(self.is_deterministic)), self.eval_seed
+        self._fill_head_args(a, y, d["hw"], d["hc"])
+        a.deterministic, a.seed = int(bool(self.is_deterministic)), self.eval_seed
         a.mu_out, a.action_out, a.dones_out = d["mu"].data_ptr(), d["action"].data_ptr(), d["dones"].data_ptr()
-        a.h_state, a.c_state = self.rnn_states[0].data_ptr(), self.rnn_states[1].data_ptr()
-        # the operand copy of h that the NEXT step reads (the buffer _infer just switched to)
-        a.h_op = f["xh2"][f["cur"]].data_ptr() + 4 * f["XW"]
-        a.h_op_stride = f["XW"] + f["H"]
         a.episode, a.totals = d["episode"].data_ptr(), d["totals"].data_ptr()
         d["slot"] ^= 1
         env.step_eval_into(a, d["obs_ring"][d["slot"]])
@@ -237,9 +233,8 @@ class PpoPlayerContinuous(FastInferenceMixin):
 
     @torch.no_grad()
     def _run_device(self, n_steps):
-        from . import fused
         env = getattr(self.vec_env, "env", self.vec_env)
-        d, f, net = self._device_buffers(env), self._fast, self.model.a2c_network
+        d = self._device_buffers(env)
         obs = self.vec_env.reset()["obs"]
         d["slot"] = 0
         d["obs_ring"][0].copy_(obs)
@@ -250,11 +245,7 @@ class PpoPlayerContinuous(FastInferenceMixin):
         d["totals"].zero_()
         # operand copies of the weights (restore() may have changed them since the last run) and of h
         self._infer_begin()
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        fused._check(fused._lib().vine_rollout_head_prep(net.layer_norm.weight.data_ptr(), net.layer_norm.bias.data_ptr(),
-                                                         net.mu.weight.data_ptr(), net.mu.bias.data_ptr(),
-                                                         net.value.weight.data_ptr(), net.value.bias.data_ptr(),
-                                                         d["hw"].data_ptr(), d["hc"].data_ptr(), st), "vine_rollout_head_prep")
+        self._head_prep(d["hw"], d["hc"])
         # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph)
         graphed = self.graph_steps > 0 and n_steps >= self.graph_steps and getattr(env, "video", None) is None
         done = 0
