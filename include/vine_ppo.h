@@ -590,6 +590,28 @@ int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, f
                        const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
                        float* found_inf, void* stream);
 
+/* Gradient clipping by global norm (rl_games `truncate_grads: True` / `grad_norm`, torch.nn.utils.clip_grad_norm_) as part
+ * of the optimiser step: two launches, no rewrite of the gradient block, capturable.
+ *
+ * vine_grad_sqnorm writes vine_grad_sqnorm_parts(n) (<= 256, a function of n alone) float64 partial sums of squares of
+ * grads[0, n) into `partial`: fixed assignment of elements to workgroups and a fixed reduction order inside one, no
+ * atomics and nothing to clear beforehand, so two launches over the same block give the same bits.  n need not be a
+ * multiple of 4; grads must be 16-byte aligned (VINE_ERR_UNSUPPORTED otherwise).
+ *
+ * vine_adam_step_clip is vine_adam_step_amp with the clip folded in: every workgroup adds the same `nparts` partials in
+ * the same order, norm = sqrt(sum) * grad_scale / loss scale (the norm of the unscaled, averaged gradient),
+ * coef = min(1, max_norm / (norm + 1e-6)), and coef multiplies the factor the kernel applies to every gradient anyway.
+ * coef == 1 leaves the step bit-identical to vine_adam_step_amp.  With amp_state / found_inf a non-finite norm is an
+ * overflow: the step is skipped exactly as for a raised flag; without them nothing is skipped.  clip_out (nullable, device
+ * float[2]) receives {norm, coef}. */
+int32_t vine_grad_sqnorm_parts(int64_t n);
+int vine_grad_sqnorm(int64_t n, const float* grads, double* partial, void* stream);
+int vine_adam_step_clip(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
+                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
+                        const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
+                        float* found_inf, const double* sq_partial, int32_t nparts, float max_norm, float* clip_out,
+                        void* stream);
+
 /* rl_games' AdaptiveScheduler on device scalars (`schedule_type: legacy`, PY:64-66):
  * kl > 2*thr -> lr = max(lr/1.5, min_lr); kl < 0.5*thr -> lr = min(lr*1.5, max_lr).  kl_scale = 1/world. */
 int vine_adaptive_lr(float* lr, const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr,

@@ -273,6 +273,11 @@ PPO_PROTOTYPES = {
                                        C.c_float, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
     "vine_adam_step_amp": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_float, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP, _VP, _VP]),
+    "vine_grad_sqnorm_parts": (C.c_int32, [_I64]),
+    "vine_grad_sqnorm": (C.c_int, [_I64, _VP, _VP, _VP]),
+    "vine_adam_step_clip": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP, _VP,
+                                      _VP, C.c_int32, C.c_float, _VP, _VP]),
     "vine_adaptive_lr": (C.c_int, [_VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
 }
 

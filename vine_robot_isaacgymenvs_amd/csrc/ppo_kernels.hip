@@ -4035,14 +4035,100 @@ __global__ __launch_bounds__(512) void trunk_phases_kernel(const TrunkPhasesArgs
 // and the 16-bit parameter copies keep their values; the gradient block is still cleared) and the scale is halved;
 // after `growth interval` consecutive good steps it is doubled.  The learning-rate schedule runs either way
 // (rl_games updates it after scaler.step whatever that did).
+//
+// CLIP (vine_adam_step_clip): rl_games' `truncate_grads` folded in.  sq_partial holds the nparts float64 partial sums of
+// squares of the gradient block (grad_sqnorm_kernel below); wave 0 of EVERY workgroup folds them in the same order, so the
+// whole grid holds the same norm = sqrt(sum) * gscale (the norm of the unscaled, averaged gradient) and the same
+// coef = min(1, max_norm / (norm + 1e-6)), which multiplies into gscale: the gradient block is never rewritten.  A
+// non-finite norm under loss scaling is an overflow like a raised flag (uniform over the grid for the same reason).
+// CLIP = false compiles to the kernel without any of it.
+#define GRAD_SQNORM_MAX_PARTS 256
+// wave_sum (above) for a double: the same DPP row shifts and row broadcasts, each moving the two halves of the lane-shifted
+// operand (lanes outside the pattern receive 0.0), total in lane 63, returned to every lane.  Needs all 64 lanes active.
+template <int CTRL, int ROW_MASK, int BANK_MASK>
+__device__ __forceinline__ double dpp_f64(double v) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, CTRL, ROW_MASK, BANK_MASK, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, ROW_MASK, BANK_MASK, true);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    double s = v + dpp_f64<0x111, 0xf, 0xf>(v);
+    s += dpp_f64<0x112, 0xf, 0xf>(v);
+    s += dpp_f64<0x113, 0xf, 0xf>(v);
+    s += dpp_f64<0x114, 0xf, 0xe>(s);      // row_shr:4 into lanes 4..15
+    s += dpp_f64<0x118, 0xf, 0xc>(s);      // row_shr:8 into lanes 8..15
+    s += dpp_f64<0x142, 0xa, 0xf>(s);      // row_bcast:15 into rows 1, 3
+    s += dpp_f64<0x143, 0xc, 0xf>(s);      // row_bcast:31 into rows 2, 3
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, s);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// Sum of squares of n floats as gridDim.x float64 partials: float4 i belongs to workgroup i / 256 modulo the grid and to
+// thread i % 256 of it (the grid is a function of n alone: vine_grad_sqnorm_parts), every thread adds its elements in
+// index order (two float4 per trip, both loads in flight together: at 1.6 MB that is every load of the launch), the lanes
+// of a wave meet in wave_sum_f64, the four waves are added in wave order.  No atomics, nothing to clear beforehand:
+// every launch writes every partial.
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(long long n, const float* __restrict__ g,
+                                                          double* __restrict__ partial) {
+    __shared__ double ws[4];
+    const long long n4 = n >> 2, stride = (long long)gridDim.x * 256;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += 2 * stride) {
+        const bool more = i + stride < n4;
+        const float4 x = ld4(g + 4 * i);
+        const float4 y = more ? ld4(g + 4 * (i + stride)) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        a0 = fma((double)x.x, (double)x.x, a0);
+        a1 = fma((double)x.y, (double)x.y, a1);
+        a2 = fma((double)x.z, (double)x.z, a2);
+        a3 = fma((double)x.w, (double)x.w, a3);
+        a0 = fma((double)y.x, (double)y.x, a0);
+        a1 = fma((double)y.y, (double)y.y, a1);
+        a2 = fma((double)y.z, (double)y.z, a2);
+        a3 = fma((double)y.w, (double)y.w, a3);
+    }
+    if (blockIdx.x == 0 && (long long)threadIdx.x < (n & 3)) {      // tail (n not a multiple of 4)
+        const double x = (double)g[(n4 << 2) + threadIdx.x];
+        a0 = fma(x, x, a0);
+    }
+    const double w = wave_sum_f64((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = w;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+template <bool CLIP>
 __global__ void adam_kernel(long long n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, float* lr_p, float* step_p,
                             float beta1, float beta2, float eps, float wd, float gscale, lp16_t* __restrict__ shadow,
                             const float* kl, float kl_scale, float kl_thr, float min_lr, float max_lr,
-                            float* amp, float* found_inf, unsigned int* ticket, unsigned int* sub) {
+                            float* amp, float* found_inf, unsigned int* ticket, unsigned int* sub,
+                            const double* __restrict__ sq_partial, int nparts, float max_norm, float* clip_out) {
     const float loss_scale = amp ? amp[0] : 1.0f;
-    const bool skip = found_inf && *found_inf != 0.0f;
+    bool skip = found_inf && *found_inf != 0.0f;
     if (amp) gscale = gscale / loss_scale;
+    float clip_norm = 0.0f, clip_coef = 1.0f;
+    if constexpr (CLIP) {
+        __shared__ double sq_total;
+        if (threadIdx.x < 64) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < GRAD_SQNORM_MAX_PARTS / 64; ++k) {      // (independent loads, added in index order)
+                const int j = (int)threadIdx.x + 64 * k;
+                s += j < nparts ? sq_partial[j] : 0.0;
+            }
+            s = wave_sum_f64(s);
+            if (threadIdx.x == 0) sq_total = s;
+        }
+        __syncthreads();
+        clip_norm = (float)(sqrt(sq_total) * (double)gscale);
+        const float c = max_norm / (clip_norm + 1e-6f);
+        clip_coef = c > 1.0f ? 1.0f : c;                  // (a NaN norm stays a NaN coefficient, as torch's clamp leaves it)
+        if (found_inf && !isfinite(clip_norm)) skip = true;
+        gscale *= clip_coef;
+    }
     if (skip) {      // (uniform over the grid) clear the gradient block, touch nothing else
         const long long n4s = n >> 2;
         for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4s; i += (long long)gridDim.x * blockDim.x)
@@ -4113,6 +4199,9 @@ __global__ void adam_kernel(long long n, float* __restrict__ p, float* __restric
                 }
             }
             if (found_inf) *found_inf = 0.0f;
+            if constexpr (CLIP) {
+                if (clip_out) { clip_out[0] = clip_norm; clip_out[1] = clip_coef; }
+            }
             if (kl) {
                 const float k = *kl * kl_scale;
                 float out = lr;
@@ -6344,11 +6433,13 @@ int vine_rollout_post_defer(int64_t N, int64_t H, const float* rew, const int64_
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 
-int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
-                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
-                       const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
-                       float* found_inf, void* stream) {
+static int adam_launch(bool clip, int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr,
+                       float* step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                       void* lp16_shadow, const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr,
+                       float* amp_state, float* found_inf, const double* sq_partial, int32_t nparts, float max_norm,
+                       float* clip_out, void* stream) {
     if (n <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !lr || !step) return VINE_ERR_INVALID_ARG;
+    if (clip && (!sq_partial || nparts < 1 || nparts > GRAD_SQNORM_MAX_PARTS || !(max_norm > 0.0f))) return VINE_ERR_INVALID_ARG;
     unsigned int* ticket = ticket_slot(stream, TICKET_ADAM);
     if (!ticket) return VINE_ERR_DEVICE;
     const int threads = 256;
@@ -6357,9 +6448,43 @@ int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, f
     // 4 KB of parameters.  Hence a two-level election (8 group words 128 B apart, then the common word) on the full grid
     const int blocks = grid_for((n + 3) / 4, threads);
     unsigned int* sub = ticket_sub_of(ticket);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(threads), 0, (hipStream_t)stream, (long long)n,
-                       params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
-                       (lp16_t*)lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, ticket, sub);
+    hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream,
+                       (long long)n, params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
+                       (lp16_t*)lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, ticket, sub,
+                       sq_partial, (int)nparts, max_norm, clip_out);
+    return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
+}
+
+int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
+                       const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
+                       float* found_inf, void* stream) {
+    return adam_launch(false, n, params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
+                       lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, nullptr, 0, 0.0f,
+                       nullptr, stream);
+}
+
+int vine_adam_step_clip(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
+                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
+                        const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
+                        float* found_inf, const double* sq_partial, int32_t nparts, float max_norm, float* clip_out,
+                        void* stream) {
+    return adam_launch(true, n, params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
+                       lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, sq_partial, nparts,
+                       max_norm, clip_out, stream);
+}
+
+int32_t vine_grad_sqnorm_parts(int64_t n) {
+    // one float4 per thread up to 256 workgroups (one per CU), grid-stride beyond: a function of n alone
+    const long long wg = ((n + 3) / 4 + 255) / 256;
+    return (int32_t)(wg < 1 ? 1 : wg > GRAD_SQNORM_MAX_PARTS ? GRAD_SQNORM_MAX_PARTS : wg);
+}
+
+int vine_grad_sqnorm(int64_t n, const float* grads, double* partial, void* stream) {
+    if (n <= 0 || !grads || !partial) return VINE_ERR_INVALID_ARG;
+    if (((uintptr_t)grads & 15) || ((uintptr_t)partial & 7)) return VINE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)vine_grad_sqnorm_parts(n)), dim3(256), 0, (hipStream_t)stream,
+                       (long long)n, grads, partial);
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
 }
 

@@ -1018,15 +1018,10 @@ class A2CAgent(FastInferenceMixin):
             buf = self.optimizer.comm_buffer if not self.use_grad_scaler else self.flat_grads
             dist.all_reduce(buf, op=dist.ReduceOp.SUM)                 # RCCL over xGMI, in place, 1.63 MB
         if not self.use_grad_scaler:
-            if self.truncate_grads:
-                if self.multi_gpu:
-                    self.flat_grads.div_(self.rank_size)
-                # the fp16 fused update leaves loss-scaled gradients here (unscaled inside the Adam kernel): clip against
-                # the unscaled norm, as rl_games does after scaler.unscale_
-                self.optimizer.clip_grad_norm_(self.grad_norm)
-                self.optimizer.step()
-            else:
-                self.optimizer.step(grad_scale=1.0 / self.rank_size)   # /world folded into the Adam kernel
+            # /world folded into the Adam kernel; `truncate_grads`: so is the clip, against the norm of the unscaled (the
+            # fp16 fused update leaves loss-scaled gradients here), averaged gradient, as rl_games clips after
+            # scaler.unscale_ -- behind the all-reduce above
+            self.optimizer.step(grad_scale=1.0 / self.rank_size, **self._clip_args(self._next_clip_row()))
             return
         if self.multi_gpu:
             self.flat_grads.div_(self.rank_size)
@@ -1038,8 +1033,32 @@ class A2CAgent(FastInferenceMixin):
 
     def _lr_schedule_args(self):
         """Arguments of the AdaptiveScheduler folded into the Adam launch (graphed update: `legacy` schedule, KL parked
-        next to the gradients by the loss kernel, summed over the ranks by the gradient all-reduce)."""
+        next to the gradients by the loss kernel, summed over the ranks by the gradient all-reduce).  Any other
+        `lr_schedule` than `adaptive`: None -- the kernel's "no schedule" (kl = NULL), the learning rate stays."""
+        if not self.is_adaptive_lr:
+            return None
         return (self.optimizer.aux[0:1], 1.0 / self.rank_size, self.kl_threshold, self.min_lr, self.max_lr)
+
+    # `truncate_grads` on the FlatAdam path: every optimiser step leaves its {pre-clip norm, coefficient} in its own row of
+    # self._clip_rows ([optimiser steps per iteration, 2], allocated by train_epoch outside any capture).  Eager steps and
+    # the whole-update graph write their row directly; a graph that is replayed for several rows writes a buffer of its
+    # own that is copied behind the replay.  With `truncate_grads: False` none of this exists.
+    def _clip_args(self, out):
+        """FlatAdam.step's keywords that carry `truncate_grads` (``out``: where the step's {norm, coef} goes)."""
+        if not self.truncate_grads:
+            return {}
+        return {"clip": self.grad_norm, "clip_out": out}
+
+    def _next_clip_row(self, count=1):
+        """The next ``count`` rows of the iteration's clip record (None when there is none); advances the cursor."""
+        rows = getattr(self, "_clip_rows", None)
+        if rows is None:
+            return None
+        at = self._clip_cursor
+        if at + count > rows.shape[0]:       # (a step outside train_epoch's count: nothing to record it in)
+            return None
+        self._clip_cursor = at + count
+        return rows[at] if count == 1 else rows[at:at + count]
 
     def update_lr_from_kl(self, kl):
         """AdaptiveScheduler of rl_games on a device scalar (common_agent.py:217-221 shows the call site)."""
@@ -1091,6 +1110,11 @@ class A2CAgent(FastInferenceMixin):
         if getattr(self, "_stat_rows", None) is None or self._stat_rows.shape[0] != n_steps:
             self._stat_rows = torch.zeros((n_steps, 8), device=self.device, dtype=torch.float32)
         rows = self._stat_rows
+        if self.truncate_grads and self.is_cuda and isinstance(self.optimizer, FlatAdam):
+            if getattr(self, "_clip_rows", None) is None or self._clip_rows.shape[0] != n_steps:
+                self._clip_rows = torch.zeros((n_steps, 2), device=self.device, dtype=torch.float32)
+                self.optimizer.enable_clip_buffers()
+            self._clip_cursor = 0
         graphed = self._update_graphs_usable()
         kl_global = False
         # one rank: nothing has to happen between the optimiser steps of a mini-epoch, so all of them replay as ONE
@@ -1172,7 +1196,16 @@ class A2CAgent(FastInferenceMixin):
                 # times of the previous iteration (rollout start -> rollout end -> update end: the same quantity in steady state)
                 play_time, update_time = gp, gu
         m = rows.mean(0)
+        clip_rows = getattr(self, "_clip_rows", None)
+        if clip_rows is not None:
+            # mean pre-clip norm (of the steps that had a finite one) and the share of clipped steps, next to the loss
+            # statistics in the tensor the host reads them from
+            ok = torch.isfinite(clip_rows[:, 0])
+            norm = torch.where(ok, clip_rows[:, 0], torch.zeros_like(clip_rows[:, 0])).sum() / ok.sum().clamp(min=1)
+            m = torch.cat([m, norm[None], (clip_rows[:, 1] < 1.0).float().mean()[None]])
         stats = {"a_loss": m[0], "c_loss": m[1], "entropy": m[3], "kl": m[4], "b_loss": m[2]}
+        if clip_rows is not None:
+            stats["grad_norm"], stats["grad_clip_fraction"] = m[8], m[9]
         return play_time, update_time, stats
 
     # ------------------------------------------------------------------ update as hipGraphs
@@ -1185,7 +1218,7 @@ class A2CAgent(FastInferenceMixin):
         (+ running-statistics update in the first mini-epoch) + forward + loss + backward of step s] -- so an iteration is
         32 graph replays + 32 collectives + one trailing Adam graph (round 2: two graphs per step, 64 + 32)."""
         return (self.use_graphs and self.is_cuda and self.use_fused and not self.mixed_precision
-                and not self.truncate_grads and self.is_adaptive_lr and self.schedule_type == "legacy"
+                and (self.schedule_type == "legacy" or not self.is_adaptive_lr)
                 and getattr(self, "_epochs_run", 0) > 1 and not getattr(self, "_update_graphs_failed", False))
 
     def _capture_agreed(self, ok):
@@ -1211,15 +1244,25 @@ class A2CAgent(FastInferenceMixin):
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize(self.device)
                 with torch.cuda.graph(g, pool=self._upd_pool, capture_error_mode="thread_local"):
-                    self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args())
+                    self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args(),
+                                        **self._clip_args(self.optimizer.clip_out))
                 rec = self._upd_graphs["tail"] = {"G": g}
             except RuntimeError:
                 rec = None
         if rec is not None:
             with _Range("update_graph_tail_adam_lr"):
                 rec["G"].replay()
+            self._record_deferred_clip()
         else:
-            self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args())
+            self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args(),
+                                **self._clip_args(self._next_clip_row()))
+
+    def _record_deferred_clip(self):
+        """A deferred Adam (head of a per-step graph, or the tail graph) is replayed for a different row each time: it
+        leaves {norm, coef} in the optimiser's own pair, copied into the step's row behind the replay."""
+        row = self._next_clip_row()
+        if row is not None:
+            row.copy_(self.optimizer.clip_out)
 
     def _update_step_graphed(self, i):
         # the running-statistics update of the observation normaliser (first mini-epoch only) is part of the graph:
@@ -1248,6 +1291,8 @@ class A2CAgent(FastInferenceMixin):
                 return False
         with _Range("update_graph_adam_forward_loss_backward"):
             rec["G"].replay()
+        if lead:
+            self._record_deferred_clip()
         if self.multi_gpu:
             with _Range("grad_all_reduce"):
                 dist.all_reduce(self.optimizer.comm_buffer, op=dist.ReduceOp.SUM)      # gradients + KL, RCCL over xGMI
@@ -1373,6 +1418,10 @@ class A2CAgent(FastInferenceMixin):
             rec["replayed"] = True
         if rec["stats"].data_ptr() != rows_out.data_ptr():      # (the whole-update graph writes the iteration's rows itself)
             rows_out.copy_(rec["stats"])
+        if rec.get("clip") is not None:
+            clip_rows = self._next_clip_row(n_epochs * self.num_minibatches)
+            if rec["clip"].data_ptr() != clip_rows.data_ptr():
+                clip_rows.copy_(rec["clip"])
         if n_epochs > 1 and self.normalize_input:
             self.model.running_mean_std.eval()                   # (as the per-mini-epoch loop leaves the module)
         per = "iteration" if n_epochs > 1 else "mini-epoch"
@@ -1408,6 +1457,11 @@ class A2CAgent(FastInferenceMixin):
         # the iteration's rows themselves (a persistent buffer of the agent: self._stat_rows)
         stats_all = (rows_out if n_epochs > 1 else
                      torch.zeros((nb, 8), device=self.device, dtype=torch.float32))     # (never allocate zeros in capture)
+        # `truncate_grads`: likewise {norm, coef} of every step (the whole update: the iteration's rows at the cursor)
+        clip_all = None
+        if getattr(self, "_clip_rows", None) is not None:
+            clip_all = (self._clip_rows[self._clip_cursor:self._clip_cursor + n_epochs * nb] if n_epochs > 1 else
+                        torch.zeros((nb, 2), device=self.device, dtype=torch.float32))
         keep = []
         rms_training = bool(key[1])
         try:
@@ -1423,7 +1477,8 @@ class A2CAgent(FastInferenceMixin):
                         if self.multi_gpu:
                             # gradients + KL + overflow flag, SUM over the ranks (RCCL over xGMI): a node of the graph
                             dist.all_reduce(self.optimizer.comm_buffer, op=dist.ReduceOp.SUM)
-                        self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args())
+                        self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args(),
+                                            **self._clip_args(None if clip_all is None else clip_all[ep * nb + i]))
                         keep.append((mb, stats, mu_d))
                     keep.append(ahead)
                     if n_epochs > 1 and self.normalize_input:
@@ -1431,7 +1486,7 @@ class A2CAgent(FastInferenceMixin):
         finally:
             if n_epochs > 1 and self.normalize_input and rms_training:
                 self.model.running_mean_std.train()              # (the caller switches it after the replay)
-        rec = {"G": g, "stats": stats_all, "keep": keep}
+        rec = {"G": g, "stats": stats_all, "clip": clip_all, "keep": keep}
         self._upd_graphs[key] = rec
         return rec
 
@@ -1451,7 +1506,9 @@ class A2CAgent(FastInferenceMixin):
                 # the step behind the previous all-reduce: the KL next to the gradients is the sum over the ranks by
                 # now, the schedule runs inside the Adam launch (the dataset's mu / sigma slices were refreshed by the
                 # loss kernel of that step)
-                self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args())
+                # (`truncate_grads`: the sum of squares sits here too, behind the all-reduce: the averaged gradient's norm)
+                self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args(),
+                                    **self._clip_args(self.optimizer.clip_out))
             mb = self.get_minibatch(i)
             stats, mu_d, _logstd_d = self._fused_grad_half(mb, stats_out=self._step_stats[i])
         rec = {"G": g, "stats": stats, "keep": (mb, stats, mu_d)}
@@ -1577,6 +1634,9 @@ class A2CAgent(FastInferenceMixin):
             w.add_scalar("info/loss_scale", self.optimizer.loss_scale, frame)
         w.add_scalar("info/e_clip", self.e_clip, frame)
         w.add_scalar("info/kl", stats["kl"], frame)
+        if "grad_norm" in stats:                                        # `truncate_grads` on the device (FlatAdam)
+            w.add_scalar("info/grad_norm", stats["grad_norm"], frame)
+            w.add_scalar("info/grad_clip_fraction", stats["grad_clip_fraction"], frame)
         w.add_scalar("info/epochs", epoch_num, frame)
 
 

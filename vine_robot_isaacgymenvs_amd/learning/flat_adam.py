@@ -48,6 +48,8 @@ class FlatAdam:
         self.found_inf = self.aux[1:2]
         self.check_grads = False    # look for non-finite gradients here (set when the backward pass does not check itself)
         self._lib = None
+        self._clip_partial = None   # float64 partial sums of squares of the gradient block (step(clip=...) on the GPU)
+        self.clip_out = None        # {norm, coef} of the last clipped step
         if dev.type == "cuda":
             from . import fused
             self._lib = fused._lib()        # (also readies the library's per-device bookkeeping outside any capture)
@@ -108,10 +110,23 @@ class FlatAdam:
         self.flat_grads.mul_(coef)
         return norm
 
+    def enable_clip_buffers(self):
+        """The device clip's persistent buffers (call this outside any capture; ``step(clip=...)`` does on first use): the
+        float64 partial sums of squares and ``clip_out``, a step's ``{norm, coef}`` unless ``step`` is given another place."""
+        if self._clip_partial is None:
+            parts = int(self._lib.vine_grad_sqnorm_parts(self.numel))
+            self._clip_partial = torch.zeros(parts, device=self.flat_params.device, dtype=torch.float64)
+            self.clip_out = torch.zeros(2, device=self.flat_params.device, dtype=torch.float32)
+        return self.clip_out
+
     @torch.no_grad()
-    def step(self, grad_scale=1.0, lr_schedule=None):
+    def step(self, grad_scale=1.0, lr_schedule=None, clip=None, clip_out=None):
         """``lr_schedule`` = (kl device scalar, kl_scale, kl_threshold, min_lr, max_lr): rl_games' AdaptiveScheduler
-        applied to ``self.lr`` AFTER this step used the old value, by the same launch (GPU path only)."""
+        applied to ``self.lr`` AFTER this step used the old value, by the same launch (GPU path only).
+        ``clip`` = max_norm: ``clip_grad_norm_`` (of the gradient block times ``grad_scale``) as part of the step.  On the
+        GPU: one sum-of-squares launch over ``flat_grads`` (the ``aux`` words are not part of the norm) and the
+        coefficient folded into the Adam launch -- the block is never rewritten; ``{norm, coef}`` of the step lands in
+        ``clip_out`` (default: ``self.clip_out``)."""
         b1, b2 = self.betas
         if self._lib is not None:
             kl, kscale, thr, lo, hi = lr_schedule if lr_schedule is not None else (None, 0.0, 0.0, 0.0, 0.0)
@@ -119,19 +134,32 @@ class FlatAdam:
             if amp and self.check_grads:
                 # backward passes whose kernels do not flag overflows themselves: one reduction over the gradient block
                 self.found_inf.add_((~torch.isfinite(self.flat_grads)).any().to(torch.float32))
-            rc = self._lib.vine_adam_step_amp(self.numel, self.flat_params.data_ptr(), self.flat_grads.data_ptr(),
-                                              self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.lr.data_ptr(),
-                                              self.step_t.data_ptr(), b1, b2, self.eps, self.weight_decay,
-                                              float(grad_scale),
-                                              self.shadow.data_ptr() if self.shadow is not None else None,
-                                              kl.data_ptr() if kl is not None else None, float(kscale), float(thr),
-                                              float(lo), float(hi), self.amp_state.data_ptr() if amp else None,
-                                              self.found_inf.data_ptr() if amp else None,
-                                              torch.cuda.current_stream(self.flat_params.device).cuda_stream)
+            stream = torch.cuda.current_stream(self.flat_params.device).cuda_stream
+            args = (self.numel, self.flat_params.data_ptr(), self.flat_grads.data_ptr(), self.exp_avg.data_ptr(),
+                    self.exp_avg_sq.data_ptr(), self.lr.data_ptr(), self.step_t.data_ptr(), b1, b2, self.eps,
+                    self.weight_decay, float(grad_scale), self.shadow.data_ptr() if self.shadow is not None else None,
+                    kl.data_ptr() if kl is not None else None, float(kscale), float(thr), float(lo), float(hi),
+                    self.amp_state.data_ptr() if amp else None, self.found_inf.data_ptr() if amp else None)
+            if clip is None:
+                name, rc = "vine_adam_step_amp", self._lib.vine_adam_step_amp(*args, stream)
+            else:
+                self.enable_clip_buffers()
+                out = self.clip_out if clip_out is None else clip_out
+                partial = self._clip_partial
+                rc = self._lib.vine_grad_sqnorm(self.numel, self.flat_grads.data_ptr(), partial.data_ptr(), stream)
+                if rc != 0:
+                    raise RuntimeError("vine_grad_sqnorm failed with status %d" % rc)
+                name, rc = "vine_adam_step_clip", self._lib.vine_adam_step_clip(
+                    *args, partial.data_ptr(), partial.numel(), float(clip), out.data_ptr(), stream)
             if rc != 0:
-                raise RuntimeError("vine_adam_step_amp failed with status %d" % rc)
+                raise RuntimeError("%s failed with status %d" % (name, rc))
             return
         assert lr_schedule is None, "the fused learning-rate schedule exists on the GPU path only"
+        if clip is not None:
+            if grad_scale != 1.0:           # the threshold applies to the averaged gradient, as on the GPU
+                self.flat_grads.mul_(grad_scale)
+                grad_scale = 1.0
+            self.clip_grad_norm_(clip)
         g = self.flat_grads * grad_scale
         if self.weight_decay:
             g = g + self.weight_decay * self.flat_params
