@@ -5,6 +5,8 @@ profiles/eval_player/player_paths.txt.
 
   python scripts/ubench/eval_player_bench.py                       # both configurations, both paths
   python scripts/ubench/eval_player_bench.py --trace-device pipe   # device path only, short: a workload for a kernel trace
+  python scripts/ubench/eval_player_bench.py --record 64 --out profiles/record_trajectories/player_paths.txt
+                                                                   # + the device path with RECORD_TRAJECTORIES of 64 envs
 """
 import argparse
 import contextlib
@@ -26,9 +28,13 @@ from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map  # noqa: E402
 CONFIGS = {"free": ["task.env.CREATE_PIPE=False"], "pipe": []}
 
 
-def make(name, n, device_rollout):
+def make(name, n, device_rollout, record=0):
     cfg = load_config(overrides=["num_envs=%d" % n] + CONFIGS[name])
     cfg["task"]["seed"] = 42
+    if record:      # the task's default window: maxEpisodeLength (500) steps every 1000, files into a scratch directory
+        import tempfile
+        cfg["task"]["env"].update(RECORD_TRAJECTORIES=True, RECORD_TRAJECTORIES_ENVS=record,
+                                  RECORD_TRAJECTORIES_DIR=tempfile.mkdtemp(prefix="vine_trajectories_"))
     env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
                                                   graphics_device_id=0, headless=True)
     params = cfg["train"]["params"]
@@ -52,10 +58,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-device", choices=sorted(CONFIGS), default=None)
+    ap.add_argument("--record", type=int, default=0, help="also time the device path with RECORD_TRAJECTORIES of this many envs")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_player", "player_paths.txt"))
     args = ap.parse_args()
     if args.trace_device:
-        player, env = make(args.trace_device, args.envs, True)
+        player, env = make(args.trace_device, args.envs, True, args.record)
         timed_run(player, 64)
         dt = timed_run(player, 512)
         assert player.device_path is True
@@ -66,18 +73,29 @@ def main():
     lines = []
     for name in CONFIGS:
         players = {path: make(name, args.envs, path == "device") for path in ("stock", "device")}
+        if args.record:
+            players["device+record"] = make(name, args.envs, True, args.record)
         for path, (player, _) in players.items():
-            timed_run(player, 64 if path == "device" else 16)           # warm-up (device: the graph capture too)
-            assert player.device_path is (path == "device")
+            timed_run(player, 64 if path != "stock" else 16)            # warm-up (device: the graph capture too)
+            assert player.device_path is (path != "stock")
         for rnd in range(args.rounds):
             for path, (player, _) in players.items():
                 dt = timed_run(player, args.steps)
                 rec = {"config": name, "path": path, "round": rnd, "envs": args.envs, "steps": args.steps, "seconds": round(dt, 6),
                        "env_steps_per_s": round(args.envs * args.steps / dt, 1), "report": player.report}
+                trajectory = getattr(players[path][1], "trajectory", None)
+                if trajectory is not None:
+                    rec.update(files=len(trajectory.written), skipped=len(trajectory.skipped),
+                               harvest_ms=[round(1e3 * t, 3) for t in trajectory.harvest_seconds],
+                               write_ms=[round(1e3 * t, 3) for t in trajectory.write_seconds])
                 lines.append(json.dumps(rec))
                 print(lines[-1], flush=True)
         for _, env in players.values():
+            scratch = getattr(getattr(env, "trajectory", None), "directory", None)
             env.close()
+            if scratch:                       # the MAT files of the timed runs are not the result
+                import shutil
+                shutil.rmtree(scratch, ignore_errors=True)
     with open(args.out, "w") as f:
         f.write("\n".join(lines) + "\n")
 

@@ -382,6 +382,48 @@ def declare_render(lib):
     return lib
 
 
+# ---- include/vine_record.h (product library only)
+RECORD_ABI_VERSION = 1
+RECORD_FIELDS = 32
+RECORD_MAX_ENVS = 64
+# VineRecordField = columns of a row
+VRF_Q0, VRF_QD0 = 0, 6
+VRF_TIP_Y, VRF_TIP_Z, VRF_TIP_VY, VRF_TIP_VZ = 12, 13, 14, 15
+VRF_TARGET_Y, VRF_TARGET_Z = 16, 17
+VRF_ACTION0 = 18
+VRF_SMOOTHED_U, VRF_REWARD, VRF_RESET, VRF_TIMEOUT, VRF_PROGRESS = 20, 21, 22, 23, 24
+VRF_OBJ_DEPTH, VRF_OBJ_ANGLE, VRF_CONTACT = 25, 26, 27
+VRF_RESERVED0 = 28
+
+
+class VineRecordConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("record_every", C.c_int32),
+        ("num_steps", C.c_int32),
+        ("num_envs", C.c_int32),
+    ]
+
+
+RECORD_PROTOTYPES = {
+    "vine_record_config_default": (C.c_int, [_P(VineRecordConfig)]),
+    "vine_record_config_size": (C.c_int, []),
+    "vine_record_ring_bytes": (C.c_int64, [_P(VineRecordConfig)]),
+    "vine_record": (C.c_int, [_H, _P(VineRecordConfig), C.c_int32] + [_VP] * 9),
+    "vine_record_scheduled": (C.c_int, [_H, _P(VineRecordConfig)] + [_VP] * 9),
+}
+
+
+def declare_record(lib):
+    for name, (restype, argtypes) in RECORD_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.vine_record_config_size() != C.sizeof(VineRecordConfig):
+        raise RuntimeError("VineRecordConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     for name, (restype, argtypes) in PPO_PROTOTYPES.items():
         fn = getattr(lib, name)

@@ -1610,10 +1610,11 @@ class A2CAgent(FastInferenceMixin):
                 dist.broadcast(flag, 0)
                 should_exit = bool(flag.item())
             if should_exit:
-                video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
-                if video is not None:            # CAPTURE_VIDEO: the last harvested window is on disk when train() returns
-                    torch.cuda.synchronize(self.device)
-                    video.drain()
+                env_ = getattr(self.vec_env, "env", self.vec_env)
+                for side in (getattr(env_, "video", None), getattr(env_, "trajectory", None)):
+                    if side is not None:         # CAPTURE_VIDEO / RECORD_TRAJECTORIES: the last harvested window is on disk
+                        torch.cuda.synchronize(self.device)                                  # when train() returns
+                        side.drain()
                 return self.last_mean_rewards, epoch_num
 
     def write_stats(self, total_time, epoch_num, play_time, update_time, stats, curr_frames):

@@ -113,10 +113,11 @@ class PpoPlayerContinuous(FastInferenceMixin):
         return self._run_stock(n_steps)
 
     def _finish(self, mean_r, mean_l, games):
-        video = getattr(getattr(self.vec_env, "env", self.vec_env), "video", None)
-        if video is not None:                    # CAPTURE_VIDEO: every harvested window is on disk when run() returns
-            torch.cuda.synchronize(self.device)
-            video.drain()
+        env = getattr(self.vec_env, "env", self.vec_env)
+        for side in (getattr(env, "video", None), getattr(env, "trajectory", None)):
+            if side is not None:                 # CAPTURE_VIDEO / RECORD_TRAJECTORIES: every harvested window is on disk
+                torch.cuda.synchronize(self.device)                                      # when run() returns
+                side.drain()
         print("reward:", mean_r, "steps:", mean_l, "games:", games)
         print(format_report(self.report))
         return mean_r, mean_l
@@ -206,6 +207,8 @@ class PpoPlayerContinuous(FastInferenceMixin):
         live = [env.state, env.reset_buf, env.progress_buf, env.rew_buf, env.timeout_buf, self.rnn_states[0], self.rnn_states[1],
                 f["xh2"][0], f["xh2"][1], d["obs_ring"][0], d["obs_ring"][1], d["episode"], d["totals"], d["mu"], d["action"],
                 d["dones"]]
+        if getattr(env, "trajectory", None) is not None:     # RECORD_TRAJECTORIES: the warm-up pass writes rows too
+            live += env.trajectory.live_tensors()
         backup = [t.clone() for t in live]
         step, num_steps, rng = env.step_count, env.num_steps, torch.cuda.get_rng_state(self.device)
         video_paused = getattr(env, "video_paused", contextlib.nullcontext)
@@ -246,14 +249,20 @@ class PpoPlayerContinuous(FastInferenceMixin):
         # operand copies of the weights (restore() may have changed them since the last run) and of h
         self._infer_begin()
         self._head_prep(d["hw"], d["hc"])
-        # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph)
+        # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph).  RECORD_TRAJECTORIES is: its
+        # launches are captured with the steps, and the host is told of every replay.
         graphed = self.graph_steps > 0 and n_steps >= self.graph_steps and getattr(env, "video", None) is None
+        replayed = getattr(env, "video_replayed", None) if getattr(env, "trajectory", None) is not None else None
         done = 0
         if graphed:
             if self._eval_graph is None:
                 self._eval_graph = self._capture(env)
             for _ in range(n_steps // self.graph_steps):
+                if replayed is not None:
+                    replayed(self.graph_steps, before=True)
                 self._eval_graph.replay()
+                if replayed is not None:
+                    replayed(self.graph_steps)
                 env.num_steps += self.graph_steps
             done = n_steps // self.graph_steps * self.graph_steps
         for _ in range(n_steps - done):

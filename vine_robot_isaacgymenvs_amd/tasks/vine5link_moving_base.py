@@ -145,6 +145,8 @@ class Vine5LinkMovingBase(VecTask):
         if self.cfg["env"].get("CREATE_PIPE", False):
             self.logger.info("CREATE_PIPE: the pipe mesh is simulated as its planar cross-section (two walls)")
         self._video = None
+        self._trajectory = None
+        self._observers = []       # what rides behind every step: the video capture and the trajectory recorder
 
         self._lib = None
         self._handle = None
@@ -176,6 +178,11 @@ class Vine5LinkMovingBase(VecTask):
                 self._setup_video()
             else:           # every rank would write the same file names: rank 0 records its env, the others do not draw
                 self.logger.info("CAPTURE_VIDEO: recorded by rank 0 only")
+        if self.cfg["env"].get("RECORD_TRAJECTORIES", False):
+            if int(os.getenv("LOCAL_RANK", "0")) == 0:
+                self._setup_trajectory()
+            else:
+                self.logger.info("RECORD_TRAJECTORIES: recorded by rank 0 only")
 
     # ------------------------------------------------------------------ CAPTURE_VIDEO (V5:205-221, 1169-1207)
     def _setup_video(self):
@@ -192,6 +199,7 @@ class Vine5LinkMovingBase(VecTask):
         self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")                      # V5:145
         self._video = video.VideoCapture(self._lib, self._handle, rcfg, views, self.progress_buf, self.device,
                                          self.log_dir, self.time_str, self.control_dt, self.logger)
+        self._observers.append(self._video)
         self.logger.info(f"CAPTURE_VIDEO: {rcfg.num_frames} frames of {rcfg.num_views} view(s) at "
                          f"{rcfg.width} x {rcfg.height} every {rcfg.capture_every} steps -> "
                          f"{self.log_dir}/{self.time_str}_video_<num_steps>.png")
@@ -202,25 +210,73 @@ class Vine5LinkMovingBase(VecTask):
         return self._video
 
     def video_paused(self):
-        """Context manager: steps enqueued inside are not counted towards the capture (the warm-up and capture passes of
-        a hipGraph, whose effects are rolled back or not executed at all)."""
+        """Context manager: steps enqueued inside are not counted towards the capture or the recording (the warm-up and
+        capture passes of a hipGraph, whose effects are rolled back or not executed at all)."""
         import contextlib
 
         @contextlib.contextmanager
         def paused():
-            if self._video is not None:
-                self._video.paused += 1
+            held = list(self._observers)
+            for o in held:
+                # such a pass still launches the draw / record kernels, which write the rings from the device's counter:
+                # a harvest copy still in flight on an observer's side stream must have read its ring first
+                if o.copy_done is not None and not torch.cuda.is_current_stream_capturing():
+                    torch.cuda.current_stream(self.device).wait_event(o.copy_done)
+                    o.copy_done = None
+                o.paused += 1
             try:
                 yield
             finally:
-                if self._video is not None:
-                    self._video.paused -= 1
+                for o in held:
+                    o.paused -= 1
         return paused()
 
     def video_replayed(self, n_steps, before=False):
-        """A captured graph holding ``n_steps`` steps (and their draws) is about to be / has been replayed."""
-        if self._video is not None:
-            (self._video.before if before else self._video.advance)(n_steps)
+        """A captured graph holding ``n_steps`` steps (and their draw / record launches) is about to be / has been
+        replayed."""
+        for o in self._observers:
+            (o.before if before else o.advance)(n_steps)
+
+    # ------------------------------------------------------------------ RECORD_TRAJECTORIES (include/vine_record.h)
+    def _setup_trajectory(self):
+        """The recorded envs, the device row ring and the writer; rows are written by a launch behind every step, see
+        utils/trajectory.py for the harvest and the MAT files."""
+        import datetime
+        from ..utils import trajectory
+        env = self.cfg["env"]
+        every = int(env.get("RECORD_TRAJECTORIES_EVERY", 1000))
+        steps = min(int(env.get("RECORD_TRAJECTORIES_STEPS", 0) or self.max_episode_length), every)
+        which = env.get("RECORD_TRAJECTORIES_ENVS", 1)
+        if isinstance(which, (int, float, str)):
+            envs = [(self.index_to_view + k) % self.num_envs for k in range(int(which))]
+        else:
+            envs = [int(e) for e in which]
+        if not 1 <= len(envs) <= abi.RECORD_MAX_ENVS:
+            raise ValueError(f"RECORD_TRAJECTORIES_ENVS: 1 .. {abi.RECORD_MAX_ENVS} envs can be recorded, not {len(envs)}")
+        if any(e < 0 or e >= self.num_envs for e in envs):
+            raise ValueError(f"RECORD_TRAJECTORIES_ENVS: env indices must lie in [0, {self.num_envs}): {envs}")
+        rcfg = trajectory.record_config(self._lib, every, steps, len(envs))
+        directory = env.get("RECORD_TRAJECTORIES_DIR") or os.path.join("runs", self.cfg["name"])
+        if not hasattr(self, "time_str"):
+            self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+        self._trajectory = trajectory.TrajectoryRecorder(
+            self._lib, self._handle, rcfg, envs, (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf),
+            self.device, directory, self.time_str, self.control_dt, self.logger)
+        self._observers.append(self._trajectory)
+        self.logger.info(f"RECORD_TRAJECTORIES: {steps} steps of env(s) {envs} every {every} steps -> "
+                         f"{directory}/{self.time_str}_trajectory_<num_steps>_env<e>.mat")
+
+    @property
+    def trajectory(self):
+        """The ``TrajectoryRecorder`` of this env (``None`` unless ``RECORD_TRAJECTORIES``)."""
+        return self._trajectory
+
+    def _observe(self, actions):
+        """Behind a step launch: every observer's launch on the same stream, then its host-side count.  ``actions``:
+        device address of the action buffer the step consumed."""
+        for o in self._observers:
+            o.enqueue(self._stream(), actions)
+            o.advance(1)
 
     # ------------------------------------------------------------------ MAT_FILE replay (V5:281-297, 947-982)
     def read_mat_file(self, filename):
@@ -269,11 +325,12 @@ class Vine5LinkMovingBase(VecTask):
         self._handle = h
 
     def close(self):
-        if self._video is not None:
+        if self._observers:
             torch.cuda.synchronize(self.device)
-            self._video.drain()
-            self._video.close()
-            self._video = None
+            for o in self._observers:
+                o.drain()
+                o.close()
+            self._observers, self._video, self._trajectory = [], None, None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -291,14 +348,12 @@ class Vine5LinkMovingBase(VecTask):
     def _native_step(self, actions, obs_out):
         if self.mat is not None:
             self.overwrite_with_mat()
-        if self._video is not None:
-            self._video.before(1)
+        for o in self._observers:
+            o.before(1)
         native.check(self._lib.vine_step(self._handle, actions.data_ptr(), obs_out.data_ptr(), self.rew_buf.data_ptr(),
                                          self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
                                          self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        if self._video is not None:
-            self._video.enqueue(self._stream())
-            self._video.advance(1)
+        self._observe(actions.data_ptr())
         self.num_steps += 1
 
     def rollout_step_blocks(self):
@@ -312,14 +367,12 @@ class Vine5LinkMovingBase(VecTask):
         ``_rollout_body_fused``); ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.RolloutArgs; the
         observation goes to ``obs_out`` and the buffers are re-bound exactly as ``step_into`` does."""
         import ctypes as C
-        if self._video is not None:
-            self._video.before(1)
+        for o in self._observers:
+            o.before(1)
         native.check(self._lib.vine_step_rollout(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
                                                  self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
                                                  self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        if self._video is not None:
-            self._video.enqueue(self._stream())
-            self._video.advance(1)
+        self._observe(args.action_out)
         self.num_steps += 1
         self.obs_buf = obs_out
         self.obs_dict["obs"] = obs_out.to(self.rl_device)
@@ -337,14 +390,12 @@ class Vine5LinkMovingBase(VecTask):
         path; ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.EvalArgs; the observation goes to ``obs_out``
         and the buffers are re-bound exactly as ``step_into`` does."""
         import ctypes as C
-        if self._video is not None:
-            self._video.before(1)
+        for o in self._observers:
+            o.before(1)
         native.check(self._lib.vine_step_eval(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
                                               self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
                                               self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        if self._video is not None:
-            self._video.enqueue(self._stream())
-            self._video.advance(1)
+        self._observe(args.action_out)
         self.num_steps += 1
         self.obs_buf = obs_out
         self.obs_dict["obs"] = obs_out.to(self.rl_device)
@@ -494,8 +545,8 @@ class Vine5LinkMovingBase(VecTask):
     @step_count.setter
     def step_count(self, v):
         native.check(self._lib.vine_set_step_count(self._handle, int(v)), self._lib)
-        if self._video is not None:
-            self._video.set_steps(int(v))
+        for o in self._observers:
+            o.set_steps(int(v))
 
     @property
     def state(self):

@@ -105,8 +105,9 @@ class VideoCapture:
         self.writer.start()
 
     # -- device side -------------------------------------------------------------------------------------------------
-    def enqueue(self, stream):
-        """The scheduled draw, behind the step just enqueued on ``stream`` (captured with it inside a hipGraph)."""
+    def enqueue(self, stream, actions=None):
+        """The scheduled draw, behind the step just enqueued on ``stream`` (captured with it inside a hipGraph).
+        (``actions``, the step's action buffer, is what the task hands every step observer; the picture has no use for it.)"""
         native.check(self.lib.vine_render_scheduled(self.handle, self.rcfg, self.view_envs.data_ptr(),
                                                     self.progress_buf.data_ptr(), self.ring.data_ptr(), stream), self.lib)
 
