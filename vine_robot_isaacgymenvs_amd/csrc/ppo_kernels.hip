@@ -9,20 +9,9 @@
 #include "../../include/vine.h"
 #include "../../include/vine_ppo.h"
 #include "vine_policy_head.h"      // Philox, the head's lane tail and the rollout bookkeeping, shared with vine_hip.hip
+#include "vine_ppo_formulas.h"     // LSTM cell, ELU, normalisers, the PPO loss of a row: the formulas, each stated once
 
 namespace {
-
-// v_rcp_f32 (1 ulp) instead of the IEEE division sequence (~10 VALU instructions): the LSTM step kernel spent 800 of
-// its 1800 VALU instructions per wave on the 80 divisions of its gate non-linearities
-__device__ __forceinline__ float rcpf_(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float sigmoidf_(float x) { return rcpf_(1.0f + __expf(-x)); }
-__device__ __forceinline__ float tanhf_(float x) {
-    // tanh via exp of -2|x|: accurate to ~2e-7 relative, no overflow
-    const float ax = fabsf(x);
-    const float e = __expf(-2.0f * ax);
-    const float t = (1.0f - e) * rcpf_(1.0f + e);
-    return copysignf(t, x);
-}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
@@ -130,14 +119,8 @@ __global__ void lstm_fwd_kernel(long long B, int H, const float* __restrict__ ig
         const float cpv[4] = {cp.x, cp.y, cp.z, cp.w};
         float cn[4], hn[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            gi[u] = sigmoidf_(gi[u]);
-            gf[u] = sigmoidf_(gf[u]);
-            gg[u] = tanhf_(gg[u]);
-            go[u] = sigmoidf_(go[u]);
-            cn[u] = gf[u] * (keep * cpv[u]) + gi[u] * gg[u];
-            hn[u] = go[u] * tanhf_(cn[u]);
-        }
+        for (int u = 0; u < 4; ++u)      // (in place: a gate's activation replaces its pre-activation)
+            lstm_cell(gi[u], gf[u], gg[u], go[u], keep * cpv[u], gi[u], gf[u], gg[u], go[u], cn[u], hn[u]);
         st4(c_out + b * H + j, make_float4(cn[0], cn[1], cn[2], cn[3]));
         st4(h_out + b * h_stride + j, make_float4(hn[0], hn[1], hn[2], hn[3]));
         if (hp_next) {   // the masked hidden state step t+1 consumes (operand of the recurrent weight gradient)
@@ -252,14 +235,8 @@ __global__ __launch_bounds__(256) void lstm_step_mfma_kernel(
     const float cpv[4] = {cp.x, cp.y, cp.z, cp.w};
     float gi[4], gf[4], gg[4], go[4], cn[4], hn[4];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        gi[u] = sigmoidf_(pre[0][u]);
-        gf[u] = sigmoidf_(pre[1][u]);
-        gg[u] = tanhf_(pre[2][u]);
-        go[u] = sigmoidf_(pre[3][u]);
-        cn[u] = gf[u] * (keep * cpv[u]) + gi[u] * gg[u];
-        hn[u] = go[u] * tanhf_(cn[u]);
-    }
+    for (int u = 0; u < 4; ++u)
+        lstm_cell(pre[0][u], pre[1][u], pre[2][u], pre[3][u], keep * cpv[u], gi[u], gf[u], gg[u], go[u], cn[u], hn[u]);
     st4(c_out + b * H + j, make_float4(cn[0], cn[1], cn[2], cn[3]));
     st4(h_out + b * h_stride + j, make_float4(hn[0], hn[1], hn[2], hn[3]));
     if (hp_next) st4(hp_next + b * hp_stride + j, make_float4(kn * hn[0], kn * hn[1], kn * hn[2], kn * hn[3]));
@@ -410,14 +387,8 @@ __global__ __launch_bounds__(256) void lstm_step_mfma64_kernel(
         const float cpv[4] = {cp.x, cp.y, cp.z, cp.w};
         float gi[4], gf[4], gg[4], go[4], cn[4], hn[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            gi[u] = sigmoidf_(pre[0][u]);
-            gf[u] = sigmoidf_(pre[1][u]);
-            gg[u] = tanhf_(pre[2][u]);
-            go[u] = sigmoidf_(pre[3][u]);
-            cn[u] = gf[u] * (keep * cpv[u]) + gi[u] * gg[u];
-            hn[u] = go[u] * tanhf_(cn[u]);
-        }
+        for (int u = 0; u < 4; ++u)
+            lstm_cell(pre[0][u], pre[1][u], pre[2][u], pre[3][u], keep * cpv[u], gi[u], gf[u], gg[u], go[u], cn[u], hn[u]);
         st4(c_out + b * H + j, make_float4(cn[0], cn[1], cn[2], cn[3]));
         st4(h_out + b * h_stride + j, make_float4(hn[0], hn[1], hn[2], hn[3]));
         if (hp_next) st4(hp_next + b * hp_stride + j, make_float4(kn * hn[0], kn * hn[1], kn * hn[2], kn * hn[3]));
@@ -451,8 +422,8 @@ __global__ __launch_bounds__(256) void lstm_step_mfma64_kernel(
 // Tiled weight layout (built by lstm_tile_weights_kernel, one 16-B chunk per lane):
 //   chunk(w, kk, j = 2 g + ut, lane)  =  Wsrc[row(g, unit)][32 kk + 8 (lane >> 4) .. + 8],
 //   unit = 32 w + 8 ((lane & 15) >> 2) + 4 ut + (lane & 3),  at chunk index ((w * KSTEPS + kk) * NJ + j) * 64 + lane.
-__device__ __forceinline__ float dpp_i2f(int x);
-__device__ __forceinline__ int dpp_f2i(float x);
+__device__ __forceinline__ float dpp_i2f(int x) { return __builtin_bit_cast(float, x); }
+__device__ __forceinline__ int dpp_f2i(float x) { return __builtin_bit_cast(int, x); }
 constexpr int SEQ_ROWS = 32;           // sequences per workgroup
 // Row skew of the 16-bit LDS operand images that are read as MFMA fragments (lane = row + 16 x chunk, one ds_read_b128): on
 // gfx950 such a read is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... -- over 64 banks,
@@ -708,15 +679,10 @@ __device__ __forceinline__ void lstm_seq_fwd_body(
                                         {bo.x, bo.y, bo.z, bo.w}};
                 float gi[4], gf[4], gg[4], go[4], hn[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    gi[u] = sigmoidf_(acc[0][ut][rt][u] + bv[0][u]);
-                    gf[u] = sigmoidf_(acc[1][ut][rt][u] + bv[1][u]);
-                    gg[u] = tanhf_(acc[2][ut][rt][u] + bv[2][u]);
-                    go[u] = sigmoidf_(acc[3][ut][rt][u] + bv[3][u]);
-                    const float cn = gf[u] * (keep * c[rt][4 * ut + u]) + gi[u] * gg[u];
-                    c[rt][4 * ut + u] = cn;
-                    hn[u] = go[u] * tanhf_(cn);
-                }
+                for (int u = 0; u < 4; ++u)
+                    lstm_cell(acc[0][ut][rt][u] + bv[0][u], acc[1][ut][rt][u] + bv[1][u], acc[2][ut][rt][u] + bv[2][u],
+                              acc[3][ut][rt][u] + bv[3][u], keep * c[rt][4 * ut + u], gi[u], gf[u], gg[u], go[u],
+                              c[rt][4 * ut + u], hn[u]);
                 if (!(ablate & 1)) {
                     const float4 cv = make_float4(c[rt][4 * ut], c[rt][4 * ut + 1], c[rt][4 * ut + 2], c[rt][4 * ut + 3]);
                     if (sizeof(CT) == 2 && last) st4(cl + 4 * ut, cv);
@@ -910,14 +876,8 @@ __device__ __forceinline__ void lstm_seq_bwd_body(
                     // (with `first` a compile-time constant the product above would be contracted into the sum below as one
                     // fma -- the step kernels, where it sits behind a select, round it separately: keep the two bit-identical)
                     if (!first) asm volatile("" : "+v"(dc));
-                    const float tc = tanhf_(cnew[rt][e]);
-                    const float d_o = dh * tc;
-                    const float d_c = dc + dh * go[u] * (1.0f - tc * tc);
-                    di[u] = d_c * gg[u] * gi[u] * (1.0f - gi[u]);
-                    df[u] = d_c * (keep * cp[u]) * gf[u] * (1.0f - gf[u]);
-                    dg[u] = d_c * gi[u] * (1.0f - gg[u] * gg[u]);
-                    dout[u] = d_o * go[u] * (1.0f - go[u]);
-                    dcarry[rt][e] = d_c * gf[u];
+                    lstm_cell_bwd(dh, dc, cnew[rt][e], keep * cp[u], gi[u], gf[u], gg[u], go[u], di[u], df[u], dg[u], dout[u],
+                                  dcarry[rt][e]);
                     cnew[rt][e] = cp[u];                          // c_{t-1} is c_new of the next (earlier) step
                     bsum[0][e] += di[u]; bsum[1][e] += df[u]; bsum[2][e] += dg[u]; bsum[3][e] += dout[u];
                 }
@@ -1025,7 +985,7 @@ __global__ __launch_bounds__(256) void linear_elu_mfma_kernel(long long n, int N
         const float x[4] = {acc[t][0] + bbv[t].x, acc[t][1] + bbv[t].y, acc[t][2] + bbv[t].z, acc[t][3] + bbv[t].w};
         float y[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) y[u] = x[u] > 0.0f ? x[u] : alpha * (__expf(x[u]) - 1.0f);
+        for (int u = 0; u < 4; ++u) y[u] = elu1(x[u], alpha);
         st4(out + b * out_stride + u0 + 16 * t + 4 * (lane >> 4), make_float4(y[0], y[1], y[2], y[3]));
     }
 }
@@ -1393,7 +1353,37 @@ __device__ void copy_scatter_forms(const CopyBatchArgs& batch, int vblock, int v
 __device__ __forceinline__ int mlp3_tile_row(int u) {      // unit -> LDS row: 32 kk + 8 q + 4 ut + j  ->  32 kk + 16 ut + 4 q + j
     return (u & ~31) | ((u & 4) << 2) | ((u >> 1) & 12) | (u & 3);
 }
-__device__ __forceinline__ float elu1(float x, float alpha) { return x > 0.0f ? x : alpha * (__expf(x) - 1.0f); }
+
+// The observation statistics of a one-launch MLP (at most 32 columns).  The float64 mean and variance are read by the first
+// 32 threads of the workgroup (obs_stats_request: early, the round trip runs under the caller's other requests), handed
+// round through LDS as (mean, sqrt(var + eps)) (obs_stats_publish, then a barrier), and a thread normalises its 8
+// consecutive columns c0 .. c0 + 7, zero beyond F_in (obs_normalize8).  Read by every thread instead, 16 float64 loads
+// compile to one memory round trip each: the conversion of one is waited for before the next is requested.
+__device__ __forceinline__ void obs_stats_request(int tid, int F_in, const double* mean, const double* var, double& stat_mean,
+                                                  double& stat_var) {
+    if (tid < 32) {
+        stat_mean = mean[min(tid, F_in - 1)];
+        stat_var = var[min(tid, F_in - 1)];
+    }
+}
+__device__ __forceinline__ void obs_stats_publish(int tid, const double& stat_mean, const double& stat_var, float eps,
+                                                  float* stat_m, float* stat_sd) {
+    if (tid < 32) {
+        stat_m[tid] = (float)stat_mean;
+        stat_sd[tid] = obs_std(stat_var, eps);
+    }
+}
+__device__ __forceinline__ void obs_normalize8(const float (&rv)[8], const float* stat_m, const float* stat_sd, int c0, int F_in,
+                                               float clip, float (&y)[8]) {
+    const float4 m0 = ld4(stat_m + c0), m1 = ld4(stat_m + c0 + 4), d0 = ld4(stat_sd + c0), d1 = ld4(stat_sd + c0 + 4);
+    const float ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+    const float sds[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float v = obs_normalize(rv[e], ms[e], sds[e], clip);
+        y[e] = c0 + e < F_in ? v : 0.0f;
+    }
+}
 
 #ifdef SPLIT_TIMING
 // (debug build, scripts/ubench/mlp_split_clock.py / mlp_mfma_clock.py) per wave: s_memtime / s_memrealtime at up to 8 points
@@ -1453,18 +1443,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
             s1[it] = u32x4_t{d[0], d[1], d[2], d[3]};
         }
     }
-    // ---- this lane's B fragment of layer 1: columns 8 q .. 8 q + 7 of its row.  The float64 statistics are read and turned
-    // into (mean, sqrt(var + eps)) by 32 threads, once per workgroup, and handed round through LDS: 16 float64 loads per
-    // thread compile to one memory round trip each (the conversion of one is waited for before the next is requested),
-    // and per-column `if`s around the observation loads to one round trip per column -- clamped addresses instead
+    // ---- this lane's B fragment of layer 1: columns 8 q .. 8 q + 7 of its row (per-column `if`s around the observation
+    // loads compile to one round trip per column -- clamped addresses instead)
     __shared__ float stat_m[32], stat_sd[32];
     float rv[8];
     double stat_mean = 0.0, stat_var = 1.0;
     if (raw) {
-        if (tid < 32) {
-            stat_mean = mean[min(tid, F_in - 1)];
-            stat_var = var[min(tid, F_in - 1)];
-        }
+        obs_stats_request(tid, F_in, mean, var, stat_mean, stat_var);
 #pragma unroll
         for (int e = 0; e < 8; ++e) rv[e] = raw[b * F_in + min(8 * q + e, F_in - 1)];
     }
@@ -1490,21 +1475,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
     }
     lp16x8_t af1;
     if (raw) {
-        if (tid < 32) {
-            // same arithmetic as normalize_obs_kernel: statistics cast to float first
-            stat_m[tid] = (float)stat_mean;
-            stat_sd[tid] = sqrtf((float)stat_var + eps);
-        }
+        obs_stats_publish(tid, stat_mean, stat_var, eps, stat_m, stat_sd);
         __syncthreads();
         float v[8];
-        const float4 m0 = ld4(stat_m + 8 * q), m1 = ld4(stat_m + 8 * q + 4), d0 = ld4(stat_sd + 8 * q), d1 = ld4(stat_sd + 8 * q + 4);
-        const float ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-        const float sds[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float y = fminf(fmaxf((rv[e] - ms[e]) / sds[e], -clip), clip);
-            v[e] = 8 * q + e < F_in ? y : 0.0f;
-        }
+        obs_normalize8(rv, stat_m, stat_sd, 8 * q, F_in, clip, v);
         const uint4 pk = pack_lp16x8(v);
         af1 = __builtin_bit_cast(lp16x8_t, pk);
         *reinterpret_cast<uint4*>(x + b * ldx + 8 * q) = pk;     // the LSTM operand's observation block (+ zero pad)
@@ -1653,7 +1627,7 @@ __global__ __launch_bounds__(256) void linear_bwd_elu_mfma_kernel(long long n, i
     for (int t = 0; t < 4; ++t) {
         const float aa[4] = {av[t].x, av[t].y, av[t].z, av[t].w};
 #pragma unroll
-        for (int u = 0; u < 4; ++u) d[t][u] = acc[t][u] * (aa[u] > 0.0f ? 1.0f : aa[u] + alpha);
+        for (int u = 0; u < 4; ++u) d[t][u] = acc[t][u] * elu_grad(aa[u], alpha);
         st4(gz + b * gz_stride + u0 + 16 * t + 4 * (lane >> 4), make_float4(d[t][0], d[t][1], d[t][2], d[t][3]));
     }
     if (partial) {
@@ -1750,7 +1724,7 @@ __global__ __launch_bounds__(256) void linear_bwd_elu_mfma_chunked_kernel(
     for (int t = 0; t < 4; ++t) {
         const float aa[4] = {av[t].x, av[t].y, av[t].z, av[t].w};
 #pragma unroll
-        for (int u = 0; u < 4; ++u) d[t][u] = acc[t][u] * (aa[u] > 0.0f ? 1.0f : aa[u] + alpha);
+        for (int u = 0; u < 4; ++u) d[t][u] = acc[t][u] * elu_grad(aa[u], alpha);
         st4(gz + b * gz_stride + u0 + 16 * t + 4 * (lane >> 4), make_float4(d[t][0], d[t][1], d[t][2], d[t][3]));
     }
     if (partial) {
@@ -1882,8 +1856,8 @@ __device__ __forceinline__ void mlp3_bwd_elu_mfma_body(
         float av_[8], d_[8];                                                                                   \
         unpack_lp16x8(areg, av_);                                                                              \
         _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                        \
-            d_[e] = (a_lo)[e] * (av_[e] > 0.0f ? 1.0f : av_[e] + alpha);                                       \
-            d_[4 + e] = (a_hi)[e] * (av_[4 + e] > 0.0f ? 1.0f : av_[4 + e] + alpha);                           \
+            d_[e] = (a_lo)[e] * elu_grad(av_[e], alpha);                                                       \
+            d_[4 + e] = (a_hi)[e] * elu_grad(av_[4 + e], alpha);                                               \
         }                                                                                                      \
         pk = pack_lp16x8(d_);                                                                                  \
         *reinterpret_cast<uint4*>(gzptr) = pk;                                                                 \
@@ -2019,16 +1993,8 @@ __global__ void lstm_bwd_kernel(long long B, int H, const float* __restrict__ g_
         const float cn[4] = {cn4.x, cn4.y, cn4.z, cn4.w}, cp[4] = {cp4.x, cp4.y, cp4.z, cp4.w};
         float di[4], df[4], dg[4], dout[4], dcp[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float tc = tanhf_(cn[u]);
-            const float d_o = dh[u] * tc;
-            const float d_c = dc[u] + dh[u] * go[u] * (1.0f - tc * tc);
-            di[u] = d_c * gg[u] * gi[u] * (1.0f - gi[u]);
-            df[u] = d_c * (keep * cp[u]) * gf[u] * (1.0f - gf[u]);
-            dg[u] = d_c * gi[u] * (1.0f - gg[u] * gg[u]);
-            dout[u] = d_o * go[u] * (1.0f - go[u]);
-            dcp[u] = d_c * gf[u];
-        }
+        for (int u = 0; u < 4; ++u)
+            lstm_cell_bwd(dh[u], dc[u], cn[u], keep * cp[u], gi[u], gf[u], gg[u], go[u], di[u], df[u], dg[u], dout[u], dcp[u]);
         DG* dgp = dgates + b * dg_stride;
         st4(dgp + 0 * H + j, make_float4(di[0], di[1], di[2], di[3]));
         st4(dgp + 1 * H + j, make_float4(df[0], df[1], df[2], df[3]));
@@ -2188,16 +2154,8 @@ __global__ __launch_bounds__(256) void lstm_bwd_mfma_kernel(
         const float cn[4] = {cn4.x, cn4.y, cn4.z, cn4.w}, cp[4] = {cp4.x, cp4.y, cp4.z, cp4.w};
         float di[4], df[4], dg[4], dout[4], dcp[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float tc = tanhf_(cn[u]);
-            const float d_o = dh[u] * tc;
-            const float d_c = dc[u] + dh[u] * go[u] * (1.0f - tc * tc);
-            di[u] = d_c * gg[u] * gi[u] * (1.0f - gi[u]);
-            df[u] = d_c * (keep * cp[u]) * gf[u] * (1.0f - gf[u]);
-            dg[u] = d_c * gi[u] * (1.0f - gg[u] * gg[u]);
-            dout[u] = d_o * go[u] * (1.0f - go[u]);
-            dcp[u] = d_c * gf[u];
-        }
+        for (int u = 0; u < 4; ++u)
+            lstm_cell_bwd(dh[u], dc[u], cn[u], keep * cp[u], gi[u], gf[u], gg[u], go[u], di[u], df[u], dg[u], dout[u], dcp[u]);
         lp16_t* dgp = dgates + b * dg_stride;
         st4(dgp + 0 * H + j, make_float4(di[0], di[1], di[2], di[3]));
         st4(dgp + 1 * H + j, make_float4(df[0], df[1], df[2], df[3]));
@@ -2564,8 +2522,6 @@ __global__ __launch_bounds__(512) void wgrad_cat_wide_kernel(int stages, int mti
 // Sum over the 64 lanes, returned to every lane: DPP row shifts and row broadcasts (7 VALU adds with a lane-shifted
 // operand, total in lane 63) + one v_readlane, instead of 6 ds_bpermute round trips through the LDS crossbar.
 // Needs all 64 lanes active (every caller runs it from wave-uniform control flow).
-__device__ __forceinline__ float dpp_i2f(int x) { return __builtin_bit_cast(float, x); }
-__device__ __forceinline__ int dpp_f2i(float x) { return __builtin_bit_cast(int, x); }
 __device__ __forceinline__ float wave_sum(float v) {
     const int x = dpp_f2i(v);
     // row_shr:1..3 of the input: lane i of a 16-lane row holds v[i-3 .. i] (lanes shifted in from outside the row: 0)
@@ -2605,12 +2561,12 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(long long n, const f
             const float a = xv[v].x - mean, b = xv[v].y - mean, c = xv[v].z - mean, d = xv[v].w - mean;
             q += (a * a + b * b) + (c * c + d * d);
         }
-        const float rstd = rsqrtf(wave_sum(q) * (1.0f / H) + eps);
+        const float rstd = layernorm_rstd(wave_sum(q), H, eps);
 #pragma unroll
         for (int v = 0; v < NV; ++v)
             st4(y + r * H + 256 * v + 4 * lane,
-                make_float4((xv[v].x - mean) * rstd * gm[v].x + bt[v].x, (xv[v].y - mean) * rstd * gm[v].y + bt[v].y,
-                            (xv[v].z - mean) * rstd * gm[v].z + bt[v].z, (xv[v].w - mean) * rstd * gm[v].w + bt[v].w));
+                make_float4(layernorm_affine(xv[v].x - mean, rstd, gm[v].x, bt[v].x), layernorm_affine(xv[v].y - mean, rstd, gm[v].y, bt[v].y),
+                            layernorm_affine(xv[v].z - mean, rstd, gm[v].z, bt[v].z), layernorm_affine(xv[v].w - mean, rstd, gm[v].w, bt[v].w)));
         if (lane == 0 && mean_out) { mean_out[r] = mean; rstd_out[r] = rstd; }
     }
 }
@@ -2684,10 +2640,7 @@ __global__ void normalize_obs_kernel(long long n, int F, const float* __restrict
          idx += (long long)gridDim.x * blockDim.x) {
         const long long r = idx / F;
         const int c = (int)(idx - r * F);
-        // same arithmetic as the module: statistics cast to float first, then (x - mean) / sqrt(var + eps)
-        const float m = (float)mean[c], sd = sqrtf((float)var[c] + eps);
-        float y = (x[idx] - m) / sd;
-        y = fminf(fmaxf(y, -clip), clip);
+        const float y = obs_normalize(x[idx], (float)mean[c], obs_std(var[c], eps), clip);
         if (sizeof(OT) == 2) reinterpret_cast<lp16_t*>(out)[r * out_stride + c] = f2lp(y);
         else reinterpret_cast<float*>(out)[r * out_stride + c] = y;
     }
@@ -3058,7 +3011,7 @@ __global__ __launch_bounds__(256) void bias_elu_kernel(long long n, int C, const
         const float x[4] = {zv.x + bv.x, zv.y + bv.y, zv.z + bv.z, zv.w + bv.w};
         float y[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) y[u] = x[u] > 0.0f ? x[u] : alpha * (__expf(x[u]) - 1.0f);
+        for (int u = 0; u < 4; ++u) y[u] = elu1(x[u], alpha);
         st4(out + r * out_stride + j, make_float4(y[0], y[1], y[2], y[3]));
     }
 }
@@ -3083,9 +3036,9 @@ __global__ __launch_bounds__(256) void ln_heads_fwd_kernel(long long n, const fl
         const float4 xv = ld4(x + r * H + 4 * lane);
         const float mean = wave_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / H);
         const float a = xv.x - mean, b = xv.y - mean, c = xv.z - mean, d = xv.w - mean;
-        const float rstd = rsqrtf(wave_sum((a * a + b * b) + (c * c + d * d)) * (1.0f / H) + eps);
-        const float y0 = a * rstd * gm.x + bt.x, y1 = b * rstd * gm.y + bt.y, y2 = c * rstd * gm.z + bt.z,
-                    y3 = d * rstd * gm.w + bt.w;
+        const float rstd = layernorm_rstd(wave_sum((a * a + b * b) + (c * c + d * d)), H, eps);
+        const float y0 = layernorm_affine(a, rstd, gm.x, bt.x), y1 = layernorm_affine(b, rstd, gm.y, bt.y), y2 = layernorm_affine(c, rstd, gm.z, bt.z),
+                    y3 = layernorm_affine(d, rstd, gm.w, bt.w);
         float p[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) p[h] = wave_sum((y0 * wv[h].x + y1 * wv[h].y) + (y2 * wv[h].z + y3 * wv[h].w));
@@ -3178,8 +3131,8 @@ __global__ __launch_bounds__(256) void elu_bwd_kernel(long long n, int C, const 
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (long long r = (long long)blockIdx.x * rows_per_pass + rq; r < n; r += (long long)gridDim.x * rows_per_pass) {
         const float4 gv = ld4(g + r * g_stride + j), av = ld4(a + r * a_stride + j);
-        const float4 d = make_float4(gv.x * (av.x > 0.0f ? 1.0f : av.x + alpha), gv.y * (av.y > 0.0f ? 1.0f : av.y + alpha),
-                                     gv.z * (av.z > 0.0f ? 1.0f : av.z + alpha), gv.w * (av.w > 0.0f ? 1.0f : av.w + alpha));
+        const float4 d = make_float4(gv.x * elu_grad(av.x, alpha), gv.y * elu_grad(av.y, alpha), gv.z * elu_grad(av.z, alpha),
+                                     gv.w * elu_grad(av.w, alpha));
         st4(out + r * out_stride + j, d);
         acc[0] += d.x; acc[1] += d.y; acc[2] += d.z; acc[3] += d.w;
     }
@@ -3280,12 +3233,69 @@ struct ColsumBatch {
     VineLossFinalize fin;  // fin.partial != NULL: one more workgroup folds the loss kernel's per-workgroup rows
 };
 __device__ __forceinline__ bool not_finite(float v) { return !(fabsf(v) <= 3.0e38f); }
+// rows of `partial` -> stats[8], grad_logstd[A] and (added into) the two head-bias gradients
+// (run by the LAST workgroup of ppo_loss_kernel to finish: 256 threads)
 __device__ __forceinline__ void ppo_loss_finalize(int blocks, int A, long long n, const float* partial,
                                                   const float* __restrict__ logstd, float critic_coef, float entropy_coef,
                                                   float bounds_coef, float* __restrict__ stats,
                                                   float* __restrict__ grad_logstd, float* __restrict__ grad_mu_bias,
                                                   float* __restrict__ grad_value_bias, float* __restrict__ kl_out,
-                                                  float* __restrict__ logstd_grad_accum, float S);
+                                                  float* __restrict__ logstd_grad_accum, float S) {
+    // S: loss scale; the partial sums are unscaled, every GRADIENT written here is multiplied by it
+    // (called by whole workgroups of 256 or 512 threads: the first 256 do the work, all take part in the barriers)
+    const int q = threadIdx.x & (PPO_LOSS_ROW - 1), rl = threadIdx.x / PPO_LOSS_ROW;     // 32 columns x 8 row-lanes
+    __shared__ float fred[8][PPO_LOSS_ROW];
+    __shared__ float tot[PPO_LOSS_ROW];
+    if (threadIdx.x < 256) {
+        // this is the serial tail of the launch (one workgroup, every load an L2 round trip): 16 rows in flight per
+        // thread, added in the order of one at a time
+        float acc = 0.0f;
+        int b = rl;
+        for (; b + 120 < blocks; b += 128) {
+            float v[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = partial[(long long)(b + 8 * k) * PPO_LOSS_ROW + q];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc += v[k];
+        }
+        for (; b + 24 < blocks; b += 32) {
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = partial[(long long)(b + 8 * k) * PPO_LOSS_ROW + q];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc += v[k];
+        }
+        for (; b < blocks; b += 8) acc += partial[(long long)b * PPO_LOSS_ROW + q];
+        fred[rl][q] = acc;
+    }
+    __syncthreads();
+    if (rl == 0) {
+        float v = 0.0f;
+        for (int k = 0; k < 8; ++k) v += fred[k][q];
+        tot[q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float inv_n = 1.0f / (float)n;
+        float sum_ls = 0.0f;
+        for (int k = 0; k < A; ++k) sum_ls += logstd[k];
+        const float ent = A * (0.5f + 0.9189385332046727f) + sum_ls;
+        const float a = tot[0] * inv_n, c = tot[1] * inv_n, b = tot[2] * inv_n, kl = tot[3] * inv_n;
+        stats[0] = a; stats[1] = c; stats[2] = b; stats[3] = ent; stats[4] = kl;
+        stats[5] = a + 0.5f * critic_coef * c + bounds_coef * b - entropy_coef * ent;
+        stats[6] = 0.0f; stats[7] = 0.0f;
+        for (int k = 0; k < A; ++k) {
+            const float gl = (tot[PPO_SLOT_GLS + k] - entropy_coef) * S;
+            grad_logstd[k] = gl;
+            if (logstd_grad_accum) logstd_grad_accum[k] += gl;
+        }
+        if (kl_out) kl_out[0] = kl;
+        if (grad_mu_bias) {
+            for (int k = 0; k < A; ++k) grad_mu_bias[k] += tot[PPO_SLOT_GMU + k] * S;
+            grad_value_bias[0] += tot[PPO_SLOT_GV] * S;
+        }
+    }
+}
 __global__ __launch_bounds__(256) void colsum_batched_kernel(ColsumBatch batch) {
     // (workgroup 0: it is the longest job of the launch -- two dependent passes over the rows -- so it starts first)
     const int fin_blocks = batch.fin.partial ? 1 : 0;
@@ -3367,72 +3377,6 @@ __global__ __launch_bounds__(256) void colsum_batched_kernel(ColsumBatch batch) 
     }
 }
 
-#define PPO_MAX_A 8
-#define PPO_LOSS_ROW 32          // floats per workgroup row of the loss kernel's partial sums (22 used)
-// rows of `partial` -> stats[8], grad_logstd[A] and (added into) the two head-bias gradients
-// (run by the LAST workgroup of ppo_loss_kernel to finish: 256 threads)
-__device__ __forceinline__ void ppo_loss_finalize(int blocks, int A, long long n, const float* partial,
-                                                  const float* __restrict__ logstd, float critic_coef, float entropy_coef,
-                                                  float bounds_coef, float* __restrict__ stats,
-                                                  float* __restrict__ grad_logstd, float* __restrict__ grad_mu_bias,
-                                                  float* __restrict__ grad_value_bias, float* __restrict__ kl_out,
-                                                  float* __restrict__ logstd_grad_accum, float S) {
-    // S: loss scale; the partial sums are unscaled, every GRADIENT written here is multiplied by it
-    // (called by whole workgroups of 256 or 512 threads: the first 256 do the work, all take part in the barriers)
-    const int q = threadIdx.x & (PPO_LOSS_ROW - 1), rl = threadIdx.x / PPO_LOSS_ROW;     // 32 columns x 8 row-lanes
-    __shared__ float fred[8][PPO_LOSS_ROW];
-    __shared__ float tot[PPO_LOSS_ROW];
-    if (threadIdx.x < 256) {
-        // this is the serial tail of the launch (one workgroup, every load an L2 round trip): 16 rows in flight per
-        // thread, added in the order of one at a time
-        float acc = 0.0f;
-        int b = rl;
-        for (; b + 120 < blocks; b += 128) {
-            float v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = partial[(long long)(b + 8 * k) * PPO_LOSS_ROW + q];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc += v[k];
-        }
-        for (; b + 24 < blocks; b += 32) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = partial[(long long)(b + 8 * k) * PPO_LOSS_ROW + q];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc += v[k];
-        }
-        for (; b < blocks; b += 8) acc += partial[(long long)b * PPO_LOSS_ROW + q];
-        fred[rl][q] = acc;
-    }
-    __syncthreads();
-    if (rl == 0) {
-        float v = 0.0f;
-        for (int k = 0; k < 8; ++k) v += fred[k][q];
-        tot[q] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float inv_n = 1.0f / (float)n;
-        float sum_ls = 0.0f;
-        for (int k = 0; k < A; ++k) sum_ls += logstd[k];
-        const float ent = A * (0.5f + 0.9189385332046727f) + sum_ls;
-        const float a = tot[0] * inv_n, c = tot[1] * inv_n, b = tot[2] * inv_n, kl = tot[3] * inv_n;
-        stats[0] = a; stats[1] = c; stats[2] = b; stats[3] = ent; stats[4] = kl;
-        stats[5] = a + 0.5f * critic_coef * c + bounds_coef * b - entropy_coef * ent;
-        stats[6] = 0.0f; stats[7] = 0.0f;
-        for (int k = 0; k < A; ++k) {
-            const float gl = (tot[5 + k] - entropy_coef) * S;
-            grad_logstd[k] = gl;
-            if (logstd_grad_accum) logstd_grad_accum[k] += gl;
-        }
-        if (kl_out) kl_out[0] = kl;
-        if (grad_mu_bias) {
-            for (int k = 0; k < A; ++k) grad_mu_bias[k] += tot[5 + PPO_MAX_A + k] * S;
-            grad_value_bias[0] += tot[5 + 2 * PPO_MAX_A] * S;
-        }
-    }
-}
-
 // Ticket of the loss / Adam kernels' workgroups (the last one to finish runs the finalize step and resets it: a launch
 // always finds 0).  The word is NOT a module global: the host wrappers hand every (device, stream) pair its own zeroed
 // slot (ticket_slot below), so launches in flight on different streams -- two agents in one process, a warm-up on a side
@@ -3466,8 +3410,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(long long n, int A, const
     float sum_ls = 0.0f;
     for (int k = 0; k < A; ++k) {
         ls[k] = logstd[k];
-        sg[k] = __expf(ls[k]);
-        isg2[k] = 1.0f / (sg[k] * sg[k]);
+        ppo_sigma(ls[k], sg[k], isg2[k]);
         sum_ls += ls[k];
     }
     float acc[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};                   // a, c, b, kl, (unused)
@@ -3476,51 +3419,23 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(long long n, int A, const
     for (int k = 0; k <= PPO_MAX_A; ++k) gmb[k] = 0.0f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float z2[PPO_MAX_A], dm[PPO_MAX_A], m[PPO_MAX_A];
-        float nlp = 0.9189385332046727f * A + sum_ls;
+        float nlp = gauss_neglogp_const(A) + sum_ls;
         for (int k = 0; k < A; ++k) {
             m[k] = mu[i * mu_stride + k];
-            dm[k] = actions[i * A + k] - m[k];
-            z2[k] = dm[k] * dm[k] * isg2[k];
-            nlp += 0.5f * z2[k];
+            ppo_z2(actions[i * A + k], m[k], isg2[k], dm[k], z2[k], nlp);
         }
-        const float a = adv[i];
-        const float ratio = __expf(old_neglogp[i] - nlp);
-        const float rc = fminf(fmaxf(ratio, 1.0f - e_clip), 1.0f + e_clip);
-        const float s1 = -a * ratio, s2 = -a * rc;
-        const bool first = s1 >= s2;                     // torch.max sends the tie's gradient to the first operand
-        const float a_loss = first ? s1 : s2;
-        const float inside = (ratio > 1.0f - e_clip && ratio < 1.0f + e_clip) ? 1.0f : 0.0f;
-        const float dL_dratio = first ? -a : -a * inside;
-        const float dL_dnlp = -ratio * dL_dratio * inv_n;    // d ratio / d nlp = -ratio
-        // value loss
-        const float v = value[i * value_stride], vp = old_values[i], R = returns[i];
-        float c_loss, dL_dv;
-        if (clip_value) {
-            const float dv = v - vp;
-            const float vc = vp + fminf(fmaxf(dv, -e_clip), e_clip);
-            const float l1 = (v - R) * (v - R), l2 = (vc - R) * (vc - R);
-            if (l1 >= l2) { c_loss = l1; dL_dv = 2.0f * (v - R); }
-            else { c_loss = l2; dL_dv = (dv > -e_clip && dv < e_clip) ? 2.0f * (vc - R) : 0.0f; }
-        } else {
-            c_loss = (R - v) * (R - v);
-            dL_dv = 2.0f * (v - R);
-        }
-        const float gval = 0.5f * critic_coef * dL_dv * inv_n;
+        float a_loss, dL_dnlp, c_loss, gval;
+        ppo_surrogate(nlp, old_neglogp[i], adv[i], e_clip, inv_n, a_loss, dL_dnlp);
+        ppo_value_loss(value[i * value_stride], old_values[i], returns[i], e_clip, clip_value, critic_coef, inv_n, c_loss, gval);
         grad_value[i * value_stride] = gval * S;
         gmb[PPO_MAX_A] += gval;
         float b_loss = 0.0f, kl = 0.0f;
         for (int k = 0; k < A; ++k) {
-            const float hi = fmaxf(m[k] - soft_bound, 0.0f), lo = fminf(m[k] + soft_bound, 0.0f);
-            b_loss += hi * hi + lo * lo;
-            // d nlp / d mu = -(a - mu)/sigma^2 ; d nlp / d logstd = 1 - z^2
-            const float gm = dL_dnlp * (-dm[k] * isg2[k]) + bounds_coef * inv_n * 2.0f * (hi + lo);
+            const float gm = ppo_g_mu(m[k], dm[k], isg2[k], dL_dnlp, bounds_coef, soft_bound, inv_n, b_loss);
             grad_mu[i * mu_stride + k] = gm * S;
             gmb[k] += gm;
-            gls[k] += dL_dnlp * (1.0f - z2[k]);
-            const float om = old_mu[i * A + k], os = old_sigma[i * A + k];
-            const float c1 = __logf(os / sg[k] + 1e-5f);
-            const float c2 = (sg[k] * sg[k] + (om - m[k]) * (om - m[k])) / (2.0f * (os * os + 1e-5f));
-            kl += c1 + c2 - 0.5f;
+            gls[k] += ppo_g_logstd(dL_dnlp, z2[k]);
+            ppo_kl(m[k], sg[k], old_mu[i * A + k], old_sigma[i * A + k], kl);
             if (mu_store) {      // dataset.update_mu_sigma: may alias old_mu / old_sigma (read above by this thread)
                 mu_store[i * A + k] = m[k];
                 sigma_store[i * A + k] = sg[k];
@@ -3530,27 +3445,23 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(long long n, int A, const
     }
     // block reduction (wave shuffles, then LDS across the 4 waves) into one row of `partial` per workgroup; the
     // finalize kernel adds the rows in a fixed order: no float atomics, results are bit-reproducible
-    constexpr int NRED = 5 + 2 * PPO_MAX_A + 1;
-    __shared__ float red[4][NRED];
+    __shared__ float red[4][PPO_NRED];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float vals[NRED];
+    float vals[PPO_NRED];
     for (int q = 0; q < 4; ++q) vals[q] = acc[q];
     vals[4] = 0.0f;
-    for (int k = 0; k < PPO_MAX_A; ++k) vals[5 + k] = (k < A) ? gls[k] : 0.0f;
-    for (int k = 0; k <= PPO_MAX_A; ++k) vals[5 + PPO_MAX_A + k] = gmb[k];
+    for (int k = 0; k < PPO_MAX_A; ++k) vals[PPO_SLOT_GLS + k] = (k < A) ? gls[k] : 0.0f;
+    for (int k = 0; k <= PPO_MAX_A; ++k) vals[PPO_SLOT_GMU + k] = gmb[k];
 #pragma unroll
-    for (int q = 0; q < NRED; ++q) {
-        // slots of actions k >= A hold zeros: skip their reductions (A is uniform, so is the branch)
-        const bool live = q < 4 || (q >= 5 && q < 5 + A) || (q >= 5 + PPO_MAX_A && q < 5 + PPO_MAX_A + A) ||
-                          q == 5 + 2 * PPO_MAX_A;
-        const float x = live ? wave_sum(vals[q]) : 0.0f;
+    for (int q = 0; q < PPO_NRED; ++q) {
+        const float x = ppo_slot_live(q, A) ? wave_sum(vals[q]) : 0.0f;
         if (lane == 0) red[wave][q] = x;
     }
     __syncthreads();
     if (threadIdx.x < PPO_LOSS_ROW) {
         const int q = threadIdx.x;
         partial[(long long)blockIdx.x * PPO_LOSS_ROW + q] =
-            q < NRED ? (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]) : 0.0f;
+            q < PPO_NRED ? (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]) : 0.0f;
         __threadfence();                                    // the row is visible device-wide before the ticket is taken
     }
     // the last workgroup to get here adds the rows in a fixed order (formerly a second 1-workgroup launch)
@@ -3628,7 +3539,6 @@ __device__ __forceinline__ void ln_heads_loss_body(
     // loss scale: applied where the per-row head gradients are formed, so dx and every parameter partial sum of this
     // kernel carry it; the bias / log-sigma gradients of the finalize step are multiplied there; statistics unscaled
     const float S = loss_scale ? *loss_scale : 1.0f;
-    constexpr int NRED = 5 + 2 * PPO_MAX_A + 1;
     float (*red)[W] = reinterpret_cast<float (*)[W]>(lds_red);
     float (*lred)[PPO_LOSS_ROW] = reinterpret_cast<float (*)[PPO_LOSS_ROW]>(lds_lred);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3710,7 +3620,7 @@ __device__ __forceinline__ void ln_heads_loss_body(
                 xa[j][u] -= mean;
                 q += xa[j][u] * xa[j][u];
             }
-        const float rstd = rsqrtf(row_allsum16(q) * (1.0f / H) + eps);
+        const float rstd = layernorm_rstd(row_allsum16(q), H, eps);
         float ph[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) ph[h] = 0.0f;
@@ -3718,7 +3628,7 @@ __device__ __forceinline__ void ln_heads_loss_body(
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float y = xa[j][u] * rstd * gm[j][u] + bt[j][u];
+                const float y = layernorm_affine(xa[j][u], rstd, gm[j][u], bt[j][u]);
 #pragma unroll
                 for (int h = 0; h < NH; ++h) ph[h] += y * wv[h][j][u];
             }
@@ -3736,65 +3646,37 @@ __device__ __forceinline__ void ln_heads_loss_body(
     float gh[NH];
 #pragma unroll
     for (int h = 0; h < NH; ++h) gh[h] = 0.0f;
-    float vals[NRED];
+    float vals[PPO_NRED];
 #pragma unroll
-    for (int qq = 0; qq < NRED; ++qq) vals[qq] = 0.0f;
+    for (int qq = 0; qq < PPO_NRED; ++qq) vals[qq] = 0.0f;
     if (cl < NP) {
         const long long i = r0 + 4 * cl + sub;
         const float inv_n = 1.0f / (float)n;
-        float nlp = 0.9189385332046727f * A;
+        float nlp = gauss_neglogp_const(A);
         float sg[A], isg2[A], z2[A], dm[A];
 #pragma unroll
         for (int k = 0; k < A; ++k) {
             const float l = logstd[k];
-            sg[k] = __expf(l);
-            isg2[k] = 1.0f / (sg[k] * sg[k]);
+            ppo_sigma(l, sg[k], isg2[k]);
             nlp += l;
         }
 #pragma unroll
-        for (int k = 0; k < A; ++k) {
-            dm[k] = (X16 ? q_act[k] : actions[i * A + k]) - myp[k];
-            z2[k] = dm[k] * dm[k] * isg2[k];
-            nlp += 0.5f * z2[k];
-        }
-        const float a = X16 ? q_adv : adv[i];
-        const float ratio = __expf((X16 ? q_onl : old_neglogp[i]) - nlp);
-        const float rc = fminf(fmaxf(ratio, 1.0f - e_clip), 1.0f + e_clip);
-        const float s1 = -a * ratio, s2 = -a * rc;
-        const bool first = s1 >= s2;                     // torch.max sends the tie's gradient to the first operand
-        const float a_loss = first ? s1 : s2;
-        const float inside = (ratio > 1.0f - e_clip && ratio < 1.0f + e_clip) ? 1.0f : 0.0f;
-        const float dL_dratio = first ? -a : -a * inside;
-        const float dL_dnlp = -ratio * dL_dratio * inv_n;
-        const float v = myp[A], vp = X16 ? q_ov : old_values[i], R = X16 ? q_ret : returns[i];
-        float c_loss, dL_dv;
-        if (clip_value) {
-            const float dv = v - vp;
-            const float vc = vp + fminf(fmaxf(dv, -e_clip), e_clip);
-            const float l1 = (v - R) * (v - R), l2 = (vc - R) * (vc - R);
-            if (l1 >= l2) { c_loss = l1; dL_dv = 2.0f * (v - R); }
-            else { c_loss = l2; dL_dv = (dv > -e_clip && dv < e_clip) ? 2.0f * (vc - R) : 0.0f; }
-        } else {
-            c_loss = (R - v) * (R - v);
-            dL_dv = 2.0f * (v - R);
-        }
-        const float gval = 0.5f * critic_coef * dL_dv * inv_n;
+        for (int k = 0; k < A; ++k) ppo_z2(X16 ? q_act[k] : actions[i * A + k], myp[k], isg2[k], dm[k], z2[k], nlp);
+        float a_loss, dL_dnlp, c_loss, gval;
+        ppo_surrogate(nlp, X16 ? q_onl : old_neglogp[i], X16 ? q_adv : adv[i], e_clip, inv_n, a_loss, dL_dnlp);
+        ppo_value_loss(myp[A], X16 ? q_ov : old_values[i], X16 ? q_ret : returns[i], e_clip, clip_value, critic_coef, inv_n,
+                       c_loss, gval);
         gh[A] = gval * S;
-        vals[5 + 2 * PPO_MAX_A] = gval;
+        vals[PPO_SLOT_GV] = gval;
         float b_loss = 0.0f, kl = 0.0f;
 #pragma unroll
         for (int k = 0; k < A; ++k) {
             const float m = myp[k];
-            const float hi = fmaxf(m - soft_bound, 0.0f), lo = fminf(m + soft_bound, 0.0f);
-            b_loss += hi * hi + lo * lo;
-            const float gmk = dL_dnlp * (-dm[k] * isg2[k]) + bounds_coef * inv_n * 2.0f * (hi + lo);
+            const float gmk = ppo_g_mu(m, dm[k], isg2[k], dL_dnlp, bounds_coef, soft_bound, inv_n, b_loss);
             gh[k] = gmk * S;
-            vals[5 + PPO_MAX_A + k] = gmk;
-            vals[5 + k] = dL_dnlp * (1.0f - z2[k]);
-            const float om = X16 ? q_om[k] : old_mu[i * A + k], os = X16 ? q_os[k] : old_sigma[i * A + k];
-            const float c1 = __logf(os / sg[k] + 1e-5f);
-            const float c2 = (sg[k] * sg[k] + (om - m) * (om - m)) / (2.0f * (os * os + 1e-5f));
-            kl += c1 + c2 - 0.5f;
+            vals[PPO_SLOT_GMU + k] = gmk;
+            vals[PPO_SLOT_GLS + k] = ppo_g_logstd(dL_dnlp, z2[k]);
+            ppo_kl(m, sg[k], X16 ? q_om[k] : old_mu[i * A + k], X16 ? q_os[k] : old_sigma[i * A + k], kl);
             if (mu_store) {      // dataset.update_mu_sigma: may alias old_mu / old_sigma (read above by this lane)
                 mu_store[i * A + k] = m;
                 sigma_store[i * A + k] = sg[k];
@@ -3806,13 +3688,11 @@ __device__ __forceinline__ void ln_heads_loss_body(
     }
     // the wave's rows added (inactive lanes hold zeros), one row of partial sums per wave
 #pragma unroll
-    for (int qq = 0; qq < NRED; ++qq) {
-        const bool live = qq < 4 || (qq >= 5 && qq < 5 + A) || (qq >= 5 + PPO_MAX_A && qq < 5 + PPO_MAX_A + A) ||
-                          qq == 5 + 2 * PPO_MAX_A;
-        const float t = live ? wave_sum(vals[qq]) : 0.0f;
+    for (int qq = 0; qq < PPO_NRED; ++qq) {
+        const float t = ppo_slot_live(qq, A) ? wave_sum(vals[qq]) : 0.0f;
         if (lane == 0) lred[wave][qq] = t;
     }
-    if (lane >= NRED && lane < PPO_LOSS_ROW) lred[wave][lane] = 0.0f;
+    if (lane >= PPO_NRED && lane < PPO_LOSS_ROW) lred[wave][lane] = 0.0f;
 #ifndef BWD_STAMPS
     TRUNK_STAMP(6)
 #endif
@@ -4248,14 +4128,14 @@ __global__ __launch_bounds__(256) void policy_head_kernel(long long N, int A, in
             const float4 xv = ld4(y + e * H + 4 * lane);
             ln_mean = wave_sum((xv.x + xv.y) + (xv.z + xv.w)) * (1.0f / 256.0f);
             const float a = xv.x - ln_mean, b = xv.y - ln_mean, c = xv.z - ln_mean, d = xv.w - ln_mean;
-            ln_rstd = rsqrtf(wave_sum((a * a + b * b) + (c * c + d * d)) * (1.0f / 256.0f) + ln_eps);
+            ln_rstd = layernorm_rstd(wave_sum((a * a + b * b) + (c * c + d * d)), 256, ln_eps);
         }
         for (int j = lane * 4; j < H; j += 256) {
             float4 yy = ld4(y + e * H + j);
             if (ln_gamma) {
                 const float4 gm = ld4(ln_gamma + j), bt = ld4(ln_beta + j);
-                yy = make_float4((yy.x - ln_mean) * ln_rstd * gm.x + bt.x, (yy.y - ln_mean) * ln_rstd * gm.y + bt.y,
-                                 (yy.z - ln_mean) * ln_rstd * gm.z + bt.z, (yy.w - ln_mean) * ln_rstd * gm.w + bt.w);
+                yy = make_float4(layernorm_affine(yy.x - ln_mean, ln_rstd, gm.x, bt.x), layernorm_affine(yy.y - ln_mean, ln_rstd, gm.y, bt.y),
+                                 layernorm_affine(yy.z - ln_mean, ln_rstd, gm.z, bt.z), layernorm_affine(yy.w - ln_mean, ln_rstd, gm.w, bt.w));
             }
 #pragma unroll
             for (int k = 0; k < HEAD_MAX_A; ++k) {
@@ -4310,14 +4190,14 @@ __global__ __launch_bounds__(256) void policy_head16_kernel(long long N, int A, 
             xa[j][u] -= mean;
             q += xa[j][u] * xa[j][u];
         }
-    const float rstd = rsqrtf(row_allsum16(q) * (1.0f / H) + ln_eps);
+    const float rstd = layernorm_rstd(row_allsum16(q), H, ln_eps);
     float acc[HEAD_MAX_A + 1] = {};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = 4 * (cl + 16 * j);
         const float4 gm = ld4(ln_gamma + c), bt = ld4(ln_beta + c);
-        const float yy[4] = {xa[j][0] * rstd * gm.x + bt.x, xa[j][1] * rstd * gm.y + bt.y, xa[j][2] * rstd * gm.z + bt.z,
-                             xa[j][3] * rstd * gm.w + bt.w};
+        const float yy[4] = {layernorm_affine(xa[j][0], rstd, gm.x, bt.x), layernorm_affine(xa[j][1], rstd, gm.y, bt.y),
+                             layernorm_affine(xa[j][2], rstd, gm.z, bt.z), layernorm_affine(xa[j][3], rstd, gm.w, bt.w)};
 #pragma unroll
         for (int k = 0; k < HEAD_MAX_A; ++k) {
             if (k < A) {
@@ -4533,10 +4413,9 @@ __global__ __launch_bounds__(256, 4) void lstm_step_f32_kernel(long long N, cons
         float cn[4], hn[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float gi = sigmoidf_(acc[0][t][r] + bia[r]), gf = sigmoidf_(acc[1][t][r] + bfa[r]);
-            const float gc = tanhf_(acc[2][t][r] + bga[r]), go = sigmoidf_(acc[3][t][r] + boa[r]);
-            cn[r] = gf * cpa[r] + gi * gc;
-            hn[r] = go * tanhf_(cn[r]);
+            float gi, gf, gc, go;
+            lstm_cell(acc[0][t][r] + bia[r], acc[1][t][r] + bfa[r], acc[2][t][r] + bga[r], acc[3][t][r] + boa[r], cpa[r], gi, gf,
+                      gc, go, cn[r], hn[r]);
         }
         st4(c_out + row * H + unit, make_float4(cn[0], cn[1], cn[2], cn[3]));
         st4(h_out + row * ldh + unit, make_float4(hn[0], hn[1], hn[2], hn[3]));
@@ -4583,18 +4462,29 @@ __device__ __forceinline__ unsigned bf16_pack2(float a, float b) {          // v
     const f32x2_t v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
 }
-// eight fp32 values -> the three bf16 pieces of each (packed pairs), v = hi + mid + lo exactly
+// Three-way bf16 split of a pair of fp32 values: h, m, l hold the packed pieces, v = hi + mid + lo exactly.  The pieces
+// round to nearest even; each residual is exact.  PK: the two residual subtractions of a step as one packed instruction
+// (the one-launch MLP) or as two scalar ones (the LSTM step, whose conversions ride in the gaps of its MFMA stream).
+template <bool PK>
+__device__ __forceinline__ f32x2_t split3_residual(const f32x2_t& x, unsigned piece) {
+    const f32x2_t pf = {__uint_as_float(piece << 16), __uint_as_float(piece & 0xFFFF0000u)};
+    if constexpr (PK) return x - pf;
+    else { const float ra = x[0] - pf[0], rb = x[1] - pf[1]; return f32x2_t{ra, rb}; }
+}
+template <bool PK>
+__device__ __forceinline__ void split3_bf16_pair(const float& a, const float& b, unsigned& h, unsigned& m, unsigned& l) {
+    const f32x2_t ab = {a, b};
+    h = __builtin_bit_cast(unsigned, __builtin_convertvector(ab, bf16x2_t));
+    const f32x2_t r = split3_residual<PK>(ab, h);
+    m = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
+    const f32x2_t s2 = split3_residual<PK>(r, m);
+    l = __builtin_bit_cast(unsigned, __builtin_convertvector(s2, bf16x2_t));
+}
+// eight fp32 values -> the three bf16 pieces of each (packed pairs)
 __device__ __forceinline__ void split3_bf16x8(const float (&v)[8], uint4& hi, uint4& mid, uint4& lo) {
     unsigned h[4], m[4], l[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float a = v[2 * i], b = v[2 * i + 1];
-        h[i] = bf16_pack2(a, b);
-        const float ra = a - __uint_as_float(h[i] << 16), rb = b - __uint_as_float(h[i] & 0xFFFF0000u);
-        m[i] = bf16_pack2(ra, rb);
-        const float sa = ra - __uint_as_float(m[i] << 16), sb = rb - __uint_as_float(m[i] & 0xFFFF0000u);
-        l[i] = bf16_pack2(sa, sb);
-    }
+    for (int i = 0; i < 4; ++i) split3_bf16_pair<false>(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
     hi = make_uint4(h[0], h[1], h[2], h[3]);
     mid = make_uint4(m[0], m[1], m[2], m[3]);
     lo = make_uint4(l[0], l[1], l[2], l[3]);
@@ -4734,10 +4624,9 @@ __global__ __launch_bounds__(256, 2) void lstm_step_split_kernel(long long N, co
             float cn[4], hn[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float gi = sigmoidf_(acc[0 + ut][rt][r] + bia[r]), gf = sigmoidf_(acc[2 + ut][rt][r] + bfa[r]);
-                const float gc = tanhf_(acc[4 + ut][rt][r] + bga[r]), go = sigmoidf_(acc[6 + ut][rt][r] + boa[r]);
-                cn[r] = gf * cpa[r] + gi * gc;
-                hn[r] = go * tanhf_(cn[r]);
+                float gi, gf, gc, go;
+                lstm_cell(acc[0 + ut][rt][r] + bia[r], acc[2 + ut][rt][r] + bfa[r], acc[4 + ut][rt][r] + bga[r],
+                          acc[6 + ut][rt][r] + boa[r], cpa[r], gi, gf, gc, go, cn[r], hn[r]);
             }
             st4(c_out + row * H + unit, make_float4(cn[0], cn[1], cn[2], cn[3]));
             st4(h_out + row * ldh + unit, make_float4(hn[0], hn[1], hn[2], hn[3]));
@@ -4886,10 +4775,8 @@ __global__ __launch_bounds__(256, 3) void lstm_step_nsplit_kernel(long long N, c
         float cn[4], hn[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float gi = sigmoidf_(pi[r]), gf = sigmoidf_(pf[r]);
-            const float gc = tanhf_(pg[r]), go = sigmoidf_(po[r]);
-            cn[r] = gf * cpa[r] + gi * gc;
-            hn[r] = go * tanhf_(cn[r]);
+            float gi, gf, gc, go;
+            lstm_cell(pi[r], pf[r], pg[r], po[r], cpa[r], gi, gf, gc, go, cn[r], hn[r]);
         }
         st4(c_out + row * H + unit, make_float4(cn[0], cn[1], cn[2], cn[3]));
         st4(h_out + row * ldh + unit, make_float4(hn[0], hn[1], hn[2], hn[3]));
@@ -4955,12 +4842,7 @@ __global__ __launch_bounds__(256) void mlp3_elu_f32_kernel(long long n, float* _
         for (int i = 0; i < 4; ++i) {
             const int c = 16 * j + 4 * g + i;
             float y = 0.0f;
-            if (c < F_in) {
-                // same arithmetic as normalize_obs_kernel: statistics cast to float first
-                const float m = (float)mean[c], sd = sqrtf((float)var[c] + eps);
-                y = (raw[row * F_in + c] - m) / sd;
-                y = fminf(fmaxf(y, -clip), clip);
-            }
+            if (c < F_in) y = obs_normalize(raw[row * F_in + c], (float)mean[c], obs_std(var[c], eps), clip);
             xn[j][i] = y;
         }
 #pragma unroll
@@ -5094,17 +4976,7 @@ __global__ __launch_bounds__(256) void mlp3_elu_f32_kernel(long long n, float* _
 __device__ __forceinline__ void split3_bf16x4(const float (&v)[4], uint2& hi, uint2& mid, uint2& lo) {
     unsigned h[2], m[2], l[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        // (two values at a time: the residual subtractions as one packed instruction each)
-        const f32x2_t ab = {v[2 * i], v[2 * i + 1]};
-        h[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(ab, bf16x2_t));
-        const f32x2_t hf = {__uint_as_float(h[i] << 16), __uint_as_float(h[i] & 0xFFFF0000u)};
-        const f32x2_t r = ab - hf;
-        m[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_t));
-        const f32x2_t mf = {__uint_as_float(m[i] << 16), __uint_as_float(m[i] & 0xFFFF0000u)};
-        const f32x2_t s2 = r - mf;
-        l[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(s2, bf16x2_t));
-    }
+    for (int i = 0; i < 2; ++i) split3_bf16_pair<true>(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
     hi = make_uint2(h[0], h[1]);
     mid = make_uint2(m[0], m[1]);
     lo = make_uint2(l[0], l[1]);
@@ -5216,14 +5088,10 @@ __global__ __launch_bounds__(256) void mlp3_elu_split_kernel(long long n, float*
     const bool obs_thread = tid < 4 * R;
     const int rl = tid >> 2, gq = tid & 3;
     const long long row = row_base + rl;
-    // (branch-free: clamped addresses, every load in flight at once -- per-column `if`s compile to one round trip each; the
-    // float64 statistics -> (mean, sqrt(var + eps)) by 32 threads through LDS, as in mlp3_elu_mfma_kernel)
+    // (branch-free: clamped addresses, every load in flight at once -- per-column `if`s compile to one round trip each)
     __shared__ float stat_m[32], stat_sd[32];
     double stat_mean = 0.0, stat_var = 1.0;
-    if (tid < 32) {
-        stat_mean = mean[min(tid, F_in - 1)];
-        stat_var = var[min(tid, F_in - 1)];
-    }
+    obs_stats_request(tid, F_in, mean, var, stat_mean, stat_var);
     float rv[8];
     const float* rrow = raw + (obs_thread ? row : row_base) * F_in;
 #pragma unroll
@@ -5243,22 +5111,11 @@ __global__ __launch_bounds__(256) void mlp3_elu_split_kernel(long long n, float*
     // ---- normalised observations: thread (row, 8-column group) -> the LSTM operand's observation block (fp32) and A0
     // (computed AND written to LDS by every thread -- threads without a row write into the still unused A1 region: with
     // every use under `if (obs_thread)` the compiler sinks the loads into the branch, behind the weight requests)
-    if (tid < 32) {
-        // same arithmetic as normalize_obs_kernel: statistics cast to float first
-        stat_m[tid] = (float)stat_mean;
-        stat_sd[tid] = sqrtf((float)stat_var + eps);
-    }
+    obs_stats_publish(tid, stat_mean, stat_var, eps, stat_m, stat_sd);
     __syncthreads();
     {
         float y[8];
-        const float4 m0 = ld4(stat_m + 8 * gq), m1 = ld4(stat_m + 8 * gq + 4), d0 = ld4(stat_sd + 8 * gq), d1 = ld4(stat_sd + 8 * gq + 4);
-        const float ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-        const float sds[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float v = fminf(fmaxf((rv[i] - ms[i]) / sds[i], -clip), clip);
-            y[i] = 8 * gq + i < F_in ? v : 0.0f;
-        }
+        obs_normalize8(rv, stat_m, stat_sd, 8 * gq, F_in, clip, y);
         uint4 pc[3];
         split3_bf16x8(y, pc[0], pc[1], pc[2]);
         if (obs_thread) {

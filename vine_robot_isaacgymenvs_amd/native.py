@@ -22,7 +22,7 @@ FINGERPRINT = LIB + ".fingerprint"
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HEADERS = [os.path.join(_INC, "vine.h"), os.path.join(_INC, "vine_ppo.h"), os.path.join(_INC, "vine_render.h"),
             os.path.join(_INC, "vine_record.h"), os.path.join(_HERE, "csrc", "vine_geometry.h"), os.path.join(_HERE, "csrc", "vine_render_internal.h"),
-            os.path.join(_HERE, "csrc", "vine_policy_head.h")]
+            os.path.join(_HERE, "csrc", "vine_policy_head.h"), os.path.join(_HERE, "csrc", "vine_ppo_formulas.h")]
 DEPS = [SRC, SRC_PPO, SRC_RENDER, SRC_RECORD] + _HEADERS
 
 _lib = None
