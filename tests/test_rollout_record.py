@@ -1,0 +1,396 @@
+"""The whole rollout record against a float64 replay of every step.
+
+Three consecutive ``play_steps_rnn()`` calls (eager, 16 steps each, 6-step episodes with the wider success / tip-limit
+resets of tests/test_eval_step.py, a perturbed model whose two normalisers really normalise) and everything they leave
+behind -- every rollout buffer, the stored and the live LSTM state, ``last_values``, the episode accumulators, the meters,
+the rollout counter, the dataset's returns / values / advantages -- held to the references of tests/rollout_reference.py:
+
+* network: ``mus``, ``values``, ``neglogpacs`` of every step, every stored LSTM-state snapshot, the live state behind the
+  rollout and ``last_values`` against the float64 replay, teacher-forced at the stored states;
+* plumbing, bit for bit: a rollout starts from the state, observation and done flags the previous one ended with, slot 0 of
+  the snapshots is that state, the operand copy of ``h`` is ``h``, finished envs have zero state rows and the others do not;
+* sampling: the noise ``(actions - mu) / sigma`` has mean 0 / deviation 1 within 0.02, lag-1 correlation across steps and
+  across neighbouring envs below 0.02, no draw twice; the rollout counter advances by the horizon;
+* env: a CPU oracle loaded with the device's own state in front of every step and stepped with the stored actions gives the
+  next observation, the reset / time-out / done flags (exactly) and the shaped reward with its time-out bootstrap, at the
+  single-step tolerances of tests/test_hip_parity.py (float32 oracle tight, float64 oracle loose);
+* bookkeeping, last values, GAE and the value normaliser's two updates in float64.
+
+Tolerance of the network tensors: the same model in plain float32 torch on the same teacher-forced inputs (the replay's
+own composition with float32 parameters: ``agent.model`` itself runs project kernels on the device, the normalisation
+and the LSTM among them) gives a baseline error against float64 per tensor in two norms, max |d| / max |ref| and ||d|| / ||ref||; the
+kernels' error may be at most ``K`` times that baseline, or ``K`` times ``FLOOR`` (the float32 unit round-off, relative to
+the tensor's magnitude) where torch happens to be nearly exact.  ``mus`` and ``neglogpacs`` also keep the absolute 2e-4 of
+test_fused_rollout_matches_stock_and_graph_replay.  ``sigmas``: exp() of a parameter, 4 float32 ulps (the hardware exp2 of
+x log2(e): one rounding of the product, whose error |x| log2(e) 2^-24 <= 2 ulps at |x| < 1, and one ulp of the instruction).
+
+An env-step is left out of the flag and reward comparison only where float32 round-off may decide a flag
+(``rollout_reference.undecided``); at most ``MAX_UNDECIDED`` per case.  Negative controls (n512_fused): the reference
+recomputed from subtly wrong inputs must break the same bounds by ``CONTROL_MARGIN`` on some compared tensor.
+
+The agent's seed (19; the task's is 42).  The action noise is a counter-based generator keyed by seed, env and step, so its
+statistics do not depend on the trajectories; a numpy restatement of the generator gives all four within 0.007 at all six
+sizes for this seed (at 72 envs x 48 steps x 2 components 0.02 is only 1.7 standard deviations of a sample mean).  With seed 11
+(test_fused_rollout_matches_stock_and_graph_replay's) everything above holds as well except at one env-step of the 73728 of
+n1536_pipe18 (step 22, env 904: a reset in a step with pipe contact), where the float32 ORACLE's tip velocity is 8 % from
+the float64 oracle's and its observation 4.3e-3, beyond the 2e-3 it is held to, while the device is within 1e-5 of the
+float64 oracle in every state field: the tight reference's own round-off, reproduced with the two oracles alone on the CPU.
+
+Measured on an MI355X, the worst tensor of each case (kernel error / max(float32 torch error, FLOOR); under 1: closer to
+float64 than torch's float32), max-relative | rms-relative, env-steps left out, seconds:
+    n512_fused          1.305 (h_end)    | 1.216 (h_end)     0    2.2
+    n1536_pipe18        1.348 (c_end)    | 1.231 (snap_h)    4    3.6
+    n512_three_launch   1.275 (h_end)    | 1.214 (h_end)     0    1.3
+    n512_native_fp32    2.805 (snap_h)   | 2.099 (snap_c)    0    1.2
+    n200_generic28      3.049 (snap_c)   | 2.104 (snap_c)    0    1.0
+    n72_generic18       3.047 (snap_h)   | 2.193 (c_end)     1    0.9
+hence K = 5 (1.5 x 3.05 = 4.6).  The heads (mus, values, neglogpacs, last_values) are at 0.47 - 1.42 on every route, the LSTM
+state at 1.0 - 1.35 on the split routes and at 2.0 - 3.05 on the native-fp32 and the generic route; |mus - float64| <= 8.5e-7.
+The negative controls (n512_fused) exceed the bound by a factor of 6.5e4 (value left normalised: shaped rewards) to 1.2e6
+(dones shifted: snap_c), far beyond CONTROL_MARGIN: against a bound of a few float32 round-offs any of these bugs is an
+error of order 0.1.  Each run prints the figures; profiles/rollout_record/ratios.txt has the whole table (every tensor, the
+absolute errors, the resets and the noise statistics of every case).
+"""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+from tests import rollout_reference as rr
+from tests import update_reference as ur
+from tests.test_update_gradients import CONTROL_MARGIN, _errs
+
+K = 5.0                     # kernel error <= K x max(float32-torch error, FLOOR), per tensor and norm
+FLOOR = 2.0 ** -24          # float32 unit round-off
+MAX_UNDECIDED = 8           # env-steps per case whose flags float32 round-off may decide
+ROLLOUTS = 3
+# tests/test_hip_parity.py single_step_case / compare_step: (precision, obs atol, reward rtol, reward atol)
+ENV_TOL = (("f32", 2e-3, 1e-5, max(1e-4, 0.2 * 2e-3)), ("f64", 1e-2, 1e-5, max(1e-4, 0.2 * 1e-2)))
+GAE_TOL = 1e-5              # test_gae_kernel_matches_reference_loop
+WIDE_RESETS = ["task.env.maxEpisodeLength=6", "task.env.SUCCESS_DIST=0.25", "task.env.MIN_TARGET_Y=-0.4",
+               "task.env.MAX_TARGET_Y=0.0", "task.env.USE_TIP_LIMIT_HIT_RESET=True"]
+FREE, PIPE18 = ["task.env.CREATE_PIPE=False"], ["task.env.CREATE_PIPE=True", "OBSERVATION_TYPE=TIP_AND_CART_AND_OBJ_INFO"]
+FREE18 = ["task.env.CREATE_PIPE=False", "OBSERVATION_TYPE=TIP_AND_CART_AND_OBJ_INFO"]
+
+# (id, envs, task overrides, agent config, observation width, launches per step, fp32 matrix-core route, env entry)
+CASES = [
+    ("n512_fused", 512, FREE, {}, 28, 3, True, "step_rollout_into"),
+    ("n1536_pipe18", 1536, PIPE18, {}, 18, 3, True, "step_rollout_into"),
+    ("n512_three_launch", 512, FREE, {"rollout_step_fused": False}, 28, 5, True, "step_into"),
+    ("n512_native_fp32", 512, FREE, {"rollout_f32_terms": 0}, 28, 3, True, "step_rollout_into"),
+    ("n200_generic28", 200, FREE, {}, 28, 6, False, "step_into"),
+    ("n72_generic18", 72, FREE18, {}, 18, 6, False, "step_into"),
+]
+NETWORK = ("mus", "values", "neglogpacs", "snap_h", "snap_c", "h_end", "c_end", "last_values")
+
+
+def _build(n, overrides, config):
+    from vine_robot_isaacgymenvs_amd import load_config
+    from vine_robot_isaacgymenvs_amd.learning.a2c_continuous import A2CAgent
+    from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
+    cfg = load_config(overrides=["num_envs=%d" % n, "minibatch_size=%d" % (4 * n), "seed=19"] + WIDE_RESETS + overrides)
+    cfg["task"]["seed"] = 42
+    env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
+                                                  graphics_device_id=0, headless=True)
+    params = cfg["train"]["params"]
+    params["config"].update(write_files=False, print_stats=False, use_graphs=False, **config)
+    torch.manual_seed(0)
+    agent = A2CAgent("t", params, vec_env=env)
+    agent.init_tensors()
+    agent.obs = agent.env_reset()["obs"]
+    ur.perturb_model(agent.model, seed=1)                   # biases, log-sigma, the observation normaliser off 0 / 1
+    vms = agent.model.value_mean_std
+    vms.running_mean.fill_(0.37); vms.running_var.fill_(2.3)          # a head that really un-normalises
+    if agent.fused_mixed:
+        agent.optimizer.refresh_shadow()                    # the 16-bit operand copies of the perturbed weights
+    agent.set_eval()
+    return agent, env
+
+
+def _snapshot(env):
+    return {"state": env.state.clone(), "reset": env.reset_buf.clone(), "progress": env.progress_buf.clone(),
+            "timeout": env.timeout_buf.clone(), "rew": env.rew_buf.clone(), "step_count": int(env.step_count)}
+
+
+def _watch(env, monkeypatch, snaps, calls):
+    """Every step entry of ``env`` first stores what the env holds in front of the step."""
+    for name in ("step_rollout_into", "step_into", "step"):
+        def entry(*a, _orig=getattr(env, name), _name=name, **kw):
+            snaps.append(_snapshot(env))
+            calls[_name] = calls.get(_name, 0) + 1
+            return _orig(*a, **kw)
+        monkeypatch.setattr(env, name, entry)
+
+
+def _got(rec):
+    return {"mus": rec["mus"], "values": rec["values"], "neglogpacs": rec["neglogpacs"], "snap_h": rec["mb_h"],
+            "snap_c": rec["mb_c"], "h_end": rec["h_end"], "c_end": rec["c_end"], "last_values": rec["last_values"]}
+
+
+def _replay_all(m, recs, seq_len, control=None):
+    """``rollout_reference.replay`` over consecutive rollouts, the reference's own state carried from one to the next
+    -> {tensor name: the rollouts' tensors stacked}."""
+    dt = next(m.parameters()).dtype
+    h = torch.zeros_like(recs[0]["h_end"], dtype=dt)
+    c = torch.zeros_like(h)
+    outs = []
+    with torch.no_grad():
+        for rec in recs:
+            out = rr.replay(m, rec, h, c, seq_len, control)
+            h, c = out["h_end"], out["c_end"]
+            outs.append(out)
+    res = {k: torch.stack([o[k] for o in outs]) for k in NETWORK}
+    res["sigmas"] = outs[0]["sigmas"]
+    return res
+
+
+def _bounds(ref, base):
+    out = {}
+    for k in NETWORK:
+        bm, br = _errs(base[k], ref[k])
+        assert np.isfinite(bm) and np.isfinite(br), ("float32 baseline not finite", k)
+        out[k] = (K * max(bm, FLOOR), K * max(br, FLOOR))
+    return out
+
+
+def _ratios(got, ref, bounds):
+    r = {}
+    for k in NETWORK:
+        em, er = _errs(got[k], ref[k])
+        r[k] = (em / bounds[k][0], er / bounds[k][1])
+    return r
+
+
+def _check_plumbing(agent, recs, T):
+    """What must hold bit for bit, whatever the arithmetic."""
+    zero = torch.zeros_like(recs[0]["h_end"])
+    for r, rec in enumerate(recs):
+        prev_h, prev_c = (recs[r - 1]["h_end"], recs[r - 1]["c_end"]) if r else (zero, zero)
+        assert torch.equal(rec["h_start"], prev_h) and torch.equal(rec["c_start"], prev_c), ("state carried over", r)
+        assert torch.equal(rec["mb_h"][:, 0], prev_h) and torch.equal(rec["mb_c"][:, 0], prev_c), ("snapshot 0", r)
+        if r:
+            assert torch.equal(rec["obses"][0], recs[r - 1]["obs_end"]), ("slot 0 observation", r)
+            assert torch.equal(rec["dones"][0], recs[r - 1]["dones_end"]), ("slot 0 done flags", r)
+        else:
+            assert bool((rec["dones"][0] == 1).all())                  # init_tensors: every env starts an episode
+        assert torch.equal(rec["h_operand"], rec["h_end"]), ("operand copy of h", r)
+        done = rec["dones_end"] != 0
+        assert bool(done.any()) and bool((~done).any())
+        for s in (rec["h_end"], rec["c_end"], rec["h_operand"]):
+            assert float(s[done].abs().max()) == 0.0, ("state of finished envs", r)
+            assert float(s[~done].abs().sum(1).min()) > 0.0, ("state of running envs", r)
+        assert rec["counter"] == T * (r + 1), ("rollout counter", r, rec["counter"])
+        # the dataset's transposed tensors are the buffers (the state snapshots: views in dataset order)
+        for bk, k in (("obs", "obses"), ("obses", "obses"), ("actions", "actions"), ("dones", "dones"), ("mu", "mus"),
+                      ("mus", "mus"), ("sigma", "sigmas"), ("sigmas", "sigmas"), ("old_logp_actions", "neglogpacs"),
+                      ("neglogpacs", "neglogpacs")):
+            if "batch_" + bk in rec:
+                want = rec[k].transpose(0, 1).reshape(rec["batch_" + bk].shape)
+                assert torch.equal(rec["batch_" + bk], want), ("dataset", bk, r)
+        for s, mb in zip(rec["batch_rnn_states"], (rec["mb_h"], rec["mb_c"])):
+            assert torch.equal(s[0], mb.reshape(-1, mb.shape[-1])), ("dataset rnn_states", r)
+
+
+def _oracles(agent, env, recs):
+    """Both oracles, one step from the device's state in front of every step of the record."""
+    T = agent.horizon_length
+    snaps = [s for rec in recs for s in rec["snaps"][:T]]
+    assert [s["step_count"] for s in snaps] == list(range(snaps[0]["step_count"], snaps[0]["step_count"] + len(snaps)))
+    actions = torch.cat([rec["actions"] for rec in recs]).cpu().numpy()
+    return {p: rr.oracle_steps(env._vcfg, p, snaps, actions) for p in ("f32", "f64")}
+
+
+def _check_env(agent, env, recs, orc, report, value_normalised=False):
+    """The record against the oracles.  ``value_normalised``: the negative control whose bootstrap term takes the
+    normalised value; returns the worst reward error / tolerance instead of asserting."""
+    cfg, T = env._vcfg, agent.horizon_length
+    vms = agent.model.value_mean_std
+    v_mean, v_std = float(vms.running_mean), float(np.sqrt(float(vms.running_var) + vms.epsilon))
+    gamma = float(agent.gamma) if agent.value_bootstrap else 0.0
+    shift, scale = float(agent.reward_shift), float(agent.reward_scale)
+    after = [s for rec in recs for s in rec["snaps"][1:T + 1]]                    # what the env held behind each step
+    values = torch.cat([rec["values"] for rec in recs]).cpu().numpy()[:, :, 0].astype(np.float64)
+    if value_normalised:
+        values = (values - v_mean) / v_std
+    rewards = torch.cat([rec["rewards"] for rec in recs]).cpu().numpy()[:, :, 0].astype(np.float64)
+    obs_next = torch.cat([torch.cat([rec["obses"][1:], rec["obs_end"][None]]) for rec in recs]).cpu().numpy()
+    dones_next = torch.cat([torch.cat([rec["dones"][1:], rec["dones_end"][None]]) for rec in recs]).cpu().numpy()
+    dev_reset = np.stack([s["reset"] for s in after])
+    dev_timeout = np.stack([s["timeout"] for s in after]).astype(np.uint8)
+    dev_rew = np.stack([s["rew"] for s in after]).astype(np.float64)
+    skip = rr.undecided(cfg, orc["f32"], orc["f64"])
+    worst = 0.0
+    for precision, obs_tol, rew_rtol, rew_atol in ENV_TOL:
+        o = orc[precision]
+        shaped = (o["rew"].astype(np.float64) + shift) * scale + gamma * values * o["timeouts"]
+        tol = scale * (rew_atol + rew_rtol * np.abs(o["rew"])) + 1e-6 * np.abs(gamma * values)
+        err = np.where(skip, 0.0, np.abs(rewards - shaped) / tol)
+        worst = max(worst, float(err.max()))
+        if value_normalised:
+            continue
+        report["obs_err_" + precision] = float(np.abs(obs_next - o["obs"]).max())
+        report["rew_err_" + precision] = float(err.max())
+        assert report["obs_err_" + precision] <= obs_tol, (precision, report)
+        assert float(err.max()) <= 1.0, (precision, "shaped reward", report)
+        raw = np.where(skip, 0.0, np.abs(dev_rew - o["rew"]) / (rew_atol + rew_rtol * np.abs(o["rew"])))
+        assert float(raw.max()) <= 1.0, (precision, "reward", float(raw.max()))
+        for name, dev, ref in (("reset", dev_reset, o["reset"]), ("time-out", dev_timeout, o["timeouts"]),
+                               ("done", dones_next, (o["reset"] != 0).astype(np.uint8))):
+            assert np.array_equal(dev[~skip], ref[~skip]), (precision, name, int((dev != ref)[~skip].sum()))
+    if value_normalised:
+        return worst
+    o = orc["f32"]
+    report["undecided"] = int(skip.sum())
+    report["resets"] = {"all": int((o["reset"] != 0).sum()), "time-outs": int(o["timeouts"].sum())}
+    assert int(skip.sum()) <= MAX_UNDECIDED, report
+    # ends other than time-outs occur, and time-outs do
+    assert report["resets"]["time-outs"] > 0 and report["resets"]["all"] > report["resets"]["time-outs"], report
+    return dev_rew, dev_reset
+
+
+def _check_books(agent, recs, dev_rew, dev_reset, report):
+    """Episode accumulators and meters in float64 from the device's rewards and reset flags."""
+    T, N = agent.horizon_length, agent.num_actors
+    books = rr.Books(N, agent.games_to_track)
+    finished = 0
+    for r, rec in enumerate(recs):
+        for n in range(T):
+            books.step(dev_rew[r * T + n], dev_reset[r * T + n])
+            finished += int(books.last[2])
+        tol = 1e-6 * books.scale              # float32 accumulators: <= 6 additions of 2^-24 relative round-off each
+        assert float(np.abs(rec["cur_r"].cpu().numpy()[:, 0] - books.cur_r).max()) <= tol, ("current_rewards", r)
+        assert np.array_equal(rec["cur_l"].cpu().numpy(), books.cur_l), ("current_lengths", r)
+        want, got = books.meter(), rec["meter"].cpu().double().numpy()[:7]
+        assert got[1] == want[1] and got[3] == want[3] and got[5] == want[5] and got[6] == want[6], (r, got, want)
+        # the step's sum of finished returns: float32, folded as a tree of depth <= ~20 -> 2e-6 of the sum of magnitudes
+        assert abs(got[4] - want[4]) <= 2e-6 * max(1.0, books.last_abs), (r, got, want)
+        # the windowed means: <= 48 updates of a few float32 roundings each, relative to the largest return
+        assert abs(got[0] - want[0]) <= 2e-5 * books.scale and abs(got[2] - want[2]) <= 2e-5 * T, (r, got, want)
+    report["episodes"] = finished
+    assert finished >= 2 * N, report              # every env finishes several episodes
+
+
+def _check_dataset(agent, recs, report):
+    """GAE over the record, and (where the dataset was assembled on the device) the value normaliser's two updates and the
+    normalised series, in float64."""
+    vms = agent.model.value_mean_std
+    mean0, var0, count0 = float(vms.running_mean), float(vms.running_var), float(vms.count)
+    worst = 0.0
+    for r, rec in enumerate(recs):
+        advs, rets = rr.gae(rec["rewards"], rec["values"], rec["dones"], rec["last_values"], rec["dones_end"],
+                            float(agent.gamma), float(agent.tau))
+        flat = lambda t: t.transpose(0, 1).reshape(-1, 1)
+        rets, vals, advs = flat(rets), flat(rec["values"].double()), flat(advs)[:, 0]
+        if not rec["assembled"]:
+            err = float((rec["batch_returns"].double() - rets).abs().max())
+            assert torch.equal(rec["batch_values"], flat(rec["values"]))
+        else:
+            m1, v1, c1 = rr.rms_update(mean0, var0, count0, vals)
+            m2, v2, c2 = rr.rms_update(m1, v1, c1, rets)
+            pend = rec["vms_pending"].cpu().numpy()
+            for got, want in zip(pend, (m2, v2, c2)):
+                assert abs(got - want) <= 2e-6 * max(1.0, abs(want)), ("value normaliser", r, pend, (m2, v2, c2))
+            s1, s2 = np.sqrt(v1 + vms.epsilon), np.sqrt(v2 + vms.epsilon)
+            # GAE_TOL in the un-normalised unit: the normalised series is 1 / std of it
+            err = float((rec["batch_returns"].double() - ((rets - m2) / s2).clamp(-5, 5)).abs().max()) * s2
+            err = max(err, float((rec["batch_old_values"].double() - ((vals - m1) / s1).clamp(-5, 5)).abs().max()) * s1)
+            if agent.normalize_advantage:
+                advs = (advs - advs.mean()) / (advs.std() + 1e-8)
+            a_err = float((rec["batch_advantages"].double() - advs).abs().max())
+            assert a_err <= 2e-5, ("advantages", r, a_err)          # test_dataset_assemble_matches_the_stock_composition
+        worst = max(worst, err)
+    report["returns_err"] = worst
+    assert worst <= GAE_TOL, ("returns", report)
+    assert (float(vms.running_mean), float(vms.running_var), float(vms.count)) == (mean0, var0, count0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_rollout_record_against_float64_replay(case, monkeypatch):
+    name, N, overrides, config, width, launches, f32_mfma, entry = case
+    t0 = time.time()
+    dev = torch.device("cuda:0")
+    agent, env = _build(N, overrides, config)
+    T, L = agent.horizon_length, agent.seq_len
+    assert agent._can_fuse_rollout() and agent._fast is not None and agent._fast["op"] == torch.float32
+    assert agent.obs_shape == (width,) and T == 16 and L == 4 and agent.normalize_value and agent.value_bootstrap
+    env.set_introspection(True)                 # the tip / cart fields of `state` are current in front of every step
+    snaps, calls, recs = [], {}, []
+    _watch(env, monkeypatch, snaps, calls)
+    with torch.no_grad():
+        for r in range(ROLLOUTS):
+            del snaps[:]
+            start = [s[0].clone() for s in agent.rnn_states]
+            batch = agent.play_steps_rnn()
+            torch.cuda.synchronize()
+            snaps.append(_snapshot(env))
+            assert len(snaps) == T + 1 and agent._pending_fin is None
+            recs.append(rr.record(agent, snaps, batch, start))
+    # ---- the route this case is about
+    f = agent._fast
+    assert agent.rollout_step_launches == launches and bool(f["f32_mfma"]) == f32_mfma, (name, agent.rollout_step_launches)
+    assert calls == {entry: ROLLOUTS * T}, calls
+    if name == "n512_native_fp32":
+        assert f["f32_split"] == 0 and f["wt_f32"] is not None and f["mlp_wt_split"] is None
+    elif f32_mfma:
+        from vine_robot_isaacgymenvs_amd.learning import fused
+        assert f["f32_split"] == 6 and f["mlp_wt_split"] is not None and fused.rollout_f32_nsplit(N) == 3
+    else:
+        assert f["f32_split"] == 0 and f["mlp_wt_split"] is None and f["wt_f32"] is None and f["ln_in_head"]
+    assert all(rec["assembled"] == (N % 64 == 0) for rec in recs)
+    report = {"launches": agent.rollout_step_launches, "entry": entry, "step_kernel": env.step_kernel_name}
+
+    _check_plumbing(agent, recs, T)
+
+    # ---- network: float64 replay, float32 torch baseline, K x baseline
+    m64, m32 = rr.model_copy(agent.model, torch.float64, dev), rr.model_copy(agent.model, torch.float32, dev)
+    ref, base = _replay_all(m64, recs, L), _replay_all(m32, recs, L)
+    got = {k: torch.stack([_got(rec)[k] for rec in recs]) for k in NETWORK}
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    bounds = _bounds(ref, base)
+    ratios = _ratios(got, ref, bounds)
+    worst_m, worst_r = max(ratios, key=lambda k: ratios[k][0]), max(ratios, key=lambda k: ratios[k][1])
+    report["worst_max"] = (worst_m, round(ratios[worst_m][0] * K, 3))         # kernel error / max(baseline error, FLOOR)
+    report["worst_rms"] = (worst_r, round(ratios[worst_r][1] * K, 3))
+    report["ratios"] = {k: (round(v[0] * K, 3), round(v[1] * K, 3)) for k, v in ratios.items()}
+    report["mus_abs"] = float((got["mus"].double() - ref["mus"]).abs().max())
+    report["nlp_abs"] = float((got["neglogpacs"].double() - ref["neglogpacs"]).abs().max())
+    sig = torch.stack([rec["sigmas"] for rec in recs]).double()
+    report["sigma_rel"] = float(((sig - ref["sigmas"]) / ref["sigmas"]).abs().max())
+
+    orc = _oracles(agent, env, recs)
+
+    # ---- negative controls: the reference from subtly wrong inputs must leave the bounds
+    margins = {}
+    if name == "n512_fused":
+        for control in rr.CONTROLS:
+            cr = _ratios(got, _replay_all(m64, recs, L, control), bounds)
+            k_ = max(cr, key=lambda k: max(cr[k]))
+            margins[control] = (k_, round(max(cr[k_]), 1))
+        margins["value left normalised"] = ("rewards", round(_check_env(agent, env, recs, orc, {}, value_normalised=True), 1))
+    report["controls"] = margins
+
+    # ---- sampling
+    eps = torch.cat([(rec["actions"] - rec["mus"]) / rec["sigmas"] for rec in recs])
+    report["noise"] = {k: round(v, 4) for k, v in rr.noise_statistics(eps).items()}
+
+    # ---- env, bookkeeping, dataset
+    dev_rew, dev_reset = _check_env(agent, env, recs, orc, report)
+    _check_books(agent, recs, dev_rew, dev_reset, report)
+    _check_dataset(agent, recs, report)
+    env.close()
+    report["seconds"] = round(time.time() - t0, 1)
+    print("\n[rollout record] %s %s" % (name, report), flush=True)
+
+    bad = {k: v for k, v in report["ratios"].items() if max(v) > K}
+    assert not bad, (name, "kernel error / max(float32 torch error, FLOOR) above K = %g" % K, bad)
+    assert report["mus_abs"] <= 2e-4 and report["nlp_abs"] <= 2e-4, report
+    assert report["sigma_rel"] <= 4 * 2.0 ** -23, report
+    nz = report["noise"]
+    assert abs(nz["mean"]) < 0.02 and abs(nz["std"] - 1.0) < 0.02, nz
+    assert abs(nz["lag1_steps"]) < 0.02 and abs(nz["lag1_envs"]) < 0.02 and nz["repeats"] == 0, nz
+    for control, (k_, m) in margins.items():
+        assert m >= CONTROL_MARGIN, ("negative control within the bound", control, k_, m)
+    if name == "n512_fused":
+        assert set(margins) == set(rr.CONTROLS) | {"value left normalised"}
