@@ -7,6 +7,8 @@ profiles/eval_player/player_paths.txt.
   python scripts/ubench/eval_player_bench.py --trace-device pipe   # device path only, short: a workload for a kernel trace
   python scripts/ubench/eval_player_bench.py --record 64 --out profiles/record_trajectories/player_paths.txt
                                                                    # + the device path with RECORD_TRAJECTORIES of 64 envs
+  python scripts/ubench/eval_player_bench.py --episode-log --out profiles/episode_log/player_paths.txt
+                                                                   # + the device path with EPISODE_LOG, with and without the table
 """
 import argparse
 import contextlib
@@ -28,13 +30,17 @@ from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map  # noqa: E402
 CONFIGS = {"free": ["task.env.CREATE_PIPE=False"], "pipe": []}
 
 
-def make(name, n, device_rollout, record=0):
+def make(name, n, device_rollout, record=0, episode_log=None):
     cfg = load_config(overrides=["num_envs=%d" % n] + CONFIGS[name])
     cfg["task"]["seed"] = 42
     if record:      # the task's default window: maxEpisodeLength (500) steps every 1000, files into a scratch directory
         import tempfile
         cfg["task"]["env"].update(RECORD_TRAJECTORIES=True, RECORD_TRAJECTORIES_ENVS=record,
                                   RECORD_TRAJECTORIES_DIR=tempfile.mkdtemp(prefix="vine_trajectories_"))
+    if episode_log:  # "table" or "totals"; the file goes into a scratch directory
+        import tempfile
+        cfg["task"]["env"].update(EPISODE_LOG=True, EPISODE_LOG_TABLE=episode_log == "table",
+                                  EPISODE_LOG_DIR=tempfile.mkdtemp(prefix="vine_episodes_"))
     env = isaacgym_task_map["Vine5LinkMovingBase"](cfg=cfg["task"], rl_device="cuda:0", sim_device="cuda:0",
                                                   graphics_device_id=0, headless=True)
     params = cfg["train"]["params"]
@@ -59,6 +65,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--trace-device", choices=sorted(CONFIGS), default=None)
     ap.add_argument("--record", type=int, default=0, help="also time the device path with RECORD_TRAJECTORIES of this many envs")
+    ap.add_argument("--episode-log", action="store_true", help="also time the device path with EPISODE_LOG (table / totals only)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "eval_player", "player_paths.txt"))
     args = ap.parse_args()
     if args.trace_device:
@@ -75,6 +82,9 @@ def main():
         players = {path: make(name, args.envs, path == "device") for path in ("stock", "device")}
         if args.record:
             players["device+record"] = make(name, args.envs, True, args.record)
+        if args.episode_log:
+            players["device+episodes"] = make(name, args.envs, True, episode_log="table")
+            players["device+episodes(totals only)"] = make(name, args.envs, True, episode_log="totals")
         for path, (player, _) in players.items():
             timed_run(player, 64 if path != "stock" else 16)            # warm-up (device: the graph capture too)
             assert player.device_path is (path != "stock")
@@ -88,10 +98,15 @@ def main():
                     rec.update(files=len(trajectory.written), skipped=len(trajectory.skipped),
                                harvest_ms=[round(1e3 * t, 3) for t in trajectory.harvest_seconds],
                                write_ms=[round(1e3 * t, 3) for t in trajectory.write_seconds])
+                log = getattr(players[path][1], "episode_log", None)
+                if log is not None:
+                    rec.update(rows=int(len(log.rows()["env"])), dropped=log.dropped)
                 lines.append(json.dumps(rec))
                 print(lines[-1], flush=True)
         for _, env in players.values():
             scratch = getattr(getattr(env, "trajectory", None), "directory", None)
+            if getattr(env, "episode_log", None) is not None:
+                scratch = os.path.dirname(env.episode_log.path)
             env.close()
             if scratch:                       # the MAT files of the timed runs are not the result
                 import shutil

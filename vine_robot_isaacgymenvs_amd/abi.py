@@ -424,6 +424,46 @@ def declare_record(lib):
     return lib
 
 
+# ---- include/vine_episodes.h (product library only)
+EPISODES_ABI_VERSION = 1
+EPISODES_WORDS = 16
+EPISODES_THREADS = 256
+# VineEpisodeWord = the 32-bit words of a row
+VEW_ENV, VEW_END_STEP, VEW_LENGTH, VEW_RETURN = 0, 1, 2, 3
+VEW_REACHED_EVER, VEW_REACHED_AT_END, VEW_FIRST_REACH, VEW_FINAL_DIST, VEW_MIN_DIST = 4, 5, 6, 7, 8
+VEW_END_REASON = 9
+VEW_TARGET_Y, VEW_TARGET_Z, VEW_OBJ_DEPTH, VEW_OBJ_ANGLE = 10, 11, 12, 13
+VEW_RESERVED0 = 14
+EPISODES_END_TIMEOUT, EPISODES_END_RAIL_LIMIT, EPISODES_END_TIP_LIMIT, EPISODES_END_CONTACT = 1, 2, 4, 8
+
+
+class VineEpisodesConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("reserved", C.c_int32),
+        ("capacity", C.c_int64),
+    ]
+
+
+EPISODES_PROTOTYPES = {
+    "vine_episodes_config_default": (C.c_int, [_P(VineEpisodesConfig)]),
+    "vine_episodes_config_size": (C.c_int, []),
+    "vine_episodes_rows": (C.c_int, [_H]),
+    "vine_episodes_table_bytes": (C.c_int64, [_P(VineEpisodesConfig)]),
+    "vine_episodes_scheduled": (C.c_int, [_H, _P(VineEpisodesConfig)] + [_VP] * 9),
+}
+
+
+def declare_episodes(lib):
+    for name, (restype, argtypes) in EPISODES_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.vine_episodes_config_size() != C.sizeof(VineEpisodesConfig):
+        raise RuntimeError("VineEpisodesConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     for name, (restype, argtypes) in PPO_PROTOTYPES.items():
         fn = getattr(lib, name)

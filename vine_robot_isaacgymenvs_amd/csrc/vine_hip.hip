@@ -2732,6 +2732,7 @@ int vine_render_info(VineHandle* h, VineRenderInfo* out) {
     out->soft_limit = h->P.soft_limit; out->success_dist = h->P.success_dist;
     return VINE_OK;
 }
+const float* vine_reward_matrix_of(VineHandle* h) { return h ? h->reward_matrix : nullptr; }
 void vine_set_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 
 #ifdef VSQ_TIMING

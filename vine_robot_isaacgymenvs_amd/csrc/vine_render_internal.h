@@ -1,5 +1,5 @@
-// vine_render_internal.h — what vine_render.hip needs of a VineHandle (defined in vine_hip.hip).  Not part of the C ABI:
-// the two functions are hidden symbols of libvine_hip.so.
+// vine_render_internal.h — what vine_render.hip (and the other observers of a step: vine_record.hip, vine_episodes.hip)
+// needs of a VineHandle (defined in vine_hip.hip).  Not part of the C ABI: the functions are hidden symbols of libvine_hip.so.
 #ifndef VINE_RENDER_INTERNAL_H
 #define VINE_RENDER_INTERNAL_H
 
@@ -17,6 +17,7 @@ struct VineRenderInfo {
 
 extern "C" {
 __attribute__((visibility("hidden"))) int vine_render_info(VineHandle* h, VineRenderInfo* out);
+__attribute__((visibility("hidden"))) const float* vine_reward_matrix_of(VineHandle* h);   // the bound [N,13] matrix, or NULL
 __attribute__((visibility("hidden"))) void vine_set_error(const char* msg);    // sets vine_last_error()'s thread-local text
 }
 

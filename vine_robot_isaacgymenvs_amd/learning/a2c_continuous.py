@@ -862,6 +862,8 @@ class A2CAgent(FastInferenceMixin):
                 "step": env.step_count, "rng": torch.cuda.get_rng_state(self.device)}
         if getattr(self, "fused_rollout", False):
             snap["agent"] = [t.clone() for t in (self.meter, self.roll_counter)]
+        if getattr(env, "episode_log", None) is not None:     # EPISODE_LOG: the warm-up pass finishes episodes too
+            snap["episodes"] = [(t, t.clone()) for t in env.episode_log.live_tensors()]
         return snap
 
     def _restore_env(self, snap):
@@ -873,6 +875,8 @@ class A2CAgent(FastInferenceMixin):
         if "agent" in snap:
             self.meter.copy_(snap["agent"][0])
             self.roll_counter.copy_(snap["agent"][1])
+        for t, b in snap.get("episodes", ()):
+            t.copy_(b)
 
     # ------------------------------------------------------------------ dataset (R5)
     def prepare_dataset(self, batch):
@@ -1573,6 +1577,7 @@ class A2CAgent(FastInferenceMixin):
                     print(f"fps step and policy inference: {curr_frames / play_time:.0f} "
                           f"fps total: {curr_frames / sum_time:.0f} epoch: {epoch_num}/{self.max_epochs}")
                 self.write_stats(total_time, epoch_num, play_time, update_time, stats, curr_frames)
+                self.write_episode_stats()
                 if self.algo_observer is not None:
                     env = getattr(self.vec_env, "env", self.vec_env)
                     self.algo_observer.process_infos({k: v for k, v in getattr(env, "extras", {}).items()}, None)
@@ -1611,11 +1616,28 @@ class A2CAgent(FastInferenceMixin):
                 should_exit = bool(flag.item())
             if should_exit:
                 env_ = getattr(self.vec_env, "env", self.vec_env)
-                for side in (getattr(env_, "video", None), getattr(env_, "trajectory", None)):
-                    if side is not None:         # CAPTURE_VIDEO / RECORD_TRAJECTORIES: the last harvested window is on disk
-                        torch.cuda.synchronize(self.device)                                  # when train() returns
+                for side in (getattr(env_, "video", None), getattr(env_, "trajectory", None), getattr(env_, "episode_log", None)):
+                    if side is not None:         # CAPTURE_VIDEO / RECORD_TRAJECTORIES / EPISODE_LOG: what was harvested is on
+                        torch.cuda.synchronize(self.device)                                  # disk when train() returns
                         side.drain()
                 return self.last_mean_rewards, epoch_num
+
+    def write_episode_stats(self):
+        """EPISODE_LOG: ``episodes/<key>`` for the player's ``REPORT_KEYS`` over the episodes finished in this iteration, from
+        the difference of the log's folded float64 totals; a key whose denominator is zero is skipped.  Also the
+        iteration's harvest of the row ring (the host synchronises here anyway)."""
+        log = getattr(getattr(self.vec_env, "env", self.vec_env), "episode_log", None)
+        if log is None:
+            return
+        from .player import eval_report
+        log.harvest()
+        totals = log.folded_totals()
+        prev = getattr(self, "_episode_totals", None)
+        self._episode_totals = totals
+        if self.writer:
+            for k, v in eval_report(totals - prev if prev is not None else totals).items():
+                if v == v:                       # nan: no episode (or none that reached) finished in this iteration
+                    self.writer.add_scalar("episodes/" + k, v, self.frame)
 
     def write_stats(self, total_time, epoch_num, play_time, update_time, stats, curr_frames):
         if not self.writer:

@@ -114,16 +114,44 @@ class PpoPlayerContinuous(FastInferenceMixin):
 
     def _finish(self, mean_r, mean_l, games):
         env = getattr(self.vec_env, "env", self.vec_env)
-        for side in (getattr(env, "video", None), getattr(env, "trajectory", None)):
-            if side is not None:                 # CAPTURE_VIDEO / RECORD_TRAJECTORIES: every harvested window is on disk
-                torch.cuda.synchronize(self.device)                                      # when run() returns
+        for side in (getattr(env, "video", None), getattr(env, "trajectory", None), getattr(env, "episode_log", None)):
+            if side is not None:                 # CAPTURE_VIDEO / RECORD_TRAJECTORIES / EPISODE_LOG: what was harvested is on
+                torch.cuda.synchronize(self.device)                                      # disk when run() returns
                 side.drain()
         print("reward:", mean_r, "steps:", mean_l, "games:", games)
         print(format_report(self.report))
+        if getattr(env, "episode_log", None) is not None and env.episode_log.table is not None:
+            print(self._binned_report(env))
         return mean_r, mean_l
+
+    # ------------------------------------------------------------------ EPISODE_LOG
+    def _episodes_begin(self, env):
+        """The log's totals and the env's step count when a run starts: the run reports the episodes finished since."""
+        log = getattr(env, "episode_log", None)
+        if log is not None:
+            log.harvest()
+            self._episodes_start = (log.folded_totals(), int(env.step_count))
+
+    def _binned_report(self, env, bins=5):
+        """``reached_ever_rate`` of this run's episodes by obstacle depth when an obstacle is configured, else by target z."""
+        from ..utils import episodes
+        rows = env.episode_log.rows()
+        keep = rows["end_step"] >= self._episodes_start[1]
+        rows = {k: v[keep] for k, v in rows.items()}
+        obstacle = bool(env.cfg["env"].get("CREATE_SHELF", False) or env.cfg["env"].get("CREATE_PIPE", False))
+        column = "obj_depth" if obstacle else "target_z"
+        if not len(rows["env"]):
+            return "  reached_ever_rate by %s: no episode finished" % column
+        rate, count, edges = episodes.binned_rate(rows, column, bins)
+        lines = ["  reached_ever_rate by %s:" % column]
+        lines += ["    [%.4g, %.4g%s  %.4g  (%d episodes)" % (edges[i], edges[i + 1], "]" if i == len(rate) - 1 else ")", rate[i],
+                                                            count[i]) for i in range(len(rate))]
+        return "\n".join(lines)
 
     # ------------------------------------------------------------------ stock path
     def _run_stock(self, n_steps):
+        env = getattr(self.vec_env, "env", self.vec_env)
+        self._episodes_begin(env)
         obs = self.vec_env.reset()["obs"].to(self.device)
         n = obs.shape[0]
         cur_r = torch.zeros(n, device=self.device)
@@ -150,6 +178,10 @@ class PpoPlayerContinuous(FastInferenceMixin):
         played = int(games) > 0
         self.report = {"episodes": int(games), "return_mean": mean_r if played else math.nan,
                        "length_mean": mean_l if played else math.nan}
+        log = getattr(env, "episode_log", None)
+        if log is not None:                      # EPISODE_LOG: the task figures of the episodes the log saw finish in this run
+            full = eval_report(log.folded_totals() - self._episodes_start[0])
+            self.report.update({k: full[k] for k in REPORT_KEYS[3:]})
         return self._finish(mean_r, mean_l, int(games))
 
     # ------------------------------------------------------------------ device path
@@ -209,6 +241,8 @@ class PpoPlayerContinuous(FastInferenceMixin):
                 d["dones"]]
         if getattr(env, "trajectory", None) is not None:     # RECORD_TRAJECTORIES: the warm-up pass writes rows too
             live += env.trajectory.live_tensors()
+        if getattr(env, "episode_log", None) is not None:    # EPISODE_LOG: and finishes episodes
+            live += env.episode_log.live_tensors()
         backup = [t.clone() for t in live]
         step, num_steps, rng = env.step_count, env.num_steps, torch.cuda.get_rng_state(self.device)
         video_paused = getattr(env, "video_paused", contextlib.nullcontext)
@@ -237,6 +271,7 @@ class PpoPlayerContinuous(FastInferenceMixin):
     @torch.no_grad()
     def _run_device(self, n_steps):
         env = getattr(self.vec_env, "env", self.vec_env)
+        self._episodes_begin(env)
         d = self._device_buffers(env)
         obs = self.vec_env.reset()["obs"]
         d["slot"] = 0
@@ -249,10 +284,11 @@ class PpoPlayerContinuous(FastInferenceMixin):
         # operand copies of the weights (restore() may have changed them since the last run) and of h
         self._infer_begin()
         self._head_prep(d["hw"], d["hc"])
-        # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph).  RECORD_TRAJECTORIES is: its
-        # launches are captured with the steps, and the host is told of every replay.
+        # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph).  RECORD_TRAJECTORIES and
+        # EPISODE_LOG are: their launches are captured with the steps, and the host is told of every replay.
         graphed = self.graph_steps > 0 and n_steps >= self.graph_steps and getattr(env, "video", None) is None
-        replayed = getattr(env, "video_replayed", None) if getattr(env, "trajectory", None) is not None else None
+        observed = getattr(env, "trajectory", None) is not None or getattr(env, "episode_log", None) is not None
+        replayed = getattr(env, "video_replayed", None) if observed else None
         done = 0
         if graphed:
             if self._eval_graph is None:

@@ -146,7 +146,8 @@ class Vine5LinkMovingBase(VecTask):
             self.logger.info("CREATE_PIPE: the pipe mesh is simulated as its planar cross-section (two walls)")
         self._video = None
         self._trajectory = None
-        self._observers = []       # what rides behind every step: the video capture and the trajectory recorder
+        self._episode_log = None
+        self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log
 
         self._lib = None
         self._handle = None
@@ -183,6 +184,11 @@ class Vine5LinkMovingBase(VecTask):
                 self._setup_trajectory()
             else:
                 self.logger.info("RECORD_TRAJECTORIES: recorded by rank 0 only")
+        if self.cfg["env"].get("EPISODE_LOG", False):
+            if int(os.getenv("LOCAL_RANK", "0")) == 0:
+                self._setup_episode_log()
+            else:
+                self.logger.info("EPISODE_LOG: logged by rank 0 only")
 
     # ------------------------------------------------------------------ CAPTURE_VIDEO (V5:205-221, 1169-1207)
     def _setup_video(self):
@@ -271,6 +277,33 @@ class Vine5LinkMovingBase(VecTask):
         """The ``TrajectoryRecorder`` of this env (``None`` unless ``RECORD_TRAJECTORIES``)."""
         return self._trajectory
 
+    # ------------------------------------------------------------------ EPISODE_LOG (include/vine_episodes.h)
+    def _setup_episode_log(self):
+        """The accumulators, totals and row ring of the per-episode task log; a launch behind every step keeps them, see
+        utils/episodes.py for the harvest and the file.  The log reads the step's reward-matrix row, so a matrix is bound
+        here (arming introspection) before anything is captured; one bound for a dashboard already is shared."""
+        import datetime
+        from ..utils import episodes
+        env = self.cfg["env"]
+        if self._reward_matrix is None:
+            self.bind_reward_matrix()
+        capacity = int(env.get("EPISODE_LOG_CAPACITY", 1048576))
+        directory = env.get("EPISODE_LOG_DIR") or os.path.join("runs", self.cfg["name"])
+        if not hasattr(self, "time_str"):
+            self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+        task = {k: env[k] for k in episodes.TASK_KEYS if k in env}
+        self._episode_log = episodes.EpisodeLog(
+            self._lib, self._handle, self.num_envs, capacity, bool(env.get("EPISODE_LOG_TABLE", True)),
+            (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf), self.device, directory, self.time_str,
+            task, self.logger)
+        self._observers.append(self._episode_log)
+        self.logger.info(f"EPISODE_LOG: one row per finished episode (ring of {capacity}) -> {self._episode_log.path}")
+
+    @property
+    def episode_log(self):
+        """The ``EpisodeLog`` of this env (``None`` unless ``EPISODE_LOG``)."""
+        return self._episode_log
+
     def _observe(self, actions):
         """Behind a step launch: every observer's launch on the same stream, then its host-side count.  ``actions``:
         device address of the action buffer the step consumed."""
@@ -330,7 +363,7 @@ class Vine5LinkMovingBase(VecTask):
             for o in self._observers:
                 o.drain()
                 o.close()
-            self._observers, self._video, self._trajectory = [], None, None
+            self._observers, self._video, self._trajectory, self._episode_log = [], None, None, None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -410,6 +443,8 @@ class Vine5LinkMovingBase(VecTask):
         native.check(self._lib.vine_reset_idx(self._handle, ids.data_ptr(), ids.numel(), self.rew_buf.data_ptr(),
                                               self.reset_buf.data_ptr(), self.progress_buf.data_ptr(), self._stream()),
                      self._lib)
+        if self._episode_log is not None:        # EPISODE_LOG: their running episode is discarded without a row
+            self._episode_log.reset_envs(ids)
 
     # ------------------------------------------------------------------ metrics side channel (V5:1250-1322)
     def collect_stats(self):
@@ -523,6 +558,8 @@ class Vine5LinkMovingBase(VecTask):
     # ------------------------------------------------------------------ test / tooling hooks
     def bind_reward_matrix(self):
         """Ask the kernel to also write the [N,13] unweighted reward matrix (V5:1272) each step."""
+        if self._episode_log is not None:    # EPISODE_LOG reads the matrix it bound at set-up: that one is shared
+            return self._reward_matrix
         self._reward_matrix = torch.zeros((self.num_envs, abi.NUM_REWARDS), device=self.device)
         native.check(self._lib.vine_bind_reward_matrix(self._handle, self._reward_matrix.data_ptr()), self._lib)
         self._introspection = True           # the library arms VINE_FLAG_INTROSPECT together with the matrix

@@ -1,0 +1,241 @@
+"""EPISODE_LOG on the host side: the accumulators, totals and row ring of ``vine_episodes_scheduled``
+(include/vine_episodes.h), the harvest, and the ``.npz`` file.
+
+The rows are written on the device by a launch behind every step (any step entry point, both step kernels): one row per
+finished episode of every env.  ``EpisodeLog`` is a step observer like ``video.VideoCapture`` and
+``trajectory.TrajectoryRecorder`` (``before`` / ``enqueue`` / ``advance`` / ``paused`` / ``copy_done``).  Its harvest reads
+the device cursor and copies the rows appended since the last one; that synchronises, so it runs where the host
+synchronises anyway (once per training iteration, at the end of a player's run) and, inside a long run of steps, whenever
+the worst case -- every env finishing every step -- could have filled half the ring since the last harvest.  Used through
+the task class the ring can therefore never lap unharvested rows; ``dropped`` is kept, logged and stored all the same.
+
+One file per run, ``<dir>/<time_str>_episodes.npz``: the rows sorted by (end step, env) as named columns, the folded
+totals, ``dropped`` and the config keys that define the task.  ``load`` / ``report`` / ``binned_rate`` read it back."""
+import logging
+import math
+import os
+
+import numpy as np
+import torch
+
+from .. import abi, native
+
+# the columns of a harvested row, in the order of the device's 16 words (include/vine_episodes.h); integer words as int64
+COLUMNS = ("env", "end_step", "length", "return", "reached_ever", "reached_at_end", "first_reach", "final_dist", "min_dist",
+           "end_reason", "target_y", "target_z", "obj_depth", "obj_angle")
+INT_COLUMNS = ("env", "end_step", "end_reason")
+TASK_KEYS = ("SUCCESS_DIST", "MIN_TARGET_DEPTH_IN_OBSTACLE", "MAX_TARGET_DEPTH_IN_OBSTACLE", "MIN_TARGET_Y", "MAX_TARGET_Y",
+             "MIN_TARGET_Z", "MAX_TARGET_Z", "RANDOMIZE_TARGETS", "CREATE_SHELF", "CREATE_PIPE", "USE_TARGET_REACHED_RESET",
+             "USE_TIP_LIMIT_HIT_RESET", "USE_NONZERO_CONTACT_FORCE_RESET", "maxEpisodeLength")
+
+
+def episodes_config(lib, capacity):
+    c = abi.VineEpisodesConfig()
+    native.check(lib.vine_episodes_config_default(c), lib)
+    c.capacity = int(capacity)
+    return c
+
+
+def dropped_rows(cursor, harvested, capacity):
+    """Rows the writer lapped before they were copied: ``max(0, cursor - harvested - capacity)``."""
+    return max(0, int(cursor) - int(harvested) - int(capacity))
+
+
+def decode_rows(words):
+    """``words[R, abi.EPISODES_WORDS]`` of 32-bit words as the device wrote them -> dict of columns (``COLUMNS``), sorted by
+    (end step, env).  Float columns keep the device's bits (float32)."""
+    w = np.ascontiguousarray(np.asarray(words).reshape(-1, abi.EPISODES_WORDS)).view(np.uint32)
+    order = np.lexsort((w[:, abi.VEW_ENV].view(np.int32), w[:, abi.VEW_END_STEP].view(np.int32)))
+    w = w[order]
+    rows = {}
+    for k, name in enumerate(COLUMNS):
+        col = np.ascontiguousarray(w[:, k])
+        rows[name] = col.view(np.int32).astype(np.int64) if name in INT_COLUMNS else col.view(np.float32).copy()
+    return rows
+
+
+def concat_rows(parts):
+    """Several ``decode_rows`` results as one, sorted by (end step, env)."""
+    parts = [p for p in parts if len(p["env"])]
+    if not parts:
+        return {name: np.zeros(0, dtype=np.int64 if name in INT_COLUMNS else np.float32) for name in COLUMNS}
+    rows = {name: np.concatenate([p[name] for p in parts]) for name in COLUMNS}
+    order = np.lexsort((rows["env"], rows["end_step"]))
+    return {name: v[order] for name, v in rows.items()}
+
+
+def totals_of(rows):
+    """The twelve totals of ``vine_step_eval`` (abi.EVAL_*) from rows, summed in float64."""
+    t = np.zeros(abi.EVAL_NUM_TOTALS, dtype=np.float64)
+    f64 = lambda name: np.asarray(rows[name], dtype=np.float64)       # noqa: E731
+    reason = np.asarray(rows["end_reason"], dtype=np.int64)
+    t[abi.EVAL_EPISODES] = len(reason)
+    t[abi.EVAL_RETURN_SUM] = f64("return").sum()
+    t[abi.EVAL_LENGTH_SUM] = f64("length").sum()
+    t[abi.EVAL_REACHED_EVER] = f64("reached_ever").sum()
+    t[abi.EVAL_REACHED_AT_END] = f64("reached_at_end").sum()
+    t[abi.EVAL_FIRST_REACH_SUM] = f64("first_reach").sum()
+    t[abi.EVAL_FINAL_DIST_SUM] = f64("final_dist").sum()
+    t[abi.EVAL_MIN_DIST_SUM] = f64("min_dist").sum()
+    for col, bit in ((abi.EVAL_END_TIMEOUT, abi.EPISODES_END_TIMEOUT), (abi.EVAL_END_RAIL_LIMIT, abi.EPISODES_END_RAIL_LIMIT),
+                     (abi.EVAL_END_TIP_LIMIT, abi.EPISODES_END_TIP_LIMIT), (abi.EVAL_END_CONTACT, abi.EPISODES_END_CONTACT)):
+        t[col] = np.count_nonzero(reason & bit)
+    return t
+
+
+def report(rows):
+    """The twelve ``player.REPORT_KEYS`` from rows: ``player.eval_report`` of the rows' totals."""
+    from ..learning.player import eval_report
+    return eval_report(totals_of(rows))
+
+
+def binned_rate(rows, column, bins, of="reached_ever"):
+    """The mean of the 0/1 column ``of`` over the episodes whose ``column`` falls into each bin: ``bins`` as for
+    ``numpy.histogram`` (a count or the edges).  Returns (rate [B] with nan for an empty bin, count [B], edges [B + 1])."""
+    x = np.asarray(rows[column], dtype=np.float64)
+    y = np.asarray(rows[of], dtype=np.float64)
+    count, edges = np.histogram(x, bins=bins)
+    hit, _ = np.histogram(x, bins=edges, weights=y)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rate = np.where(count > 0, hit / count, np.nan)
+    return rate, count, edges
+
+
+def save(path, rows, totals, dropped, task):
+    """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
+    and renamed."""
+    out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    out["totals"] = np.asarray(totals, dtype=np.float64).reshape(-1, abi.EVAL_NUM_TOTALS).sum(axis=0)
+    out["dropped"] = np.array(int(dropped), dtype=np.int64)
+    for k, v in task.items():
+        out["task_" + k] = np.asarray(v)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    part = path + ".part.npz"
+    np.savez(part, **out)                  # not compressed: a player's run() ends here, with millions of rows
+    os.replace(part, path)
+    return path
+
+
+def load(path):
+    """``(rows, totals[12], dropped, task)`` of a file written by ``save``."""
+    with np.load(path) as z:
+        rows = {name: z[name] for name in COLUMNS}
+        task = {k[5:]: z[k][()] for k in z.files if k.startswith("task_")}
+        return rows, z["totals"], int(z["dropped"]), task
+
+
+class EpisodeLog:
+    """The device buffers of one env handle's episode log, the host's count of steps since the last harvest, and the
+    harvest.  Same calls as the other step observers."""
+
+    def __init__(self, lib, handle, num_envs, capacity, with_table, buffers, device, directory, time_str, task, logger=None):
+        """``buffers``: the step's output tensors ``(rew, reset, progress, timeouts)``.  A reward matrix must already be
+        bound to ``handle``."""
+        self.lib, self.handle, self.device, self.num_envs = lib, handle, device, int(num_envs)
+        self.logger = logger or logging.getLogger(__name__)
+        self.ecfg = episodes_config(lib, capacity)
+        self.capacity = int(capacity)
+        nbytes = int(lib.vine_episodes_table_bytes(self.ecfg))
+        if nbytes < 0:
+            native.check(nbytes, lib)
+        rows = int(lib.vine_episodes_rows(handle))
+        if rows < 0:
+            native.check(rows, lib)
+        self.rew, self.reset, self.progress, self.timeouts = buffers
+        self.episode = torch.zeros((abi.EVAL_EPISODE_FIELDS, self.num_envs), dtype=torch.float32, device=device)
+        self.episode[abi.EVAL_EP_MIN_DIST].fill_(math.inf)
+        self.totals = torch.zeros((rows, abi.EVAL_NUM_TOTALS), dtype=torch.float64, device=device)
+        self.table = self.cursor = None
+        if with_table:
+            self.table = torch.zeros((self.capacity, abi.EPISODES_WORDS), dtype=torch.int32, device=device)
+            assert self.table.numel() * 4 == nbytes
+            self.cursor = torch.zeros(1, dtype=torch.int64, device=device)
+        self.path = os.path.join(directory, f"{time_str}_episodes.npz")
+        self.task = dict(task)
+        self.harvested = 0           # the cursor at the last harvest
+        self.dropped = 0
+        self.pending = 0             # steps enqueued since the last harvest
+        self.parts = []              # harvested rows as the device wrote them, in harvest order
+        self._rows = None            # the same decoded and sorted, until the next harvest adds to them
+        self.paused = 0
+        self.copy_done = None        # (the harvest is synchronous: no copy is ever in flight)
+
+    def live_tensors(self):
+        """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
+        ring is not among them: rows are harvested first, and what the rolled-back pass appends lies past the restored
+        cursor, where later rows overwrite it."""
+        self.harvest()
+        return [self.episode, self.totals] + ([self.cursor] if self.cursor is not None else [])
+
+    # -- device side -------------------------------------------------------------------------------------------------
+    def enqueue(self, stream, actions=None):
+        """The accounting of the step just enqueued on ``stream`` (captured with it inside a hipGraph)."""
+        native.check(self.lib.vine_episodes_scheduled(
+            self.handle, self.ecfg, self.rew.data_ptr(), self.reset.data_ptr(), self.progress.data_ptr(),
+            self.timeouts.data_ptr(), self.episode.data_ptr(), self.totals.data_ptr(),
+            self.table.data_ptr() if self.table is not None else None,
+            self.cursor.data_ptr() if self.cursor is not None else None, stream), self.lib)
+
+    def reset_envs(self, env_ids):
+        """The envs were reset from outside the step: their running episode is discarded without a row."""
+        self.episode[:, env_ids] = torch.tensor([0.0, 0.0, math.inf, 0.0], device=self.device).unsqueeze(1)
+
+    # -- host side ---------------------------------------------------------------------------------------------------
+    def set_steps(self, steps):
+        pass                         # the end step of a row is the device's own count
+
+    def _room(self, n_steps):
+        """Could ``n_steps`` more steps, every env finishing in each, pass half the ring?"""
+        return self.num_envs * (self.pending + int(n_steps)) > self.capacity // 2
+
+    def before(self, n_steps):
+        if self.paused or self.table is None or torch.cuda.is_current_stream_capturing():
+            return
+        if self.pending and self._room(n_steps):
+            self.harvest()
+
+    def advance(self, n_steps):
+        if not self.paused:
+            self.pending += int(n_steps)
+
+    def harvest(self):
+        """Copy the rows appended since the last harvest (synchronises with the device).  Returns their number."""
+        self.pending = 0
+        if self.table is None or torch.cuda.is_current_stream_capturing():
+            return 0
+        cursor = int(self.cursor.item())
+        lost = dropped_rows(cursor, self.harvested, self.capacity)
+        if lost:
+            self.dropped += lost
+            self.logger.warning(f"EPISODE_LOG: {lost} rows were overwritten before they were harvested "
+                                f"({self.dropped} in all): raise EPISODE_LOG_CAPACITY")
+        first = max(self.harvested, cursor - self.capacity)
+        self.harvested = cursor
+        if cursor == first:
+            return 0
+        a, b = first % self.capacity, (cursor - 1) % self.capacity + 1
+        words = self.table[a:b] if a < b else torch.cat([self.table[a:], self.table[:b]])
+        self.parts.append(words.cpu().numpy())       # decoded and sorted when somebody asks for rows
+        self._rows = None
+        return cursor - first
+
+    def rows(self):
+        """Every harvested row so far, sorted by (end step, env)."""
+        if self._rows is None:
+            if len(self.parts) > 1:
+                self.parts = [np.concatenate(self.parts)]
+            self._rows = decode_rows(self.parts[0]) if self.parts else concat_rows([])
+        return self._rows
+
+    def folded_totals(self):
+        """The twelve totals, folded over the workgroups' rows in float64 on the host (synchronises)."""
+        return self.totals.cpu().numpy().sum(axis=0)
+
+    def drain(self):
+        """Harvest what is left and (re)write the file."""
+        self.harvest()
+        save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task)
+        self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
+
+    def close(self):
+        pass
