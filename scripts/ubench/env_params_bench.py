@@ -1,0 +1,80 @@
+"""Duration of the one-lane-per-env step with a per-env parameter table (include/vine_env_params.h) against the same kernel
+without one and against the four-lanes-per-env kernel: free space, default observation layout, randomisation on.
+
+Durations come from a replayed hipGraph of K back-to-back steps between two events (elapsed / K): HIP events around eager
+back-to-back launches are host-bound below about 13 us.  The variants are alternated, ROUNDS times, inside one process.
+
+usage: python scripts/ubench/env_params_bench.py [num_envs ...]        (default: 16384 1048576)"""
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
+import torch  # noqa: E402
+
+from tests.helpers import base_cfg  # noqa: E402
+from tests.hip_env import HipEnv  # noqa: E402
+from vine_robot_isaacgymenvs_amd import abi, native  # noqa: E402
+from vine_robot_isaacgymenvs_amd.utils import env_params  # noqa: E402
+
+ROUNDS = 7
+SPEC = {"DAMPING": [0.01, 0.05], "SMOOTHING_ALPHA_INFLATE": [0.6, 0.95], "SMOOTHING_ALPHA_DEFLATE": [0.6, 0.95],
+        "RAIL_VELOCITY_SCALE": [0.7, 1.3], "RAIL_P_GAIN": [7.0, 13.0], "RAIL_D_GAIN": [0.0, 0.4], "RAIL_ACCELERATION": [5.6, 10.4],
+        "ACTION_DELAY": [0, abi.MAX_DELAY], "FPAM_K": [0.8, 1.2], "FPAM_C": [0.8, 1.2], "FPAM_b": [0.8, 1.2], "FPAM_B": [0.8, 1.2]}
+# name -> (VINE_STEP_KERNEL, table: None / "own" (every column the configuration's row) / "het" (SPEC))
+VARIANTS = {"lane": ("lane", None), "lane+own_row_table": ("lane", "own"), "lane+heterogeneous_table": ("lane", "het"),
+            "quad": ("quad", None)}
+
+
+def make(n, kern, table):
+    cfg = base_cfg(n, 0, True)
+    env = type("H", (HipEnv,), {"kernel": kern})(cfg)
+    env.set_introspection(False)
+    if table is not None:
+        t = env_params.build_table(SPEC if table == "het" else {}, env.cfg, 1, n, lib=env.lib)
+        env.table_t = torch.as_tensor(t, device=env.dev).contiguous()
+        torch.cuda.synchronize()
+        native.check(env.lib.vine_bind_env_params(env.h, env.table_t.data_ptr()), env.lib)
+    k = 100 if n <= 65536 else 20
+    g = torch.Generator(device=env.dev).manual_seed(0)
+    acts = [torch.rand((n, 2), device=env.dev, generator=g) * 2 - 1 for _ in range(8)]
+    for i in range(16):                                  # episodes under way, kernels loaded
+        env.step_t(acts[i % 8], sync=False)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        for i in range(k):
+            env.step_t(acts[i % 8], sync=False)
+    graph.replay()
+    torch.cuda.synchronize()
+    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode()
+
+
+def main():
+    for n in [int(a) for a in sys.argv[1:]] or [16384, 1 << 20]:
+        envs = {name: make(n, *v) for name, v in VARIANTS.items()}
+        times = {name: [] for name in VARIANTS}
+        for _ in range(ROUNDS):
+            for name, (env, graph, k, _) in envs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) / k * 1e3)
+        print("num_envs %d, %d rounds alternated, one graph replay of %d steps each (us per step: min / median / max)"
+              % (n, ROUNDS, envs["lane"][2]))
+        for name in VARIANTS:
+            t = times[name]
+            print("  %-26s %-22s %8.1f %8.1f %8.1f" % (name, envs[name][3], min(t), statistics.median(t), max(t)), flush=True)
+        base, het, quad = (statistics.median(times[k]) for k in ("lane", "lane+heterogeneous_table", "quad"))
+        print("  heterogeneous table / unbound one-lane: %.3f   / four-lane: %.3f" % (het / base, het / quad))
+        for env, _, _, _ in envs.values():
+            env.close()
+        del envs
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()

@@ -464,6 +464,48 @@ def declare_episodes(lib):
     return lib
 
 
+# ---- include/vine_env_params.h (product library only)
+# VineEnvParam = rows of the per-env parameter table [VP_COUNT, num_envs]
+(VP_DAMPING, VP_SMOOTHING_ALPHA_INFLATE, VP_SMOOTHING_ALPHA_DEFLATE, VP_RAIL_VELOCITY_SCALE, VP_RAIL_P_GAIN, VP_RAIL_D_GAIN,
+ VP_RAIL_ACCELERATION, VP_ACTION_DELAY) = range(8)
+VP_FPAM_K0, VP_FPAM_C0, VP_FPAM_b0, VP_FPAM_B0 = 8, 13, 18, 23
+VP_COUNT = 28
+# name (the task YAML's key) -> (first row, number of rows)
+ENV_PARAM_ROWS = {
+    "DAMPING": (VP_DAMPING, 1),
+    "SMOOTHING_ALPHA_INFLATE": (VP_SMOOTHING_ALPHA_INFLATE, 1),
+    "SMOOTHING_ALPHA_DEFLATE": (VP_SMOOTHING_ALPHA_DEFLATE, 1),
+    "RAIL_VELOCITY_SCALE": (VP_RAIL_VELOCITY_SCALE, 1),
+    "RAIL_P_GAIN": (VP_RAIL_P_GAIN, 1),
+    "RAIL_D_GAIN": (VP_RAIL_D_GAIN, 1),
+    "RAIL_ACCELERATION": (VP_RAIL_ACCELERATION, 1),
+    "ACTION_DELAY": (VP_ACTION_DELAY, 1),
+    "FPAM_K": (VP_FPAM_K0, NUM_LINKS),
+    "FPAM_C": (VP_FPAM_C0, NUM_LINKS),
+    "FPAM_b": (VP_FPAM_b0, NUM_LINKS),
+    "FPAM_B": (VP_FPAM_B0, NUM_LINKS),
+}
+ENV_PARAM_NAMES = tuple(ENV_PARAM_ROWS)
+# one name per row: the FPAM vectors as NAME[j]
+ENV_PARAM_ROW_NAMES = tuple(name if cnt == 1 else "%s[%d]" % (name, j)
+                            for name, (_, cnt) in ENV_PARAM_ROWS.items() for j in range(cnt))
+
+ENV_PARAMS_PROTOTYPES = {
+    "vine_env_params_row": (C.c_int, [_P(VineConfig), _P(C.c_float)]),
+    "vine_env_params_check": (C.c_int, [_P(VineConfig), _VP, C.c_int]),
+    "vine_bind_env_params": (C.c_int, [_H, _VP]),
+    "vine_env_params_bound": (C.c_int, [_H]),
+}
+
+
+def declare_env_params(lib):
+    for name, (restype, argtypes) in ENV_PARAMS_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    return lib
+
+
 def declare_ppo(lib):
     for name, (restype, argtypes) in PPO_PROTOTYPES.items():
         fn = getattr(lib, name)

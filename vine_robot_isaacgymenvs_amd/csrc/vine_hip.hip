@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "../../include/vine.h"
+#include "../../include/vine_env_params.h"
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
 #include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
 #include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
@@ -901,20 +902,51 @@ __device__ __forceinline__ void tip_fk(const DevParams& P, float y, float vy, co
     tip[0] = ty; tip[1] = tz; tip[2] = tvy; tip[3] = tvz;
 }
 
-template <int OBS_TYPE, bool RANDOMIZE, int OBST>   // OBST bit 0: shelf, bit 1: pipe
-__global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevParams P, float* __restrict__ st,
+// ENV_PARAMS (include/vine_env_params.h): the constants of ONE env = the launch's, with the env's column of the bound table in
+// place of the fields a plant differs by.  28 coalesced loads per lane (112 B per env step beside the step's ~320); the copy
+// is per-lane registers where a field was overridden and stays the kernarg's scalar everywhere else, and everything below
+// the kernel body takes it by `const DevParams&` as it takes the launch's.  The 20 FPAM constants are held in registers
+// across the control iterations (re-reading them per iteration needs no fewer registers).  The delay
+// indexes the env's own FIFO ring and is clamped to the ring, whatever the table holds.
+__device__ __forceinline__ void env_params_of(const DevParams& P, const float* __restrict__ tab, int n, int e, DevParams& Q) {
+    Q = P;
+#define EP(p) tab[(size_t)(p) * n + e]
+    Q.damping = EP(VP_DAMPING);
+    Q.alpha_inf = EP(VP_SMOOTHING_ALPHA_INFLATE);
+    Q.alpha_def = EP(VP_SMOOTHING_ALPHA_DEFLATE);
+    Q.rail_scale = EP(VP_RAIL_VELOCITY_SCALE);
+    Q.p_gain = EP(VP_RAIL_P_GAIN);
+    Q.d_gain = EP(VP_RAIL_D_GAIN);
+    Q.rail_acc = EP(VP_RAIL_ACCELERATION);
+    Q.delay = min(max((int)EP(VP_ACTION_DELAY), 0), VINE_MAX_DELAY);
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+        Q.K[j] = EP(VP_FPAM_K0 + j);
+        Q.C[j] = EP(VP_FPAM_C0 + j);
+        Q.bb[j] = EP(VP_FPAM_b0 + j);
+        Q.B[j] = EP(VP_FPAM_B0 + j);
+    }
+#undef EP
+}
+
+template <int OBS_TYPE, bool RANDOMIZE, int OBST, bool ENV_PARAMS = false>   // OBST bit 0: shelf, bit 1: pipe
+__global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevParams PK, float* __restrict__ st,
                                                        const float* __restrict__ actions, float* __restrict__ obs,
                                                        float* __restrict__ rew, long long* __restrict__ reset,
                                                        long long* __restrict__ progress,
                                                        unsigned char* __restrict__ timeouts,
                                                        float* __restrict__ reward_matrix,
                                                        const float* __restrict__ reset_values,
-                                                       unsigned long long* __restrict__ counters) {
+                                                       unsigned long long* __restrict__ counters,
+                                                       const float* __restrict__ env_params) {
     constexpr bool SHELF = (OBST & 1) != 0, PIPE = (OBST & 2) != 0, CONTACT = OBST != 0;
-    const int n = P.n;
+    const int n = PK.n;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long step = step_of(P, counters);
+    const unsigned long long step = step_of(PK, counters);
     if (e < n) {
+        DevParams PL;                                  // ENV_PARAMS: this env's constants; otherwise never touched
+        if constexpr (ENV_PARAMS) env_params_of(PK, env_params, n, e, PL);
+        const DevParams& P = ENV_PARAMS ? PL : PK;
         // ---- VecTask.step: clamp actions (vec_task.py:333); pre_physics_step (V5:922-945) ----
         const float2 act = reinterpret_cast<const float2*>(actions)[e];
         float n0 = 0.0f, n1 = 0.0f;
@@ -2272,6 +2304,7 @@ struct VineHandle {
     unsigned long long* counters;  // [0] step-count base, [1] finished workgroups of step launches since (step_of)
     const float* reset_values;
     float* reward_matrix;
+    const float* env_params;       // bound per-env parameter table (include/vine_env_params.h) or NULL
     bool refresh_body;             // introspection was switched on since the last step: the next vine_step refreshes the lazily
                                    // stored tip / cart body states first (vine_refresh_body_kernel)
     int step_kernel;               // 0 = by size, 1 = one lane per env, 2 = four lanes per env where it applies (VINE_STEP_KERNEL)
@@ -2310,7 +2343,8 @@ bool use_quad_kernel(const VineHandle* h) {
     const bool quad_ok = h->P.cfi == 4 && (h->P.flags & VINE_FLAG_IMPLICIT_JOINT_DAMPING) && h->P.kq == 0.0f &&
                          h->P.cad == 0.0f && (h->P.obs_type == VINE_OBS_POS_AND_FD_VEL_AND_OBJ_INFO ||
                                               h->P.obs_type == VINE_OBS_TIP_AND_CART_AND_OBJ_INFO);
-    return quad_ok && (h->step_kernel == 2 || (h->step_kernel == 0 && h->P.n <= 16384));
+    // (a per-env parameter table is read by the one-lane kernel only)
+    return quad_ok && !h->env_params && (h->step_kernel == 2 || (h->step_kernel == 0 && h->P.n <= 16384));
 }
 
 // log2 of the step launch's grid: the workgroups the kernel needs, rounded up to a power of two (see step_of(); the
@@ -2324,9 +2358,9 @@ int step_grid_log2(const VineHandle* h) {
 }
 
 // What precedes a step launch: the step count re-based on the grid size if the kernel choice changed since the counters
-// were last normalised (it cannot with the present switches, all of which are fixed at creation), and the lazily stored
-// body states refreshed if introspection was switched on since the last step.
-int prepare_step_launch(VineHandle* h, const int64_t* progress, hipStream_t s) {
+// were last normalised (binding or unbinding a per-env parameter table changes it, and re-bases at once), and the lazily
+// stored body states refreshed if introspection was switched on since the last step.
+int rebase_step_count(VineHandle* h) {
     if (step_grid_log2(h) != h->P.glog) {
         const int64_t now = vine_get_step_count(h);
         if (now < 0) return fail(VINE_ERR_DEVICE, "step count unreadable");
@@ -2334,6 +2368,11 @@ int prepare_step_launch(VineHandle* h, const int64_t* progress, hipStream_t s) {
         const int rc = vine_set_step_count(h, now);
         if (rc != VINE_OK) return rc;
     }
+    return VINE_OK;
+}
+int prepare_step_launch(VineHandle* h, const int64_t* progress, hipStream_t s) {
+    const int rb = rebase_step_count(h);
+    if (rb != VINE_OK) return rb;
     if (h->refresh_body) {
         h->refresh_body = false;
         hipLaunchKernelGGL(vine_refresh_body_kernel, dim3((h->P.n + 255) / 256), dim3(256), 0, s, h->P, h->state,
@@ -2477,6 +2516,7 @@ int vine_create(const VineConfig* cfg, int device_id, float* state_storage, Vine
     make_params(*cfg, h->P);
     h->reset_values = nullptr;
     h->reward_matrix = nullptr;
+    h->env_params = nullptr;
     h->stats_psum = nullptr;
     h->stats_pmax = nullptr;
     h->step_kernel = 0;
@@ -2531,10 +2571,15 @@ int vine_step(VineHandle* h, const float* actions, float* obs, float* rew, int64
         launch_quad_step<STEP_PLAIN>(h, actions, obs, rew, reset, progress, timeouts, RollArgs{}, s);
     } else {
         with_step_instantiation(h, [&](auto ot, auto rn, auto ob) {
-            hipLaunchKernelGGL((vine_step_kernel<decltype(ot)::value, decltype(rn)::value, decltype(ob)::value>),
-                               dim3(1 << h->P.glog), dim3(VINE_STEP_THREADS), 0, s, h->P, h->state, actions, obs, rew,
-                               (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,
-                               h->reset_values, h->counters);
+            auto launch = [&](auto ep) {
+                hipLaunchKernelGGL((vine_step_kernel<decltype(ot)::value, decltype(rn)::value, decltype(ob)::value,
+                                                     decltype(ep)::value>),
+                                   dim3(1 << h->P.glog), dim3(VINE_STEP_THREADS), 0, s, h->P, h->state, actions, obs, rew,
+                                   (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,
+                                   h->reset_values, h->counters, h->env_params);
+            };
+            if (h->env_params) launch(std::true_type{});
+            else launch(std::false_type{});
         });
     }
     HIP_TRY(hipGetLastError());
@@ -2657,6 +2702,63 @@ int vine_bind_reset_values(VineHandle* h, const float* values) {
     h->reset_values = values;
     return VINE_OK;
 }
+
+// ---- include/vine_env_params.h
+namespace {
+const char* const kEnvParamNames[VP_COUNT] = {
+    "DAMPING", "SMOOTHING_ALPHA_INFLATE", "SMOOTHING_ALPHA_DEFLATE", "RAIL_VELOCITY_SCALE", "RAIL_P_GAIN", "RAIL_D_GAIN",
+    "RAIL_ACCELERATION", "ACTION_DELAY",
+    "FPAM_K[0]", "FPAM_K[1]", "FPAM_K[2]", "FPAM_K[3]", "FPAM_K[4]", "FPAM_C[0]", "FPAM_C[1]", "FPAM_C[2]", "FPAM_C[3]", "FPAM_C[4]",
+    "FPAM_b[0]", "FPAM_b[1]", "FPAM_b[2]", "FPAM_b[3]", "FPAM_b[4]", "FPAM_B[0]", "FPAM_B[1]", "FPAM_B[2]", "FPAM_B[3]", "FPAM_B[4]"};
+int bad_env_param(int p, int e, float v, const char* why) {
+    snprintf(g_err, sizeof g_err, "env params: %s of env %d is %g: %s", kEnvParamNames[p], e, (double)v, why);
+    return VINE_ERR_INVALID_ARG;
+}
+}  // namespace
+
+int vine_env_params_row(const VineConfig* c, float row[VP_COUNT]) {
+    if (!c || !row) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_env_params_row");
+    row[VP_DAMPING] = c->damping;
+    row[VP_SMOOTHING_ALPHA_INFLATE] = c->smoothing_alpha_inflate;
+    row[VP_SMOOTHING_ALPHA_DEFLATE] = c->smoothing_alpha_deflate;
+    row[VP_RAIL_VELOCITY_SCALE] = c->rail_velocity_scale;
+    row[VP_RAIL_P_GAIN] = c->rail_p_gain;
+    row[VP_RAIL_D_GAIN] = c->rail_d_gain;
+    row[VP_RAIL_ACCELERATION] = c->rail_acceleration;
+    row[VP_ACTION_DELAY] = (float)c->action_delay;
+    for (int j = 0; j < NL; ++j) {
+        row[VP_FPAM_K0 + j] = c->fpam_K[j];
+        row[VP_FPAM_C0 + j] = c->fpam_C[j];
+        row[VP_FPAM_b0 + j] = c->fpam_b[j];
+        row[VP_FPAM_B0 + j] = c->fpam_B[j];
+    }
+    return VINE_OK;
+}
+
+int vine_env_params_check(const VineConfig*, const float* t, int num_envs) {
+    if (!t || num_envs <= 0) return fail(VINE_ERR_INVALID_ARG, "null table or no envs in vine_env_params_check");
+    for (int p = 0; p < VP_COUNT; ++p) {
+        for (int e = 0; e < num_envs; ++e) {
+            const float v = t[(size_t)p * num_envs + e];
+            if (!std::isfinite(v)) return bad_env_param(p, e, v, "not finite");
+            if ((p == VP_SMOOTHING_ALPHA_INFLATE || p == VP_SMOOTHING_ALPHA_DEFLATE) && (v < 0.0f || v > 1.0f))
+                return bad_env_param(p, e, v, "outside [0, 1]");
+            if (p == VP_RAIL_ACCELERATION && v < 0.0f) return bad_env_param(p, e, v, "negative");
+            if (p == VP_ACTION_DELAY && (v < 0.0f || v > (float)VINE_MAX_DELAY || v != std::floor(v)))
+                return bad_env_param(p, e, v, "not an integer in [0, VINE_MAX_DELAY]");
+        }
+    }
+    return VINE_OK;
+}
+
+int vine_bind_env_params(VineHandle* h, const float* device_table) {
+    if (!h) return fail(VINE_ERR_INVALID_ARG, "handle is NULL");
+    h->env_params = device_table;
+    // the table decides between the two step kernels, whose grids differ: re-base the step count here, outside any capture
+    return rebase_step_count(h);
+}
+
+int vine_env_params_bound(VineHandle* h) { return (h && h->env_params) ? 1 : 0; }
 
 int vine_bind_reward_matrix(VineHandle* h, float* reward_matrix) {
     if (!h) return fail(VINE_ERR_INVALID_ARG, "handle is NULL");

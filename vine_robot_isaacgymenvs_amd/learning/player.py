@@ -122,6 +122,8 @@ class PpoPlayerContinuous(FastInferenceMixin):
         print(format_report(self.report))
         if getattr(env, "episode_log", None) is not None and env.episode_log.table is not None:
             print(self._binned_report(env))
+            if getattr(env, "env_params", None) is not None:     # ENV_PARAMS: the same rate against every varying parameter
+                print(self._param_report(env))
         return mean_r, mean_l
 
     # ------------------------------------------------------------------ EPISODE_LOG
@@ -146,6 +148,35 @@ class PpoPlayerContinuous(FastInferenceMixin):
         lines = ["  reached_ever_rate by %s:" % column]
         lines += ["    [%.4g, %.4g%s  %.4g  (%d episodes)" % (edges[i], edges[i + 1], "]" if i == len(rate) - 1 else ")", rate[i],
                                                             count[i]) for i in range(len(rate))]
+        return "\n".join(lines)
+
+    def _param_report(self, env, bins=5, exact=16):
+        """``reached_ever_rate`` of this run's episodes by every parameter of the bound per-env table that varies across
+        the envs: by exact value where the envs hold at most ``exact`` distinct ones (a ``values`` entry of ``ENV_PARAMS``),
+        else by bin.  Also kept in ``self.report["by_param"]``: name -> (values or bin edges, rate, episode count)."""
+        from ..utils import episodes
+        rows = env.episode_log.rows()
+        keep = rows["end_step"] >= self._episodes_start[1]
+        rows = {k: v[keep] for k, v in rows.items()}
+        table = env.env_params_of(range(int(env.num_envs)))
+        rows = episodes.with_env_params(rows, table, env.env_param_names)
+        by_param, lines = {}, []
+        for column in [k for k in rows if k.startswith("param_")]:
+            lines.append("  reached_ever_rate by %s:" % column)
+            first = abi.ENV_PARAM_ROWS[column[6:]][0]
+            if not len(rows["env"]):
+                lines[-1] += " no episode finished"
+                continue
+            if len(np.unique(table[first])) <= exact:
+                values, rate, count = episodes.value_rate(rows, column)
+                by_param[column] = (values, rate, count)
+                lines += ["    %.6g  %.4g  (%d episodes)" % (values[i], rate[i], count[i]) for i in range(len(values))]
+            else:
+                rate, count, edges = episodes.binned_rate(rows, column, bins)
+                by_param[column] = (edges, rate, count)
+                lines += ["    [%.4g, %.4g%s  %.4g  (%d episodes)" % (edges[i], edges[i + 1], "]" if i == len(rate) - 1 else ")",
+                                                                    rate[i], count[i]) for i in range(len(rate))]
+        self.report["by_param"] = by_param
         return "\n".join(lines)
 
     # ------------------------------------------------------------------ stock path

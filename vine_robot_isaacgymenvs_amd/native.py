@@ -22,7 +22,8 @@ ARCH = "gfx950"
 FINGERPRINT = LIB + ".fingerprint"
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HEADERS = [os.path.join(_INC, "vine.h"), os.path.join(_INC, "vine_ppo.h"), os.path.join(_INC, "vine_render.h"),
-            os.path.join(_INC, "vine_record.h"), os.path.join(_INC, "vine_episodes.h"), os.path.join(_HERE, "csrc", "vine_geometry.h"), os.path.join(_HERE, "csrc", "vine_render_internal.h"),
+            os.path.join(_INC, "vine_record.h"), os.path.join(_INC, "vine_episodes.h"), os.path.join(_INC, "vine_env_params.h"),
+            os.path.join(_HERE, "csrc", "vine_geometry.h"), os.path.join(_HERE, "csrc", "vine_render_internal.h"),
             os.path.join(_HERE, "csrc", "vine_policy_head.h"), os.path.join(_HERE, "csrc", "vine_ppo_formulas.h")]
 DEPS = [SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES] + _HEADERS
 
@@ -109,7 +110,7 @@ def load():
     if _lib is None and os.environ.get("VINE_HIP_LIB"):
         # experiments only (A/B builds of the kernels with other compile flags): load exactly this file
         import torch  # noqa: F401
-        _lib = abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(os.environ["VINE_HIP_LIB"]))))))
+        _lib = abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(os.environ["VINE_HIP_LIB"])))))))
         return _lib
     if _lib is None:
         # PyTorch-ROCm ships its own libamdhip64.so.7; it must be the HIP runtime of the process, so it is
@@ -131,7 +132,7 @@ def load():
                         build()
             else:
                 raise RuntimeError("libvine_hip.so was built from different sources and no hipcc is available")
-        _lib = abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(LIB))))))
+        _lib = abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(LIB)))))))
     return _lib
 
 

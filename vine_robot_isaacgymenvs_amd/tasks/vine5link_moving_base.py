@@ -268,6 +268,8 @@ class Vine5LinkMovingBase(VecTask):
         self._trajectory = trajectory.TrajectoryRecorder(
             self._lib, self._handle, rcfg, envs, (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf),
             self.device, directory, self.time_str, self.control_dt, self.logger)
+        if self.env_params is not None:          # ENV_PARAMS: a recording says which plant produced it
+            self._trajectory.env_params_of, self._trajectory.env_param_names = self.env_params_of, self.env_param_names
         self._observers.append(self._trajectory)
         self.logger.info(f"RECORD_TRAJECTORIES: {steps} steps of env(s) {envs} every {every} steps -> "
                          f"{directory}/{self.time_str}_trajectory_<num_steps>_env<e>.mat")
@@ -296,6 +298,8 @@ class Vine5LinkMovingBase(VecTask):
             self._lib, self._handle, self.num_envs, capacity, bool(env.get("EPISODE_LOG_TABLE", True)),
             (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf), self.device, directory, self.time_str,
             task, self.logger)
+        if self.env_params is not None:          # ENV_PARAMS: the file holds the table its env column indexes
+            self._episode_log.env_params_of, self._episode_log.env_param_names = self.env_params_of, self.env_param_names
         self._observers.append(self._episode_log)
         self.logger.info(f"EPISODE_LOG: one row per finished episode (ring of {capacity}) -> {self._episode_log.path}")
 
@@ -356,6 +360,68 @@ class Vine5LinkMovingBase(VecTask):
         native.check(self._lib.vine_create(C.byref(self._vcfg), self.device_id, self._state.data_ptr(), C.byref(h)),
                      self._lib)
         self._handle = h
+        self.env_params = None                   # ENV_PARAMS: the bound device table [VP_COUNT, N], else None
+        self.env_param_names = abi.ENV_PARAM_ROW_NAMES
+        self._env_params_host = None             # its host mirror (numpy), what the checks run on
+        spec = self.cfg["env"].get("ENV_PARAMS") or {}
+        if len(spec):
+            self._setup_env_params(spec)
+
+    # ------------------------------------------------------------------ ENV_PARAMS (include/vine_env_params.h)
+    def _setup_env_params(self, spec):
+        """The per-env parameter table of the spec (utils/env_params.py), checked on the host, uploaded and bound: from
+        here on every env steps with its own column, on the one-lane-per-env kernel."""
+        from ..utils import env_params
+        before = self.step_kernel_name
+        table = env_params.build_table(spec, self._vcfg, int(self._vcfg.seed), self.num_envs, int(self._vcfg.env_id_offset),
+                                       lib=self._lib)
+        self._env_params_host = table
+        self.env_params = torch.as_tensor(table, device=self.device).contiguous()
+        torch.cuda.synchronize(self.device)
+        native.check(self._lib.vine_bind_env_params(self._handle, self.env_params.data_ptr()), self._lib)
+        varying = [self.env_param_names[p] for p in env_params.varying_rows(table)]
+        self.logger.info(f"ENV_PARAMS: {len(varying)} of {abi.VP_COUNT} table rows vary across the {self.num_envs} envs "
+                         f"({', '.join(varying) or 'none'}); step kernel {before} -> {self.step_kernel_name}")
+
+    def set_env_params(self, values):
+        """Rewrite rows of the bound table in place: ``values`` maps a name to a scalar or an array [N].  Names are
+        ``abi.ENV_PARAM_NAMES`` -- an FPAM vector's value is a factor on the configuration's five constants, as in the
+        ``ENV_PARAMS`` spec -- or a single row of ``env_param_names`` (``"FPAM_K[2]"``: the constant itself).  The new table
+        is checked on the host first; a captured hipGraph reads the new contents at its next replay.  Not inside a graph
+        capture."""
+        import numpy as np
+        from ..utils import env_params
+        if self.env_params is None:
+            raise RuntimeError("set_env_params(): no per-env parameter table is bound (task.env.ENV_PARAMS is empty)")
+        table = self._env_params_host.copy()
+        base = env_params.config_row(self._lib, self._vcfg)
+        rows = []
+        for name, v in values.items():
+            v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != self.num_envs):
+                raise ValueError(f"set_env_params: {name} takes a scalar or an array [{self.num_envs}], not {v.shape}")
+            if name in abi.ENV_PARAM_ROWS:
+                first, count = abi.ENV_PARAM_ROWS[name]
+                for p in range(first, first + count):
+                    table[p] = (v if count == 1 else base[p].astype(np.float64) * v).astype(np.float32)
+                    rows.append(p)
+            elif name in self.env_param_names:
+                p = self.env_param_names.index(name)
+                table[p] = v.astype(np.float32)
+                rows.append(p)
+            else:
+                raise ValueError(f"set_env_params: unknown parameter {name!r}")
+        env_params.check_table(self._lib, self._vcfg, table)
+        for p in rows:
+            self.env_params[p].copy_(torch.from_numpy(table[p]))
+        self._env_params_host = table
+
+    def env_params_of(self, envs):
+        """The host mirror's columns of ``envs`` as float64 [VP_COUNT, len(envs)] (``None`` without a bound table)."""
+        import numpy as np
+        if self._env_params_host is None:
+            return None
+        return self._env_params_host[:, list(envs)].astype(np.float64)
 
     def close(self):
         if self._observers:

@@ -1,0 +1,154 @@
+"""ENV_PARAMS on the host side: the per-env parameter table of ``vine_bind_env_params`` (include/vine_env_params.h) from a
+spec in the task config.
+
+``task.env.ENV_PARAMS`` maps a parameter name (``abi.ENV_PARAM_NAMES``: the task YAML's own keys) to one of
+
+  a number               every env gets it;
+  ``[lo, hi]``           uniform per env (for ``ACTION_DELAY``: over the integers lo..hi, both ends included);
+  ``{values: [v0, ..]}`` env ``g`` gets ``values[digit]``: the ``values`` entries of a spec together count ``g`` in a mixed
+                         radix, the first entry being the fastest digit, so every combination recurs every ``prod(len)`` envs.
+
+A name that is absent keeps the configuration's value (``vine_env_params_row``).  The four FPAM vectors (``FPAM_K``, ``FPAM_C``,
+``FPAM_b``, ``FPAM_B``) take all three forms as a FACTOR on the configuration's five constants, which differ by design.
+
+What env ``g`` gets depends on ``(seed, name, g)`` with ``g`` the GLOBAL env id (``env_id_offset`` + local index), never on
+the batch size: a rank's shard equals its slice of the whole batch, the rule the step's own random streams follow."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+
+from .. import abi
+from .config import ConfigError
+
+def _mix(x):
+    """splitmix64's finaliser on uint64 arrays."""
+    x = np.asarray(x, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def uniform01(seed, name, gids):
+    """One float64 in [0, 1) per global env id, a pure function of ``(seed, name, id)``."""
+    key = int.from_bytes(hashlib.sha256(name.encode()).digest()[:8], "little")
+    g = np.asarray(gids, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix(_mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(key)) + g * np.uint64(0x9E3779B97F4A7C15))
+    return (h >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def config_row(lib, vcfg):
+    """``vine_env_params_row``: the configuration's own value of every row, float32 [VP_COUNT]."""
+    row = (C.c_float * abi.VP_COUNT)()
+    rc = lib.vine_env_params_row(C.byref(vcfg), row)
+    if rc != abi.OK:
+        raise ValueError(lib.vine_last_error().decode(errors="replace"))
+    return np.array(row, dtype=np.float32)
+
+
+def check_table(lib, vcfg, table):
+    """``vine_env_params_check`` on a host table [VP_COUNT, N]; raises ``ValueError`` naming the parameter and the env."""
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if t.ndim != 2 or t.shape[0] != abi.VP_COUNT or t.shape[1] < 1:
+        raise ValueError("env params: the table must be [%d, num_envs], not %s" % (abi.VP_COUNT, t.shape))
+    rc = lib.vine_env_params_check(C.byref(vcfg) if vcfg is not None else None, t.ctypes.data, t.shape[1])
+    if rc != abi.OK:
+        raise ValueError(lib.vine_last_error().decode(errors="replace"))
+    return t
+
+
+def _number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ConfigError("ENV_PARAMS.%s: %r is not a number" % (name, v))
+    return float(v)
+
+
+def _form(name, entry):
+    """('scalar', v) / ('range', lo, hi) / ('values', [..])."""
+    if hasattr(entry, "keys"):
+        if list(entry.keys()) != ["values"]:
+            raise ConfigError("ENV_PARAMS.%s: a mapping must hold the one key 'values', not %s" % (name, sorted(entry.keys())))
+        vals = entry["values"]
+        if not isinstance(vals, (list, tuple)) or len(vals) == 0:
+            raise ConfigError("ENV_PARAMS.%s: 'values' must be a non-empty list" % name)
+        return ("values", [_number(name, v) for v in vals])
+    if isinstance(entry, (list, tuple)):
+        if len(entry) != 2:
+            raise ConfigError("ENV_PARAMS.%s: a range is [lo, hi], not %r" % (name, list(entry)))
+        lo, hi = _number(name, entry[0]), _number(name, entry[1])
+        if lo > hi:
+            raise ConfigError("ENV_PARAMS.%s: lo > hi in [%g, %g]" % (name, lo, hi))
+        return ("range", lo, hi)
+    return ("scalar", _number(name, entry))
+
+
+def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
+    """The table float32 [VP_COUNT, num_envs] of the envs with global ids ``env_id_offset .. env_id_offset + num_envs - 1``
+    (see the module's docstring for ``spec``).  ``vcfg``: the handle's ``abi.VineConfig``.  Raises ``ConfigError`` for an
+    unknown name or a malformed entry and ``ValueError`` for a value ``vine_env_params_check`` refuses."""
+    if lib is None:
+        from .. import native
+        lib = native.load()
+    num_envs = int(num_envs)
+    if num_envs < 1:
+        raise ValueError("ENV_PARAMS: num_envs must be positive")
+    spec = spec or {}
+    if not hasattr(spec, "keys"):
+        raise ConfigError("ENV_PARAMS must be a mapping of parameter names, not %r" % (spec,))
+    for name in spec.keys():
+        if name not in abi.ENV_PARAM_ROWS:
+            raise ConfigError("ENV_PARAMS: unknown parameter %r (known: %s)" % (name, ", ".join(abi.ENV_PARAM_NAMES)))
+    base = config_row(lib, vcfg)
+    table = np.repeat(base[:, None], num_envs, axis=1)
+    gids = np.arange(num_envs, dtype=np.int64) + int(env_id_offset)
+    radix = 1                                     # product of the lengths of the `values` entries before this one
+    forms = {name: _form(name, spec[name]) for name in spec.keys()}
+    f = forms.get("ACTION_DELAY")
+    if f is not None and f[0] == "range" and (f[1] != np.floor(f[1]) or f[2] != np.floor(f[2])):
+        raise ConfigError("ENV_PARAMS.ACTION_DELAY: an integer parameter takes an integer range, not [%g, %g]" % (f[1], f[2]))
+    # what the spec CAN give an env is checked whatever this batch happens to draw: both ends of a range, every value
+    cand = {name: list(f[1]) if f[0] == "values" else list(f[1:]) for name, f in forms.items()}
+    width = max([len(c) for c in cand.values()] + [1])
+    probe = np.repeat(base[:, None], width, axis=1)
+    for name, c in cand.items():
+        first, count = abi.ENV_PARAM_ROWS[name]
+        v = np.asarray([c[i % len(c)] for i in range(width)], dtype=np.float64)
+        probe[first:first + count] = (v[None, :] * (base[first:first + count, None].astype(np.float64) if count > 1 else 1.0)
+                                      ).astype(np.float32)
+    try:
+        check_table(lib, vcfg, probe)
+    except ValueError as e:
+        raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
+    for name in spec.keys():
+        form = forms[name]
+        integer = name == "ACTION_DELAY"
+        if form[0] == "scalar":
+            v = np.full(num_envs, form[1], dtype=np.float64)
+        elif form[0] == "range":
+            lo, hi = form[1], form[2]
+            u = uniform01(seed, name, gids)
+            if integer:
+                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
+            else:
+                v = lo + (hi - lo) * u
+        else:
+            vals = np.asarray(form[1], dtype=np.float64)
+            v = vals[(gids // radix) % len(vals)]
+            radix *= len(vals)
+        first, count = abi.ENV_PARAM_ROWS[name]
+        if count == 1:
+            table[first] = v.astype(np.float32)
+        else:                                     # an FPAM vector: a factor on the configuration's five constants
+            table[first:first + count] = (base[first:first + count, None].astype(np.float64) * v[None, :]).astype(np.float32)
+    try:
+        return check_table(lib, vcfg, table)
+    except ValueError as e:
+        raise ValueError("ENV_PARAMS: %s" % e) from None
+
+
+def varying_rows(table):
+    """Indices of the rows whose values differ across envs."""
+    t = np.asarray(table)
+    return [p for p in range(t.shape[0]) if np.any(t[p] != t[p, 0])]

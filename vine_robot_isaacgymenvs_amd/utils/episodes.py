@@ -101,10 +101,37 @@ def binned_rate(rows, column, bins, of="reached_ever"):
     return rate, count, edges
 
 
-def save(path, rows, totals, dropped, task):
+def with_env_params(rows, table, names):
+    """``rows`` with one more column per parameter that varies across the envs of ``table`` ([VP_COUNT, N], the bound per-env
+    parameter table; ``names``: one per table row, ``abi.ENV_PARAM_ROW_NAMES``): ``param_<NAME>`` = the value of the row's
+    env, an FPAM vector reduced to joint 0's value (``param_FPAM_K``).  ``binned_rate`` works on them like on any column."""
+    t = np.asarray(table)
+    env = np.asarray(rows["env"], dtype=np.int64)
+    out = dict(rows)
+    for name, (first, count) in abi.ENV_PARAM_ROWS.items():
+        if any(np.any(t[p] != t[p, 0]) for p in range(first, first + count)):
+            assert names[first] == (name if count == 1 else name + "[0]"), (names[first], name)
+            out["param_" + name] = t[first][env]
+    return out
+
+
+def value_rate(rows, column, of="reached_ever"):
+    """The mean of the 0/1 column ``of`` over the episodes of each distinct value of ``column``: (values [V] ascending,
+    rate [V], count [V])."""
+    x = np.asarray(rows[column], dtype=np.float64)
+    y = np.asarray(rows[of], dtype=np.float64)
+    values, inverse, count = np.unique(x, return_inverse=True, return_counts=True)
+    hit = np.bincount(inverse, weights=y, minlength=len(values))
+    return values, hit / np.maximum(count, 1), count
+
+
+def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
-    and renamed."""
+    and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if env_params is not None:
+        out["env_params"] = np.asarray(env_params, dtype=np.float32)
+        out["env_param_names"] = np.array(list(env_param_names))
     out["totals"] = np.asarray(totals, dtype=np.float64).reshape(-1, abi.EVAL_NUM_TOTALS).sum(axis=0)
     out["dropped"] = np.array(int(dropped), dtype=np.int64)
     for k, v in task.items():
@@ -122,6 +149,14 @@ def load(path):
         rows = {name: z[name] for name in COLUMNS}
         task = {k[5:]: z[k][()] for k in z.files if k.startswith("task_")}
         return rows, z["totals"], int(z["dropped"]), task
+
+
+def load_env_params(path):
+    """``(table [VP_COUNT, N], names)`` of a file written with a bound per-env parameter table, else ``(None, None)``."""
+    with np.load(path) as z:
+        if "env_params" not in z.files:
+            return None, None
+        return z["env_params"], [str(n) for n in z["env_param_names"]]
 
 
 class EpisodeLog:
@@ -159,6 +194,7 @@ class EpisodeLog:
         self._rows = None            # the same decoded and sorted, until the next harvest adds to them
         self.paused = 0
         self.copy_done = None        # (the harvest is synchronous: no copy is ever in flight)
+        self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -234,7 +270,8 @@ class EpisodeLog:
     def drain(self):
         """Harvest what is left and (re)write the file."""
         self.harvest()
-        save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task)
+        table = self.env_params_of(range(self.num_envs)) if self.env_params_of is not None else None
+        save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -32,9 +32,10 @@ def record_config(lib, every, steps, num_envs):
     return c
 
 
-def trajectory_arrays(rows, steps, control_dt, env=0):
+def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param_names=None):
     """The MAT file's variables from the rows of ONE env, ``rows[T, abi.RECORD_FIELDS]`` float32, and the step index of
-    every row.  The reference's six keys (V5:281-297) hold positions as (3, T) with a zero x row: the scene is the y-z
+    every row (with ``env_params``, the env's column of a bound per-env parameter table, also ``env_params`` (VP_COUNT, 1)
+    and ``env_param_names``).  The reference's six keys (V5:281-297) hold positions as (3, T) with a zero x row: the scene is the y-z
     plane.  float32 -> float64 is exact, so a file read back holds the device's values."""
     r = np.asarray(rows)
     assert r.ndim == 2 and r.shape[1] == abi.RECORD_FIELDS, r.shape
@@ -44,7 +45,12 @@ def trajectory_arrays(rows, steps, control_dt, env=0):
     def xyz(y, z):
         return np.stack([np.zeros(T), d[y], d[z]])
 
+    extra = {}
+    if env_params is not None:                   # ENV_PARAMS: the recorded env's column of the bound table, (VP_COUNT, 1)
+        extra = {"env_params": np.asarray(env_params, dtype=np.float64).reshape(-1, 1),
+                 "env_param_names": np.array(list(env_param_names), dtype=object)}
     return {
+        **extra,
         "cart_pos": d[f.VRF_Q0:f.VRF_Q0 + 1].copy(),
         "Q": d[f.VRF_Q0 + 1:f.VRF_Q0 + abi.NUM_DOFS].copy(),
         "moving_target_pos": xyz(f.VRF_TARGET_Y, f.VRF_TARGET_Z),
@@ -67,12 +73,12 @@ def trajectory_arrays(rows, steps, control_dt, env=0):
     }
 
 
-def write_trajectory_mat(path, rows, steps, control_dt, env=0):
+def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, env_param_names=None):
     """``trajectory_arrays`` as a MATLAB 5 file at ``path`` (written beside it and renamed: no reader sees half a file)."""
     import scipy.io
     part = path + ".part"
     with open(part, "wb") as fh:
-        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env))
+        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env, env_params, env_param_names))
     os.replace(part, path)
     return path
 
@@ -113,6 +119,7 @@ class TrajectoryRecorder:
         self.written, self.skipped = collections.deque(maxlen=KEEP), collections.deque(maxlen=KEEP)
         self.harvest_seconds, self.write_seconds = collections.deque(maxlen=KEEP), collections.deque(maxlen=KEEP)
         self.windows_written = self.windows_skipped = 0
+        self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
         import scipy.io  # noqa: F401  (here, not in the writer thread: the first import takes 0.3 s, longer than a window)
         self.writer = threading.Thread(target=self._write_loop, name="vine-trajectory-writer", daemon=True)
         self.writer.start()
@@ -182,7 +189,8 @@ class TrajectoryRecorder:
             done = torch.cuda.Event()
             done.record(self.side)
         self.copy_done = done
-        self.jobs.put((done, start, last))
+        params = self.env_params_of(self.env_ids) if self.env_params_of is not None else None
+        self.jobs.put((done, start, last, params))
         self.harvest_seconds.append(time.perf_counter() - t0)
 
     def path(self, last, env):
@@ -193,7 +201,7 @@ class TrajectoryRecorder:
             job = self.jobs.get()
             if job is None:
                 return
-            done, start, last = job
+            done, start, last, params = job
             try:
                 done.synchronize()
                 t0 = time.perf_counter()
@@ -202,7 +210,9 @@ class TrajectoryRecorder:
                     raise RuntimeError(f"window {start}..{last}: the device recorded steps {steps.tolist()}")
                 os.makedirs(self.directory, exist_ok=True)
                 for k, e in enumerate(self.env_ids):
-                    self.written.append(write_trajectory_mat(self.path(last, e), rows[:, k], steps, self.control_dt, e))
+                    self.written.append(write_trajectory_mat(
+                        self.path(last, e), rows[:, k], steps, self.control_dt, e,
+                        params[:, k] if params is not None else None, self.env_param_names))
                 self.write_seconds.append(time.perf_counter() - t0)
                 self.windows_written += 1
                 self.logger.info(f"Saved {len(self.env_ids)} trajectories of steps {start}..{last} to "
