@@ -506,6 +506,39 @@ def declare_env_params(lib):
     return lib
 
 
+# ---- include/vine_sysid.h (product library only)
+SYSID_ABI_VERSION = 1
+SYSID_FIELDS = 16
+
+
+class VineSysidConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_rows", C.c_int32),
+        ("horizon", C.c_int32),
+        ("reserved", C.c_int32),
+        ("weights", C.c_float * SYSID_FIELDS),
+    ]
+
+
+SYSID_PROTOTYPES = {
+    "vine_sysid_config_default": (C.c_int, [_P(VineSysidConfig)]),
+    "vine_sysid_config_size": (C.c_int, []),
+    "vine_sysid_pin": (C.c_int, [_H, _P(VineSysidConfig), _VP, C.c_int64] + [_VP] * 6),
+    "vine_sysid_scheduled": (C.c_int, [_H, _P(VineSysidConfig)] + [_VP] * 7),
+}
+
+
+def declare_sysid(lib):
+    for name, (restype, argtypes) in SYSID_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
+    if lib.vine_sysid_config_size() != C.sizeof(VineSysidConfig):
+        raise RuntimeError("VineSysidConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     for name, (restype, argtypes) in PPO_PROTOTYPES.items():
         fn = getattr(lib, name)

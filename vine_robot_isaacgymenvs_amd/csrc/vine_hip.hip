@@ -32,6 +32,7 @@
 #include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
 #include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
 #include "vine_render_internal.h"
+#include "vine_task_shared.h"            // the action -> command map (shared with the sysid pin), clampf
 
 #define NL VINE_NUM_LINKS
 #define ND VINE_NUM_DOFS
@@ -601,8 +602,6 @@ __device__ __forceinline__ void pipe_link_contact_coop(const DevParams& P, int t
     }
 }
 
-__device__ __forceinline__ float clampf(float v, float lim) { return fminf(fmaxf(v, -lim), lim); }
-
 // ================================================================================================================
 // The task, stated once: what Vine5LinkMovingBase computes around the physics, as per-lane arithmetic on values the caller
 // holds in registers.  vine_step_kernel (one lane per env) and vine_step_quad_kernel (four lanes per env, everything here
@@ -610,19 +609,8 @@ __device__ __forceinline__ float clampf(float v, float lim) { return fminf(fmaxf
 // stores sit, who holds which joint, the solver -- stays in the kernels.  No memory access and no cross-lane operation in
 // here.  (oracle/vine_oracle.c restates the task independently and shares nothing with this section.)
 
-// VecTask.step's clamp (vec_task.py:333) and the first half of pre_physics_step (V5:922-934): the action, with its noise
-// deviates n0, n1, becomes the command (new_rail, new_fpam).
-template <bool RANDOMIZE>
-__device__ __forceinline__ void task_new_command(const DevParams& P, float2 act, float n0, float n1, float& new_rail,
-                                                 float& new_fpam) {
-    float a0 = clampf(act.x, P.clip_act), a1 = clampf(act.y, P.clip_act);
-    if (RANDOMIZE && P.act_noise != 0.0f) {
-        a0 += P.act_noise * n0;
-        a1 += P.act_noise * n1;
-    }
-    new_rail = a0 * P.rail_scale;
-    new_fpam = (a1 + 1.0f) * 0.5f * P.fpam_span + P.fpam_min;   // /2 == *0.5 exactly
-}
+// VecTask.step's clamp (vec_task.py:333) and the first half of pre_physics_step (V5:922-934), the action -> command map
+// task_new_command<RANDOMIZE>(P, act, n0, n1, new_rail, new_fpam): vine_task_shared.h (the sysid pin evaluates it too).
 // The second half (V5:935-945): the command in effect (u_rail, u_fpam) is the one the delay FIFO held for this step (delay > 0;
 // the caller loads it and stores the new one in its place) or the new one; then the two force flags and the FPAM smoothing.
 __device__ __forceinline__ void task_command_in_effect(const DevParams& P, float new_rail, float new_fpam, float fifo_rail,
@@ -2832,6 +2820,10 @@ int vine_render_info(VineHandle* h, VineRenderInfo* out) {
     out->flags = h->P.flags;
     out->L = h->P.L; out->z1 = h->P.z1; out->s0 = h->P.s0; out->c0 = h->P.c0;
     out->soft_limit = h->P.soft_limit; out->success_dist = h->P.success_dist;
+    out->env_params = h->env_params;
+    out->delay = h->P.delay;
+    out->clip_act = h->P.clip_act; out->rail_scale = h->P.rail_scale;
+    out->fpam_span = h->P.fpam_span; out->fpam_min = h->P.fpam_min;
     return VINE_OK;
 }
 const float* vine_reward_matrix_of(VineHandle* h) { return h ? h->reward_matrix : nullptr; }

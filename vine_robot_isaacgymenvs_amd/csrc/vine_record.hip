@@ -2,8 +2,8 @@
 //
 // One launch of one wave covers every recorded env: lane k owns env envs[k] (K <= 64).  It gathers the copied fields of
 // the SoA state block (st[f * n + e]) and the step's outputs, evaluates the tip's forward kinematics from the joint state
-// it has just read (the same fp32 sequence as tip_fk of vine_hip.hip: the state block's tip fields are not stored without
-// introspection), and writes its row of 32 floats as eight 16-byte stores.  Lane 0 also writes the step index.
+// it has just read (tip_fk_joint of vine_task_shared.h, the same fp32 sequence as tip_fk of vine_hip.hip: the state block's
+// tip fields are not stored without introspection), and writes its row of 32 floats as eight 16-byte stores.  Lane 0 also writes the step index.
 //
 // The scheduled form reads the step counter of the handle (vine_hip.hip step_of: two 8-byte loads, uniform, so they are
 // scalar loads) and returns at once outside a recording window: no other load and no store on that path.
@@ -15,6 +15,7 @@
 
 #include "../../include/vine_record.h"
 #include "vine_render_internal.h"
+#include "vine_task_shared.h"
 
 namespace {
 
@@ -55,19 +56,10 @@ __global__ __launch_bounds__(THREADS) void vine_record_kernel(const RecordParams
     if (e >= 0 && e < n) {
 #pragma unroll
         for (int f = 0; f < 2 * VINE_NUM_DOFS; ++f) row[VRF_Q0 + f] = st[(VF_Q0 + f) * n + e];      // q, qd: VF_Q0 .. VF_QD0 + 5
-        {   // tip_fk of vine_hip.hip on the recorded joint state
-            float ty = row[VRF_Q0], tz = R.z1, tvy = row[VRF_QD0], tvz = 0.0f, th = 0.0f, w = 0.0f;
-#pragma unroll
-            for (int j = 0; j < VINE_NUM_LINKS; ++j) {
-                th += row[VRF_Q0 + 1 + j];
-                w += row[VRF_QD0 + 1 + j];
-                float s, cth;
-                sincosf(th, &s, &cth);
-                const float sp = R.s0 * cth + R.c0 * s, cp = R.c0 * cth - R.s0 * s;
-                ty -= R.L * sp; tz += R.L * cp;
-                tvy -= R.L * w * cp; tvz -= R.L * w * sp;
-            }
-            row[VRF_TIP_Y] = ty; row[VRF_TIP_Z] = tz; row[VRF_TIP_VY] = tvy; row[VRF_TIP_VZ] = tvz;
+        {   // the tip's forward kinematics of the recorded joint state (vine_task_shared.h)
+            float tip[4];
+            tip_fk_joint(&row[VRF_Q0], &row[VRF_QD0], R.L, R.z1, R.s0, R.c0, tip);
+            row[VRF_TIP_Y] = tip[0]; row[VRF_TIP_Z] = tip[1]; row[VRF_TIP_VY] = tip[2]; row[VRF_TIP_VZ] = tip[3];
         }
         row[VRF_TARGET_Y] = st[VF_TARGET_Y * n + e];
         row[VRF_TARGET_Z] = st[VF_TARGET_Z * n + e];
@@ -87,16 +79,11 @@ __global__ __launch_bounds__(THREADS) void vine_record_kernel(const RecordParams
     for (int i = 0; i < VINE_RECORD_FIELDS / 4; ++i) dst[i] = make_float4(row[4 * i], row[4 * i + 1], row[4 * i + 2], row[4 * i + 3]);
 }
 
-int bad(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_INVALID_ARG;
-}
-
 int validate(const VineRecordConfig* c) {
-    if (!c) return bad("record config is NULL");
-    if (c->abi_version != VINE_RECORD_ABI_VERSION) return bad("VineRecordConfig.abi_version mismatch");
-    if (c->num_envs < 1 || c->num_envs > VINE_RECORD_MAX_ENVS) return bad("record num_envs out of range");
-    if (c->num_steps < 1 || c->record_every < c->num_steps) return bad("need 1 <= num_steps <= record_every");
+    if (!c) return vine_invalid_arg("record config is NULL");
+    if (c->abi_version != VINE_RECORD_ABI_VERSION) return vine_invalid_arg("VineRecordConfig.abi_version mismatch");
+    if (c->num_envs < 1 || c->num_envs > VINE_RECORD_MAX_ENVS) return vine_invalid_arg("record num_envs out of range");
+    if (c->num_steps < 1 || c->record_every < c->num_steps) return vine_invalid_arg("need 1 <= num_steps <= record_every");
     return VINE_OK;
 }
 
@@ -106,9 +93,9 @@ int launch(VineHandle* h, const VineRecordConfig* cfg, int slot, const int32_t* 
     int rc = validate(cfg);
     if (rc) return rc;
     if (!h || !envs || !actions || !rew || !reset || !progress || !timeouts || !ring || !steps)
-        return bad("null argument to vine_record");
-    if (!scheduled && (slot < 0 || slot >= cfg->num_steps)) return bad("record slot out of range");
-    if (reinterpret_cast<uintptr_t>(ring) & 15u) return bad("record ring must be 16-byte aligned");
+        return vine_invalid_arg("null argument to vine_record");
+    if (!scheduled && (slot < 0 || slot >= cfg->num_steps)) return vine_invalid_arg("record slot out of range");
+    if (reinterpret_cast<uintptr_t>(ring) & 15u) return vine_invalid_arg("record ring must be 16-byte aligned");
     VineRenderInfo info;
     rc = vine_render_info(h, &info);
     if (rc) return rc;
@@ -116,12 +103,8 @@ int launch(VineHandle* h, const VineRecordConfig* cfg, int slot, const int32_t* 
     R.K = cfg->num_envs; R.num_steps = cfg->num_steps; R.record_every = cfg->record_every; R.slot = scheduled ? 0 : slot;
     R.n = info.n; R.glog = info.glog; R.flags = info.flags;
     R.L = info.L; R.z1 = info.z1; R.s0 = info.s0; R.c0 = info.c0;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != info.device && hipSetDevice(info.device) != hipSuccess) {
-        vine_set_error("hipSetDevice failed");
-        return VINE_ERR_DEVICE;
-    }
+    VineDeviceScope scope(info.device);
+    if (!scope.ok) return VINE_ERR_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     if (scheduled)
         hipLaunchKernelGGL(vine_record_kernel<true>, dim3(1), dim3(THREADS), 0, s, R, info.state, info.counters,
@@ -131,15 +114,7 @@ int launch(VineHandle* h, const VineRecordConfig* cfg, int slot, const int32_t* 
         hipLaunchKernelGGL(vine_record_kernel<false>, dim3(1), dim3(THREADS), 0, s, R, info.state, info.counters,
                            (const int*)envs, actions, rew, (const long long*)reset, (const long long*)progress, timeouts, ring,
                            (long long*)steps);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != info.device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "vine_record launch: %s", hipGetErrorString(e));
-        vine_set_error(msg);
-        return VINE_ERR_DEVICE;
-    }
-    return VINE_OK;
+    return vine_launch_status("vine_record");
 }
 
 }  // namespace
@@ -147,7 +122,7 @@ int launch(VineHandle* h, const VineRecordConfig* cfg, int slot, const int32_t* 
 extern "C" {
 
 int vine_record_config_default(VineRecordConfig* c) {
-    if (!c) return bad("record config is NULL");
+    if (!c) return vine_invalid_arg("record config is NULL");
     c->abi_version = VINE_RECORD_ABI_VERSION;
     c->record_every = 1000;
     c->num_steps = 500;

@@ -1,7 +1,11 @@
-// vine_render_internal.h — what vine_render.hip (and the other observers of a step: vine_record.hip, vine_episodes.hip)
+// vine_render_internal.h — what vine_render.hip (and the other observers of a step: vine_record.hip, vine_episodes.hip, vine_sysid.hip)
 // needs of a VineHandle (defined in vine_hip.hip).  Not part of the C ABI: the functions are hidden symbols of libvine_hip.so.
 #ifndef VINE_RENDER_INTERNAL_H
 #define VINE_RENDER_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
 
 #include "../../include/vine.h"
 
@@ -13,12 +17,41 @@ struct VineRenderInfo {
     unsigned flags;
     float L, z1, s0, c0;                   // link_length, joint1_z, sin / cos of phi0
     float soft_limit, success_dist;
+    const float* env_params;               // the bound per-env parameter table [VP_COUNT][n] (include/vine_env_params.h) or NULL
+    int delay;                             // the configuration's ACTION_DELAY
+    float clip_act, rail_scale, fpam_span, fpam_min;      // the constants of task_new_command (vine_task_shared.h)
 };
 
 extern "C" {
 __attribute__((visibility("hidden"))) int vine_render_info(VineHandle* h, VineRenderInfo* out);
 __attribute__((visibility("hidden"))) const float* vine_reward_matrix_of(VineHandle* h);   // the bound [N,13] matrix, or NULL
 __attribute__((visibility("hidden"))) void vine_set_error(const char* msg);    // sets vine_last_error()'s thread-local text
+}
+
+// What every observer's launch function does around its kernel, stated once (vine_record.hip, vine_sysid.hip).
+inline int vine_invalid_arg(const char* msg) {
+    vine_set_error(msg);
+    return VINE_ERR_INVALID_ARG;
+}
+struct VineDeviceScope {      // the handle's device for the launch, the caller's afterwards
+    int prev = -1, dev;
+    bool ok = true;
+    explicit VineDeviceScope(int d) : dev(d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+        if (!ok) vine_set_error("hipSetDevice failed");
+    }
+    ~VineDeviceScope() {
+        if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
+    }
+};
+inline int vine_launch_status(const char* what) {      // hipGetLastError behind a launch, as a VineStatus
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return VINE_OK;
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s launch: %s", what, hipGetErrorString(e));
+    vine_set_error(msg);
+    return VINE_ERR_DEVICE;
 }
 
 #endif

@@ -16,6 +16,8 @@ SRC_PPO = os.path.join(_HERE, "csrc", "ppo_kernels.hip")
 SRC_RENDER = os.path.join(_HERE, "csrc", "vine_render.hip")
 SRC_RECORD = os.path.join(_HERE, "csrc", "vine_record.hip")
 SRC_EPISODES = os.path.join(_HERE, "csrc", "vine_episodes.hip")
+SRC_SYSID = os.path.join(_HERE, "csrc", "vine_sysid.hip")
+SOURCES = (SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES, SRC_SYSID)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -23,9 +25,10 @@ FINGERPRINT = LIB + ".fingerprint"
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HEADERS = [os.path.join(_INC, "vine.h"), os.path.join(_INC, "vine_ppo.h"), os.path.join(_INC, "vine_render.h"),
             os.path.join(_INC, "vine_record.h"), os.path.join(_INC, "vine_episodes.h"), os.path.join(_INC, "vine_env_params.h"),
+            os.path.join(_INC, "vine_sysid.h"), os.path.join(_HERE, "csrc", "vine_task_shared.h"),
             os.path.join(_HERE, "csrc", "vine_geometry.h"), os.path.join(_HERE, "csrc", "vine_render_internal.h"),
             os.path.join(_HERE, "csrc", "vine_policy_head.h"), os.path.join(_HERE, "csrc", "vine_ppo_formulas.h")]
-DEPS = [SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES] + _HEADERS
+DEPS = list(SOURCES) + _HEADERS
 
 _lib = None
 
@@ -64,7 +67,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The five translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The six translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -77,7 +80,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in (SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES):
+    for src in SOURCES:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)
@@ -110,7 +113,7 @@ def load():
     if _lib is None and os.environ.get("VINE_HIP_LIB"):
         # experiments only (A/B builds of the kernels with other compile flags): load exactly this file
         import torch  # noqa: F401
-        _lib = abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(os.environ["VINE_HIP_LIB"])))))))
+        _lib = abi.declare_sysid(abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(os.environ["VINE_HIP_LIB"]))))))))
         return _lib
     if _lib is None:
         # PyTorch-ROCm ships its own libamdhip64.so.7; it must be the HIP runtime of the process, so it is
@@ -132,7 +135,7 @@ def load():
                         build()
             else:
                 raise RuntimeError("libvine_hip.so was built from different sources and no hipcc is available")
-        _lib = abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(LIB)))))))
+        _lib = abi.declare_sysid(abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(LIB))))))))
     return _lib
 
 

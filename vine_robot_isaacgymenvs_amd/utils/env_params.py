@@ -91,23 +91,48 @@ def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
     if lib is None:
         from .. import native
         lib = native.load()
-    num_envs = int(num_envs)
-    if num_envs < 1:
-        raise ValueError("ENV_PARAMS: num_envs must be positive")
+    return draw_table(spec, config_row(lib, vcfg), seed, num_envs, env_id_offset, check=lambda t: check_table(lib, vcfg, t))
+
+
+def spec_forms(spec):
+    """``{name: ('scalar', v) / ('range', lo, hi) / ('values', [..])}`` of a spec, in its order; raises ``ConfigError`` for an
+    unknown name or a malformed entry."""
     spec = spec or {}
     if not hasattr(spec, "keys"):
         raise ConfigError("ENV_PARAMS must be a mapping of parameter names, not %r" % (spec,))
     for name in spec.keys():
         if name not in abi.ENV_PARAM_ROWS:
             raise ConfigError("ENV_PARAMS: unknown parameter %r (known: %s)" % (name, ", ".join(abi.ENV_PARAM_NAMES)))
-    base = config_row(lib, vcfg)
-    table = np.repeat(base[:, None], num_envs, axis=1)
-    gids = np.arange(num_envs, dtype=np.int64) + int(env_id_offset)
-    radix = 1                                     # product of the lengths of the `values` entries before this one
     forms = {name: _form(name, spec[name]) for name in spec.keys()}
     f = forms.get("ACTION_DELAY")
     if f is not None and f[0] == "range" and (f[1] != np.floor(f[1]) or f[2] != np.floor(f[2])):
         raise ConfigError("ENV_PARAMS.ACTION_DELAY: an integer parameter takes an integer range, not [%g, %g]" % (f[1], f[2]))
+    return forms
+
+
+def set_rows(table, base, name, v):
+    """Write the per-env values ``v`` (float64 [N]) of ``name`` into ``table``: the value itself, or for an FPAM vector the
+    factor on the configuration's five constants ``base``."""
+    first, count = abi.ENV_PARAM_ROWS[name]
+    if count == 1:
+        table[first] = v.astype(np.float32)
+    else:
+        table[first:first + count] = (base[first:first + count, None].astype(np.float64) * v[None, :]).astype(np.float32)
+
+
+def draw_table(spec, base, seed, num_envs, env_id_offset=0, check=None, draws=None):
+    """``build_table`` from the configuration's row ``base`` (float32 [VP_COUNT]) instead of a handle's config: pure numpy.
+    ``check``: called with the probe of what the spec can give an env and with the finished table (``check_table`` bound to
+    a library), or ``None``.  ``draws``: a dict that receives, per name, the float64 [N] values (factors for the FPAM
+    vectors) the table was formed from."""
+    num_envs = int(num_envs)
+    if num_envs < 1:
+        raise ValueError("ENV_PARAMS: num_envs must be positive")
+    forms = spec_forms(spec)
+    base = np.asarray(base, dtype=np.float32)
+    table = np.repeat(base[:, None], num_envs, axis=1)
+    gids = np.arange(num_envs, dtype=np.int64) + int(env_id_offset)
+    radix = 1                                     # product of the lengths of the `values` entries before this one
     # what the spec CAN give an env is checked whatever this batch happens to draw: both ends of a range, every value
     cand = {name: list(f[1]) if f[0] == "values" else list(f[1:]) for name, f in forms.items()}
     width = max([len(c) for c in cand.values()] + [1])
@@ -117,12 +142,12 @@ def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
         v = np.asarray([c[i % len(c)] for i in range(width)], dtype=np.float64)
         probe[first:first + count] = (v[None, :] * (base[first:first + count, None].astype(np.float64) if count > 1 else 1.0)
                                       ).astype(np.float32)
-    try:
-        check_table(lib, vcfg, probe)
-    except ValueError as e:
-        raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
-    for name in spec.keys():
-        form = forms[name]
+    if check is not None:
+        try:
+            check(probe)
+        except ValueError as e:
+            raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
+    for name, form in forms.items():
         integer = name == "ACTION_DELAY"
         if form[0] == "scalar":
             v = np.full(num_envs, form[1], dtype=np.float64)
@@ -137,13 +162,14 @@ def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
             vals = np.asarray(form[1], dtype=np.float64)
             v = vals[(gids // radix) % len(vals)]
             radix *= len(vals)
-        first, count = abi.ENV_PARAM_ROWS[name]
-        if count == 1:
-            table[first] = v.astype(np.float32)
-        else:                                     # an FPAM vector: a factor on the configuration's five constants
-            table[first:first + count] = (base[first:first + count, None].astype(np.float64) * v[None, :]).astype(np.float32)
+        set_rows(table, base, name, v)
+        if draws is not None:
+            draws[name] = v
+    table = np.ascontiguousarray(table, dtype=np.float32)
+    if check is None:
+        return table
     try:
-        return check_table(lib, vcfg, table)
+        return check(table)
     except ValueError as e:
         raise ValueError("ENV_PARAMS: %s" % e) from None
 
