@@ -241,13 +241,13 @@ def _player(tmp_path, graph_steps, record):
     player = Paced(params, vec_env=env)
     player.seen, player.trajectory = [], env.trajectory
     if record:
-        replayed = env.video_replayed
+        replayed = env.observers_replayed
 
         def paced(n_steps, before=False):
             replayed(n_steps, before=before)
             if not before:
                 env.trajectory.drain()
-        env.video_replayed = paced
+        env.observers_replayed = paced
     return player, env
 
 

@@ -372,11 +372,16 @@ RENDER_PROTOTYPES = {
 }
 
 
-def declare_render(lib):
-    for name, (restype, argtypes) in RENDER_PROTOTYPES.items():
+def _attach(lib, prototypes):
+    """Attach prototypes; raises AttributeError naming the first missing symbol."""
+    for name, (restype, argtypes) in prototypes.items():
         fn = getattr(lib, name)
         fn.restype = restype
         fn.argtypes = argtypes
+
+
+def declare_render(lib):
+    _attach(lib, RENDER_PROTOTYPES)
     if lib.vine_render_config_size() != C.sizeof(VineRenderConfig):
         raise RuntimeError("VineRenderConfig: the library's struct size differs from the ctypes mirror")
     return lib
@@ -415,10 +420,7 @@ RECORD_PROTOTYPES = {
 
 
 def declare_record(lib):
-    for name, (restype, argtypes) in RECORD_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, RECORD_PROTOTYPES)
     if lib.vine_record_config_size() != C.sizeof(VineRecordConfig):
         raise RuntimeError("VineRecordConfig: the library's struct size differs from the ctypes mirror")
     return lib
@@ -455,10 +457,7 @@ EPISODES_PROTOTYPES = {
 
 
 def declare_episodes(lib):
-    for name, (restype, argtypes) in EPISODES_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, EPISODES_PROTOTYPES)
     if lib.vine_episodes_config_size() != C.sizeof(VineEpisodesConfig):
         raise RuntimeError("VineEpisodesConfig: the library's struct size differs from the ctypes mirror")
     return lib
@@ -499,10 +498,7 @@ ENV_PARAMS_PROTOTYPES = {
 
 
 def declare_env_params(lib):
-    for name, (restype, argtypes) in ENV_PARAMS_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, ENV_PARAMS_PROTOTYPES)
     return lib
 
 
@@ -530,27 +526,24 @@ SYSID_PROTOTYPES = {
 
 
 def declare_sysid(lib):
-    for name, (restype, argtypes) in SYSID_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, SYSID_PROTOTYPES)
     if lib.vine_sysid_config_size() != C.sizeof(VineSysidConfig):
         raise RuntimeError("VineSysidConfig: the library's struct size differs from the ctypes mirror")
     return lib
 
 
 def declare_ppo(lib):
-    for name, (restype, argtypes) in PPO_PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, PPO_PROTOTYPES)
     return lib
 
 
 def declare(lib):
-    """Attach prototypes; raises AttributeError naming the first missing symbol."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype = restype
-        fn.argtypes = argtypes
+    _attach(lib, PROTOTYPES)
+    return lib
+
+
+def declare_all(lib):
+    """Every prototype of the library, and the struct-size checks of the observers' configurations."""
+    for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_sysid):
+        declare_one(lib)
     return lib

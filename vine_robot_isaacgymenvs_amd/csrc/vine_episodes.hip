@@ -20,10 +20,8 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/vine_episodes.h"
-#include "vine_render_internal.h"
+#include "vine_observer.h"
 
 namespace {
 
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(THREADS) void vine_episodes_kernel(const EpisodesPa
                                                                 float* __restrict__ episode, double* __restrict__ totals,
                                                                 unsigned* __restrict__ table,
                                                                 unsigned long long* __restrict__ cursor) {
-    const unsigned long long c = counters[0] + (counters[1] >> E.glog);      // steps completed (vine_hip.hip step_of)
+    const unsigned long long c = vine_steps_completed(counters, E.glog);
     if (c == 0ull) return;
     const int end_step = (int)(c - 1ull);
     const int n = E.n, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -177,16 +175,11 @@ __global__ __launch_bounds__(THREADS) void vine_episodes_kernel(const EpisodesPa
     if (SERIAL && table && threadIdx.x == 0) cursor[0] = base0 + (unsigned long long)step_rows;
 }
 
-int bad(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_INVALID_ARG;
-}
-
 int validate(const VineEpisodesConfig* c) {
-    if (!c) return bad("episodes config is NULL");
-    if (c->abi_version != VINE_EPISODES_ABI_VERSION) return bad("VineEpisodesConfig.abi_version mismatch");
-    if (c->reserved != 0) return bad("VineEpisodesConfig.reserved must be 0");
-    if (c->capacity < 1 || c->capacity > (int64_t)1 << 40) return bad("episodes capacity out of range");
+    if (!c) return vine_invalid_arg("episodes config is NULL");
+    if (c->abi_version != VINE_EPISODES_ABI_VERSION) return vine_invalid_arg("VineEpisodesConfig.abi_version mismatch");
+    if (c->reserved != 0) return vine_invalid_arg("VineEpisodesConfig.reserved must be 0");
+    if (c->capacity < 1 || c->capacity > (int64_t)1 << 40) return vine_invalid_arg("episodes capacity out of range");
     return VINE_OK;
 }
 
@@ -195,7 +188,7 @@ int validate(const VineEpisodesConfig* c) {
 extern "C" {
 
 int vine_episodes_config_default(VineEpisodesConfig* c) {
-    if (!c) return bad("episodes config is NULL");
+    if (!c) return vine_invalid_arg("episodes config is NULL");
     c->abi_version = VINE_EPISODES_ABI_VERSION;
     c->reserved = 0;
     c->capacity = 1048576;
@@ -205,9 +198,9 @@ int vine_episodes_config_default(VineEpisodesConfig* c) {
 int vine_episodes_config_size(void) { return (int)sizeof(VineEpisodesConfig); }
 
 int vine_episodes_rows(VineHandle* h) {
-    if (!h) return bad("null argument to vine_episodes_rows");
-    VineRenderInfo info;
-    const int rc = vine_render_info(h, &info);
+    if (!h) return vine_invalid_arg("null argument to vine_episodes_rows");
+    VineHandleInfo info;
+    const int rc = vine_handle_info(h, &info);
     if (rc) return rc;
     return (info.n + THREADS - 1) / THREADS;
 }
@@ -224,25 +217,21 @@ int vine_episodes_scheduled(VineHandle* h, const VineEpisodesConfig* cfg, const 
     int rc = validate(cfg);
     if (rc) return rc;
     if (!h || !rew || !reset || !progress || !timeouts || !episode || !totals)
-        return bad("null argument to vine_episodes_scheduled");
-    if ((table == nullptr) != (cursor == nullptr)) return bad("episodes table and cursor go together: both or neither");
-    if (reinterpret_cast<uintptr_t>(table) & 15u) return bad("episodes table must be 16-byte aligned");
-    VineRenderInfo info;
-    rc = vine_render_info(h, &info);
+        return vine_invalid_arg("null argument to vine_episodes_scheduled");
+    if ((table == nullptr) != (cursor == nullptr)) return vine_invalid_arg("episodes table and cursor go together: both or neither");
+    if (reinterpret_cast<uintptr_t>(table) & 15u) return vine_invalid_arg("episodes table must be 16-byte aligned");
+    VineHandleInfo info;
+    rc = vine_handle_info(h, &info);
     if (rc) return rc;
     const float* rmat = vine_reward_matrix_of(h);
     if (!rmat)
-        return bad("vine_episodes_scheduled needs a reward matrix bound to the handle (vine_bind_reward_matrix) before the "
-                   "step it accounts for");
+        return vine_invalid_arg("vine_episodes_scheduled needs a reward matrix bound to the handle (vine_bind_reward_matrix) "
+                                "before the step it accounts for");
     EpisodesParams E;
     E.n = info.n; E.glog = info.glog; E.nchunks = (info.n + THREADS - 1) / THREADS;
     E.flags = info.flags; E.capacity = cfg->capacity;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != info.device && hipSetDevice(info.device) != hipSuccess) {
-        vine_set_error("hipSetDevice failed");
-        return VINE_ERR_DEVICE;
-    }
+    VineDeviceScope scope(info.device);
+    if (!scope.ok) return VINE_ERR_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     if (table && cfg->capacity < info.n)      // one step could lap itself: one workgroup hands out the slots in env order
         hipLaunchKernelGGL(vine_episodes_kernel<true>, dim3(1), dim3(THREADS), 0, s, E, info.state, info.counters, rmat, rew,
@@ -251,15 +240,7 @@ int vine_episodes_scheduled(VineHandle* h, const VineEpisodesConfig* cfg, const 
         hipLaunchKernelGGL(vine_episodes_kernel<false>, dim3(E.nchunks), dim3(THREADS), 0, s, E, info.state, info.counters, rmat,
                            rew, (const long long*)reset, timeouts, episode, totals, (unsigned*)table,
                            (unsigned long long*)cursor);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != info.device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "vine_episodes launch: %s", hipGetErrorString(e));
-        vine_set_error(msg);
-        return VINE_ERR_DEVICE;
-    }
-    return VINE_OK;
+    return vine_launch_status("vine_episodes");
 }
 
 }  // extern "C"

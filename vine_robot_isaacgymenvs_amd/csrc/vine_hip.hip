@@ -31,7 +31,7 @@
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
 #include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
 #include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
-#include "vine_render_internal.h"
+#include "vine_observer.h"
 #include "vine_task_shared.h"            // the action -> command map (shared with the sysid pin), clampf
 
 #define NL VINE_NUM_LINKS
@@ -93,7 +93,7 @@ __device__ __forceinline__ void rng4(const DevParams& P, unsigned env, unsigned 
 // the last arrival writing step + 1 -- a returning atomic on one word from 256 workgroups, a barrier and a fence behind the
 // workgroup's stores, and two dependent writes by the last workgroup: 2-3 us at the tail of a 24 us kernel.)
 __device__ __forceinline__ unsigned long long step_of(const DevParams& P, const unsigned long long* counters) {
-    return counters[0] + (counters[1] >> P.glog);
+    return vine_steps_completed(counters, P.glog);
 }
 __device__ __forceinline__ void step_arrive(unsigned long long* counters) {
     __builtin_amdgcn_s_barrier();      // every wave of the workgroup has read the counters long ago; no fence: nothing is published
@@ -2796,7 +2796,7 @@ int64_t vine_get_step_count(VineHandle* h) {
     unsigned long long v[2] = {0ull, 0ull};
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpy(v, h->counters, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return (int64_t)(v[0] + (v[1] >> h->P.glog));      // (step_of)
+    return (int64_t)vine_steps_completed(v, h->P.glog);
 }
 
 int vine_set_step_count(VineHandle* h, int64_t step_count) {
@@ -2808,9 +2808,9 @@ int vine_set_step_count(VineHandle* h, int64_t step_count) {
     return VINE_OK;
 }
 
-// What the renderer (vine_render.hip, its own translation unit) needs to know of a handle.
-int vine_render_info(VineHandle* h, VineRenderInfo* out) {
-    if (!h || !out) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_render_info");
+// What the observers (their own translation units) need to know of a handle.
+int vine_handle_info(VineHandle* h, VineHandleInfo* out) {
+    if (!h || !out) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_handle_info");
     out->state = h->state;
     out->counters = h->counters;
     out->glog = h->P.glog;

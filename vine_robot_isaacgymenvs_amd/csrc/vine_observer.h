@@ -1,7 +1,7 @@
-// vine_render_internal.h — what vine_render.hip (and the other observers of a step: vine_record.hip, vine_episodes.hip, vine_sysid.hip)
-// needs of a VineHandle (defined in vine_hip.hip).  Not part of the C ABI: the functions are hidden symbols of libvine_hip.so.
-#ifndef VINE_RENDER_INTERNAL_H
-#define VINE_RENDER_INTERNAL_H
+// vine_observer.h — what the observers of a step (vine_render.hip, vine_record.hip, vine_episodes.hip, vine_sysid.hip) need of a
+// VineHandle (defined in vine_hip.hip), and what each of their launch functions does around its kernel.  Not part of the C ABI: the functions are hidden symbols of libvine_hip.so.
+#ifndef VINE_OBSERVER_H
+#define VINE_OBSERVER_H
 
 #include <hip/hip_runtime.h>
 
@@ -9,9 +9,9 @@
 
 #include "../../include/vine.h"
 
-struct VineRenderInfo {
+struct VineHandleInfo {
     float* state;                          // SoA block, VF_COUNT * n floats
-    const unsigned long long* counters;    // [0] step-count base, [1] finished workgroups of step launches (vine_hip.hip step_of)
+    const unsigned long long* counters;    // [0] step-count base, [1] finished workgroups of step launches (vine_steps_completed)
     int glog;                              // log2 of the step launch's grid
     int n, device, max_len;
     unsigned flags;
@@ -23,12 +23,18 @@ struct VineRenderInfo {
 };
 
 extern "C" {
-__attribute__((visibility("hidden"))) int vine_render_info(VineHandle* h, VineRenderInfo* out);
+__attribute__((visibility("hidden"))) int vine_handle_info(VineHandle* h, VineHandleInfo* out);
 __attribute__((visibility("hidden"))) const float* vine_reward_matrix_of(VineHandle* h);   // the bound [N,13] matrix, or NULL
 __attribute__((visibility("hidden"))) void vine_set_error(const char* msg);    // sets vine_last_error()'s thread-local text
 }
 
-// What every observer's launch function does around its kernel, stated once (vine_record.hip, vine_sysid.hip).
+// The steps completed, from the handle's counter pair (vine_hip.hip step_of says why it has this form): what the step kernels
+// key their random streams by, what every observer kernel schedules itself by, and what vine_get_step_count returns.
+__host__ __device__ inline unsigned long long vine_steps_completed(const unsigned long long* counters, int glog) {
+    return counters[0] + (counters[1] >> glog);
+}
+
+// What every observer's launch function does around its kernel, stated once.
 inline int vine_invalid_arg(const char* msg) {
     vine_set_error(msg);
     return VINE_ERR_INVALID_ARG;

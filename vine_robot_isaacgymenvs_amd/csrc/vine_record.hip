@@ -5,7 +5,7 @@
 // it has just read (tip_fk_joint of vine_task_shared.h, the same fp32 sequence as tip_fk of vine_hip.hip: the state block's
 // tip fields are not stored without introspection), and writes its row of 32 floats as eight 16-byte stores.  Lane 0 also writes the step index.
 //
-// The scheduled form reads the step counter of the handle (vine_hip.hip step_of: two 8-byte loads, uniform, so they are
+// The scheduled form reads the step counter of the handle (vine_observer.h vine_steps_completed: two 8-byte loads, uniform, so they are
 // scalar loads) and returns at once outside a recording window: no other load and no store on that path.
 // No atomics; plain C++ stores only.
 
@@ -14,7 +14,7 @@
 #include <cstdio>
 
 #include "../../include/vine_record.h"
-#include "vine_render_internal.h"
+#include "vine_observer.h"
 #include "vine_task_shared.h"
 
 namespace {
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(THREADS) void vine_record_kernel(const RecordParams
                                                               const long long* __restrict__ progress,
                                                               const unsigned char* __restrict__ timeouts,
                                                               float* __restrict__ ring, long long* __restrict__ steps) {
-    const unsigned long long c = counters[0] + (counters[1] >> R.glog);      // steps completed
+    const unsigned long long c = vine_steps_completed(counters, R.glog);
     int slot = R.slot;
     if (SCHEDULED) {
         if (c == 0ull) return;
@@ -96,8 +96,8 @@ int launch(VineHandle* h, const VineRecordConfig* cfg, int slot, const int32_t* 
         return vine_invalid_arg("null argument to vine_record");
     if (!scheduled && (slot < 0 || slot >= cfg->num_steps)) return vine_invalid_arg("record slot out of range");
     if (reinterpret_cast<uintptr_t>(ring) & 15u) return vine_invalid_arg("record ring must be 16-byte aligned");
-    VineRenderInfo info;
-    rc = vine_render_info(h, &info);
+    VineHandleInfo info;
+    rc = vine_handle_info(h, &info);
     if (rc) return rc;
     RecordParams R;
     R.K = cfg->num_envs; R.num_steps = cfg->num_steps; R.record_every = cfg->record_every; R.slot = scheduled ? 0 : slot;

@@ -6,17 +6,15 @@
 // bounding box meets the tile; every pixel tests that short list in painter's order.  A tile no shape reaches writes
 // background without testing anything.
 //
-// The scheduled form reads the step counter of the handle (vine_hip.hip step_of: two 8-byte loads, uniform, so they are
+// The scheduled form reads the step counter of the handle (vine_observer.h vine_steps_completed: two 8-byte loads, uniform, so they are
 // scalar loads) and returns at once outside a capture window: no LDS, no barrier, no store on that path.
 // The shapes are those of the contact code (vine_geometry.h).  Plain C++ stores only.
 
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-
 #include "../../include/vine_render.h"
 #include "vine_geometry.h"
-#include "vine_render_internal.h"
+#include "vine_observer.h"
 
 namespace {
 
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(THREADS) void vine_render_kernel(const RenderParams
                                                               const unsigned long long* __restrict__ counters,
                                                               unsigned char* __restrict__ out) {
     if (SCHEDULED) {
-        const unsigned long long c = counters[0] + (counters[1] >> R.glog);      // steps completed
+        const unsigned long long c = vine_steps_completed(counters, R.glog);
         if (c == 0ull) return;
         const unsigned long long slot = (c - 1ull) % (unsigned long long)R.capture_every;
         if (slot >= (unsigned long long)R.num_frames) return;
@@ -190,19 +188,14 @@ __global__ __launch_bounds__(THREADS) void vine_render_kernel(const RenderParams
     }
 }
 
-int bad(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_INVALID_ARG;
-}
-
 int validate(const VineRenderConfig* c) {
-    if (!c) return bad("render config is NULL");
-    if (c->abi_version != VINE_RENDER_ABI_VERSION) return bad("VineRenderConfig.abi_version mismatch");
-    if (c->width < 1 || c->width > 8192 || c->height < 1 || c->height > 8192) return bad("render width / height out of range");
-    if (c->num_views < 1 || c->num_views > VINE_RENDER_MAX_VIEWS) return bad("num_views out of range");
-    if (c->grid_cols < 1 || c->grid_cols > c->num_views) return bad("grid_cols out of range");
-    if (c->num_frames < 1 || c->capture_every < c->num_frames) return bad("need 1 <= num_frames <= capture_every");
-    if (!(c->metres_per_pixel > 0.0f)) return bad("metres_per_pixel must be positive");
+    if (!c) return vine_invalid_arg("render config is NULL");
+    if (c->abi_version != VINE_RENDER_ABI_VERSION) return vine_invalid_arg("VineRenderConfig.abi_version mismatch");
+    if (c->width < 1 || c->width > 8192 || c->height < 1 || c->height > 8192) return vine_invalid_arg("render width / height out of range");
+    if (c->num_views < 1 || c->num_views > VINE_RENDER_MAX_VIEWS) return vine_invalid_arg("num_views out of range");
+    if (c->grid_cols < 1 || c->grid_cols > c->num_views) return vine_invalid_arg("grid_cols out of range");
+    if (c->num_frames < 1 || c->capture_every < c->num_frames) return vine_invalid_arg("need 1 <= num_frames <= capture_every");
+    if (!(c->metres_per_pixel > 0.0f)) return vine_invalid_arg("metres_per_pixel must be positive");
     return VINE_OK;
 }
 
@@ -212,9 +205,9 @@ int launch(VineHandle* h, const VineRenderConfig* cfg, const int32_t* view_envs,
            void* stream, bool scheduled) {
     int rc = validate(cfg);
     if (rc) return rc;
-    if (!h || !view_envs || !out) return bad("null argument to vine_render");
-    VineRenderInfo info;
-    rc = vine_render_info(h, &info);
+    if (!h || !view_envs || !out) return vine_invalid_arg("null argument to vine_render");
+    VineHandleInfo info;
+    rc = vine_handle_info(h, &info);
     if (rc) return rc;
     RenderParams R;
     R.W = cfg->width; R.H = cfg->height; R.views = cfg->num_views; R.cols = cfg->grid_cols;
@@ -228,12 +221,8 @@ int launch(VineHandle* h, const VineRenderConfig* cfg, const int32_t* view_envs,
     R.soft_limit = info.soft_limit; R.success_dist = info.success_dist;
     R.frame_bytes = vine_render_frame_bytes(cfg);
     const int tiles_y = (R.H + TILE_H - 1) / TILE_H;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != info.device && hipSetDevice(info.device) != hipSuccess) {
-        vine_set_error("hipSetDevice failed");
-        return VINE_ERR_DEVICE;
-    }
+    VineDeviceScope scope(info.device);
+    if (!scope.ok) return VINE_ERR_DEVICE;
     const dim3 grid(R.tiles_x * tiles_y, R.cells), block(THREADS);
     hipStream_t s = (hipStream_t)stream;
     if (scheduled)
@@ -242,15 +231,7 @@ int launch(VineHandle* h, const VineRenderConfig* cfg, const int32_t* view_envs,
     else
         hipLaunchKernelGGL(vine_render_kernel<false>, grid, block, 0, s, R, info.state, (const int*)view_envs,
                            (const long long*)progress, info.counters, out);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != info.device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "vine_render launch: %s", hipGetErrorString(e));
-        vine_set_error(msg);
-        return VINE_ERR_DEVICE;
-    }
-    return VINE_OK;
+    return vine_launch_status("vine_render");
 }
 
 const uint8_t PALETTE[VR_NUM_MATERIALS][3] = {
@@ -273,7 +254,7 @@ const uint8_t PALETTE[VR_NUM_MATERIALS][3] = {
 extern "C" {
 
 int vine_render_config_default(VineRenderConfig* c) {
-    if (!c) return bad("render config is NULL");
+    if (!c) return vine_invalid_arg("render config is NULL");
     c->abi_version = VINE_RENDER_ABI_VERSION;
     c->width = 400; c->height = 225;
     c->num_views = 1; c->grid_cols = 1;
@@ -297,7 +278,7 @@ int64_t vine_render_ring_bytes(const VineRenderConfig* c) {
 }
 
 int vine_render_palette(uint8_t rgb[][3], int* n) {
-    if (!rgb) return bad("palette buffer is NULL");
+    if (!rgb) return vine_invalid_arg("palette buffer is NULL");
     for (int i = 0; i < VR_NUM_MATERIALS; ++i)
         for (int k = 0; k < 3; ++k) rgb[i][k] = PALETTE[i][k];
     if (n) *n = VR_NUM_MATERIALS;

@@ -7,7 +7,7 @@
 // vine_sysid_pin_kernel writes the pose of a log row into every env and fills each env's delay ring with the commands the
 // log's last d actions would have left; the command is task_new_command<false> and the tip is tip_fk_joint, both of
 // vine_task_shared.h, the functions the step kernels and the recorder call.
-// vine_sysid_node_kernel reads the step counter exactly as the other observers do (vine_hip.hip step_of) and returns at once
+// vine_sysid_node_kernel reads the step counter exactly as the other observers do (vine_observer.h vine_steps_completed) and returns at once
 // outside the window.  Inside, a lane reads its env's 12 joint-state fields, adds its weighted squared distance from the log
 // row to err[e] in float64 and stores the next action: at most 65 B read (12 floats, err, the reset flag, alive) and 17 B
 // written per env and step.
@@ -20,7 +20,7 @@
 
 #include "../../include/vine_env_params.h"
 #include "../../include/vine_sysid.h"
-#include "vine_render_internal.h"
+#include "vine_observer.h"
 #include "vine_task_shared.h"
 
 namespace {
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(THREADS) void vine_sysid_pin_kernel(const SysidPara
                                                                  float* __restrict__ rew, long long* __restrict__ reset,
                                                                  long long* __restrict__ progress,
                                                                  long long* __restrict__ window) {
-    const unsigned long long c = counters[0] + (counters[1] >> S.glog);      // steps completed
+    const unsigned long long c = vine_steps_completed(counters, S.glog);
     const int n = S.n, e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e == 0) {
         window[0] = (long long)c;
@@ -115,7 +115,8 @@ __global__ __launch_bounds__(THREADS) void vine_sysid_node_kernel(const SysidPar
                                                                   float* __restrict__ actions,
                                                                   const long long* __restrict__ reset,
                                                                   double* __restrict__ err, unsigned char* __restrict__ alive) {
-    const long long c = (long long)(counters[0] + (counters[1] >> S.glog));      // steps completed
+    // vine_steps_completed, written out: through the call the compiler orders this kernel's first adds differently
+    const long long c = (long long)(counters[0] + (counters[1] >> S.glog));
     const long long k = c - window[0], r0 = window[1];
     if (k < 1 || k > (long long)S.H || r0 < 0 || r0 + k >= (long long)S.T) return;      // (rows stay inside the log whatever the words hold)
     const int n = S.n, e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -172,8 +173,8 @@ int validate(const VineSysidConfig* c) {
     return VINE_OK;
 }
 
-int prepare(VineHandle* h, const VineSysidConfig* cfg, VineRenderInfo& info, SysidParams& S) {
-    int rc = vine_render_info(h, &info);
+int prepare(VineHandle* h, const VineSysidConfig* cfg, VineHandleInfo& info, SysidParams& S) {
+    int rc = vine_handle_info(h, &info);
     if (rc) return rc;
     S.n = info.n; S.glog = info.glog; S.T = cfg->num_rows; S.H = cfg->horizon; S.delay = info.delay;
     S.row = 0;
@@ -208,7 +209,7 @@ int vine_sysid_pin(VineHandle* h, const VineSysidConfig* cfg, const float* log, 
     if (reinterpret_cast<uintptr_t>(actions) & 7u) return vine_invalid_arg("sysid actions must be 8-byte aligned");
     if (row < 0 || row >= cfg->num_rows) return vine_invalid_arg("sysid pin: row outside the log");
     if (row + cfg->horizon >= cfg->num_rows) return vine_invalid_arg("sysid pin: row + horizon outside the log");
-    VineRenderInfo info;
+    VineHandleInfo info;
     SysidParams S;
     rc = prepare(h, cfg, info, S);
     if (rc) return rc;
@@ -235,7 +236,7 @@ int vine_sysid_scheduled(VineHandle* h, const VineSysidConfig* cfg, const float*
     if (rc) return rc;
     if (!h || !log || !window || !actions || !reset || !err || !alive) return vine_invalid_arg("null argument to vine_sysid_scheduled");
     if (reinterpret_cast<uintptr_t>(actions) & 7u) return vine_invalid_arg("sysid actions must be 8-byte aligned");
-    VineRenderInfo info;
+    VineHandleInfo info;
     SysidParams S;
     rc = prepare(h, cfg, info, S);
     if (rc) return rc;

@@ -17,7 +17,6 @@ MI355X-first choices (none changes the arithmetic):
     torch.amp.GradScaler's semantics restated on the device (FlatAdam.enable_loss_scaling), not autocast; rollout
     inference runs in fp32 on the matrix cores (``_infer``: vine_mlp3_elu_f32 / vine_lstm_step_f32).
 """
-import contextlib
 import copy
 import os
 import time
@@ -26,7 +25,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import fused
+from . import fused, graph_capture
 from .. import abi
 from ..abi import ROLLOUT_POST_SCRATCH_FLOATS
 from .fast_inference import FastInferenceMixin
@@ -358,7 +357,6 @@ class A2CAgent(FastInferenceMixin):
             os.makedirs(self.nn_dir, exist_ok=True)
             self.writer = ScalarLog(self.summaries_dir)
         self._rollout_graph = None
-        self._video_replayed = None
         if self.algo_observer is not None:
             self.algo_observer.after_init(self)
 
@@ -799,6 +797,7 @@ class A2CAgent(FastInferenceMixin):
     def _play_graphed(self, body):
         """Capture the whole rollout once, then replay it.  Live state that the captured code rebinds
         (obs, dones, LSTM state, episode accumulators) is kept in static tensors copied in and out."""
+        env = getattr(self.vec_env, "env", self.vec_env)
         if self._rollout_graph is None:
             fused_mode = body == self._rollout_body_fused
             keep = (lambda t: t) if fused_mode else (lambda t: t.clone())   # meters are views of self.meter when fused
@@ -806,39 +805,20 @@ class A2CAgent(FastInferenceMixin):
                           self.current_rewards.clone(), self.current_lengths.clone(),
                           keep(self.game_rewards.mean), keep(self.game_rewards.current_size),
                           keep(self.game_lengths.mean), keep(self.game_lengths.current_size)]
-            flat = [self._g_in[0], self._g_in[1]] + self._g_in[2] + self._g_in[3:5]
-            backup = [t.clone() for t in flat]
-            snap = self._snapshot_env()
-            # CAPTURE_VIDEO: the steps of the warm-up pass are rolled back and those of the capture pass are not
-            # executed, so neither counts towards the env's capture schedule
-            env_ = getattr(self.vec_env, "env", self.vec_env)
-            video_paused = getattr(env_, "video_paused", contextlib.nullcontext)
-            self._video_replayed = getattr(env_, "video_replayed", None)
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side), video_paused():     # warm-up outside capture (lazy inits of libraries, autotuning)
-                self._load_live(self._g_in)
-                body()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            self._restore_env(snap)
-            for t, b in zip(flat, backup):
-                t.copy_(b)
-            torch.cuda.synchronize(self.device)
-            self._rollout_graph = torch.cuda.CUDAGraph()
-            self._load_live(self._g_in)
-            # thread_local: RCCL's watchdog thread may touch the HIP runtime while this thread captures
-            with torch.cuda.graph(self._rollout_graph, capture_error_mode="thread_local"), video_paused():
+            live = [self._g_in[0], self._g_in[1]] + self._g_in[2] + self._g_in[3:5]
+            if getattr(self, "fused_rollout", False):
+                live += [self.meter, self.roll_counter]
+
+            def rollout():
                 self._load_live(self._g_in)
                 body()
                 self._g_out = [self.obs, self.dones, self.rnn_states, self.current_rewards, self.current_lengths,
                                self.game_rewards.mean, self.game_rewards.current_size, self.game_lengths.mean,
                                self.game_lengths.current_size]
-        if self._video_replayed is not None:
-            self._video_replayed(self.horizon_length, before=True)
+
+            self._rollout_graph = graph_capture.capture_rolled_back(self.device, rollout, live + env.live_tensors(), env)
         with _Range("rollout_graph_replay"):
-            self._rollout_graph.replay()
-        if self._video_replayed is not None:
-            self._video_replayed(self.horizon_length)
+            graph_capture.replay_observed(self._rollout_graph, env, self.horizon_length)
         self._graph_replayed = True
         # carry the outputs over to the static inputs of the next replay
         o = self._g_out
@@ -855,28 +835,6 @@ class A2CAgent(FastInferenceMixin):
         self.current_rewards, self.current_lengths = g[3], g[4]
         self.game_rewards.mean, self.game_rewards.current_size = g[5], g[6]
         self.game_lengths.mean, self.game_lengths.current_size = g[7], g[8]
-
-    def _snapshot_env(self):
-        env = getattr(self.vec_env, "env", self.vec_env)
-        snap = {"state": env.state.clone(), "reset": env.reset_buf.clone(), "progress": env.progress_buf.clone(),
-                "step": env.step_count, "rng": torch.cuda.get_rng_state(self.device)}
-        if getattr(self, "fused_rollout", False):
-            snap["agent"] = [t.clone() for t in (self.meter, self.roll_counter)]
-        if getattr(env, "episode_log", None) is not None:     # EPISODE_LOG: the warm-up pass finishes episodes too
-            snap["episodes"] = [(t, t.clone()) for t in env.episode_log.live_tensors()]
-        return snap
-
-    def _restore_env(self, snap):
-        env = getattr(self.vec_env, "env", self.vec_env)
-        torch.cuda.synchronize(self.device)
-        env.state.copy_(snap["state"]); env.reset_buf.copy_(snap["reset"]); env.progress_buf.copy_(snap["progress"])
-        env.step_count = snap["step"]
-        torch.cuda.set_rng_state(snap["rng"], self.device)
-        if "agent" in snap:
-            self.meter.copy_(snap["agent"][0])
-            self.roll_counter.copy_(snap["agent"][1])
-        for t, b in snap.get("episodes", ()):
-            t.copy_(b)
 
     # ------------------------------------------------------------------ dataset (R5)
     def prepare_dataset(self, batch):

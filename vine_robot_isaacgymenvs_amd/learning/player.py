@@ -6,13 +6,13 @@ configuration.  The device path (the default network on the four-lanes-per-env s
 three hand-written launches per step -- the trainer's split MLP and LSTM step (``FastInferenceMixin``) and
 ``vine_step_eval`` (include/vine_ppo.h), which applies the policy head, steps the env and accounts for episodes --
 replayed as one hipGraph of ``player.graph_steps`` steps.  It reports per-episode task statistics (``eval_report``)."""
-import contextlib
 import math
 
 import numpy as np
 import torch
 
 from .. import abi
+from . import graph_capture
 from .fast_inference import FastInferenceMixin
 from .network import ModelA2CContinuousLogStd
 
@@ -265,37 +265,17 @@ class PpoPlayerContinuous(FastInferenceMixin):
     def _capture(self, env):
         """``graph_steps`` steps as one graph, as the trainer captures its rollout: a warm-up pass on a side stream whose
         effects are rolled back (env state, step count -- the key of sampled actions --, LSTM state, accounting), then the
-        capture pass, which executes nothing."""
+        capture pass, which executes nothing (``graph_capture.capture_rolled_back``)."""
         d, f = self._dev, self._fast
-        live = [env.state, env.reset_buf, env.progress_buf, env.rew_buf, env.timeout_buf, self.rnn_states[0], self.rnn_states[1],
-                f["xh2"][0], f["xh2"][1], d["obs_ring"][0], d["obs_ring"][1], d["episode"], d["totals"], d["mu"], d["action"],
-                d["dones"]]
-        if getattr(env, "trajectory", None) is not None:     # RECORD_TRAJECTORIES: the warm-up pass writes rows too
-            live += env.trajectory.live_tensors()
-        if getattr(env, "episode_log", None) is not None:    # EPISODE_LOG: and finishes episodes
-            live += env.episode_log.live_tensors()
-        backup = [t.clone() for t in live]
-        step, num_steps, rng = env.step_count, env.num_steps, torch.cuda.get_rng_state(self.device)
-        video_paused = getattr(env, "video_paused", contextlib.nullcontext)
+        live = [self.rnn_states[0], self.rnn_states[1], f["xh2"][0], f["xh2"][1], d["obs_ring"][0], d["obs_ring"][1],
+                d["episode"], d["totals"], d["mu"], d["action"], d["dones"]]
+        num_steps = env.num_steps
 
         def body():
             for _ in range(self.graph_steps):
                 self._device_step()
 
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side), video_paused():
-            body()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        for t, b in zip(live, backup):
-            t.copy_(b)
-        env.step_count = step
-        torch.cuda.set_rng_state(rng, self.device)
-        torch.cuda.synchronize(self.device)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"), video_paused():
-            body()
+        graph = graph_capture.capture_rolled_back(self.device, body, live + env.live_tensors(), env)
         env.num_steps = num_steps
         return graph
 
@@ -318,18 +298,12 @@ class PpoPlayerContinuous(FastInferenceMixin):
         # CAPTURE_VIDEO: eager throughout (the capture schedule is not wired into this graph).  RECORD_TRAJECTORIES and
         # EPISODE_LOG are: their launches are captured with the steps, and the host is told of every replay.
         graphed = self.graph_steps > 0 and n_steps >= self.graph_steps and getattr(env, "video", None) is None
-        observed = getattr(env, "trajectory", None) is not None or getattr(env, "episode_log", None) is not None
-        replayed = getattr(env, "video_replayed", None) if observed else None
         done = 0
         if graphed:
             if self._eval_graph is None:
                 self._eval_graph = self._capture(env)
             for _ in range(n_steps // self.graph_steps):
-                if replayed is not None:
-                    replayed(self.graph_steps, before=True)
-                self._eval_graph.replay()
-                if replayed is not None:
-                    replayed(self.graph_steps)
+                graph_capture.replay_observed(self._eval_graph, env, self.graph_steps)
                 env.num_steps += self.graph_steps
             done = n_steps // self.graph_steps * self.graph_steps
         for _ in range(n_steps - done):

@@ -23,11 +23,10 @@ ARCH = "gfx950"
 
 FINGERPRINT = LIB + ".fingerprint"
 _INC = os.path.join(os.path.dirname(_HERE), "include")
-_HEADERS = [os.path.join(_INC, "vine.h"), os.path.join(_INC, "vine_ppo.h"), os.path.join(_INC, "vine_render.h"),
-            os.path.join(_INC, "vine_record.h"), os.path.join(_INC, "vine_episodes.h"), os.path.join(_INC, "vine_env_params.h"),
-            os.path.join(_INC, "vine_sysid.h"), os.path.join(_HERE, "csrc", "vine_task_shared.h"),
-            os.path.join(_HERE, "csrc", "vine_geometry.h"), os.path.join(_HERE, "csrc", "vine_render_internal.h"),
-            os.path.join(_HERE, "csrc", "vine_policy_head.h"), os.path.join(_HERE, "csrc", "vine_ppo_formulas.h")]
+_HEADERS = ([os.path.join(_INC, h) for h in ("vine.h", "vine_ppo.h", "vine_render.h", "vine_record.h", "vine_episodes.h",
+                                              "vine_env_params.h", "vine_sysid.h")]
+            + [os.path.join(_HERE, "csrc", h) for h in ("vine_task_shared.h", "vine_geometry.h", "vine_observer.h",
+                                                        "vine_policy_head.h", "vine_ppo_formulas.h")])
 DEPS = list(SOURCES) + _HEADERS
 
 _lib = None
@@ -113,7 +112,7 @@ def load():
     if _lib is None and os.environ.get("VINE_HIP_LIB"):
         # experiments only (A/B builds of the kernels with other compile flags): load exactly this file
         import torch  # noqa: F401
-        _lib = abi.declare_sysid(abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(os.environ["VINE_HIP_LIB"]))))))))
+        _lib = abi.declare_all(C.CDLL(os.environ["VINE_HIP_LIB"]))
         return _lib
     if _lib is None:
         # PyTorch-ROCm ships its own libamdhip64.so.7; it must be the HIP runtime of the process, so it is
@@ -135,7 +134,7 @@ def load():
                         build()
             else:
                 raise RuntimeError("libvine_hip.so was built from different sources and no hipcc is available")
-        _lib = abi.declare_sysid(abi.declare_env_params(abi.declare_episodes(abi.declare_record(abi.declare_render(abi.declare_ppo(abi.declare(C.CDLL(LIB))))))))
+        _lib = abi.declare_all(C.CDLL(LIB))
     return _lib
 
 

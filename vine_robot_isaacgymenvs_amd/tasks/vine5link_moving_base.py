@@ -7,6 +7,7 @@ The per-step work of the reference's hooks -- ``pre_physics_step`` (V5:922), the
 ``compute_reward`` (V5:1218) -- is one kernel launch behind ``vine_step`` (include/vine.h).
 This class keeps the constructor signature, the buffers and the attributes callers read.
 """
+import contextlib
 import ctypes as C
 import logging
 import os
@@ -174,38 +175,99 @@ class Vine5LinkMovingBase(VecTask):
             # replay overwrites the DOF state before every step without moving the bodies: the step kernel must keep
             # reading the tip / cart rigid-body states from memory, which it does with introspection on
             self.set_introspection(True)
-        if self.cfg["env"].get("CAPTURE_VIDEO", False):
-            if int(os.getenv("LOCAL_RANK", "0")) == 0:
-                self._setup_video()
-            else:           # every rank would write the same file names: rank 0 records its env, the others do not draw
-                self.logger.info("CAPTURE_VIDEO: recorded by rank 0 only")
-        if self.cfg["env"].get("RECORD_TRAJECTORIES", False):
-            if int(os.getenv("LOCAL_RANK", "0")) == 0:
-                self._setup_trajectory()
-            else:
-                self.logger.info("RECORD_TRAJECTORIES: recorded by rank 0 only")
-        if self.cfg["env"].get("EPISODE_LOG", False):
-            if int(os.getenv("LOCAL_RANK", "0")) == 0:
-                self._setup_episode_log()
-            else:
-                self.logger.info("EPISODE_LOG: logged by rank 0 only")
+        if self._on_rank0("CAPTURE_VIDEO", "recorded"):
+            self._setup_video()
+        if self._on_rank0("RECORD_TRAJECTORIES", "recorded"):
+            self._setup_trajectory()
+        if self._on_rank0("EPISODE_LOG", "logged"):
+            self._setup_episode_log()
+
+    # ------------------------------------------------------------------ step observers (utils/observers.py)
+    def _on_rank0(self, key, done):
+        """Is ``env.<key>`` on, and is this the rank that does it?  Every rank would write the same file names: rank 0
+        records its env, the others launch nothing."""
+        if not self.cfg["env"].get(key, False):
+            return False
+        if int(os.getenv("LOCAL_RANK", "0")) == 0:
+            return True
+        self.logger.info(f"{key}: {done} by rank 0 only")
+        return False
+
+    def _stamp(self):
+        """``time_str`` (V5:145), made once: every observer's files carry the same stamp."""
+        if not hasattr(self, "time_str"):
+            import datetime
+            self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
+        return self.time_str
+
+    def _out_dir(self, key):
+        return self.cfg["env"].get(key + "_DIR") or os.path.join("runs", self.cfg["name"])     # V5:140
+
+    def _add_observer(self, observer):
+        if self.env_params is not None and hasattr(observer, "env_params_of"):
+            # ENV_PARAMS: a recording says which plant produced it, the episode file holds the table its env column indexes
+            observer.env_params_of, observer.env_param_names = self.env_params_of, self.env_param_names
+        self._observers.append(observer)
+        return observer
+
+    @property
+    def observers(self):
+        """What rides behind every step, in launch order (the protocol: utils/observers.py)."""
+        return list(self._observers)
+
+    def live_tensors(self):
+        """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore of
+        the env and of its observers (in their order: the episode log harvests here)."""
+        live = [self._state, self.reset_buf, self.progress_buf, self.rew_buf, self.timeout_buf]
+        for o in self._observers:
+            live += o.live_tensors()
+        return live
+
+    @contextlib.contextmanager
+    def observers_paused(self):
+        """Steps enqueued inside are not counted by any observer (the warm-up and capture passes of a hipGraph, whose
+        effects are rolled back or not executed at all)."""
+        held = list(self._observers)
+        for o in held:
+            # such a pass still launches the draw / record kernels, which write the rings from the device's counter:
+            # a harvest copy still in flight on an observer's side stream must have read its ring first
+            if o.copy_done is not None and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(self.device).wait_event(o.copy_done)
+                o.copy_done = None
+            o.paused += 1
+        try:
+            yield
+        finally:
+            for o in held:
+                o.paused -= 1
+
+    def observers_replayed(self, n_steps, before=False):
+        """A captured graph holding ``n_steps`` steps (and their observers' launches) is about to be / has been
+        replayed."""
+        for o in self._observers:
+            (o.before if before else o.advance)(n_steps)
+
+    def _observe(self, actions):
+        """Behind a step launch: every observer's launch on the same stream, then its host-side count.  ``actions``:
+        device address of the action buffer the step consumed."""
+        for o in self._observers:
+            o.enqueue(self._stream(), actions)
+            o.advance(1)
 
     # ------------------------------------------------------------------ CAPTURE_VIDEO (V5:205-221, 1169-1207)
     def _setup_video(self):
         """The camera of V5:206-221 as a ``VineRenderConfig`` (include/vine_render.h), the device frame ring and the
-        writer.  Frames are drawn by a launch behind every step; see utils/video.py for the harvest."""
-        import datetime
+        writer.  Frames are drawn by a launch behind every step."""
         from ..utils import video
         env = self.cfg["env"]
         torch.cuda.synchronize(self.device)
         tip_y = float(self._state[abi.VF_TIP_Y, self.index_to_view])         # cam_target, V5:206-207
         rcfg = video.render_config(self._lib, env, tip_y, INIT_Z)
         views = [(self.index_to_view + v) % self.num_envs for v in range(rcfg.num_views)]
-        self.log_dir = env.get("CAPTURE_VIDEO_DIR") or os.path.join("runs", self.cfg["name"])     # V5:140
-        self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")                      # V5:145
-        self._video = video.VideoCapture(self._lib, self._handle, rcfg, views, self.progress_buf, self.device,
-                                         self.log_dir, self.time_str, self.control_dt, self.logger)
-        self._observers.append(self._video)
+        self.log_dir = self._out_dir("CAPTURE_VIDEO")
+        self._video = self._add_observer(video.VideoCapture(
+            self._lib, self._handle, rcfg, views, self.progress_buf, self.device, self.log_dir, self._stamp(),
+            self.control_dt, self.logger))
         self.logger.info(f"CAPTURE_VIDEO: {rcfg.num_frames} frames of {rcfg.num_views} view(s) at "
                          f"{rcfg.width} x {rcfg.height} every {rcfg.capture_every} steps -> "
                          f"{self.log_dir}/{self.time_str}_video_<num_steps>.png")
@@ -215,39 +277,10 @@ class Vine5LinkMovingBase(VecTask):
         """The ``VideoCapture`` of this env (``None`` unless ``CAPTURE_VIDEO``)."""
         return self._video
 
-    def video_paused(self):
-        """Context manager: steps enqueued inside are not counted towards the capture or the recording (the warm-up and
-        capture passes of a hipGraph, whose effects are rolled back or not executed at all)."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def paused():
-            held = list(self._observers)
-            for o in held:
-                # such a pass still launches the draw / record kernels, which write the rings from the device's counter:
-                # a harvest copy still in flight on an observer's side stream must have read its ring first
-                if o.copy_done is not None and not torch.cuda.is_current_stream_capturing():
-                    torch.cuda.current_stream(self.device).wait_event(o.copy_done)
-                    o.copy_done = None
-                o.paused += 1
-            try:
-                yield
-            finally:
-                for o in held:
-                    o.paused -= 1
-        return paused()
-
-    def video_replayed(self, n_steps, before=False):
-        """A captured graph holding ``n_steps`` steps (and their draw / record launches) is about to be / has been
-        replayed."""
-        for o in self._observers:
-            (o.before if before else o.advance)(n_steps)
-
     # ------------------------------------------------------------------ RECORD_TRAJECTORIES (include/vine_record.h)
     def _setup_trajectory(self):
         """The recorded envs, the device row ring and the writer; rows are written by a launch behind every step, see
-        utils/trajectory.py for the harvest and the MAT files."""
-        import datetime
+        utils/trajectory.py for the MAT files."""
         from ..utils import trajectory
         env = self.cfg["env"]
         every = int(env.get("RECORD_TRAJECTORIES_EVERY", 1000))
@@ -262,15 +295,10 @@ class Vine5LinkMovingBase(VecTask):
         if any(e < 0 or e >= self.num_envs for e in envs):
             raise ValueError(f"RECORD_TRAJECTORIES_ENVS: env indices must lie in [0, {self.num_envs}): {envs}")
         rcfg = trajectory.record_config(self._lib, every, steps, len(envs))
-        directory = env.get("RECORD_TRAJECTORIES_DIR") or os.path.join("runs", self.cfg["name"])
-        if not hasattr(self, "time_str"):
-            self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
-        self._trajectory = trajectory.TrajectoryRecorder(
+        directory = self._out_dir("RECORD_TRAJECTORIES")
+        self._trajectory = self._add_observer(trajectory.TrajectoryRecorder(
             self._lib, self._handle, rcfg, envs, (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf),
-            self.device, directory, self.time_str, self.control_dt, self.logger)
-        if self.env_params is not None:          # ENV_PARAMS: a recording says which plant produced it
-            self._trajectory.env_params_of, self._trajectory.env_param_names = self.env_params_of, self.env_param_names
-        self._observers.append(self._trajectory)
+            self.device, directory, self._stamp(), self.control_dt, self.logger))
         self.logger.info(f"RECORD_TRAJECTORIES: {steps} steps of env(s) {envs} every {every} steps -> "
                          f"{directory}/{self.time_str}_trajectory_<num_steps>_env<e>.mat")
 
@@ -284,36 +312,22 @@ class Vine5LinkMovingBase(VecTask):
         """The accumulators, totals and row ring of the per-episode task log; a launch behind every step keeps them, see
         utils/episodes.py for the harvest and the file.  The log reads the step's reward-matrix row, so a matrix is bound
         here (arming introspection) before anything is captured; one bound for a dashboard already is shared."""
-        import datetime
         from ..utils import episodes
         env = self.cfg["env"]
         if self._reward_matrix is None:
             self.bind_reward_matrix()
         capacity = int(env.get("EPISODE_LOG_CAPACITY", 1048576))
-        directory = env.get("EPISODE_LOG_DIR") or os.path.join("runs", self.cfg["name"])
-        if not hasattr(self, "time_str"):
-            self.time_str = datetime.datetime.now().strftime("%Y-%m-%d_%H-%M-%S")
         task = {k: env[k] for k in episodes.TASK_KEYS if k in env}
-        self._episode_log = episodes.EpisodeLog(
+        self._episode_log = self._add_observer(episodes.EpisodeLog(
             self._lib, self._handle, self.num_envs, capacity, bool(env.get("EPISODE_LOG_TABLE", True)),
-            (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf), self.device, directory, self.time_str,
-            task, self.logger)
-        if self.env_params is not None:          # ENV_PARAMS: the file holds the table its env column indexes
-            self._episode_log.env_params_of, self._episode_log.env_param_names = self.env_params_of, self.env_param_names
-        self._observers.append(self._episode_log)
+            (self.rew_buf, self.reset_buf, self.progress_buf, self.timeout_buf), self.device,
+            self._out_dir("EPISODE_LOG"), self._stamp(), task, self.logger))
         self.logger.info(f"EPISODE_LOG: one row per finished episode (ring of {capacity}) -> {self._episode_log.path}")
 
     @property
     def episode_log(self):
         """The ``EpisodeLog`` of this env (``None`` unless ``EPISODE_LOG``)."""
         return self._episode_log
-
-    def _observe(self, actions):
-        """Behind a step launch: every observer's launch on the same stream, then its host-side count.  ``actions``:
-        device address of the action buffer the step consumed."""
-        for o in self._observers:
-            o.enqueue(self._stream(), actions)
-            o.advance(1)
 
     # ------------------------------------------------------------------ MAT_FILE replay (V5:281-297, 947-982)
     def read_mat_file(self, filename):
@@ -444,16 +458,27 @@ class Vine5LinkMovingBase(VecTask):
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _launch_step(self, fn, first_arg, actions_ptr, obs_out):
+        """One step launch (``vine_step``, ``vine_step_rollout`` or ``vine_step_eval``: ``first_arg`` is the action buffer
+        or the address of the argument block) with the observers around it."""
+        for o in self._observers:
+            o.before(1)
+        native.check(fn(self._handle, first_arg, obs_out.data_ptr(), self.rew_buf.data_ptr(), self.reset_buf.data_ptr(),
+                        self.progress_buf.data_ptr(), self.timeout_buf.data_ptr(), self._stream()), self._lib)
+        self._observe(actions_ptr)
+        self.num_steps += 1
+
+    def _rebind(self, obs_out):
+        """The buffers re-bound exactly as ``step_into`` does."""
+        self.obs_buf = obs_out
+        self.obs_dict["obs"] = obs_out.to(self.rl_device)
+        self.extras["time_outs"] = self.timeout_buf.to(self.rl_device)
+        return obs_out
+
     def _native_step(self, actions, obs_out):
         if self.mat is not None:
             self.overwrite_with_mat()
-        for o in self._observers:
-            o.before(1)
-        native.check(self._lib.vine_step(self._handle, actions.data_ptr(), obs_out.data_ptr(), self.rew_buf.data_ptr(),
-                                         self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
-                                         self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        self._observe(actions.data_ptr())
-        self.num_steps += 1
+        self._launch_step(self._lib.vine_step, actions.data_ptr(), actions.data_ptr(), obs_out)
 
     def rollout_step_blocks(self):
         """Rows of the per-workgroup episode sums ``step_rollout_into`` writes (0: this configuration does not run the
@@ -465,18 +490,8 @@ class Vine5LinkMovingBase(VecTask):
         rows in front of the step, the rollout bookkeeping behind it -- an extension for the PPO loop (the trainer's
         ``_rollout_body_fused``); ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.RolloutArgs; the
         observation goes to ``obs_out`` and the buffers are re-bound exactly as ``step_into`` does."""
-        import ctypes as C
-        for o in self._observers:
-            o.before(1)
-        native.check(self._lib.vine_step_rollout(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
-                                                 self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
-                                                 self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        self._observe(args.action_out)
-        self.num_steps += 1
-        self.obs_buf = obs_out
-        self.obs_dict["obs"] = obs_out.to(self.rl_device)
-        self.extras["time_outs"] = self.timeout_buf.to(self.rl_device)
-        return obs_out
+        self._launch_step(self._lib.vine_step_rollout, C.addressof(args), args.action_out, obs_out)
+        return self._rebind(obs_out)
 
     def eval_step_rows(self):
         """Rows of the per-workgroup float64 totals ``step_eval_into`` adds to (0: this configuration does not run the
@@ -488,18 +503,8 @@ class Vine5LinkMovingBase(VecTask):
         output rows in front of the step, per-episode task statistics behind it -- an extension for the player's device
         path; ``VecTask.step`` / ``step_into`` are untouched.  ``args``: abi.EvalArgs; the observation goes to ``obs_out``
         and the buffers are re-bound exactly as ``step_into`` does."""
-        import ctypes as C
-        for o in self._observers:
-            o.before(1)
-        native.check(self._lib.vine_step_eval(self._handle, C.addressof(args), obs_out.data_ptr(), self.rew_buf.data_ptr(),
-                                              self.reset_buf.data_ptr(), self.progress_buf.data_ptr(),
-                                              self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        self._observe(args.action_out)
-        self.num_steps += 1
-        self.obs_buf = obs_out
-        self.obs_dict["obs"] = obs_out.to(self.rl_device)
-        self.extras["time_outs"] = self.timeout_buf.to(self.rl_device)
-        return obs_out
+        self._launch_step(self._lib.vine_step_eval, C.addressof(args), args.action_out, obs_out)
+        return self._rebind(obs_out)
 
     def reset_idx(self, env_ids):
         """V5:774-839 for callers outside the step (reset_done, V5:715-718)."""

@@ -2,8 +2,7 @@
 (include/vine_episodes.h), the harvest, and the ``.npz`` file.
 
 The rows are written on the device by a launch behind every step (any step entry point, both step kernels): one row per
-finished episode of every env.  ``EpisodeLog`` is a step observer like ``video.VideoCapture`` and
-``trajectory.TrajectoryRecorder`` (``before`` / ``enqueue`` / ``advance`` / ``paused`` / ``copy_done``).  Its harvest reads
+finished episode of every env.  ``EpisodeLog`` is a step observer (the protocol: utils/observers.py).  Its harvest reads
 the device cursor and copies the rows appended since the last one; that synchronises, so it runs where the host
 synchronises anyway (once per training iteration, at the end of a player's run) and, inside a long run of steps, whenever
 the worst case -- every env finishing every step -- could have filled half the ring since the last harvest.  Used through
@@ -161,7 +160,7 @@ def load_env_params(path):
 
 class EpisodeLog:
     """The device buffers of one env handle's episode log, the host's count of steps since the last harvest, and the
-    harvest.  Same calls as the other step observers."""
+    harvest.  A step observer (the protocol: utils/observers.py); not windowed, so its harvest is its own."""
 
     def __init__(self, lib, handle, num_envs, capacity, with_table, buffers, device, directory, time_str, task, logger=None):
         """``buffers``: the step's output tensors ``(rew, reset, progress, timeouts)``.  A reward matrix must already be

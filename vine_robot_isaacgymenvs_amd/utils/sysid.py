@@ -129,7 +129,7 @@ class Evaluator:
         self.window = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.err = torch.zeros(n, dtype=torch.float64, device=self.device)
         self.alive = torch.ones(n, dtype=torch.uint8, device=self.device)
-        self.use_graph = bool(graph) and bool(getattr(task, "graph_capturable", False)) and not task._observers
+        self.use_graph = bool(graph) and bool(getattr(task, "graph_capturable", False)) and not task.observers
         self.graph = None
         self.steps_run = 0
 

@@ -1,28 +1,18 @@
-"""RECORD_TRAJECTORIES on the host side: the harvest of the device row ring and the MAT files.
+"""RECORD_TRAJECTORIES on the host side: the row ring of the step-observer protocol (utils/observers.py) and the MAT files.
 
 The rows are written on the device by ``vine_record_scheduled`` (include/vine_record.h), a launch behind every step that
 decides from the device's step counter whether the step just finished belongs to a recording window -- the numeric twin
-of CAPTURE_VIDEO (utils/video.py), with the same schedule (``video.capture_schedule``) and the same harvest: the host
-counts the steps it has enqueued, a completed window is copied to pinned host memory on a side stream and handed to a
-writer thread, and the training loop never waits for the disk.
+of CAPTURE_VIDEO (utils/video.py), with the same schedule and the same harvest (``observers.WindowRing``).
 
 One file per recorded env and window, ``<dir>/<time_str>_trajectory_<last>_env<e>.mat``, in the layout ``MAT_FILE``
 reads (tasks/vine5link_moving_base.py ``read_mat_file``; V5:281-297) with extra keys beside the reference's six."""
-import collections
-import logging
 import os
-import queue
-import threading
-import time
 
 import numpy as np
 import torch
 
 from .. import abi, native
-from .video import capture_schedule
-
-
-KEEP = 256       # entries of a recorder's bookkeeping lists
+from .observers import KEEP, WindowRing  # noqa: F401  (KEEP: importable from here as before)
 
 
 def record_config(lib, every, steps, num_envs):
@@ -83,16 +73,16 @@ def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, 
     return path
 
 
-class TrajectoryRecorder:
-    """The row ring of one env handle, the host's count of its steps, and the harvest.  Same calls as
-    ``video.VideoCapture``: ``before`` / ``enqueue`` / ``advance`` around the steps, ``paused``, ``set_steps``,
-    ``drain`` / ``close``."""
+class TrajectoryRecorder(WindowRing):
+    """The row ring of one env handle: a ``WindowRing`` of ``rcfg.num_steps`` rows per recorded env every
+    ``rcfg.record_every`` steps."""
+
+    SKIPPED, WRITER = "Trajectories", "trajectory"
 
     def __init__(self, lib, handle, rcfg, envs, buffers, device, directory, time_str, control_dt, logger=None):
         """``buffers``: the step's output tensors ``(rew, reset, progress, timeouts)``; ``envs``: the K env indices, checked
         by the caller against the env count."""
-        self.lib, self.handle, self.rcfg, self.device = lib, handle, rcfg, device
-        self.logger = logger or logging.getLogger(__name__)
+        self.lib, self.handle, self.rcfg = lib, handle, rcfg
         self.directory, self.time_str, self.control_dt = directory, time_str, float(control_dt)
         self.env_ids = [int(e) for e in envs]
         assert len(self.env_ids) == rcfg.num_envs
@@ -106,128 +96,40 @@ class TrajectoryRecorder:
         self.steps = torch.full((rcfg.num_steps,), -1, dtype=torch.int64, device=device)
         self.host = torch.empty(self.ring.shape, dtype=torch.float32, pin_memory=True)
         self.host_steps = torch.empty(self.steps.shape, dtype=torch.int64, pin_memory=True)
-        self.steps_done = 0          # the device's step count, as the host knows it from what it has enqueued
-        self.valid_from = 0
-        self.paused = 0
-        self.side = torch.cuda.Stream(device=device)
-        self.copy_done = None        # event behind the last ring -> host copy, until the ring may be overwritten again
-        self.host_free = threading.Event()
-        self.host_free.set()
-        self.jobs = queue.Queue()
-        # the most recent files and skipped windows, and the host cost of the most recent windows (the harvest call, the
-        # writer thread); bounded: a long training completes thousands of windows
-        self.written, self.skipped = collections.deque(maxlen=KEEP), collections.deque(maxlen=KEEP)
-        self.harvest_seconds, self.write_seconds = collections.deque(maxlen=KEEP), collections.deque(maxlen=KEEP)
-        self.windows_written = self.windows_skipped = 0
         self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
         import scipy.io  # noqa: F401  (here, not in the writer thread: the first import takes 0.3 s, longer than a window)
-        self.writer = threading.Thread(target=self._write_loop, name="vine-trajectory-writer", daemon=True)
-        self.writer.start()
+        super().__init__(device, logger)
 
     def live_tensors(self):
-        """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore."""
         return [self.ring, self.steps]
 
-    # -- device side -------------------------------------------------------------------------------------------------
     def enqueue(self, stream, actions):
-        """The scheduled record, behind the step just enqueued on ``stream`` (captured with it inside a hipGraph).
-        ``actions``: device address of the [N, 2] action buffer that step consumed."""
+        """The scheduled record, behind the step just enqueued on ``stream`` (captured with it inside a hipGraph)."""
         native.check(self.lib.vine_record_scheduled(self.handle, self.rcfg, self.envs.data_ptr(), actions,
                                                     self.rew.data_ptr(), self.reset.data_ptr(), self.progress.data_ptr(),
                                                     self.timeouts.data_ptr(), self.ring.data_ptr(), self.steps.data_ptr(),
                                                     stream), self.lib)
 
-    # -- host side ---------------------------------------------------------------------------------------------------
-    def set_steps(self, steps):
-        """The step count was set from outside: windows already open at that count are not complete."""
-        if int(steps) == self.steps_done:
-            return
-        self.steps_done = int(steps)
-        self.valid_from = int(steps)
+    def _window(self):
+        return self.rcfg.record_every, self.rcfg.num_steps
 
-    def before(self, n_steps):
-        """Call before enqueueing ``n_steps`` steps: if they open a window, the copy of the previous one must be
-        complete before slot 0 is written again."""
-        if self.paused or self.copy_done is None:
-            return
-        _, _, opens = capture_schedule(self.steps_done, n_steps, self.rcfg.record_every, self.rcfg.num_steps)
-        if opens:
-            torch.cuda.current_stream(self.device).wait_event(self.copy_done)
-            self.copy_done = None
+    def _copies(self):
+        return [(self.ring, self.host), (self.steps, self.host_steps)]
 
-    def advance(self, n_steps):
-        """Call after enqueueing ``n_steps`` steps (each with its scheduled record behind it)."""
-        if self.paused:
-            return
-        _, completed, _ = capture_schedule(self.steps_done, n_steps, self.rcfg.record_every, self.rcfg.num_steps,
-                                           self.valid_from)
-        self.steps_done += int(n_steps)
-        for start, last in completed:
-            if self.steps_done > start + self.rcfg.record_every:
-                self._skip(last, "the next window began within the same batch of steps")
-            else:
-                self._harvest(start, last)
-
-    def _skip(self, last, why):
-        self.skipped.append(last)
-        self.windows_skipped += 1
-        self.logger.info(f"Trajectories of the window ending at step {last} not saved: {why}")
-
-    def _harvest(self, start, last):
-        if not self.host_free.is_set():
-            self._skip(last, "the writer still holds the host buffer")
-            return
-        t0 = time.perf_counter()
-        self.host_free.clear()
-        main = torch.cuda.current_stream(self.device)
-        recorded = torch.cuda.Event()
-        recorded.record(main)
-        self.side.wait_event(recorded)
-        with torch.cuda.stream(self.side):
-            self.host.copy_(self.ring, non_blocking=True)
-            self.host_steps.copy_(self.steps, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(self.side)
-        self.copy_done = done
-        params = self.env_params_of(self.env_ids) if self.env_params_of is not None else None
-        self.jobs.put((done, start, last, params))
-        self.harvest_seconds.append(time.perf_counter() - t0)
+    def _job_extra(self):
+        return self.env_params_of(self.env_ids) if self.env_params_of is not None else None
 
     def path(self, last, env):
         return os.path.join(self.directory, f"{self.time_str}_trajectory_{last}_env{env}.mat")
 
-    def _write_loop(self):
-        while True:
-            job = self.jobs.get()
-            if job is None:
-                return
-            done, start, last, params = job
-            try:
-                done.synchronize()
-                t0 = time.perf_counter()
-                rows, steps = self.host.numpy(), self.host_steps.numpy()
-                if not np.array_equal(steps, np.arange(start, last + 1)):       # the device's own account of slot <-> step
-                    raise RuntimeError(f"window {start}..{last}: the device recorded steps {steps.tolist()}")
-                os.makedirs(self.directory, exist_ok=True)
-                for k, e in enumerate(self.env_ids):
-                    self.written.append(write_trajectory_mat(
-                        self.path(last, e), rows[:, k], steps, self.control_dt, e,
-                        params[:, k] if params is not None else None, self.env_param_names))
-                self.write_seconds.append(time.perf_counter() - t0)
-                self.windows_written += 1
-                self.logger.info(f"Saved {len(self.env_ids)} trajectories of steps {start}..{last} to "
-                                 f"{self.path(last, '<e>')}")
-            except Exception:                     # the training loop does not die of a full disk
-                self.logger.exception("trajectory writer failed")
-            finally:
-                self.host_free.set()
-
-    def drain(self):
-        """Wait until every harvested window is on disk."""
-        self.host_free.wait()          # at most one window is in flight: the buffer is taken before its job is queued
-
-    def close(self):
-        if self.writer is not None:
-            self.jobs.put(None)
-            self.writer.join()
-            self.writer = None
+    def _write(self, start, last, params):
+        rows, steps = self.host.numpy(), self.host_steps.numpy()
+        if not np.array_equal(steps, np.arange(start, last + 1)):       # the device's own account of slot <-> step
+            raise RuntimeError(f"window {start}..{last}: the device recorded steps {steps.tolist()}")
+        os.makedirs(self.directory, exist_ok=True)
+        for k, e in enumerate(self.env_ids):
+            self.written.append(write_trajectory_mat(
+                self.path(last, e), rows[:, k], steps, self.control_dt, e,
+                params[:, k] if params is not None else None, self.env_param_names))
+        self.logger.info(f"Saved {len(self.env_ids)} trajectories of steps {start}..{last} to "
+                         f"{self.path(last, '<e>')}")
