@@ -13,8 +13,11 @@
  * behaves as if it had never been bound.
  *
  * What cannot be overridden per env, and why:
- *   - masses, lengths, inertias, gravity, dt: their composites (the constant coefficients a_ij, b_i, g b_i of the
- *     absolute-angle Lagrangian, the substep, the reciprocals) are formed in double on the host when the handle is created;
+ *   - the cart's and the links' masses and inertias: not in THIS table.  include/vine_env_inertia.h binds a second table
+ *     beside it that holds them per env, with the composites the step reads (the constant coefficients a_ij, b_i, g b_i of
+ *     the absolute-angle Lagrangian) formed from them in double on the host, as they are when a handle is created;
+ *   - lengths, gravity, dt: they reach the kinematics, the contact geometry, the renderer and the recorder, or are
+ *     per-launch constants of the substep (the reciprocals);
  *   - STIFFNESS and the link angular damping: whether they are zero selects the substep instantiation of the whole launch;
  *   - the physics-mode flags (implicit joint damping, held FPAM damping, stale body state): they select code paths of the
  *     whole launch as well.

@@ -1,5 +1,6 @@
-"""Duration of the one-lane-per-env step with a per-env parameter table (include/vine_env_params.h) against the same kernel
-without one and against the four-lanes-per-env kernel: free space, default observation layout, randomisation on.
+"""Duration of the one-lane-per-env step with a per-env parameter table (include/vine_env_params.h), and with the inertia
+table beside it (include/vine_env_inertia.h), against the same kernel without one and against the four-lanes-per-env kernel:
+free space, default observation layout, randomisation on.
 
 Durations come from a replayed hipGraph of K back-to-back steps between two events (elapsed / K): HIP events around eager
 back-to-back launches are host-bound below about 13 us.  The variants are alternated, ROUNDS times, inside one process.
@@ -22,12 +23,15 @@ ROUNDS = 7
 SPEC = {"DAMPING": [0.01, 0.05], "SMOOTHING_ALPHA_INFLATE": [0.6, 0.95], "SMOOTHING_ALPHA_DEFLATE": [0.6, 0.95],
         "RAIL_VELOCITY_SCALE": [0.7, 1.3], "RAIL_P_GAIN": [7.0, 13.0], "RAIL_D_GAIN": [0.0, 0.4], "RAIL_ACCELERATION": [5.6, 10.4],
         "ACTION_DELAY": [0, abi.MAX_DELAY], "FPAM_K": [0.8, 1.2], "FPAM_C": [0.8, 1.2], "FPAM_b": [0.8, 1.2], "FPAM_B": [0.8, 1.2]}
-# name -> (VINE_STEP_KERNEL, table: None / "own" (every column the configuration's row) / "het" (SPEC))
-VARIANTS = {"lane": ("lane", None), "lane+own_row_table": ("lane", "own"), "lane+heterogeneous_table": ("lane", "het"),
-            "quad": ("quad", None)}
+MASSES = {"CART_MASS": [0.35, 0.7], "LINK_MASS": [0.7, 1.4], "TIP_LINK_MASS": [0.8, 2.0]}
+# name -> (VINE_STEP_KERNEL, table: None / "own" (every column the configuration's row) / "het" (SPEC),
+#          inertia table beside it: None / "own" / "het" (MASSES: all 31 rows vary))
+VARIANTS = {"lane": ("lane", None, None), "lane+own_row_table": ("lane", "own", None),
+            "lane+heterogeneous_table": ("lane", "het", None), "lane+het_table+own_inertia": ("lane", "het", "own"),
+            "lane+het_table+het_inertia": ("lane", "het", "het"), "quad": ("quad", None, None)}
 
 
-def make(n, kern, table):
+def make(n, kern, table, inertia=None):
     cfg = base_cfg(n, 0, True)
     env = type("H", (HipEnv,), {"kernel": kern})(cfg)
     env.set_introspection(False)
@@ -36,6 +40,11 @@ def make(n, kern, table):
         env.table_t = torch.as_tensor(t, device=env.dev).contiguous()
         torch.cuda.synchronize()
         native.check(env.lib.vine_bind_env_params(env.h, env.table_t.data_ptr()), env.lib)
+    if inertia is not None:
+        t = env_params.build_inertia_table(MASSES if inertia == "het" else {"LINK_MASS": 1.0}, env.cfg, 1, n, lib=env.lib)
+        env.inertia_t = torch.as_tensor(t, device=env.dev).contiguous()
+        torch.cuda.synchronize()
+        native.check(env.lib.vine_bind_env_inertia(env.h, env.inertia_t.data_ptr()), env.lib)
     k = 100 if n <= 65536 else 20
     g = torch.Generator(device=env.dev).manual_seed(0)
     acts = [torch.rand((n, 2), device=env.dev, generator=g) * 2 - 1 for _ in range(8)]
@@ -67,9 +76,11 @@ def main():
               % (n, ROUNDS, envs["lane"][2]))
         for name in VARIANTS:
             t = times[name]
-            print("  %-26s %-22s %8.1f %8.1f %8.1f" % (name, envs[name][3], min(t), statistics.median(t), max(t)), flush=True)
+            print("  %-28s %-22s %8.1f %8.1f %8.1f" % (name, envs[name][3], min(t), statistics.median(t), max(t)), flush=True)
         base, het, quad = (statistics.median(times[k]) for k in ("lane", "lane+heterogeneous_table", "quad"))
         print("  heterogeneous table / unbound one-lane: %.3f   / four-lane: %.3f" % (het / base, het / quad))
+        mass = statistics.median(times["lane+het_table+het_inertia"])
+        print("  heterogeneous table and inertia table / heterogeneous table: %.3f   / unbound one-lane: %.3f" % (mass / het, mass / base))
         for env, _, _, _ in envs.values():
             env.close()
         del envs

@@ -5,6 +5,9 @@
       'params={DAMPING: [0.005, 0.1], ACTION_DELAY: {values: [0, 1, 2, 3]}, FPAM_K: [0.7, 1.3]}' \\
       num_envs=4096 iterations=8 horizon=50 stride=25
 
+``params`` also takes the masses: ``CART_MASS`` in kg, ``LINK_MASS`` and ``TIP_LINK_MASS`` as factors on
+the configuration's link masses and inertias, e.g. ``'params={CART_MASS: [0.5, 2.0], LINK_MASS: [0.7, 1.4], DAMPING: [0.005, 0.1]}'``.
+
 ``log``, ``params`` (an ``ENV_PARAMS``-style spec), ``iterations``, ``horizon``, ``stride``, ``weights`` (16 numbers, one per
 row field), ``elite_fraction`` and ``out`` (directory of the .npz; default ``runs/sysid``) are this tool's own
 keys; every other ``key=value`` is an override of the project's configuration, in its syntax (``num_envs=``, ``seed=``,

@@ -502,6 +502,35 @@ def declare_env_params(lib):
     return lib
 
 
+# ---- include/vine_env_inertia.h (product library only)
+# VineEnvInertia = rows of the per-env inertia table [VI_COUNT, num_envs]: 11 primary rows (what a user states), 20 derived
+# rows (what the step kernel reads; vine_env_inertia_derive fills them)
+VI_CART_MASS, VI_LINK_MASS0, VI_LINK_INERTIA0, VI_PRIMARY_COUNT = 0, 1, 6, 11
+VI_MTOT, VI_B0, VI_GB0, VI_ADIAG0, VI_AOFF1 = 11, 12, 17, 22, 27
+VI_COUNT = 31
+# one name per row, the library's own (vine_env_inertia_check names a refused value by it)
+ENV_INERTIA_ROW_NAMES = (("CART_MASS",) + tuple("LINK_MASS[%d]" % i for i in range(NUM_LINKS))
+                         + tuple("LINK_INERTIA[%d]" % i for i in range(NUM_LINKS)) + ("MTOT",)
+                         + tuple("%s[%d]" % (name, i) for name in ("B", "GB", "ADIAG") for i in range(NUM_LINKS))
+                         + tuple("AOFF[%d]" % i for i in range(1, NUM_LINKS)))
+# the names of the ENV_PARAMS spec that fill this table instead of the parameter table (utils/env_params.py): CART_MASS in
+# kg, LINK_MASS a factor on the configuration's five link masses and inertias, TIP_LINK_MASS a further factor on link 4's
+ENV_INERTIA_NAMES = ("CART_MASS", "LINK_MASS", "TIP_LINK_MASS")
+
+ENV_INERTIA_PROTOTYPES = {
+    "vine_env_inertia_row": (C.c_int, [_P(VineConfig), _P(C.c_float)]),
+    "vine_env_inertia_derive": (C.c_int, [_P(VineConfig), _VP, C.c_int]),
+    "vine_env_inertia_check": (C.c_int, [_P(VineConfig), _VP, C.c_int]),
+    "vine_bind_env_inertia": (C.c_int, [_H, _VP]),
+    "vine_env_inertia_bound": (C.c_int, [_H]),
+}
+
+
+def declare_env_inertia(lib):
+    _attach(lib, ENV_INERTIA_PROTOTYPES)
+    return lib
+
+
 # ---- include/vine_sysid.h (product library only)
 SYSID_ABI_VERSION = 1
 SYSID_FIELDS = 16
@@ -544,6 +573,7 @@ def declare(lib):
 
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
-    for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_sysid):
+    for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
+                        declare_sysid):
         declare_one(lib)
     return lib

@@ -28,6 +28,7 @@
 
 #include "../../include/vine.h"
 #include "../../include/vine_env_params.h"
+#include "../../include/vine_env_inertia.h"
 #include "../../include/vine_ppo.h"      // VineRolloutArgs (vine_step_rollout)
 #include "vine_geometry.h"               // link / shelf / pipe shapes (shared with the renderer)
 #include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
@@ -917,7 +918,31 @@ __device__ __forceinline__ void env_params_of(const DevParams& P, const float* _
 #undef EP
 }
 
-template <int OBS_TYPE, bool RANDOMIZE, int OBST, bool ENV_PARAMS = false>   // OBST bit 0: shelf, bit 1: pipe
+// ENV_PARAMS mode 2 (include/vine_env_inertia.h): the env's column of the DERIVED rows of the bound inertia table in place of
+// the mass composites the step reads -- mtot, b[], gb[], the diagonal of a[][] and its column 0 (a_ij = L b_i for every
+// j < i; substep reads column 0 only) -- 20 more coalesced loads, 80 B per env step.  The link inertias themselves are read
+// by the substep only where joint stiffness or link angular damping is switched on (a uniform branch of the launch): five
+// more loads there, none elsewhere.
+__device__ __forceinline__ void env_inertia_of(const float* __restrict__ tab, int n, int e, DevParams& Q) {
+#define EI(r) tab[(size_t)(r) * n + e]
+    Q.mtot = EI(VI_MTOT);
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        Q.b[i] = EI(VI_B0 + i);
+        Q.gb[i] = EI(VI_GB0 + i);
+        Q.a[i][i] = EI(VI_ADIAG0 + i);
+    }
+#pragma unroll
+    for (int i = 1; i < NL; ++i) Q.a[i][0] = EI(VI_AOFF1 + i - 1);
+    if (Q.kq != 0.0f || Q.cad != 0.0f) {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) Q.I[i] = EI(VI_LINK_INERTIA0 + i);
+    }
+#undef EI
+}
+
+// ENV_PARAMS: 0 = the launch's constants for every env, 1 = the parameter table, 2 = the parameter table and the inertia table
+template <int OBS_TYPE, bool RANDOMIZE, int OBST, int ENV_PARAMS = 0>   // OBST bit 0: shelf, bit 1: pipe
 __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevParams PK, float* __restrict__ st,
                                                        const float* __restrict__ actions, float* __restrict__ obs,
                                                        float* __restrict__ rew, long long* __restrict__ reset,
@@ -926,15 +951,17 @@ __global__ __launch_bounds__(VINE_STEP_THREADS) void vine_step_kernel(const DevP
                                                        float* __restrict__ reward_matrix,
                                                        const float* __restrict__ reset_values,
                                                        unsigned long long* __restrict__ counters,
-                                                       const float* __restrict__ env_params) {
+                                                       const float* __restrict__ env_params,
+                                                       const float* __restrict__ env_inertia) {
     constexpr bool SHELF = (OBST & 1) != 0, PIPE = (OBST & 2) != 0, CONTACT = OBST != 0;
     const int n = PK.n;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned long long step = step_of(PK, counters);
     if (e < n) {
         DevParams PL;                                  // ENV_PARAMS: this env's constants; otherwise never touched
-        if constexpr (ENV_PARAMS) env_params_of(PK, env_params, n, e, PL);
-        const DevParams& P = ENV_PARAMS ? PL : PK;
+        if constexpr (ENV_PARAMS != 0) env_params_of(PK, env_params, n, e, PL);
+        if constexpr (ENV_PARAMS == 2) env_inertia_of(env_inertia, n, e, PL);
+        const DevParams& P = ENV_PARAMS != 0 ? PL : PK;
         // ---- VecTask.step: clamp actions (vec_task.py:333); pre_physics_step (V5:922-945) ----
         const float2 act = reinterpret_cast<const float2*>(actions)[e];
         float n0 = 0.0f, n1 = 0.0f;
@@ -2238,6 +2265,27 @@ int validate(const VineConfig* c) {
     return VINE_OK;
 }
 
+// The constant coefficients of the absolute-angle Lagrangian from the masses, accumulated in double: the one statement of
+// them.  make_params rounds them into the handle's constants, vine_env_inertia_derive into a table column
+// (include/vine_env_inertia.h), so a uniform handle and a column of the same float32 masses hold the same bits.
+struct InertiaComposites {
+    double mtot, b[NL], gb[NL], adiag[NL], aoff[NL];      // aoff[i] = L b_i = a_ij for every j < i
+};
+void inertia_composites(float cart_mass, const float* link_mass, const float* link_inertia, float link_length, float link_com,
+                        float gravity, InertiaComposites& o) {
+    double m[NL], mt = cart_mass, L = link_length, l = link_com;
+    for (int i = 0; i < NL; ++i) { m[i] = link_mass[i]; mt += m[i]; }
+    o.mtot = mt;
+    for (int i = 0; i < NL; ++i) {
+        double distal = 0;
+        for (int k = i + 1; k < NL; ++k) distal += m[k];
+        o.b[i] = m[i] * l + L * distal;
+        o.gb[i] = (double)gravity * o.b[i];
+        o.adiag[i] = m[i] * l * l + L * L * distal + (double)link_inertia[i];
+        o.aoff[i] = L * o.b[i];
+    }
+}
+
 void make_params(const VineConfig& c, DevParams& P) {
     memset(&P, 0, sizeof P);
     P.n = c.num_envs; P.num_obs = vine_num_obs(&c); P.obs_type = c.obs_type; P.cfi = c.control_freq_inv;
@@ -2259,23 +2307,18 @@ void make_params(const VineConfig& c, DevParams& P) {
     P.obs_noise = c.obs_noise_std; P.act_noise = c.action_noise_std;
     P.g = c.gravity; P.L = c.link_length; P.z1 = c.joint1_z;
     P.s0 = (float)sin((double)c.phi0); P.c0 = (float)cos((double)c.phi0);
-    // composite constants of the absolute-angle Lagrangian, accumulated in double
-    double m[NL], mt = c.cart_mass, L = c.link_length, l = c.link_com;
-    for (int i = 0; i < NL; ++i) { m[i] = c.link_mass[i]; mt += m[i]; }
-    P.mtot = (float)mt;
-    double b[NL];
+    InertiaComposites ic;
+    inertia_composites(c.cart_mass, c.link_mass, c.link_inertia, c.link_length, c.link_com, c.gravity, ic);
+    P.mtot = (float)ic.mtot;
     for (int i = 0; i < NL; ++i) {
-        double distal = 0;
-        for (int k = i + 1; k < NL; ++k) distal += m[k];
-        b[i] = m[i] * l + L * distal;
-        P.b[i] = (float)b[i];
-        P.gb[i] = (float)((double)c.gravity * b[i]);
+        P.b[i] = (float)ic.b[i];
+        P.gb[i] = (float)ic.gb[i];
         P.I[i] = c.link_inertia[i];
-        P.a[i][i] = (float)(m[i] * l * l + L * L * distal + (double)c.link_inertia[i]);
+        P.a[i][i] = (float)ic.adiag[i];
     }
     for (int i = 0; i < NL; ++i)
         for (int j = 0; j < NL; ++j)
-            if (i != j) P.a[i][j] = (float)(L * b[i > j ? i : j]);
+            if (i != j) P.a[i][j] = (float)ic.aoff[i > j ? i : j];
     for (int i = 0; i < NL; ++i) { P.K[i] = c.fpam_K[i]; P.C[i] = c.fpam_C[i]; P.bb[i] = c.fpam_b[i]; P.B[i] = c.fpam_B[i]; }
     for (int i = 0; i < VINE_NUM_REWARDS; ++i) P.rw[i] = c.reward_weights[i];
     for (int i = 0; i < VINE_MAX_OBS; ++i) P.inv_obs_scale[i] = (float)(1.0 / (double)c.obs_scaling[i]);
@@ -2293,6 +2336,7 @@ struct VineHandle {
     const float* reset_values;
     float* reward_matrix;
     const float* env_params;       // bound per-env parameter table (include/vine_env_params.h) or NULL
+    const float* env_inertia;      // bound per-env inertia table (include/vine_env_inertia.h) or NULL; only beside env_params
     bool refresh_body;             // introspection was switched on since the last step: the next vine_step refreshes the lazily
                                    // stored tip / cart body states first (vine_refresh_body_kernel)
     int step_kernel;               // 0 = by size, 1 = one lane per env, 2 = four lanes per env where it applies (VINE_STEP_KERNEL)
@@ -2505,6 +2549,7 @@ int vine_create(const VineConfig* cfg, int device_id, float* state_storage, Vine
     h->reset_values = nullptr;
     h->reward_matrix = nullptr;
     h->env_params = nullptr;
+    h->env_inertia = nullptr;
     h->stats_psum = nullptr;
     h->stats_pmax = nullptr;
     h->step_kernel = 0;
@@ -2564,10 +2609,11 @@ int vine_step(VineHandle* h, const float* actions, float* obs, float* rew, int64
                                                      decltype(ep)::value>),
                                    dim3(1 << h->P.glog), dim3(VINE_STEP_THREADS), 0, s, h->P, h->state, actions, obs, rew,
                                    (long long*)reset, (long long*)progress, (unsigned char*)timeouts, h->reward_matrix,
-                                   h->reset_values, h->counters, h->env_params);
+                                   h->reset_values, h->counters, h->env_params, h->env_inertia);
             };
-            if (h->env_params) launch(std::true_type{});
-            else launch(std::false_type{});
+            if (h->env_params && h->env_inertia) launch(std::integral_constant<int, 2>{});
+            else if (h->env_params) launch(std::integral_constant<int, 1>{});
+            else launch(std::integral_constant<int, 0>{});
         });
     }
     HIP_TRY(hipGetLastError());
@@ -2741,12 +2787,99 @@ int vine_env_params_check(const VineConfig*, const float* t, int num_envs) {
 
 int vine_bind_env_params(VineHandle* h, const float* device_table) {
     if (!h) return fail(VINE_ERR_INVALID_ARG, "handle is NULL");
+    if (!device_table && h->env_inertia)
+        return fail(VINE_ERR_UNSUPPORTED, "vine_bind_env_params(NULL): an inertia table is bound and needs the parameter table; "
+                                          "unbind it first (vine_bind_env_inertia(h, NULL))");
     h->env_params = device_table;
     // the table decides between the two step kernels, whose grids differ: re-base the step count here, outside any capture
     return rebase_step_count(h);
 }
 
 int vine_env_params_bound(VineHandle* h) { return (h && h->env_params) ? 1 : 0; }
+
+// ---- include/vine_env_inertia.h
+namespace {
+const char* const kEnvInertiaNames[VI_COUNT] = {
+    "CART_MASS", "LINK_MASS[0]", "LINK_MASS[1]", "LINK_MASS[2]", "LINK_MASS[3]", "LINK_MASS[4]",
+    "LINK_INERTIA[0]", "LINK_INERTIA[1]", "LINK_INERTIA[2]", "LINK_INERTIA[3]", "LINK_INERTIA[4]",
+    "MTOT", "B[0]", "B[1]", "B[2]", "B[3]", "B[4]", "GB[0]", "GB[1]", "GB[2]", "GB[3]", "GB[4]",
+    "ADIAG[0]", "ADIAG[1]", "ADIAG[2]", "ADIAG[3]", "ADIAG[4]", "AOFF[1]", "AOFF[2]", "AOFF[3]", "AOFF[4]"};
+int bad_env_inertia(int r, int e, float v, const char* why) {
+    snprintf(g_err, sizeof g_err, "env inertia: %s of env %d is %g: %s", kEnvInertiaNames[r], e, (double)v, why);
+    return VINE_ERR_INVALID_ARG;
+}
+// the derived rows of one column from its primary rows: col[r] = row r of the env, primary rows read, derived rows written
+void derive_inertia_column(const VineConfig& c, float col[VI_COUNT]) {
+    InertiaComposites ic;
+    inertia_composites(col[VI_CART_MASS], col + VI_LINK_MASS0, col + VI_LINK_INERTIA0, c.link_length, c.link_com, c.gravity, ic);
+    col[VI_MTOT] = (float)ic.mtot;
+    for (int i = 0; i < NL; ++i) {
+        col[VI_B0 + i] = (float)ic.b[i];
+        col[VI_GB0 + i] = (float)ic.gb[i];
+        col[VI_ADIAG0 + i] = (float)ic.adiag[i];
+        if (i > 0) col[VI_AOFF1 + i - 1] = (float)ic.aoff[i];
+    }
+}
+}  // namespace
+
+int vine_env_inertia_row(const VineConfig* c, float row[VI_COUNT]) {
+    if (!c || !row) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_env_inertia_row");
+    row[VI_CART_MASS] = c->cart_mass;
+    for (int i = 0; i < NL; ++i) {
+        row[VI_LINK_MASS0 + i] = c->link_mass[i];
+        row[VI_LINK_INERTIA0 + i] = c->link_inertia[i];
+    }
+    derive_inertia_column(*c, row);
+    return VINE_OK;
+}
+
+int vine_env_inertia_derive(const VineConfig* c, float* t, int num_envs) {
+    if (!c || !t || num_envs <= 0) return fail(VINE_ERR_INVALID_ARG, "null argument or no envs in vine_env_inertia_derive");
+    for (int e = 0; e < num_envs; ++e) {
+        float col[VI_COUNT];
+        for (int r = 0; r < VI_PRIMARY_COUNT; ++r) col[r] = t[(size_t)r * num_envs + e];
+        derive_inertia_column(*c, col);
+        for (int r = VI_PRIMARY_COUNT; r < VI_COUNT; ++r) t[(size_t)r * num_envs + e] = col[r];
+    }
+    return VINE_OK;
+}
+
+int vine_env_inertia_check(const VineConfig* c, const float* t, int num_envs) {
+    if (!c || !t || num_envs <= 0) return fail(VINE_ERR_INVALID_ARG, "null argument or no envs in vine_env_inertia_check");
+    for (int r = 0; r < VI_COUNT; ++r) {
+        for (int e = 0; e < num_envs; ++e) {
+            const float v = t[(size_t)r * num_envs + e];
+            if (!std::isfinite(v)) return bad_env_inertia(r, e, v, "not finite");
+            if (r < VI_LINK_INERTIA0 && !(v > 0.0f)) return bad_env_inertia(r, e, v, "a mass must be positive");
+            if (r >= VI_LINK_INERTIA0 && r < VI_PRIMARY_COUNT && v < 0.0f) return bad_env_inertia(r, e, v, "negative");
+        }
+    }
+    for (int e = 0; e < num_envs; ++e) {
+        float col[VI_COUNT];
+        for (int r = 0; r < VI_PRIMARY_COUNT; ++r) col[r] = t[(size_t)r * num_envs + e];
+        derive_inertia_column(*c, col);
+        for (int r = VI_PRIMARY_COUNT; r < VI_COUNT; ++r) {
+            const float v = t[(size_t)r * num_envs + e];
+            if (v != col[r]) {
+                snprintf(g_err, sizeof g_err, "env inertia: %s of env %d is %.9g: not what the env's masses give (%.9g; "
+                         "vine_env_inertia_derive)", kEnvInertiaNames[r], e, (double)v, (double)col[r]);
+                return VINE_ERR_INVALID_ARG;
+            }
+        }
+    }
+    return VINE_OK;
+}
+
+int vine_bind_env_inertia(VineHandle* h, const float* device_table) {
+    if (!h) return fail(VINE_ERR_INVALID_ARG, "handle is NULL");
+    if (device_table && !h->env_params)
+        return fail(VINE_ERR_UNSUPPORTED, "vine_bind_env_inertia: bind a parameter table first (vine_bind_env_params); the step "
+                                          "kernel reads an inertia table only beside it");
+    h->env_inertia = device_table;      // the kernel and its grid stay: no re-base
+    return VINE_OK;
+}
+
+int vine_env_inertia_bound(VineHandle* h) { return (h && h->env_inertia) ? 1 : 0; }
 
 int vine_bind_reward_matrix(VineHandle* h, float* reward_matrix) {
     if (!h) return fail(VINE_ERR_INVALID_ARG, "handle is NULL");

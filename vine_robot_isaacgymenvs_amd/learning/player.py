@@ -159,15 +159,16 @@ class PpoPlayerContinuous(FastInferenceMixin):
         keep = rows["end_step"] >= self._episodes_start[1]
         rows = {k: v[keep] for k, v in rows.items()}
         table = env.env_params_of(range(int(env.num_envs)))
-        rows = episodes.with_env_params(rows, table, env.env_param_names)
+        inertia = env.env_inertia_of(range(int(env.num_envs))) if getattr(env, "env_inertia", None) is not None else None
+        per_env = episodes.varying_params(table, env.env_param_names, inertia)
+        rows = episodes.with_env_params(rows, table, env.env_param_names, inertia)
         by_param, lines = {}, []
         for column in [k for k in rows if k.startswith("param_")]:
             lines.append("  reached_ever_rate by %s:" % column)
-            first = abi.ENV_PARAM_ROWS[column[6:]][0]
             if not len(rows["env"]):
                 lines[-1] += " no episode finished"
                 continue
-            if len(np.unique(table[first])) <= exact:
+            if len(np.unique(per_env[column[6:]])) <= exact:
                 values, rate, count = episodes.value_rate(rows, column)
                 by_param[column] = (values, rate, count)
                 lines += ["    %.6g  %.4g  (%d episodes)" % (values[i], rate[i], count[i]) for i in range(len(values))]

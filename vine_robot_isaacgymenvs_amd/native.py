@@ -24,7 +24,7 @@ ARCH = "gfx950"
 FINGERPRINT = LIB + ".fingerprint"
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 _HEADERS = ([os.path.join(_INC, h) for h in ("vine.h", "vine_ppo.h", "vine_render.h", "vine_record.h", "vine_episodes.h",
-                                              "vine_env_params.h", "vine_sysid.h")]
+                                              "vine_env_params.h", "vine_env_inertia.h", "vine_sysid.h")]
             + [os.path.join(_HERE, "csrc", h) for h in ("vine_task_shared.h", "vine_geometry.h", "vine_observer.h",
                                                         "vine_policy_head.h", "vine_ppo_formulas.h")])
 DEPS = list(SOURCES) + _HEADERS

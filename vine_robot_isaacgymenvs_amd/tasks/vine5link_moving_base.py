@@ -207,6 +207,8 @@ class Vine5LinkMovingBase(VecTask):
         if self.env_params is not None and hasattr(observer, "env_params_of"):
             # ENV_PARAMS: a recording says which plant produced it, the episode file holds the table its env column indexes
             observer.env_params_of, observer.env_param_names = self.env_params_of, self.env_param_names
+            if self.env_inertia is not None:     # ENV_INERTIA: and its masses, beside it
+                observer.env_inertia_of, observer.env_inertia_names = self.env_inertia_of, self.env_inertia_names
         self._observers.append(observer)
         return observer
 
@@ -377,9 +379,14 @@ class Vine5LinkMovingBase(VecTask):
         self.env_params = None                   # ENV_PARAMS: the bound device table [VP_COUNT, N], else None
         self.env_param_names = abi.ENV_PARAM_ROW_NAMES
         self._env_params_host = None             # its host mirror (numpy), what the checks run on
+        self.env_inertia = None                  # ENV_INERTIA: the bound device table [VI_COUNT, N] of masses, else None
+        self.env_inertia_names = abi.ENV_INERTIA_ROW_NAMES
+        self._env_inertia_host = None
+        self._env_inertia_draws = {}             # LINK_MASS / TIP_LINK_MASS: the per-env factors the link rows were formed from
         spec = self.cfg["env"].get("ENV_PARAMS") or {}
         if len(spec):
             self._setup_env_params(spec)
+            self._setup_env_inertia(spec)
 
     # ------------------------------------------------------------------ ENV_PARAMS (include/vine_env_params.h)
     def _setup_env_params(self, spec):
@@ -397,16 +404,86 @@ class Vine5LinkMovingBase(VecTask):
         self.logger.info(f"ENV_PARAMS: {len(varying)} of {abi.VP_COUNT} table rows vary across the {self.num_envs} envs "
                          f"({', '.join(varying) or 'none'}); step kernel {before} -> {self.step_kernel_name}")
 
+    def _setup_env_inertia(self, spec):
+        """The per-env inertia table of the spec's CART_MASS / LINK_MASS / TIP_LINK_MASS (utils/env_params.py), derived and
+        checked through the library, uploaded and bound beside the parameter table (which a spec of masses alone leaves at
+        the configuration's row in every column).  Nothing happens for a spec without the three names."""
+        from ..utils import env_params
+        draws = {}
+        table = env_params.draw_inertia_table(
+            spec, env_params.inertia_config_row(self._lib, self._vcfg), int(self._vcfg.seed), self.num_envs,
+            lambda t: env_params.derive_inertia(self._lib, self._vcfg, t), int(self._vcfg.env_id_offset),
+            check=lambda t: env_params.check_inertia_table(self._lib, self._vcfg, t), draws=draws)
+        if table is None:
+            return
+        self._bind_env_inertia(table, draws)
+        varying = [self.env_inertia_names[r] for r in env_params.varying_rows(table[:abi.VI_PRIMARY_COUNT])]
+        self.logger.info(f"ENV_PARAMS: {len(varying)} of {abi.VI_PRIMARY_COUNT} masses and inertias vary across the "
+                         f"{self.num_envs} envs ({', '.join(varying) or 'none'})")
+
+    def _bind_env_inertia(self, table, draws):
+        self._env_inertia_host = table
+        self._env_inertia_draws = {k: draws[k] for k in ("LINK_MASS", "TIP_LINK_MASS") if k in draws}
+        self.env_inertia = torch.as_tensor(table, device=self.device).contiguous()
+        torch.cuda.synchronize(self.device)
+        native.check(self._lib.vine_bind_env_inertia(self._handle, self.env_inertia.data_ptr()), self._lib)
+
+    def _set_env_inertia(self, values):
+        """The inertia-table half of ``set_env_params``: the new primary rows, re-derived and checked on the host, then
+        every changed row rewritten in place on the device.  A table is built and bound on first use."""
+        import numpy as np
+        from ..utils import env_params
+        base = env_params.inertia_config_row(self._lib, self._vcfg)
+        table = (self._env_inertia_host.copy() if self._env_inertia_host is not None
+                 else np.repeat(base[:, None], self.num_envs, axis=1))
+        draws = dict(self._env_inertia_draws)
+        full = lambda v: np.broadcast_to(v, (self.num_envs,)).astype(np.float64)      # noqa: E731
+        factors = {k: full(v) for k, v in values.items() if k in ("LINK_MASS", "TIP_LINK_MASS")}
+        if factors:                              # the link rows anew from the configuration's and the two factors
+            draws.update(factors)
+            cart = table[abi.VI_CART_MASS].copy()
+            env_params.set_inertia_rows(table, base, draws)
+            table[abi.VI_CART_MASS] = cart
+        for name, v in values.items():           # then the rows stated themselves
+            if name == "CART_MASS":
+                table[abi.VI_CART_MASS] = full(v).astype(np.float32)
+            elif name not in factors:
+                table[self.env_inertia_names.index(name)] = full(v).astype(np.float32)
+        table = env_params.derive_inertia(self._lib, self._vcfg, table)
+        env_params.check_inertia_table(self._lib, self._vcfg, table)
+        if self.env_inertia is None:
+            self._bind_env_inertia(table, draws)
+            return
+        for r in range(abi.VI_COUNT):
+            if not np.array_equal(table[r].view(np.uint32), self._env_inertia_host[r].view(np.uint32)):
+                self.env_inertia[r].copy_(torch.from_numpy(table[r]))
+        self._env_inertia_host, self._env_inertia_draws = table, draws
+
     def set_env_params(self, values):
         """Rewrite rows of the bound table in place: ``values`` maps a name to a scalar or an array [N].  Names are
         ``abi.ENV_PARAM_NAMES`` -- an FPAM vector's value is a factor on the configuration's five constants, as in the
         ``ENV_PARAMS`` spec -- or a single row of ``env_param_names`` (``"FPAM_K[2]"``: the constant itself).  The new table
         is checked on the host first; a captured hipGraph reads the new contents at its next replay.  Not inside a graph
-        capture."""
+        capture.
+
+        The names of the inertia table go the same way (include/vine_env_inertia.h): ``CART_MASS`` in kg, ``LINK_MASS`` and
+        ``TIP_LINK_MASS`` as factors on the configuration's link masses and inertias (either one re-forms all ten link
+        rows from the configuration's and the two factors in force), or a primary row of ``env_inertia_names``
+        (``"LINK_MASS[2]"``, ``"LINK_INERTIA[4]"``: the value itself).  The derived rows are formed anew on the host.  The
+        first such call binds an inertia table if none is bound yet: call it before a step is captured."""
         import numpy as np
         from ..utils import env_params
         if self.env_params is None:
             raise RuntimeError("set_env_params(): no per-env parameter table is bound (task.env.ENV_PARAMS is empty)")
+        primary = self.env_inertia_names[:abi.VI_PRIMARY_COUNT]
+        inertia = {}
+        for name in [k for k in values if k in abi.ENV_INERTIA_NAMES or k in primary]:
+            v = values[name]
+            v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != self.num_envs):
+                raise ValueError(f"set_env_params: {name} takes a scalar or an array [{self.num_envs}], not {v.shape}")
+            inertia[name] = v
+        values = {k: v for k, v in values.items() if k not in inertia}
         table = self._env_params_host.copy()
         base = env_params.config_row(self._lib, self._vcfg)
         rows = []
@@ -426,6 +503,8 @@ class Vine5LinkMovingBase(VecTask):
             else:
                 raise ValueError(f"set_env_params: unknown parameter {name!r}")
         env_params.check_table(self._lib, self._vcfg, table)
+        if inertia:                              # (checked before anything is written: a refusal leaves both tables as they were)
+            self._set_env_inertia(inertia)
         for p in rows:
             self.env_params[p].copy_(torch.from_numpy(table[p]))
         self._env_params_host = table
@@ -436,6 +515,13 @@ class Vine5LinkMovingBase(VecTask):
         if self._env_params_host is None:
             return None
         return self._env_params_host[:, list(envs)].astype(np.float64)
+
+    def env_inertia_of(self, envs):
+        """The inertia table's host mirror, columns ``envs``, as float64 [VI_COUNT, len(envs)] (``None`` without one)."""
+        import numpy as np
+        if self._env_inertia_host is None:
+            return None
+        return self._env_inertia_host[:, list(envs)].astype(np.float64)
 
     def close(self):
         if self._observers:

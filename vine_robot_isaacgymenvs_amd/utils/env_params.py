@@ -11,6 +11,12 @@ spec in the task config.
 A name that is absent keeps the configuration's value (``vine_env_params_row``).  The four FPAM vectors (``FPAM_K``, ``FPAM_C``,
 ``FPAM_b``, ``FPAM_B``) take all three forms as a FACTOR on the configuration's five constants, which differ by design.
 
+Three more names fill the inertia table of ``vine_bind_env_inertia`` (include/vine_env_inertia.h) instead, in the same three
+forms and in the same mixed-radix count: ``CART_MASS`` in kg; ``LINK_MASS``, one factor per env on the configuration's five
+link masses and on their inertias about the COM (the geometry is unchanged, so the inertia scales with the mass);
+``TIP_LINK_MASS``, a further factor on link 4's mass and inertia only, the payload case: link 4 gets
+``configuration * LINK_MASS * TIP_LINK_MASS``.  ``build_table`` passes over them, ``build_inertia_table`` over the others.
+
 What env ``g`` gets depends on ``(seed, name, g)`` with ``g`` the GLOBAL env id (``env_id_offset`` + local index), never on
 the batch size: a rank's shard equals its slice of the whole batch, the rule the step's own random streams follow."""
 import ctypes as C
@@ -59,6 +65,40 @@ def check_table(lib, vcfg, table):
     return t
 
 
+def inertia_config_row(lib, vcfg):
+    """``vine_env_inertia_row``: the configuration's own value of every row, primary and derived, float32 [VI_COUNT]."""
+    row = (C.c_float * abi.VI_COUNT)()
+    rc = lib.vine_env_inertia_row(C.byref(vcfg), row)
+    if rc != abi.OK:
+        raise ValueError(lib.vine_last_error().decode(errors="replace"))
+    return np.array(row, dtype=np.float32)
+
+
+def _inertia_table(table):
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    if t.ndim != 2 or t.shape[0] != abi.VI_COUNT or t.shape[1] < 1:
+        raise ValueError("env inertia: the table must be [%d, num_envs], not %s" % (abi.VI_COUNT, t.shape))
+    return t
+
+
+def derive_inertia(lib, vcfg, table):
+    """``vine_env_inertia_derive``: a copy of the host table [VI_COUNT, N] with the derived rows filled from the primary."""
+    t = _inertia_table(table).copy()
+    rc = lib.vine_env_inertia_derive(C.byref(vcfg), t.ctypes.data, t.shape[1])
+    if rc != abi.OK:
+        raise ValueError(lib.vine_last_error().decode(errors="replace"))
+    return t
+
+
+def check_inertia_table(lib, vcfg, table):
+    """``vine_env_inertia_check`` on a host table [VI_COUNT, N]; raises ``ValueError`` naming the row and the env."""
+    t = _inertia_table(table)
+    rc = lib.vine_env_inertia_check(C.byref(vcfg), t.ctypes.data, t.shape[1])
+    if rc != abi.OK:
+        raise ValueError(lib.vine_last_error().decode(errors="replace"))
+    return t
+
+
 def _number(name, v):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
         raise ConfigError("ENV_PARAMS.%s: %r is not a number" % (name, v))
@@ -101,8 +141,9 @@ def spec_forms(spec):
     if not hasattr(spec, "keys"):
         raise ConfigError("ENV_PARAMS must be a mapping of parameter names, not %r" % (spec,))
     for name in spec.keys():
-        if name not in abi.ENV_PARAM_ROWS:
-            raise ConfigError("ENV_PARAMS: unknown parameter %r (known: %s)" % (name, ", ".join(abi.ENV_PARAM_NAMES)))
+        if name not in abi.ENV_PARAM_ROWS and name not in abi.ENV_INERTIA_NAMES:
+            raise ConfigError("ENV_PARAMS: unknown parameter %r (known: %s)" % (
+                name, ", ".join(abi.ENV_PARAM_NAMES + abi.ENV_INERTIA_NAMES)))
     forms = {name: _form(name, spec[name]) for name in spec.keys()}
     f = forms.get("ACTION_DELAY")
     if f is not None and f[0] == "range" and (f[1] != np.floor(f[1]) or f[2] != np.floor(f[2])):
@@ -120,6 +161,96 @@ def set_rows(table, base, name, v):
         table[first:first + count] = (base[first:first + count, None].astype(np.float64) * v[None, :]).astype(np.float32)
 
 
+def set_inertia_rows(table, base, draws):
+    """Write the PRIMARY rows of the inertia ``table`` [VI_COUNT, N] from the configuration's row ``base`` and the per-env
+    values ``draws`` (name -> float64 [N]; an absent name keeps the configuration's): the cart's mass itself; link i's mass
+    and inertia = the configuration's * LINK_MASS (* TIP_LINK_MASS for link 4), formed in float64 and rounded once.  The
+    derived rows are left for ``derive_inertia``."""
+    n = table.shape[1]
+    base = np.asarray(base, dtype=np.float64)
+    table[abi.VI_CART_MASS] = (draws["CART_MASS"] if "CART_MASS" in draws else np.full(n, base[abi.VI_CART_MASS])).astype(np.float32)
+    link = np.asarray(draws.get("LINK_MASS", np.ones(n)), dtype=np.float64)
+    tip = np.asarray(draws.get("TIP_LINK_MASS", np.ones(n)), dtype=np.float64)
+    for i in range(abi.NUM_LINKS):
+        f = link * tip if i == abi.NUM_LINKS - 1 else link
+        table[abi.VI_LINK_MASS0 + i] = (base[abi.VI_LINK_MASS0 + i] * f).astype(np.float32)
+        table[abi.VI_LINK_INERTIA0 + i] = (base[abi.VI_LINK_INERTIA0 + i] * f).astype(np.float32)
+
+
+def _candidates(forms):
+    """What a spec CAN give an env, per name: both ends of a range, every listed value, the number."""
+    return {name: list(f[1]) if f[0] == "values" else list(f[1:]) for name, f in forms.items()}
+
+
+def _draw(forms, seed, gids):
+    """name -> float64 [N], the per-env value of every name of a spec: the ``values`` entries count the global env id in
+    one mixed radix over ALL names of the spec, in its order, whichever table a name fills."""
+    out, radix = {}, 1
+    for name, form in forms.items():
+        if form[0] == "scalar":
+            v = np.full(len(gids), form[1], dtype=np.float64)
+        elif form[0] == "range":
+            lo, hi = form[1], form[2]
+            u = uniform01(seed, name, gids)
+            if name == "ACTION_DELAY":
+                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
+            else:
+                v = lo + (hi - lo) * u
+        else:
+            vals = np.asarray(form[1], dtype=np.float64)
+            v = vals[(gids // radix) % len(vals)]
+            radix *= len(vals)
+        out[name] = v
+    return out
+
+
+def draw_inertia_table(spec, base, seed, num_envs, derive, env_id_offset=0, check=None, draws=None):
+    """``build_inertia_table`` from the configuration's row ``base`` (float32 [VI_COUNT]).  ``derive(table)`` returns the
+    table with its derived rows filled (``derive_inertia`` bound to a library and a configuration); ``check`` and ``draws``
+    as in ``draw_table``.  ``None`` when the spec names none of ``abi.ENV_INERTIA_NAMES``."""
+    num_envs = int(num_envs)
+    if num_envs < 1:
+        raise ValueError("ENV_PARAMS: num_envs must be positive")
+    forms = spec_forms(spec)
+    if not any(name in forms for name in abi.ENV_INERTIA_NAMES):
+        return None
+    base = np.asarray(base, dtype=np.float32)
+    gids = np.arange(num_envs, dtype=np.int64) + int(env_id_offset)
+    cand = {name: c for name, c in _candidates(forms).items() if name in abi.ENV_INERTIA_NAMES}
+    width = max(len(c) for c in cand.values())
+    probe = np.repeat(base[:, None], width, axis=1)
+    set_inertia_rows(probe, base, {name: np.asarray([c[i % len(c)] for i in range(width)], dtype=np.float64)
+                                   for name, c in cand.items()})
+    if check is not None:
+        try:
+            check(derive(probe))
+        except ValueError as e:
+            raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
+    drawn = {name: v for name, v in _draw(forms, seed, gids).items() if name in abi.ENV_INERTIA_NAMES}
+    table = np.repeat(base[:, None], num_envs, axis=1)
+    set_inertia_rows(table, base, drawn)
+    if draws is not None:
+        draws.update(drawn)
+    table = derive(table)
+    if check is None:
+        return table
+    try:
+        return check(table)
+    except ValueError as e:
+        raise ValueError("ENV_PARAMS: %s" % e) from None
+
+
+def build_inertia_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
+    """The inertia table float32 [VI_COUNT, num_envs] of the envs with global ids ``env_id_offset ..`` from the names
+    ``CART_MASS``, ``LINK_MASS`` and ``TIP_LINK_MASS`` of ``spec`` (the module's docstring), derived rows filled and the whole
+    checked through the library; ``None`` when the spec names none of the three.  Raises as ``build_table`` does."""
+    if lib is None:
+        from .. import native
+        lib = native.load()
+    return draw_inertia_table(spec, inertia_config_row(lib, vcfg), seed, num_envs, lambda t: derive_inertia(lib, vcfg, t),
+                              env_id_offset, check=lambda t: check_inertia_table(lib, vcfg, t))
+
+
 def draw_table(spec, base, seed, num_envs, env_id_offset=0, check=None, draws=None):
     """``build_table`` from the configuration's row ``base`` (float32 [VP_COUNT]) instead of a handle's config: pure numpy.
     ``check``: called with the probe of what the spec can give an env and with the finished table (``check_table`` bound to
@@ -132,9 +263,9 @@ def draw_table(spec, base, seed, num_envs, env_id_offset=0, check=None, draws=No
     base = np.asarray(base, dtype=np.float32)
     table = np.repeat(base[:, None], num_envs, axis=1)
     gids = np.arange(num_envs, dtype=np.int64) + int(env_id_offset)
-    radix = 1                                     # product of the lengths of the `values` entries before this one
     # what the spec CAN give an env is checked whatever this batch happens to draw: both ends of a range, every value
-    cand = {name: list(f[1]) if f[0] == "values" else list(f[1:]) for name, f in forms.items()}
+    # (the names of the inertia table are draw_inertia_table's to place: here they only take part in the mixed radix)
+    cand = {name: c for name, c in _candidates(forms).items() if name in abi.ENV_PARAM_ROWS}
     width = max([len(c) for c in cand.values()] + [1])
     probe = np.repeat(base[:, None], width, axis=1)
     for name, c in cand.items():
@@ -147,22 +278,9 @@ def draw_table(spec, base, seed, num_envs, env_id_offset=0, check=None, draws=No
             check(probe)
         except ValueError as e:
             raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
-    for name, form in forms.items():
-        integer = name == "ACTION_DELAY"
-        if form[0] == "scalar":
-            v = np.full(num_envs, form[1], dtype=np.float64)
-        elif form[0] == "range":
-            lo, hi = form[1], form[2]
-            u = uniform01(seed, name, gids)
-            if integer:
-                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
-            else:
-                v = lo + (hi - lo) * u
-        else:
-            vals = np.asarray(form[1], dtype=np.float64)
-            v = vals[(gids // radix) % len(vals)]
-            radix *= len(vals)
-        set_rows(table, base, name, v)
+    for name, v in _draw(forms, seed, gids).items():
+        if name in abi.ENV_PARAM_ROWS:
+            set_rows(table, base, name, v)
         if draws is not None:
             draws[name] = v
     table = np.ascontiguousarray(table, dtype=np.float32)

@@ -100,17 +100,38 @@ def binned_rate(rows, column, bins, of="reached_ever"):
     return rate, count, edges
 
 
-def with_env_params(rows, table, names):
-    """``rows`` with one more column per parameter that varies across the envs of ``table`` ([VP_COUNT, N], the bound per-env
-    parameter table; ``names``: one per table row, ``abi.ENV_PARAM_ROW_NAMES``): ``param_<NAME>`` = the value of the row's
-    env, an FPAM vector reduced to joint 0's value (``param_FPAM_K``).  ``binned_rate`` works on them like on any column."""
+def varying_params(table, names, inertia=None):
+    """``{NAME: values [N]}``: one value per env of every parameter that varies across the envs.  ``table`` ([VP_COUNT, N],
+    the bound per-env parameter table; ``names``: one per table row, ``abi.ENV_PARAM_ROW_NAMES``): the row's value, an FPAM
+    vector reduced to joint 0's.  ``inertia`` ([VI_COUNT, N] or ``None``, the bound inertia table): ``CART_MASS`` = the
+    cart's mass; ``LINK_MASS`` = link 0's mass, where it varies (one factor scales all five); ``TIP_LINK_MASS`` = link 4's
+    mass, where its ratio to link 0's varies (the tip was scaled on its own).  All in kg."""
     t = np.asarray(table)
-    env = np.asarray(rows["env"], dtype=np.int64)
-    out = dict(rows)
+    out = {}
     for name, (first, count) in abi.ENV_PARAM_ROWS.items():
         if any(np.any(t[p] != t[p, 0]) for p in range(first, first + count)):
             assert names[first] == (name if count == 1 else name + "[0]"), (names[first], name)
-            out["param_" + name] = t[first][env]
+            out[name] = t[first]
+    if inertia is not None:
+        m = np.asarray(inertia)
+        cart, m0, m4 = m[abi.VI_CART_MASS], m[abi.VI_LINK_MASS0], m[abi.VI_LINK_MASS0 + abi.NUM_LINKS - 1]
+        if np.any(cart != cart[0]):
+            out["CART_MASS"] = cart
+        if np.any(m0 != m0[0]):
+            out["LINK_MASS"] = m0
+        ratio = m4.astype(np.float64) / m0.astype(np.float64)
+        if np.any(np.abs(ratio - ratio[0]) > 4e-7 * np.abs(ratio[0])):      # (beyond the rounding of two float32 masses)
+            out["TIP_LINK_MASS"] = m4
+    return out
+
+
+def with_env_params(rows, table, names, inertia=None):
+    """``rows`` with one more column per parameter that varies across the envs (``varying_params``): ``param_<NAME>`` = the
+    value of the row's env.  ``binned_rate`` works on them like on any column."""
+    env = np.asarray(rows["env"], dtype=np.int64)
+    out = dict(rows)
+    for name, values in varying_params(table, names, inertia).items():
+        out["param_" + name] = values[env]
     return out
 
 
@@ -124,13 +145,17 @@ def value_rate(rows, column, of="reached_ever"):
     return values, hit / np.maximum(count, 1), count
 
 
-def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None):
+def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
-    and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``."""
+    and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
+    bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
     if env_params is not None:
         out["env_params"] = np.asarray(env_params, dtype=np.float32)
         out["env_param_names"] = np.array(list(env_param_names))
+    if env_inertia is not None:
+        out["env_inertia"] = np.asarray(env_inertia, dtype=np.float32)
+        out["env_inertia_names"] = np.array(list(env_inertia_names))
     out["totals"] = np.asarray(totals, dtype=np.float64).reshape(-1, abi.EVAL_NUM_TOTALS).sum(axis=0)
     out["dropped"] = np.array(int(dropped), dtype=np.int64)
     for k, v in task.items():
@@ -156,6 +181,14 @@ def load_env_params(path):
         if "env_params" not in z.files:
             return None, None
         return z["env_params"], [str(n) for n in z["env_param_names"]]
+
+
+def load_env_inertia(path):
+    """``(table [VI_COUNT, N], names)`` of a file written with a bound inertia table, else ``(None, None)``."""
+    with np.load(path) as z:
+        if "env_inertia" not in z.files:
+            return None, None
+        return z["env_inertia"], [str(n) for n in z["env_inertia_names"]]
 
 
 class EpisodeLog:
@@ -194,6 +227,7 @@ class EpisodeLog:
         self.paused = 0
         self.copy_done = None        # (the harvest is synchronous: no copy is ever in flight)
         self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
+        self.env_inertia_of, self.env_inertia_names = None, None   # ENV_INERTIA: likewise
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -270,7 +304,9 @@ class EpisodeLog:
         """Harvest what is left and (re)write the file."""
         self.harvest()
         table = self.env_params_of(range(self.num_envs)) if self.env_params_of is not None else None
-        save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names)
+        inertia = self.env_inertia_of(range(self.num_envs)) if self.env_inertia_of is not None else None
+        save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
+             self.env_inertia_names)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -238,7 +238,7 @@ def _seed_of(seed, iteration):
     return (int(seed) + int(iteration) * _GOLDEN) & 0xFFFFFFFFFFFFFFFF
 
 
-def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1, check=None, log=None):
+def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1, check=None, log=None, inertia=None):
     """Cross-entropy search over an ``ENV_PARAMS``-style ``spec`` (utils/env_params.py), host only.
 
     ``evaluate(table)`` takes a float32 table [VP_COUNT, num_envs] and returns one error per column (+inf allowed).
@@ -252,10 +252,18 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
     same hash picks one elite per env); a number stays.  Column 0 carries the best candidate so far, unchanged, from
     iteration 1 on, so the best error never increases.
 
+    A spec that names ``CART_MASS``, ``LINK_MASS`` or ``TIP_LINK_MASS`` needs ``inertia = (base_row, derive, check)``: the
+    configuration's own row of the inertia table (``env_params.inertia_config_row``), ``derive(table)`` returning the
+    table with its derived rows filled and ``check(table)`` (``env_params.derive_inertia`` / ``check_inertia_table`` bound
+    to a library and a configuration).  The inertia table [VI_COUNT, num_envs] is then carried beside the parameter table:
+    the three names are drawn and redrawn by the rules above like any ``[lo, hi]`` / ``values`` name, column 0 keeps the
+    best candidate's column of BOTH tables, every inertia table is derived and checked, and ``evaluate(table, inertia)``
+    gets both.
+
     Returns ``(best_column, best_error, history)``: float32 [VP_COUNT], float, and one dict per iteration with
     ``best_error`` (so far), ``iteration_best``, ``finite`` (candidates with a finite error), ``ranges`` (name -> [lo, hi]
     drawn from) and ``counts`` (name -> {value: elites}); the last entry also holds the final population as ``table`` and
-    ``errors``."""
+    ``errors``, and with an inertia table ``inertia`` (the final population's) and ``inertia_best`` (float32 [VI_COUNT])."""
     if check is None:
         from .. import native
         lib = native.load()
@@ -267,12 +275,20 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
         raise ValueError("cem: at least one iteration")
     forms = env_params.spec_forms(spec)
     base = np.asarray(base_row, dtype=np.float32)
+    masses = [name for name in forms if name in abi.ENV_INERTIA_NAMES]
+    if masses and inertia is None:
+        raise ValueError("cem: the spec names %s and needs inertia=(base_row, derive, check)" % ", ".join(masses))
+    if masses:
+        ibase, iderive, icheck = np.asarray(inertia[0], dtype=np.float32), inertia[1], inertia[2]
+    itable, best_icol = None, None
     gids = np.arange(N, dtype=np.int64)
     initial = {name: (f[1], f[2]) for name, f in forms.items() if f[0] == "range" and name != "ACTION_DELAY"}
     ranges = dict(initial)
     discrete = [name for name, f in forms.items() if f[0] == "values" or (name == "ACTION_DELAY" and f[0] == "range")]
     draws = {}
     table = env_params.draw_table(spec, base, seed, N, check=check, draws=draws)
+    if masses:
+        itable = env_params.draw_inertia_table(spec, ibase, seed, N, iderive, check=icheck)
     best_col, best_draw, best_err = None, None, np.inf
     n_elite = min(N, max(2, int(np.ceil(float(elite_fraction) * N))))
     history = []
@@ -293,18 +309,26 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
                 if best_draw is not None:
                     v[0] = best_draw[name]
                 draws[name] = v
-                env_params.set_rows(table, base, name, v)
+                if name not in masses:
+                    env_params.set_rows(table, base, name, v)
             if best_col is not None:
                 table[:, 0] = best_col
             table = np.ascontiguousarray(table, dtype=np.float32)
             check(table)
-        err = np.asarray(evaluate(table), dtype=np.float64)
+            if masses:
+                itable = np.repeat(ibase[:, None], N, axis=1)
+                env_params.set_inertia_rows(itable, ibase, {name: draws[name] for name in masses})
+                if best_icol is not None:
+                    itable[:, 0] = best_icol
+                itable = icheck(iderive(itable))
+        err = np.asarray(evaluate(table, itable) if masses else evaluate(table), dtype=np.float64)
         if err.shape != (N,):
             raise ValueError("cem: evaluate returned %s, expected (%d,)" % (err.shape, N))
         err = np.where(np.isnan(err), np.inf, err)
         k = int(np.argmin(err))
         if err[k] < best_err or best_col is None:
             best_err, best_col = float(err[k]), table[:, k].copy()
+            best_icol = itable[:, k].copy() if masses else None
             best_draw = {name: float(draws[name][k]) for name in forms}
         order = np.argsort(err, kind="stable")
         elites = order[:n_elite]
@@ -328,6 +352,8 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
         if log is not None:
             log(entry)
     history[-1]["table"], history[-1]["errors"] = table, err
+    if masses:
+        history[-1]["inertia"], history[-1]["inertia_best"] = itable, best_icol
     return best_col, best_err, history
 
 
@@ -345,7 +371,10 @@ def fit(cfg, log_path, spec, num_envs=4096, iterations=8, horizon=50, stride=25,
     windows (``windows``), prints one line per iteration and the
     fitted values beside the configuration's, and writes ``<directory>/<time_str>_sysid.npz`` with ``best`` (the column),
     ``best_error``, ``env_param_names``, ``history`` (JSON), ``starts``, and the final population ``table`` with its
-    ``errors``.  Returns a dict of the same."""
+    ``errors``.  Returns a dict of the same.  Where ``spec`` names ``CART_MASS``, ``LINK_MASS`` or ``TIP_LINK_MASS`` the
+    fitted masses and inertias are printed beside the configuration's too, and the dict and the file also hold ``inertia``
+    (the final population's inertia table [VI_COUNT, N]), ``inertia_best`` (the best candidate's column) and
+    ``env_inertia_names``."""
     logger = logger or logging.getLogger(__name__)
     weights = list(DEFAULT_WEIGHTS if weights is None else weights)
     log = load_log(log_path, weights)
@@ -359,9 +388,16 @@ def fit(cfg, log_path, spec, num_envs=4096, iterations=8, horizon=50, stride=25,
         names = list(task.env_param_names)
         seconds = [0.0]
 
-        def evaluate(table):
+        inames = list(task.env_inertia_names)
+        with_masses = any(name in abi.ENV_INERTIA_NAMES for name in spec)
+        ibase = env_params.inertia_config_row(task._lib, task._vcfg)
+
+        def evaluate(table, itable=None):
             t0 = time.perf_counter()
-            task.set_env_params({names[p]: table[p] for p in range(abi.VP_COUNT)})      # (checks the table, then uploads)
+            values = {names[p]: table[p] for p in range(abi.VP_COUNT)}
+            if itable is not None:               # the eleven primary rows: the task derives the rest again and checks
+                values.update({inames[r]: itable[r] for r in range(abi.VI_PRIMARY_COUNT)})
+            task.set_env_params(values)                                                  # (checks the tables, then uploads)
             err = ev.evaluate(starts)
             seconds[0] += time.perf_counter() - t0
             return err
@@ -370,9 +406,17 @@ def fit(cfg, log_path, spec, num_envs=4096, iterations=8, horizon=50, stride=25,
             num_envs, len(starts), horizon, log_path, len(log), "hipGraph replay" if ev.use_graph else "eager steps"), flush=True)
         best, best_err, history = cem(evaluate, spec, base, num_envs, iterations, seed, elite_fraction,
                                       check=lambda t: env_params.check_table(task._lib, task._vcfg, t),
-                                      log=lambda entry: print(_describe(entry), flush=True))
+                                      log=lambda entry: print(_describe(entry), flush=True),
+                                      inertia=(ibase, lambda t: env_params.derive_inertia(task._lib, task._vcfg, t),
+                                               lambda t: env_params.check_inertia_table(task._lib, task._vcfg, t))
+                                      if with_masses else None)
         for p in env_params.varying_rows(np.stack([best, base], axis=1)):
             print("sysid: %-26s fitted %-14.9g configuration %.9g" % (names[p], best[p], base[p]), flush=True)
+        inertia_best = history[-1].pop("inertia_best", None)
+        inertia = history[-1].pop("inertia", None)
+        if inertia_best is not None:
+            for r in env_params.varying_rows(np.stack([inertia_best, ibase], axis=1)[:abi.VI_PRIMARY_COUNT]):
+                print("sysid: %-26s fitted %-14.9g configuration %.9g" % (inames[r], inertia_best[r], ibase[r]), flush=True)
         rate = num_envs * ev.steps_run / max(seconds[0], 1e-9)
         print("sysid: best error %.9g; %d candidate-steps in %.3f s (%.3g candidate-steps/s)" % (
             best_err, num_envs * ev.steps_run, seconds[0], rate), flush=True)
@@ -380,13 +424,17 @@ def fit(cfg, log_path, spec, num_envs=4096, iterations=8, horizon=50, stride=25,
         table, errors = final.pop("table"), final.pop("errors")
         out = {"best": best, "best_error": best_err, "env_param_names": names, "history": history, "starts": starts,
                "table": table, "errors": errors, "candidate_steps_per_second": rate, "path": None}
+        more = {}
+        if inertia is not None:
+            more = {"inertia": inertia, "inertia_best": inertia_best, "env_inertia_names": np.array(inames)}
+            out.update(more)
         if directory is not None:
             os.makedirs(directory, exist_ok=True)
             time_str = time_str or time.strftime("%Y-%m-%d_%H-%M-%S")
             path = os.path.join(directory, "%s_sysid.npz" % time_str)
             np.savez(path, best=best, best_error=np.float64(best_err), env_param_names=np.array(names),
                      history=np.array(json.dumps(history)), starts=np.asarray(starts, dtype=np.int64), table=table,
-                     errors=errors)
+                     errors=errors, **more)
             out["path"] = path
             print("sysid: wrote %s" % path, flush=True)
         return out

@@ -22,10 +22,11 @@ def record_config(lib, every, steps, num_envs):
     return c
 
 
-def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param_names=None):
+def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None):
     """The MAT file's variables from the rows of ONE env, ``rows[T, abi.RECORD_FIELDS]`` float32, and the step index of
     every row (with ``env_params``, the env's column of a bound per-env parameter table, also ``env_params`` (VP_COUNT, 1)
-    and ``env_param_names``).  The reference's six keys (V5:281-297) hold positions as (3, T) with a zero x row: the scene is the y-z
+    and ``env_param_names``; with ``env_inertia``, the env's column of a bound inertia table, also ``env_inertia``
+    (VI_PRIMARY_COUNT, 1): its cart mass, five link masses and five link inertias).  The reference's six keys (V5:281-297) hold positions as (3, T) with a zero x row: the scene is the y-z
     plane.  float32 -> float64 is exact, so a file read back holds the device's values."""
     r = np.asarray(rows)
     assert r.ndim == 2 and r.shape[1] == abi.RECORD_FIELDS, r.shape
@@ -39,6 +40,8 @@ def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param
     if env_params is not None:                   # ENV_PARAMS: the recorded env's column of the bound table, (VP_COUNT, 1)
         extra = {"env_params": np.asarray(env_params, dtype=np.float64).reshape(-1, 1),
                  "env_param_names": np.array(list(env_param_names), dtype=object)}
+    if env_inertia is not None:                  # ENV_INERTIA: the recorded env's 11 primary values
+        extra["env_inertia"] = np.asarray(env_inertia, dtype=np.float64).reshape(-1)[:abi.VI_PRIMARY_COUNT].reshape(-1, 1)
     return {
         **extra,
         "cart_pos": d[f.VRF_Q0:f.VRF_Q0 + 1].copy(),
@@ -63,12 +66,12 @@ def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param
     }
 
 
-def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, env_param_names=None):
+def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None):
     """``trajectory_arrays`` as a MATLAB 5 file at ``path`` (written beside it and renamed: no reader sees half a file)."""
     import scipy.io
     part = path + ".part"
     with open(part, "wb") as fh:
-        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env, env_params, env_param_names))
+        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env, env_params, env_param_names, env_inertia))
     os.replace(part, path)
     return path
 
@@ -97,6 +100,7 @@ class TrajectoryRecorder(WindowRing):
         self.host = torch.empty(self.ring.shape, dtype=torch.float32, pin_memory=True)
         self.host_steps = torch.empty(self.steps.shape, dtype=torch.int64, pin_memory=True)
         self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
+        self.env_inertia_of, self.env_inertia_names = None, None   # ENV_INERTIA: likewise
         import scipy.io  # noqa: F401  (here, not in the writer thread: the first import takes 0.3 s, longer than a window)
         super().__init__(device, logger)
 
@@ -117,12 +121,14 @@ class TrajectoryRecorder(WindowRing):
         return [(self.ring, self.host), (self.steps, self.host_steps)]
 
     def _job_extra(self):
-        return self.env_params_of(self.env_ids) if self.env_params_of is not None else None
+        return (self.env_params_of(self.env_ids) if self.env_params_of is not None else None,
+                self.env_inertia_of(self.env_ids) if self.env_inertia_of is not None else None)
 
     def path(self, last, env):
         return os.path.join(self.directory, f"{self.time_str}_trajectory_{last}_env{env}.mat")
 
-    def _write(self, start, last, params):
+    def _write(self, start, last, tables):
+        params, inertia = tables
         rows, steps = self.host.numpy(), self.host_steps.numpy()
         if not np.array_equal(steps, np.arange(start, last + 1)):       # the device's own account of slot <-> step
             raise RuntimeError(f"window {start}..{last}: the device recorded steps {steps.tolist()}")
@@ -130,6 +136,7 @@ class TrajectoryRecorder(WindowRing):
         for k, e in enumerate(self.env_ids):
             self.written.append(write_trajectory_mat(
                 self.path(last, e), rows[:, k], steps, self.control_dt, e,
-                params[:, k] if params is not None else None, self.env_param_names))
+                params[:, k] if params is not None else None, self.env_param_names,
+                inertia[:, k] if inertia is not None else None))
         self.logger.info(f"Saved {len(self.env_ids)} trajectories of steps {start}..{last} to "
                          f"{self.path(last, '<e>')}")
