@@ -5,7 +5,13 @@ free space, default observation layout, randomisation on.
 Durations come from a replayed hipGraph of K back-to-back steps between two events (elapsed / K): HIP events around eager
 back-to-back launches are host-bound below about 13 us.  The variants are alternated, ROUNDS times, inside one process.
 
-usage: python scripts/ubench/env_params_bench.py [num_envs ...]        (default: 16384 1048576)"""
+With --redraw: the cost of the per-episode redraw node (include/vine_env_redraw.h) behind every step of the handle with both
+heterogeneous tables -- step + node against step alone, the step being the same in each: with no env resetting (the node is
+handed a buffer of zeros that no step writes: every lane loads its flag and leaves), with the step's own flags (the task
+YAML's episodes under random actions), and with every env resetting every step (a buffer of ones: every lane redraws all
+28 + 31 rows).
+
+usage: python scripts/ubench/env_params_bench.py [--redraw] [num_envs ...]        (default: 16384 1048576)"""
 import os
 import statistics
 import sys
@@ -31,8 +37,8 @@ VARIANTS = {"lane": ("lane", None, None), "lane+own_row_table": ("lane", "own", 
             "lane+het_table+het_inertia": ("lane", "het", "het"), "quad": ("quad", None, None)}
 
 
-def make(n, kern, table, inertia=None):
-    cfg = base_cfg(n, 0, True)
+def make(n, kern, table, inertia=None, **over):
+    cfg = base_cfg(n, 0, True, **over)
     env = type("H", (HipEnv,), {"kernel": kern})(cfg)
     env.set_introspection(False)
     if table is not None:
@@ -60,8 +66,80 @@ def make(n, kern, table, inertia=None):
     return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode()
 
 
+def make_redraw(n, which):
+    """The handle of ``lane+het_table+het_inertia`` with the redraw node behind every captured step; ``which``: the flags the
+    node reads -- "none" (zeros), "own" (the step's reset buffer), "all" (ones)."""
+    cfg = base_cfg(n, 0, True)
+    env = type("H", (HipEnv,), {"kernel": "lane"})(cfg)
+    env.set_introspection(False)
+    spec = dict(SPEC, **MASSES)
+    env.table_t = torch.as_tensor(env_params.build_table(spec, env.cfg, 1, n, lib=env.lib), device=env.dev).contiguous()
+    env.inertia_t = torch.as_tensor(env_params.build_inertia_table(spec, env.cfg, 1, n, lib=env.lib), device=env.dev).contiguous()
+    torch.cuda.synchronize()
+    native.check(env.lib.vine_bind_env_params(env.h, env.table_t.data_ptr()), env.lib)
+    native.check(env.lib.vine_bind_env_inertia(env.h, env.inertia_t.data_ptr()), env.lib)
+    rspec = env_params.redraw_spec(env.lib, env.cfg, spec)
+    episode = torch.zeros(n, dtype=torch.int32, device=env.dev)
+    flags = {"none": torch.zeros(n, dtype=torch.long, device=env.dev), "own": env.reset_t,
+             "all": torch.ones(n, dtype=torch.long, device=env.dev)}[which]
+    k = 100 if n <= 65536 else 20
+    g = torch.Generator(device=env.dev).manual_seed(0)
+    acts = [torch.rand((n, 2), device=env.dev, generator=g) * 2 - 1 for _ in range(8)]
+
+    def pair(a):
+        env.step_t(a, sync=False)
+        native.check(env.lib.vine_env_redraw_scheduled(env.h, rspec, flags.data_ptr(), env.table_t.data_ptr(), env.inertia_t.data_ptr(),
+                                                       episode.data_ptr(), torch.cuda.current_stream(env.dev).cuda_stream), env.lib)
+    for i in range(16):
+        pair(acts[i % 8])
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        for i in range(k):
+            pair(acts[i % 8])
+    graph.replay()
+    torch.cuda.synchronize()
+    env.keep = (rspec, episode, flags)
+    torch.cuda.synchronize()
+    env.reset_share = float((env.reset_t != 0).float().mean())
+    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + " + redraw"
+
+
+def main_redraw(sizes):
+    for n in sizes:
+        envs = {"step alone (both het tables)": make(n, "lane", "het", "het"),
+                "step + node, no env resetting": make_redraw(n, "none"),
+                "step + node, the step's own resets": make_redraw(n, "own"),
+                "step + node, every env resetting": make_redraw(n, "all")}
+        times = {name: [] for name in envs}
+        for _ in range(ROUNDS):
+            for name, (env, graph, k, _) in envs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) / k * 1e3)
+        print("num_envs %d, %d rounds alternated, one graph replay of %d steps each (us per step: min / median / max)"
+              % (n, ROUNDS, next(iter(envs.values()))[2]))
+        for name in envs:
+            t = times[name]
+            print("  %-36s %8.1f %8.1f %8.1f" % (name, min(t), statistics.median(t), max(t)), flush=True)
+        base = statistics.median(times["step alone (both het tables)"])
+        for name in list(envs)[1:]:
+            own = " (%.1f %% of the envs flagged after the last step)" % (100 * envs[name][0].reset_share) if "own" in name else ""
+            print("  node, %s: %+.2f us per launch%s" % (name.split(", ")[1], statistics.median(times[name]) - base, own))
+        for env, _, _, _ in envs.values():
+            env.close()
+        del envs
+        torch.cuda.empty_cache()
+
+
 def main():
-    for n in [int(a) for a in sys.argv[1:]] or [16384, 1 << 20]:
+    args = [a for a in sys.argv[1:] if a != "--redraw"]
+    if "--redraw" in sys.argv[1:]:
+        return main_redraw([int(a) for a in args] or [16384, 1 << 20])
+    for n in [int(a) for a in args] or [16384, 1 << 20]:
         envs = {name: make(n, *v) for name, v in VARIANTS.items()}
         times = {name: [] for name in VARIANTS}
         for _ in range(ROUNDS):

@@ -531,6 +531,59 @@ def declare_env_inertia(lib):
     return lib
 
 
+# ---- include/vine_env_redraw.h (product library only)
+ENV_REDRAW_ABI_VERSION = 1
+ENV_REDRAW_THREADS = 256
+# VineEnvRedrawSlot = the names of a spec: the twelve of the parameter table, then the three of the inertia table
+ENV_REDRAW_NAMES = ENV_PARAM_NAMES + ENV_INERTIA_NAMES
+VR_NAMES = 15
+REDRAW_ABSENT, REDRAW_NUMBER, REDRAW_RANGE, REDRAW_VALUES = range(4)
+
+
+class VineEnvRedrawName(C.Structure):
+    _fields_ = [
+        ("form", C.c_int32),
+        ("values_first", C.c_int32),
+        ("values_count", C.c_int32),
+        ("reserved", C.c_int32),
+        ("key", C.c_uint64),
+        ("radix", C.c_uint64),
+        ("lo", C.c_double),
+        ("hi", C.c_double),
+    ]
+
+
+class VineEnvRedrawSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_values", C.c_int32),
+        ("seed", C.c_uint64),
+        ("values", C.c_void_p),
+        ("name", VineEnvRedrawName * VR_NAMES),
+        ("base_params", C.c_float * VP_COUNT),
+        ("base_inertia", C.c_float * VI_PRIMARY_COUNT),
+        ("link_length", C.c_float),
+        ("link_com", C.c_float),
+        ("gravity", C.c_float),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+ENV_REDRAW_PROTOTYPES = {
+    "vine_env_redraw_spec_size": (C.c_int, []),
+    "vine_env_redraw_spec": (C.c_int, [_P(VineConfig), _P(VineEnvRedrawName), _VP, _VP, C.c_int, _P(VineEnvRedrawSpec)]),
+    "vine_env_redraw_scheduled": (C.c_int, [_H, _P(VineEnvRedrawSpec)] + [_VP] * 5),
+}
+
+
+def declare_env_redraw(lib):
+    _attach(lib, ENV_REDRAW_PROTOTYPES)
+    if lib.vine_env_redraw_spec_size() != C.sizeof(VineEnvRedrawSpec):
+        raise RuntimeError("VineEnvRedrawSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_sysid.h (product library only)
 SYSID_ABI_VERSION = 1
 SYSID_FIELDS = 16
@@ -574,6 +627,6 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_sysid):
+                        declare_env_redraw, declare_sysid):
         declare_one(lib)
     return lib

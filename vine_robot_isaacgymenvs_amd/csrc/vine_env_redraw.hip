@@ -1,0 +1,280 @@
+// vine_env_redraw.hip — a new plant for every episode (ENV_PARAMS_PER_EPISODE) for MI355X (gfx950): include/vine_env_redraw.h.
+//
+// One lane per env, VINE_ENV_REDRAW_THREADS envs per workgroup, no LDS, no atomics.  A lane whose reset flag is clear loads
+// that one word and leaves; a lane whose flag is set hashes (seed, name, global env id, episode) per name of the spec, forms
+// its column in float64 and stores it: up to 28 + 31 coalesced 4-byte stores per lane, and 16 more where the delay changed.
+//
+// THIS TRANSLATION UNIT IS COMPILED WITH -ffp-contract=off (native.py): `a + b * c` must stay a multiply and an add, each
+// rounded, as numpy and the host pass form it.  Under the flags of the other translation units hipcc fuses it on gfx950, a
+// pragma or __dmul_rn notwithstanding, and a column would differ from utils/env_params.py draw_columns in the last bit.
+//
+// `redraw_value` and `redraw_column` are host and device functions: vine_env_redraw_spec forms the candidates it checks with
+// the statements the kernel forms its columns with.
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "../../include/vine_env_redraw.h"
+#include "vine_inertia_composites.h"
+#include "vine_observer.h"
+
+namespace {
+
+constexpr int THREADS = VINE_ENV_REDRAW_THREADS;
+constexpr int NL = VINE_NUM_LINKS;
+static_assert(VR_NAMES == 15 && VR_FPAM_K == 8 && VR_CART_MASS == 12, "slots 0..7 are rows 0..7, 8..11 the FPAM vectors");
+static_assert(VP_FPAM_K0 == 8 && VP_FPAM_C0 == 13 && VP_FPAM_b0 == 18 && VP_FPAM_B0 == 23 && VP_COUNT == 28, "FPAM rows");
+
+__host__ __device__ inline unsigned long long mix64(unsigned long long x) {      // splitmix64's finaliser
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// u in [0, 1) of (seed, key, global env id g, episode k); k == 0 gives utils/env_params.py uniform01
+__host__ __device__ inline double redraw_u(unsigned long long seed, unsigned long long key, unsigned long long g,
+                                           unsigned long long k) {
+    const unsigned long long pre = mix64(seed ^ key) + g * 0x9E3779B97F4A7C15ull;
+    const unsigned long long h = mix64(pre ^ mix64(k));
+    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// the value of one name (present: form != ABSENT) for env g in episode k
+__host__ __device__ inline double redraw_value(const VineEnvRedrawName& nm, bool integer, const double* values,
+                                               unsigned long long seed, unsigned long long g, unsigned long long k) {
+    if (nm.form == VINE_REDRAW_NUMBER) return nm.lo;
+    if (nm.form == VINE_REDRAW_VALUES) {
+        const unsigned long long count = (unsigned long long)nm.values_count;
+        unsigned long long i;
+        if (k == 0ull) {
+            i = (g / nm.radix) % count;
+        } else {
+            const double u = redraw_u(seed, nm.key, g, k);
+            i = (unsigned long long)floor(u * (double)nm.values_count);
+            if (i > count - 1ull) i = count - 1ull;
+        }
+        return values[(size_t)nm.values_first + i];
+    }
+    const double u = redraw_u(seed, nm.key, g, k);
+    const double lo = nm.lo, hi = nm.hi;
+    if (integer) return fmin(lo + floor(u * (hi - lo + 1.0)), hi);
+    return lo + (hi - lo) * u;
+}
+
+// the two columns of an env from the per-name values v (read where the name is present): pcol = the parameter table's 28
+// rows (the base's where a name is absent), icol = the inertia table's 31, the derived rows from the primary ones
+__host__ __device__ inline void redraw_column(const VineEnvRedrawSpec& S, const double v[VR_NAMES], float pcol[VP_COUNT],
+                                              float icol[VI_COUNT]) {
+#pragma unroll
+    for (int p = 0; p < VP_COUNT; ++p) pcol[p] = S.base_params[p];
+#pragma unroll
+    for (int s = 0; s < VR_FPAM_K; ++s)
+        if (S.name[s].form != VINE_REDRAW_ABSENT) pcol[s] = (float)v[s];
+#pragma unroll
+    for (int s = VR_FPAM_K; s <= VR_FPAM_B; ++s)
+        if (S.name[s].form != VINE_REDRAW_ABSENT) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                const int p = VP_FPAM_K0 + (s - VR_FPAM_K) * NL + j;
+                pcol[p] = (float)((double)S.base_params[p] * v[s]);
+            }
+        }
+    icol[VI_CART_MASS] = S.name[VR_CART_MASS].form != VINE_REDRAW_ABSENT ? (float)v[VR_CART_MASS] : S.base_inertia[VI_CART_MASS];
+    const double link = S.name[VR_LINK_MASS].form != VINE_REDRAW_ABSENT ? v[VR_LINK_MASS] : 1.0;
+    const double tip = S.name[VR_TIP_LINK_MASS].form != VINE_REDRAW_ABSENT ? v[VR_TIP_LINK_MASS] : 1.0;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        const double f = i == NL - 1 ? link * tip : link;
+        icol[VI_LINK_MASS0 + i] = (float)((double)S.base_inertia[VI_LINK_MASS0 + i] * f);
+        icol[VI_LINK_INERTIA0 + i] = (float)((double)S.base_inertia[VI_LINK_INERTIA0 + i] * f);
+    }
+    InertiaComposites ic;
+    inertia_composites(icol[VI_CART_MASS], icol + VI_LINK_MASS0, icol + VI_LINK_INERTIA0, S.link_length, S.link_com, S.gravity, ic);
+    icol[VI_MTOT] = (float)ic.mtot;
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        icol[VI_B0 + i] = (float)ic.b[i];
+        icol[VI_GB0 + i] = (float)ic.gb[i];
+        icol[VI_ADIAG0 + i] = (float)ic.adiag[i];
+        if (i > 0) icol[VI_AOFF1 + i - 1] = (float)ic.aoff[i];
+    }
+}
+
+__host__ __device__ inline bool names_inertia(const VineEnvRedrawSpec& S) {
+    return S.name[VR_CART_MASS].form != VINE_REDRAW_ABSENT || S.name[VR_LINK_MASS].form != VINE_REDRAW_ABSENT ||
+           S.name[VR_TIP_LINK_MASS].form != VINE_REDRAW_ABSENT;
+}
+
+__global__ __launch_bounds__(THREADS) void vine_env_redraw_kernel(const VineEnvRedrawSpec S, const int n, const unsigned env_off,
+                                                                  const long long* __restrict__ reset, float* __restrict__ st,
+                                                                  float* __restrict__ ptab, float* __restrict__ itab,
+                                                                  int* __restrict__ episode_index) {
+    const int e = blockIdx.x * THREADS + (int)threadIdx.x;
+    if (e >= n) return;
+    if (reset[e] == 0) return;
+    const int k = episode_index[e] + 1;
+    episode_index[e] = k;
+    const unsigned long long g = (unsigned long long)env_off + (unsigned long long)e;
+
+    double v[VR_NAMES];
+#pragma unroll
+    for (int s = 0; s < VR_NAMES; ++s)
+        v[s] = S.name[s].form != VINE_REDRAW_ABSENT
+                   ? redraw_value(S.name[s], s == VR_ACTION_DELAY, S.values, S.seed, g, (unsigned long long)(long long)k)
+                   : 0.0;
+    float pcol[VP_COUNT], icol[VI_COUNT];
+    redraw_column(S, v, pcol, icol);
+
+    if (S.name[VR_ACTION_DELAY].form != VINE_REDRAW_ABSENT) {
+        const float old_delay = ptab[(size_t)VP_ACTION_DELAY * n + e];
+        if (old_delay != pcol[VP_ACTION_DELAY]) {
+#pragma unroll
+            for (int j = 0; j < 2 * VINE_MAX_DELAY; ++j) st[(size_t)(VF_FIFO0 + j) * n + e] = 0.0f;
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < VR_FPAM_K; ++s)
+        if (S.name[s].form != VINE_REDRAW_ABSENT) ptab[(size_t)s * n + e] = pcol[s];
+#pragma unroll
+    for (int s = VR_FPAM_K; s <= VR_FPAM_B; ++s)
+        if (S.name[s].form != VINE_REDRAW_ABSENT) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                const int p = VP_FPAM_K0 + (s - VR_FPAM_K) * NL + j;
+                ptab[(size_t)p * n + e] = pcol[p];
+            }
+        }
+    if (itab) {
+#pragma unroll
+        for (int r = 0; r < VI_COUNT; ++r) itab[(size_t)r * n + e] = icol[r];
+    }
+}
+
+int bad_name(int s, const char* why) {
+    static const char* const kNames[VR_NAMES] = {
+        "DAMPING", "SMOOTHING_ALPHA_INFLATE", "SMOOTHING_ALPHA_DEFLATE", "RAIL_VELOCITY_SCALE", "RAIL_P_GAIN", "RAIL_D_GAIN",
+        "RAIL_ACCELERATION", "ACTION_DELAY", "FPAM_K", "FPAM_C", "FPAM_b", "FPAM_B", "CART_MASS", "LINK_MASS", "TIP_LINK_MASS"};
+    char msg[200];
+    snprintf(msg, sizeof msg, "env redraw spec: %s: %s", kNames[s], why);
+    return vine_invalid_arg(msg);
+}
+
+// a refusal of the table checks, which saw candidate column i as a table of one env: "of env 0" -> "of candidate i"
+int refused_candidate(int rc, int i) {
+    std::string msg = vine_last_error();
+    const size_t at = msg.find(" of env 0 ");
+    if (at != std::string::npos) msg.replace(at, 10, " of candidate " + std::to_string(i) + " ");
+    vine_set_error(msg.c_str());
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vine_env_redraw_spec_size(void) { return (int)sizeof(VineEnvRedrawSpec); }
+
+int vine_env_redraw_spec(const VineConfig* cfg, const VineEnvRedrawName names[VR_NAMES], const double* host_values,
+                         const double* device_values, int num_values, VineEnvRedrawSpec* out) {
+    if (!cfg || !names || !out) return vine_invalid_arg("null argument to vine_env_redraw_spec");
+    if (num_values < 0 || (num_values > 0 && (!host_values || !device_values)))
+        return vine_invalid_arg("null argument to vine_env_redraw_spec: the value lists need a host and a device array");
+    VineEnvRedrawSpec S;
+    memset(&S, 0, sizeof S);
+    S.abi_version = VINE_ENV_REDRAW_ABI_VERSION;
+    S.num_values = num_values;
+    S.seed = cfg->seed;
+    S.values = device_values;
+    float irow[VI_COUNT];
+    int rc = vine_env_params_row(cfg, S.base_params);
+    if (rc) return rc;
+    rc = vine_env_inertia_row(cfg, irow);
+    if (rc) return rc;
+    for (int r = 0; r < VI_PRIMARY_COUNT; ++r) S.base_inertia[r] = irow[r];
+    S.link_length = cfg->link_length; S.link_com = cfg->link_com; S.gravity = cfg->gravity;
+    int width = 1;
+    bool any = false;
+    for (int s = 0; s < VR_NAMES; ++s) {
+        const VineEnvRedrawName& nm = names[s];
+        S.name[s] = nm;
+        if (nm.reserved != 0) return bad_name(s, "reserved must be 0");
+        if (nm.form == VINE_REDRAW_ABSENT) continue;
+        any = true;
+        if (nm.form == VINE_REDRAW_NUMBER) {
+            if (!std::isfinite(nm.lo)) return bad_name(s, "the number is not finite");
+        } else if (nm.form == VINE_REDRAW_RANGE) {
+            if (!std::isfinite(nm.lo) || !std::isfinite(nm.hi) || nm.lo > nm.hi) return bad_name(s, "a range needs finite lo <= hi");
+            if (s == VR_ACTION_DELAY && (nm.lo != std::floor(nm.lo) || nm.hi != std::floor(nm.hi)))
+                return bad_name(s, "an integer parameter takes an integer range");
+            if (width < 2) width = 2;
+        } else if (nm.form == VINE_REDRAW_VALUES) {
+            if (nm.values_count < 1 || nm.values_first < 0 || (long long)nm.values_first + nm.values_count > num_values)
+                return bad_name(s, "the extent of the value list lies outside the values array");
+            if (nm.radix < 1) return bad_name(s, "radix must be at least 1");
+            for (int i = 0; i < nm.values_count; ++i)
+                if (!std::isfinite(host_values[nm.values_first + i])) return bad_name(s, "a listed value is not finite");
+            if (width < nm.values_count) width = nm.values_count;
+        } else {
+            return bad_name(s, "unknown form");
+        }
+    }
+    if (!any) return vine_invalid_arg("env redraw spec: no name is present, nothing to redraw");
+    // what the spec CAN give an env: candidate column i takes every name's candidate i (mod its count)
+    for (int i = 0; i < width; ++i) {
+        double v[VR_NAMES];
+        for (int s = 0; s < VR_NAMES; ++s) {
+            const VineEnvRedrawName& nm = S.name[s];
+            v[s] = 0.0;
+            if (nm.form == VINE_REDRAW_NUMBER) v[s] = nm.lo;
+            else if (nm.form == VINE_REDRAW_RANGE) v[s] = (i & 1) ? nm.hi : nm.lo;
+            else if (nm.form == VINE_REDRAW_VALUES) v[s] = host_values[nm.values_first + i % nm.values_count];
+        }
+        float pcol[VP_COUNT], icol[VI_COUNT];
+        redraw_column(S, v, pcol, icol);
+        rc = vine_env_params_check(cfg, pcol, 1);
+        if (rc) return refused_candidate(rc, i);
+        if (names_inertia(S)) {
+            rc = vine_env_inertia_check(cfg, icol, 1);
+            if (rc) return refused_candidate(rc, i);
+        }
+    }
+    S.checked = 1u;
+    *out = S;
+    return VINE_OK;
+}
+
+int vine_env_redraw_scheduled(VineHandle* h, const VineEnvRedrawSpec* spec, const int64_t* reset, float* params_table,
+                              float* inertia_table, int32_t* episode_index, void* stream) {
+    if (!h || !spec || !reset || !params_table || !episode_index) return vine_invalid_arg("null argument to vine_env_redraw_scheduled");
+    if (spec->abi_version != VINE_ENV_REDRAW_ABI_VERSION) return vine_invalid_arg("VineEnvRedrawSpec.abi_version mismatch");
+    if (spec->checked != 1u) return vine_invalid_arg("VineEnvRedrawSpec was not filled by vine_env_redraw_spec");
+    if (spec->num_values > 0 && !spec->values) return vine_invalid_arg("VineEnvRedrawSpec.values is NULL");
+    VineHandleInfo info;
+    int rc = vine_handle_info(h, &info);
+    if (rc) return rc;
+    const float *bound_params = nullptr, *bound_inertia = nullptr;
+    unsigned env_off = 0;
+    rc = vine_env_tables_of(h, &bound_params, &bound_inertia, &env_off);
+    if (rc) return rc;
+    if (!bound_params)
+        return vine_invalid_arg("vine_env_redraw_scheduled needs a parameter table bound to the handle (vine_bind_env_params)");
+    if (bound_params != params_table)
+        return vine_invalid_arg("vine_env_redraw_scheduled: params_table is not the table bound to the handle");
+    if (names_inertia(*spec) && (!bound_inertia || !inertia_table))
+        return vine_invalid_arg("vine_env_redraw_scheduled: the spec names masses and needs an inertia table bound to the handle "
+                                "(vine_bind_env_inertia)");
+    if (inertia_table && bound_inertia != inertia_table)
+        return vine_invalid_arg("vine_env_redraw_scheduled: inertia_table is not the table bound to the handle");
+    VineDeviceScope scope(info.device);
+    if (!scope.ok) return VINE_ERR_DEVICE;
+    const int blocks = (info.n + THREADS - 1) / THREADS;
+    hipLaunchKernelGGL(vine_env_redraw_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, *spec, info.n, env_off,
+                       (const long long*)reset, info.state, params_table, names_inertia(*spec) ? inertia_table : nullptr,
+                       episode_index);
+    return vine_launch_status("vine_env_redraw");
+}
+
+}  // extern "C"

@@ -34,6 +34,7 @@
 #include "vine_policy_head.h"            // Philox, the quad's reductions, the policy head and the rollout bookkeeping of ROLL / EVAL
 #include "vine_observer.h"
 #include "vine_task_shared.h"            // the action -> command map (shared with the sysid pin), clampf
+#include "vine_inertia_composites.h"     // the Lagrangian's constant coefficients from the masses (shared with the redraw node)
 
 #define NL VINE_NUM_LINKS
 #define ND VINE_NUM_DOFS
@@ -2265,27 +2266,7 @@ int validate(const VineConfig* c) {
     return VINE_OK;
 }
 
-// The constant coefficients of the absolute-angle Lagrangian from the masses, accumulated in double: the one statement of
-// them.  make_params rounds them into the handle's constants, vine_env_inertia_derive into a table column
-// (include/vine_env_inertia.h), so a uniform handle and a column of the same float32 masses hold the same bits.
-struct InertiaComposites {
-    double mtot, b[NL], gb[NL], adiag[NL], aoff[NL];      // aoff[i] = L b_i = a_ij for every j < i
-};
-void inertia_composites(float cart_mass, const float* link_mass, const float* link_inertia, float link_length, float link_com,
-                        float gravity, InertiaComposites& o) {
-    double m[NL], mt = cart_mass, L = link_length, l = link_com;
-    for (int i = 0; i < NL; ++i) { m[i] = link_mass[i]; mt += m[i]; }
-    o.mtot = mt;
-    for (int i = 0; i < NL; ++i) {
-        double distal = 0;
-        for (int k = i + 1; k < NL; ++k) distal += m[k];
-        o.b[i] = m[i] * l + L * distal;
-        o.gb[i] = (double)gravity * o.b[i];
-        o.adiag[i] = m[i] * l * l + L * L * distal + (double)link_inertia[i];
-        o.aoff[i] = L * o.b[i];
-    }
-}
-
+// (inertia_composites, the one statement of the Lagrangian's constant coefficients from the masses: vine_inertia_composites.h)
 void make_params(const VineConfig& c, DevParams& P) {
     memset(&P, 0, sizeof P);
     P.n = c.num_envs; P.num_obs = vine_num_obs(&c); P.obs_type = c.obs_type; P.cfi = c.control_freq_inv;
@@ -2960,6 +2941,13 @@ int vine_handle_info(VineHandle* h, VineHandleInfo* out) {
     return VINE_OK;
 }
 const float* vine_reward_matrix_of(VineHandle* h) { return h ? h->reward_matrix : nullptr; }
+int vine_env_tables_of(VineHandle* h, const float** params, const float** inertia, unsigned* env_id_offset) {
+    if (!h || !params || !inertia || !env_id_offset) return fail(VINE_ERR_INVALID_ARG, "null argument to vine_env_tables_of");
+    *params = h->env_params;
+    *inertia = h->env_inertia;
+    *env_id_offset = h->P.env_off;
+    return VINE_OK;
+}
 void vine_set_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 
 #ifdef VSQ_TIMING

@@ -155,13 +155,19 @@ class PpoPlayerContinuous(FastInferenceMixin):
         the envs: by exact value where the envs hold at most ``exact`` distinct ones (a ``values`` entry of ``ENV_PARAMS``),
         else by bin.  Also kept in ``self.report["by_param"]``: name -> (values or bin edges, rate, episode count)."""
         from ..utils import episodes
-        rows = env.episode_log.rows()
-        keep = rows["end_step"] >= self._episodes_start[1]
-        rows = {k: v[keep] for k, v in rows.items()}
-        table = env.env_params_of(range(int(env.num_envs)))
-        inertia = env.env_inertia_of(range(int(env.num_envs))) if getattr(env, "env_inertia", None) is not None else None
-        per_env = episodes.varying_params(table, env.env_param_names, inertia)
-        rows = episodes.with_env_params(rows, table, env.env_param_names, inertia)
+        if getattr(env, "env_redraw", None) is not None:     # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode
+            rows = env.episode_log.rows_with_params()
+            keep = rows["end_step"] >= self._episodes_start[1]
+            rows = {k: v[keep] for k, v in rows.items()}
+            per_env = {k[6:]: v for k, v in rows.items() if k.startswith("param_")}
+        else:
+            rows = env.episode_log.rows()
+            keep = rows["end_step"] >= self._episodes_start[1]
+            rows = {k: v[keep] for k, v in rows.items()}
+            table = env.env_params_of(range(int(env.num_envs)))
+            inertia = env.env_inertia_of(range(int(env.num_envs))) if getattr(env, "env_inertia", None) is not None else None
+            per_env = episodes.varying_params(table, env.env_param_names, inertia)
+            rows = episodes.with_env_params(rows, table, env.env_param_names, inertia)
         by_param, lines = {}, []
         for column in [k for k in rows if k.startswith("param_")]:
             lines.append("  reached_ever_rate by %s:" % column)

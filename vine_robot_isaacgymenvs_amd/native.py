@@ -17,7 +17,8 @@ SRC_RENDER = os.path.join(_HERE, "csrc", "vine_render.hip")
 SRC_RECORD = os.path.join(_HERE, "csrc", "vine_record.hip")
 SRC_EPISODES = os.path.join(_HERE, "csrc", "vine_episodes.hip")
 SRC_SYSID = os.path.join(_HERE, "csrc", "vine_sysid.hip")
-SOURCES = (SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES, SRC_SYSID)
+SRC_REDRAW = os.path.join(_HERE, "csrc", "vine_env_redraw.hip")
+SOURCES = (SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES, SRC_SYSID, SRC_REDRAW)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -27,7 +28,13 @@ _HEADERS = ([os.path.join(_INC, h) for h in ("vine.h", "vine_ppo.h", "vine_rende
                                               "vine_env_params.h", "vine_env_inertia.h", "vine_sysid.h")]
             + [os.path.join(_HERE, "csrc", h) for h in ("vine_task_shared.h", "vine_geometry.h", "vine_observer.h",
                                                         "vine_policy_head.h", "vine_ppo_formulas.h")])
-DEPS = list(SOURCES) + _HEADERS
+# what only some translation units include and compile with: the others' objects do not depend on it
+_COMPOSITES = os.path.join(_HERE, "csrc", "vine_inertia_composites.h")
+_SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: [_COMPOSITES, os.path.join(_INC, "vine_env_redraw.h")]}
+# vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply
+# and an add (under -ffp-contract=fast hipcc fuses it on gfx950, a pragma in the source notwithstanding)
+_SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"]}
+DEPS = list(SOURCES) + _HEADERS + [_COMPOSITES, os.path.join(_INC, "vine_env_redraw.h")]
 
 _lib = None
 
@@ -49,24 +56,24 @@ def is_fresh():
         return False
 
 
-def _flags():
+def _flags(src=None):
     flags = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-fno-slp-vectorize", "-Wall",
-             "-Wno-unused-function"]
+             "-Wno-unused-function"] + _SOURCE_FLAGS.get(src, [])      # (a later -ffp-contract wins)
     extra = os.environ.get("VINE_HIPCC_FLAGS")       # experiments only (e.g. "-fslp-vectorize"); after the defaults, so they win
     return flags + (extra.split() if extra else [])
 
 
 def _object_fingerprint(src):
     h = hashlib.sha256()
-    for d in [src] + _HEADERS:
+    for d in [src] + _HEADERS + _SOURCE_HEADERS.get(src, []):
         with open(d, "rb") as f:
             h.update(f.read())
-    h.update(" ".join(_flags()).encode())
+    h.update(" ".join(_flags(src)).encode())
     return h.hexdigest()
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The six translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The seven translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -89,7 +96,7 @@ def build(force=False, verbose=False):
             fresh = False
         if fresh:
             continue
-        cmd = [hipcc] + _flags() + ["-c", "-o", obj, src]
+        cmd = [hipcc] + _flags(src) + ["-c", "-o", obj, src]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         if os.path.exists(obj + ".fingerprint"):

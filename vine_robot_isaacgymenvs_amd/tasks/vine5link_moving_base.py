@@ -148,10 +148,14 @@ class Vine5LinkMovingBase(VecTask):
         self._video = None
         self._trajectory = None
         self._episode_log = None
-        self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log
+        self._env_redraw = None
+        self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log,
+                                   # the per-episode redraw of the plants (last: it replaces what the others read)
 
         self._lib = None
         self._handle = None
+        from ..utils import env_params
+        self._per_episode = env_params.per_episode(self.cfg["env"])      # (refused here, before anything is created)
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -181,6 +185,8 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_trajectory()
         if self._on_rank0("EPISODE_LOG", "logged"):
             self._setup_episode_log()
+        if self._per_episode:                    # every rank: each redraws its own shard, by the global env id
+            self._setup_env_redraw()
 
     # ------------------------------------------------------------------ step observers (utils/observers.py)
     def _on_rank0(self, key, done):
@@ -331,6 +337,31 @@ class Vine5LinkMovingBase(VecTask):
         """The ``EpisodeLog`` of this env (``None`` unless ``EPISODE_LOG``)."""
         return self._episode_log
 
+    # ------------------------------------------------------------------ ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h)
+    def _setup_env_redraw(self):
+        """A launch behind every step redraws, on the device, the plant of every env that step flagged for a reset: episode
+        ``k`` of global env ``g`` runs with ``env_params.draw_columns`` of ``(g, k)``.  From here on the SPEC owns the tables:
+        ``env_params`` / ``env_inertia`` stay the device tensors, ``env_params_of`` / ``env_inertia_of`` read them, and
+        ``set_env_params`` raises.  Envs reset from outside the step (``reset_idx``) keep their plant."""
+        from ..utils import env_redraw
+        spec = self.cfg["env"].get("ENV_PARAMS") or {}
+        self._env_redraw = env_redraw.EnvRedraw(self._lib, self._handle, self._vcfg, spec, self.reset_buf, self.env_params,
+                                                self.env_inertia, self.device)
+        self._env_params_host = self._env_inertia_host = None        # no host mirror: the device redraws
+        for o in self._observers:
+            if hasattr(o, "redraw"):
+                o.redraw = self._env_redraw
+            if hasattr(o, "env_episode_of"):
+                o.env_episode_of = lambda envs: self._env_redraw.episodes_now()[list(envs)]
+        self._add_observer(self._env_redraw)
+        self.logger.info(f"ENV_PARAMS_PER_EPISODE: the plants of {len(self._env_redraw.spec)} names are redrawn on the device "
+                         f"whenever an env's episode ends")
+
+    @property
+    def env_redraw(self):
+        """The ``EnvRedraw`` of this env (``None`` unless ``ENV_PARAMS_PER_EPISODE``)."""
+        return self._env_redraw
+
     # ------------------------------------------------------------------ MAT_FILE replay (V5:281-297, 947-982)
     def read_mat_file(self, filename):
         """Recorded trajectory: cart_pos (1,T), Q (5,T), moving_target_pos (3,T), target_vel, tip_pos (3,T),
@@ -475,6 +506,9 @@ class Vine5LinkMovingBase(VecTask):
         from ..utils import env_params
         if self.env_params is None:
             raise RuntimeError("set_env_params(): no per-env parameter table is bound (task.env.ENV_PARAMS is empty)")
+        if self._env_redraw is not None:
+            raise RuntimeError("set_env_params(): task.env.ENV_PARAMS_PER_EPISODE is on, the spec owns the tables: the device "
+                               "redraws an env's column at its next reset and would overwrite what is set here")
         primary = self.env_inertia_names[:abi.VI_PRIMARY_COUNT]
         inertia = {}
         for name in [k for k in values if k in abi.ENV_INERTIA_NAMES or k in primary]:
@@ -512,6 +546,8 @@ class Vine5LinkMovingBase(VecTask):
     def env_params_of(self, envs):
         """The host mirror's columns of ``envs`` as float64 [VP_COUNT, len(envs)] (``None`` without a bound table)."""
         import numpy as np
+        if self._env_redraw is not None:         # ENV_PARAMS_PER_EPISODE: the device's table, as of now (synchronises)
+            return self.env_params[:, list(envs)].cpu().numpy().astype(np.float64)
         if self._env_params_host is None:
             return None
         return self._env_params_host[:, list(envs)].astype(np.float64)
@@ -519,6 +555,8 @@ class Vine5LinkMovingBase(VecTask):
     def env_inertia_of(self, envs):
         """The inertia table's host mirror, columns ``envs``, as float64 [VI_COUNT, len(envs)] (``None`` without one)."""
         import numpy as np
+        if self._env_redraw is not None and self.env_inertia is not None:
+            return self.env_inertia[:, list(envs)].cpu().numpy().astype(np.float64)
         if self._env_inertia_host is None:
             return None
         return self._env_inertia_host[:, list(envs)].astype(np.float64)
@@ -529,7 +567,7 @@ class Vine5LinkMovingBase(VecTask):
             for o in self._observers:
                 o.drain()
                 o.close()
-            self._observers, self._video, self._trajectory, self._episode_log = [], None, None, None
+            self._observers, self._video, self._trajectory, self._episode_log, self._env_redraw = [], None, None, None, None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)

@@ -296,3 +296,125 @@ def varying_rows(table):
     """Indices of the rows whose values differ across envs."""
     t = np.asarray(table)
     return [p for p in range(t.shape[0]) if np.any(t[p] != t[p, 0])]
+
+
+# ---- ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h): the draw of episode k, and the spec the device redraws from
+def per_episode(env_cfg):
+    """Is ``ENV_PARAMS_PER_EPISODE`` on in the ``task.env`` mapping?  ``ConfigError`` when it is and ``ENV_PARAMS`` is empty."""
+    if not env_cfg.get("ENV_PARAMS_PER_EPISODE", False):
+        return False
+    if not len(env_cfg.get("ENV_PARAMS") or {}):
+        raise ConfigError("task.env.ENV_PARAMS_PER_EPISODE needs a non-empty task.env.ENV_PARAMS: there is no plant to redraw")
+    return True
+
+
+def name_key(name):
+    """The 64-bit key of a parameter name: the first 8 bytes of its SHA-256, little endian."""
+    return int.from_bytes(hashlib.sha256(name.encode()).digest()[:8], "little")
+
+
+def uniform01_episode(seed, name, gids, episodes):
+    """One float64 in [0, 1) per (global env id, episode) pair, a pure function of ``(seed, name, id, episode)``; episode 0
+    is ``uniform01``, because ``_mix(0) == 0``."""
+    g = np.asarray(gids, dtype=np.uint64)
+    k = np.asarray(episodes, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        pre = _mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(name_key(name))) + g * np.uint64(0x9E3779B97F4A7C15)
+        h = _mix(pre ^ _mix(k))
+    return (h >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+def _draw_episode(forms, seed, gids, episodes):
+    """``_draw`` for (global env id, episode) pairs: episode 0 is ``_draw``'s value; from episode 1 on a ``values`` entry
+    takes ``values[min(floor(u * len), len - 1)]`` with its own ``u`` (the mixed-radix count of the id alone would repeat the
+    same combination for ever)."""
+    gids = np.asarray(gids, dtype=np.int64)
+    k = np.asarray(episodes, dtype=np.int64)
+    out, radix = {}, 1
+    for name, form in forms.items():
+        if form[0] == "scalar":
+            v = np.full(len(gids), form[1], dtype=np.float64)
+        elif form[0] == "range":
+            lo, hi = form[1], form[2]
+            u = uniform01_episode(seed, name, gids, k)
+            if name == "ACTION_DELAY":
+                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
+            else:
+                v = lo + (hi - lo) * u
+        else:
+            vals = np.asarray(form[1], dtype=np.float64)
+            u = uniform01_episode(seed, name, gids, k)
+            later = np.minimum(np.floor(u * float(len(vals))).astype(np.int64), len(vals) - 1)
+            v = vals[np.where(k == 0, (gids // radix) % len(vals), later)]
+            radix *= len(vals)
+        out[name] = v
+    return out
+
+
+def draw_columns(spec, base, inertia_base, derive, seed, gids, episodes):
+    """The columns of M ``(global env id, episode)`` pairs: ``(params [VP_COUNT, M], inertia [VI_COUNT, M])`` float32, formed
+    exactly as ``draw_table`` / ``draw_inertia_table`` form a table (float64 throughout, rounded once); episode 0 is bit for
+    bit their table.  ``base`` / ``inertia_base``: the configuration's rows (``config_row`` / ``inertia_config_row``);
+    ``derive(table)``: ``derive_inertia`` bound to a library and a configuration.  ``inertia`` is ``None`` when the spec names
+    none of ``abi.ENV_INERTIA_NAMES``.  What the device's redraw (include/vine_env_redraw.h) is compared against."""
+    forms = spec_forms(spec)
+    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
+    episodes = np.broadcast_to(np.asarray(episodes, dtype=np.int64), gids.shape)
+    if np.any(gids < 0) or np.any(episodes < 0):
+        raise ValueError("draw_columns: env ids and episodes are non-negative")
+    drawn = _draw_episode(forms, seed, gids, episodes)
+    base = np.asarray(base, dtype=np.float32)
+    params = np.repeat(base[:, None], len(gids), axis=1)
+    for name, v in drawn.items():
+        if name in abi.ENV_PARAM_ROWS:
+            set_rows(params, base, name, v)
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    if not any(name in forms for name in abi.ENV_INERTIA_NAMES):
+        return params, None
+    ibase = np.asarray(inertia_base, dtype=np.float32)
+    inertia = np.repeat(ibase[:, None], len(gids), axis=1)
+    set_inertia_rows(inertia, ibase, {name: v for name, v in drawn.items() if name in abi.ENV_INERTIA_NAMES})
+    return params, derive(inertia)
+
+
+def build_columns(spec, vcfg, gids, episodes, lib=None, seed=None):
+    """``draw_columns`` with the rows, the derivation and the seed of a handle's ``abi.VineConfig``."""
+    if lib is None:
+        from .. import native
+        lib = native.load()
+    return draw_columns(spec, config_row(lib, vcfg), inertia_config_row(lib, vcfg), lambda t: derive_inertia(lib, vcfg, t),
+                        int(vcfg.seed) if seed is None else seed, gids, episodes)
+
+
+def redraw_names(spec):
+    """``(abi.VineEnvRedrawName * VR_NAMES, values float64 [V])`` of a spec: per name its form, ends, key, the extent of its
+    list in ``values`` and its place in the mixed radix."""
+    forms = spec_forms(spec)
+    names = (abi.VineEnvRedrawName * abi.VR_NAMES)()
+    values, radix = [], 1
+    for name, form in forms.items():
+        nm = names[abi.ENV_REDRAW_NAMES.index(name)]
+        nm.key = name_key(name)
+        nm.radix = 1
+        if form[0] == "scalar":
+            nm.form, nm.lo, nm.hi = abi.REDRAW_NUMBER, form[1], form[1]
+        elif form[0] == "range":
+            nm.form, nm.lo, nm.hi = abi.REDRAW_RANGE, form[1], form[2]
+        else:
+            nm.form, nm.values_first, nm.values_count, nm.radix = abi.REDRAW_VALUES, len(values), len(form[1]), radix
+            values += form[1]
+            radix *= len(form[1])
+    return names, np.asarray(values, dtype=np.float64)
+
+
+def redraw_spec(lib, vcfg, spec, device_values=None):
+    """``vine_env_redraw_spec``: the checked ``abi.VineEnvRedrawSpec`` of a spec.  ``device_values``: address of the float64
+    device array holding ``redraw_names(spec)[1]`` (needed when the spec has a ``values`` entry).  Raises ``ConfigError`` for
+    a malformed spec and ``ValueError`` for one whose ends or listed values the table checks refuse."""
+    names, values = redraw_names(spec)
+    out = abi.VineEnvRedrawSpec()
+    rc = lib.vine_env_redraw_spec(C.byref(vcfg), names, values.ctypes.data if len(values) else None,
+                                  device_values if len(values) else None, len(values), C.byref(out))
+    if rc != abi.OK:
+        raise ValueError("ENV_PARAMS: %s" % lib.vine_last_error().decode(errors="replace"))
+    return out

@@ -135,6 +135,35 @@ def with_env_params(rows, table, names, inertia=None):
     return out
 
 
+def episode_ordinals(env, end_step, episode_index):
+    """The ordinal of the episode every row of ONE harvest ended, counted BACKWARDS from ``episode_index`` (int [N], the
+    device's per-env episode counter copied at the same stream point as the cursor): the m harvested rows of env e, sorted by
+    end step, are episodes ``c_e - m .. c_e - 1``.  That also holds where the ring dropped rows, because the survivors are
+    each env's newest; counting forwards from the previous harvest would be off by the rows dropped."""
+    env = np.asarray(env, dtype=np.int64)
+    end = np.asarray(end_step, dtype=np.int64)
+    c = np.asarray(episode_index, dtype=np.int64)
+    order = np.lexsort((end, env))                                   # by env, then by end step
+    e = env[order]
+    first = np.r_[0, np.flatnonzero(e[1:] != e[:-1]) + 1] if len(e) else np.zeros(0, dtype=np.int64)
+    count = np.diff(np.r_[first, len(e)])
+    rank = np.arange(len(e)) - np.repeat(first, count)                # 0 .. m - 1 within the env
+    out = np.empty(len(e), dtype=np.int64)
+    out[order] = c[e] - np.repeat(count, count) + rank
+    return out
+
+
+def with_episode_params(rows, params, names, inertia=None):
+    """``rows`` with ``param_<NAME>`` per parameter that varies across the ROWS: ``params`` [VP_COUNT, R] (``inertia``
+    [VI_COUNT, R] or ``None``) hold the column every row's episode ran with (``env_params.draw_columns`` of the rows' env and
+    ``episode``), reduced as ``varying_params`` reduces a table.  The rates then bin by episode, not by env."""
+    out = dict(rows)
+    if len(np.asarray(rows["env"])):
+        for name, values in varying_params(params, names, inertia).items():
+            out["param_" + name] = values
+    return out
+
+
 def value_rate(rows, column, of="reached_ever"):
     """The mean of the 0/1 column ``of`` over the episodes of each distinct value of ``column``: (values [V] ascending,
     rate [V], count [V])."""
@@ -145,11 +174,24 @@ def value_rate(rows, column, of="reached_ever"):
     return values, hit / np.maximum(count, 1), count
 
 
-def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None):
+def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
+         redraw=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
-    bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``."""
+    bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
+    dict of ``spec``, ``seed``, ``env_id_offset``, ``base``, ``inertia_base``, ``geometry``) the rows' ``episode`` column and
+    what ``load_env_redraw`` needs to rebuild every episode's column without a device; the two tables are then the plants
+    at the moment of writing."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if redraw is not None:
+        import json
+        out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
+        out["redraw_spec"] = np.array(json.dumps(redraw["spec"]))
+        out["redraw_seed"] = np.array(int(redraw["seed"]), dtype=np.uint64)
+        out["redraw_env_id_offset"] = np.array(int(redraw["env_id_offset"]), dtype=np.int64)
+        out["redraw_base"] = np.asarray(redraw["base"], dtype=np.float32)
+        out["redraw_inertia_base"] = np.asarray(redraw["inertia_base"], dtype=np.float32)
+        out["redraw_geometry"] = np.asarray(redraw["geometry"], dtype=np.float32)      # link_length, link_com, gravity
     if env_params is not None:
         out["env_params"] = np.asarray(env_params, dtype=np.float32)
         out["env_param_names"] = np.array(list(env_param_names))
@@ -191,6 +233,29 @@ def load_env_inertia(path):
         return z["env_inertia"], [str(n) for n in z["env_inertia_names"]]
 
 
+def load_env_redraw(path):
+    """Of a file written under ENV_PARAMS_PER_EPISODE: ``(episode [R], columns)`` with ``columns(envs, episodes)`` ->
+    ``(params [VP_COUNT, M], inertia [VI_COUNT, M] or None)``, ``env_params.draw_columns`` rebuilt from the stored spec, seed,
+    ``env_id_offset`` and base rows (host code of the library only, no device); else ``(None, None)``."""
+    import ctypes as C
+    import json
+    from . import env_params
+    with np.load(path) as z:
+        if "redraw_spec" not in z.files:
+            return None, None
+        spec, seed, offset = json.loads(str(z["redraw_spec"][()])), int(z["redraw_seed"]), int(z["redraw_env_id_offset"])
+        base, inertia_base, geometry, episode = z["redraw_base"], z["redraw_inertia_base"], z["redraw_geometry"], z["episode"]
+
+    def columns(envs, episodes_):
+        lib = native.load()
+        vcfg = abi.VineConfig()
+        native.check(lib.vine_config_default(C.byref(vcfg)), lib)
+        vcfg.link_length, vcfg.link_com, vcfg.gravity = (float(g) for g in geometry)
+        return env_params.draw_columns(spec, base, inertia_base, lambda t: env_params.derive_inertia(lib, vcfg, t), seed,
+                                       np.asarray(envs, dtype=np.int64) + offset, episodes_)
+    return episode, columns
+
+
 class EpisodeLog:
     """The device buffers of one env handle's episode log, the host's count of steps since the last harvest, and the
     harvest.  A step observer (the protocol: utils/observers.py); not windowed, so its harvest is its own."""
@@ -228,6 +293,8 @@ class EpisodeLog:
         self.copy_done = None        # (the harvest is synchronous: no copy is ever in flight)
         self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
         self.env_inertia_of, self.env_inertia_names = None, None   # ENV_INERTIA: likewise
+        self.redraw = None           # ENV_PARAMS_PER_EPISODE: the task's ``env_redraw.EnvRedraw``; rows then carry ``episode``
+        self.part_counters = []      # ... and every harvested part the device's episode_index at its harvest
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -285,16 +352,42 @@ class EpisodeLog:
         a, b = first % self.capacity, (cursor - 1) % self.capacity + 1
         words = self.table[a:b] if a < b else torch.cat([self.table[a:], self.table[:b]])
         self.parts.append(words.cpu().numpy())       # decoded and sorted when somebody asks for rows
+        if self.redraw is not None:                  # the same stream point as the cursor: nothing was enqueued in between
+            self.part_counters.append(self.redraw.episodes_now())
         self._rows = None
         return cursor - first
 
     def rows(self):
         """Every harvested row so far, sorted by (end step, env)."""
-        if self._rows is None:
+        if self._rows is None and self.redraw is not None:
+            parts = []
+            for words, counters in zip(self.parts, self.part_counters):      # ordinals count back from each harvest's counters
+                part = decode_rows(words)
+                part["episode"] = episode_ordinals(part["env"], part["end_step"], counters)
+                parts.append(part)
+            if parts:
+                rows = {name: np.concatenate([p[name] for p in parts]) for name in COLUMNS + ("episode",)}
+            else:
+                rows = dict(concat_rows([]), episode=np.zeros(0, dtype=np.int64))
+            order = np.lexsort((rows["env"], rows["end_step"]))
+            self._rows = {name: v[order] for name, v in rows.items()}
+        elif self._rows is None:
             if len(self.parts) > 1:
                 self.parts = [np.concatenate(self.parts)]
             self._rows = decode_rows(self.parts[0]) if self.parts else concat_rows([])
         return self._rows
+
+    def rows_with_params(self):
+        """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
+        (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env."""
+        rows = self.rows()
+        if self.redraw is not None:
+            params, inertia = self.redraw.columns(rows["env"], rows["episode"]) if len(rows["env"]) else (None, None)
+            return with_episode_params(rows, params, self.env_param_names, inertia)
+        if self.env_params_of is None:
+            return dict(rows)
+        inertia = self.env_inertia_of(range(self.num_envs)) if self.env_inertia_of is not None else None
+        return with_env_params(rows, self.env_params_of(range(self.num_envs)), self.env_param_names, inertia)
 
     def folded_totals(self):
         """The twelve totals, folded over the workgroups' rows in float64 on the host (synchronises)."""
@@ -305,8 +398,15 @@ class EpisodeLog:
         self.harvest()
         table = self.env_params_of(range(self.num_envs)) if self.env_params_of is not None else None
         inertia = self.env_inertia_of(range(self.num_envs)) if self.env_inertia_of is not None else None
+        redraw = None
+        if self.redraw is not None:
+            from . import env_params
+            r = self.redraw
+            redraw = {"spec": r.spec, "seed": r.seed, "env_id_offset": r.env_id_offset,
+                      "base": env_params.config_row(r.lib, r.vcfg), "inertia_base": env_params.inertia_config_row(r.lib, r.vcfg),
+                      "geometry": (r.vcfg.link_length, r.vcfg.link_com, r.vcfg.gravity)}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names)
+             self.env_inertia_names, redraw)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

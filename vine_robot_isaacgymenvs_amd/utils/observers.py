@@ -17,7 +17,10 @@ enqueued.  The task class (tasks/vine5link_moving_base.py) keeps its observers i
   copy_done                 event behind a harvest copy still reading the observer's device buffers, else ``None``
 
 The observers: ``video.VideoCapture`` (CAPTURE_VIDEO), ``trajectory.TrajectoryRecorder`` (RECORD_TRAJECTORIES) -- both a
-``WindowRing`` -- and ``episodes.EpisodeLog`` (EPISODE_LOG).
+``WindowRing`` --, ``episodes.EpisodeLog`` (EPISODE_LOG), the SYSID node of utils/sysid.py, and, last in launch order,
+``env_redraw.EnvRedraw`` (ENV_PARAMS_PER_EPISODE): the one observer that WRITES what the step reads -- the bound per-env
+tables and the delay rings of the envs the step has just flagged -- so it runs behind the others, which have then read what
+this step's plant produced.  Its ``live_tensors`` are the tables and its episode counters.
 
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer

@@ -198,6 +198,7 @@ FORCED = (
     ("env", "RECORD_TRAJECTORIES", False),
     ("env", "EPISODE_LOG", False),
     ("env", "MAT_FILE", ""),
+    ("env", "ENV_PARAMS_PER_EPISODE", False),      # a candidate keeps its plant: the table IS the search's population
 )
 
 

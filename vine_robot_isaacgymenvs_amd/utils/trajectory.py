@@ -22,7 +22,7 @@ def record_config(lib, every, steps, num_envs):
     return c
 
 
-def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None):
+def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None, env_episode=None):
     """The MAT file's variables from the rows of ONE env, ``rows[T, abi.RECORD_FIELDS]`` float32, and the step index of
     every row (with ``env_params``, the env's column of a bound per-env parameter table, also ``env_params`` (VP_COUNT, 1)
     and ``env_param_names``; with ``env_inertia``, the env's column of a bound inertia table, also ``env_inertia``
@@ -42,6 +42,8 @@ def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param
                  "env_param_names": np.array(list(env_param_names), dtype=object)}
     if env_inertia is not None:                  # ENV_INERTIA: the recorded env's 11 primary values
         extra["env_inertia"] = np.asarray(env_inertia, dtype=np.float64).reshape(-1)[:abi.VI_PRIMARY_COUNT].reshape(-1, 1)
+    if env_episode is not None:                  # ENV_PARAMS_PER_EPISODE: the ordinal of the env's episode at the harvest, whose
+        extra["env_episode"] = np.array([[int(env_episode)]], dtype=np.int64)          # plant env_params / env_inertia hold
     return {
         **extra,
         "cart_pos": d[f.VRF_Q0:f.VRF_Q0 + 1].copy(),
@@ -66,12 +68,13 @@ def trajectory_arrays(rows, steps, control_dt, env=0, env_params=None, env_param
     }
 
 
-def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None):
+def write_trajectory_mat(path, rows, steps, control_dt, env=0, env_params=None, env_param_names=None, env_inertia=None,
+                         env_episode=None):
     """``trajectory_arrays`` as a MATLAB 5 file at ``path`` (written beside it and renamed: no reader sees half a file)."""
     import scipy.io
     part = path + ".part"
     with open(part, "wb") as fh:
-        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env, env_params, env_param_names, env_inertia))
+        scipy.io.savemat(fh, trajectory_arrays(rows, steps, control_dt, env, env_params, env_param_names, env_inertia, env_episode))
     os.replace(part, path)
     return path
 
@@ -101,6 +104,7 @@ class TrajectoryRecorder(WindowRing):
         self.host_steps = torch.empty(self.steps.shape, dtype=torch.int64, pin_memory=True)
         self.env_params_of, self.env_param_names = None, None      # ENV_PARAMS: set by the task class when a table is bound
         self.env_inertia_of, self.env_inertia_names = None, None   # ENV_INERTIA: likewise
+        self.env_episode_of, self._env_episode = None, None        # ENV_PARAMS_PER_EPISODE: likewise; read at the harvest
         import scipy.io  # noqa: F401  (here, not in the writer thread: the first import takes 0.3 s, longer than a window)
         super().__init__(device, logger)
 
@@ -121,6 +125,7 @@ class TrajectoryRecorder(WindowRing):
         return [(self.ring, self.host), (self.steps, self.host_steps)]
 
     def _job_extra(self):
+        self._env_episode = self.env_episode_of(self.env_ids) if self.env_episode_of is not None else None
         return (self.env_params_of(self.env_ids) if self.env_params_of is not None else None,
                 self.env_inertia_of(self.env_ids) if self.env_inertia_of is not None else None)
 
@@ -137,6 +142,7 @@ class TrajectoryRecorder(WindowRing):
             self.written.append(write_trajectory_mat(
                 self.path(last, e), rows[:, k], steps, self.control_dt, e,
                 params[:, k] if params is not None else None, self.env_param_names,
-                inertia[:, k] if inertia is not None else None))
+                inertia[:, k] if inertia is not None else None,
+                self._env_episode[k] if self._env_episode is not None else None))
         self.logger.info(f"Saved {len(self.env_ids)} trajectories of steps {start}..{last} to "
                          f"{self.path(last, '<e>')}")
