@@ -11,7 +11,11 @@ handed a buffer of zeros that no step writes: every lane loads its flag and leav
 YAML's episodes under random actions), and with every env resetting every step (a buffer of ones: every lane redraws all
 28 + 31 rows).
 
-usage: python scripts/ubench/env_params_bench.py [--redraw] [num_envs ...]        (default: 16384 1048576)"""
+With --adr: the same three cases for the two launches of ENV_PARAMS_ADR (include/vine_env_adr.h) beside the redraw node in the
+same run.  The ADR launches read the reward matrix, and a bound matrix makes the step itself write 52 more bytes per env, so
+their baseline is the step alone WITH a matrix bound: node cost = (step + launches) - (that step).
+
+usage: python scripts/ubench/env_params_bench.py [--redraw | --adr] [num_envs ...]        (default: 16384 1048576)"""
 import os
 import statistics
 import sys
@@ -37,10 +41,17 @@ VARIANTS = {"lane": ("lane", None, None), "lane+own_row_table": ("lane", "own", 
             "lane+het_table+het_inertia": ("lane", "het", "het"), "quad": ("quad", None, None)}
 
 
-def make(n, kern, table, inertia=None, **over):
+ADR_NAMES = {"DAMPING": {"START": [0.03, 0.03], "STEP": 0.005}, "ACTION_DELAY": {"START": [4, 4], "STEP": 1},
+             "CART_MASS": {"START": [0.5, 0.5], "STEP": 0.05}, "LINK_MASS": {"START": [1.0, 1.0], "STEP": 0.05},
+             "TIP_LINK_MASS": {"START": [1.2, 1.2], "STEP": 0.1}}
+
+
+def make(n, kern, table, inertia=None, matrix=False, **over):
     cfg = base_cfg(n, 0, True, **over)
     env = type("H", (HipEnv,), {"kernel": kern})(cfg)
     env.set_introspection(False)
+    if matrix:
+        env.bind_reward_matrix()
     if table is not None:
         t = env_params.build_table(SPEC if table == "het" else {}, env.cfg, 1, n, lib=env.lib)
         env.table_t = torch.as_tensor(t, device=env.dev).contiguous()
@@ -66,12 +77,15 @@ def make(n, kern, table, inertia=None, **over):
     return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode()
 
 
-def make_redraw(n, which):
+def make_redraw(n, which, adr=False):
     """The handle of ``lane+het_table+het_inertia`` with the redraw node behind every captured step; ``which``: the flags the
-    node reads -- "none" (zeros), "own" (the step's reset buffer), "all" (ones)."""
+    node reads -- "none" (zeros), "own" (the step's reset buffer), "all" (ones).  ``adr``: the two ADR launches in the node's
+    place, a reward matrix bound."""
     cfg = base_cfg(n, 0, True)
     env = type("H", (HipEnv,), {"kernel": "lane"})(cfg)
     env.set_introspection(False)
+    if adr:
+        env.bind_reward_matrix()
     spec = dict(SPEC, **MASSES)
     env.table_t = torch.as_tensor(env_params.build_table(spec, env.cfg, 1, n, lib=env.lib), device=env.dev).contiguous()
     env.inertia_t = torch.as_tensor(env_params.build_inertia_table(spec, env.cfg, 1, n, lib=env.lib), device=env.dev).contiguous()
@@ -86,8 +100,20 @@ def make_redraw(n, which):
     g = torch.Generator(device=env.dev).manual_seed(0)
     acts = [torch.rand((n, 2), device=env.dev, generator=g) * 2 - 1 for _ in range(8)]
 
+    if adr:
+        acfg = env_params.adr_config({"ENV_PARAMS": spec, "ENV_PARAMS_PER_EPISODE": True, "ENV_PARAMS_ADR": {"NAMES": ADR_NAMES}})
+        aspec = env_params.adr_spec(env.lib, env.cfg, spec, acfg)
+        i32 = dict(dtype=torch.int32, device=env.dev)
+        state = [torch.zeros(30, **i32), torch.zeros(60, **i32), torch.zeros(n, **i32), torch.full((n,), -1, **i32),
+                 torch.zeros((acfg["HISTORY_CAPACITY"], 4), **i32), torch.zeros(1, dtype=torch.int64, device=env.dev)]
+        env.keep_adr = (aspec, state)
+
     def pair(a):
         env.step_t(a, sync=False)
+        if adr:
+            return native.check(env.lib.vine_env_adr_scheduled(
+                env.h, aspec, flags.data_ptr(), env.table_t.data_ptr(), env.inertia_t.data_ptr(), episode.data_ptr(),
+                *[t.data_ptr() for t in state], torch.cuda.current_stream(env.dev).cuda_stream), env.lib)
         native.check(env.lib.vine_env_redraw_scheduled(env.h, rspec, flags.data_ptr(), env.table_t.data_ptr(), env.inertia_t.data_ptr(),
                                                        episode.data_ptr(), torch.cuda.current_stream(env.dev).cuda_stream), env.lib)
     for i in range(16):
@@ -102,15 +128,20 @@ def make_redraw(n, which):
     env.keep = (rspec, episode, flags)
     torch.cuda.synchronize()
     env.reset_share = float((env.reset_t != 0).float().mean())
-    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + " + redraw"
+    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + (" + adr" if adr else " + redraw")
 
 
-def main_redraw(sizes):
+def main_redraw(sizes, adr=False):
     for n in sizes:
         envs = {"step alone (both het tables)": make(n, "lane", "het", "het"),
                 "step + node, no env resetting": make_redraw(n, "none"),
                 "step + node, the step's own resets": make_redraw(n, "own"),
                 "step + node, every env resetting": make_redraw(n, "all")}
+        if adr:
+            envs.update({"step alone, reward matrix bound": make(n, "lane", "het", "het", matrix=True),
+                         "step + adr, no env resetting": make_redraw(n, "none", True),
+                         "step + adr, the step's own resets": make_redraw(n, "own", True),
+                         "step + adr, every env resetting": make_redraw(n, "all", True)})
         times = {name: [] for name in envs}
         for _ in range(ROUNDS):
             for name, (env, graph, k, _) in envs.items():
@@ -126,9 +157,14 @@ def main_redraw(sizes):
             t = times[name]
             print("  %-36s %8.1f %8.1f %8.1f" % (name, min(t), statistics.median(t), max(t)), flush=True)
         base = statistics.median(times["step alone (both het tables)"])
-        for name in list(envs)[1:]:
+        for name in list(envs)[1:4]:
             own = " (%.1f %% of the envs flagged after the last step)" % (100 * envs[name][0].reset_share) if "own" in name else ""
             print("  node, %s: %+.2f us per launch%s" % (name.split(", ")[1], statistics.median(times[name]) - base, own))
+        if adr:
+            base = statistics.median(times["step alone, reward matrix bound"])
+            for name in list(envs)[5:]:
+                own = " (%.1f %% of the envs flagged after the last step)" % (100 * envs[name][0].reset_share) if "own" in name else ""
+                print("  adr launches, %s: %+.2f us per pair%s" % (name.split(", ")[1], statistics.median(times[name]) - base, own))
         for env, _, _, _ in envs.values():
             env.close()
         del envs
@@ -136,9 +172,9 @@ def main_redraw(sizes):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--redraw"]
-    if "--redraw" in sys.argv[1:]:
-        return main_redraw([int(a) for a in args] or [16384, 1 << 20])
+    args = [a for a in sys.argv[1:] if a not in ("--redraw", "--adr")]
+    if "--redraw" in sys.argv[1:] or "--adr" in sys.argv[1:]:
+        return main_redraw([int(a) for a in args] or [16384, 1 << 20], adr="--adr" in sys.argv[1:])
     for n in [int(a) for a in args] or [16384, 1 << 20]:
         envs = {name: make(n, *v) for name, v in VARIANTS.items()}
         times = {name: [] for name in VARIANTS}

@@ -584,6 +584,57 @@ def declare_env_redraw(lib):
     return lib
 
 
+# ---- include/vine_env_adr.h (product library only)
+ENV_ADR_ABI_VERSION = 1
+ENV_ADR_THREADS = 256
+ENV_ADR_HISTORY_WORDS = 4
+ENV_ADR_KEY_PROBE = 0x32006ca9afc13c78      # env_params.name_key("ADR_PROBE")
+ENV_ADR_KEY_WHICH = 0x25473c155fa82938      # env_params.name_key("ADR_WHICH")
+
+
+class VineEnvAdrName(C.Structure):
+    _fields_ = [
+        ("on", C.c_int32),
+        ("reserved", C.c_int32),
+        ("start_lo", C.c_double),
+        ("start_hi", C.c_double),
+        ("step", C.c_double),
+    ]
+
+
+class VineEnvAdrSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_adr", C.c_int32),
+        ("queue", C.c_int32),
+        ("history_capacity", C.c_int32),
+        ("boundary_fraction", C.c_double),
+        ("widen_at", C.c_double),
+        ("narrow_at", C.c_double),
+        ("name", VineEnvAdrName * VR_NAMES),
+        ("max_widen", (C.c_int32 * 2) * VR_NAMES),
+        ("adr_slot", C.c_int32 * VR_NAMES),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("redraw", VineEnvRedrawSpec),
+    ]
+
+
+ENV_ADR_PROTOTYPES = {
+    "vine_env_adr_spec_size": (C.c_int, []),
+    "vine_env_adr_spec": (C.c_int, [_P(VineConfig), _P(VineEnvRedrawSpec), _P(VineEnvAdrName), C.c_double, C.c_int, C.c_double,
+                                    C.c_double, C.c_int, _P(VineEnvAdrSpec)]),
+    "vine_env_adr_scheduled": (C.c_int, [_H, _P(VineEnvAdrSpec)] + [_VP] * 11),
+}
+
+
+def declare_env_adr(lib):
+    _attach(lib, ENV_ADR_PROTOTYPES)
+    if lib.vine_env_adr_spec_size() != C.sizeof(VineEnvAdrSpec):
+        raise RuntimeError("VineEnvAdrSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_sysid.h (product library only)
 SYSID_ABI_VERSION = 1
 SYSID_FIELDS = 16
@@ -627,6 +678,6 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_sysid):
+                        declare_env_redraw, declare_env_adr, declare_sysid):
         declare_one(lib)
     return lib

@@ -1479,9 +1479,16 @@ class A2CAgent(FastInferenceMixin):
 
 
     # ------------------------------------------------------------------ checkpoint (aux: resume)
+    def _env_adr(self):
+        """The env's ``EnvAdr`` (ENV_PARAMS_ADR), else ``None``."""
+        return getattr(getattr(self.vec_env, "env", self.vec_env), "env_adr", None)
+
     def get_full_state_weights(self):
-        return {"model": self.model.state_dict(), "epoch": self.epoch_num, "optimizer": self.optimizer.state_dict(),
-                "frame": self.frame, "last_mean_rewards": self.last_mean_rewards, "last_lr": float(self.lr)}
+        state = {"model": self.model.state_dict(), "epoch": self.epoch_num, "optimizer": self.optimizer.state_dict(),
+                 "frame": self.frame, "last_mean_rewards": self.last_mean_rewards, "last_lr": float(self.lr)}
+        if self._env_adr() is not None:          # ENV_PARAMS_ADR: how far every boundary has moved
+            state["adr"] = self._env_adr().state_dict()
+        return state
 
     def save(self, fn):
         state = self.get_full_state_weights()
@@ -1500,6 +1507,8 @@ class A2CAgent(FastInferenceMixin):
                 group["lr"] = self.lr
         if "last_lr" in ckpt:
             self.lr.fill_(ckpt["last_lr"])
+        if "adr" in ckpt and self._env_adr() is not None:
+            self._env_adr().load_state_dict(ckpt["adr"])
         if self.fused_mixed:
             self.optimizer.refresh_shadow()
 
@@ -1536,6 +1545,7 @@ class A2CAgent(FastInferenceMixin):
                           f"fps total: {curr_frames / sum_time:.0f} epoch: {epoch_num}/{self.max_epochs}")
                 self.write_stats(total_time, epoch_num, play_time, update_time, stats, curr_frames)
                 self.write_episode_stats()
+                self.write_adr_stats()
                 if self.algo_observer is not None:
                     env = getattr(self.vec_env, "env", self.vec_env)
                     self.algo_observer.process_infos({k: v for k, v in getattr(env, "extras", {}).items()}, None)
@@ -1596,6 +1606,15 @@ class A2CAgent(FastInferenceMixin):
             for k, v in eval_report(totals - prev if prev is not None else totals).items():
                 if v == v:                       # nan: no episode (or none that reached) finished in this iteration
                     self.writer.add_scalar("episodes/" + k, v, self.frame)
+
+    def write_adr_stats(self):
+        """ENV_PARAMS_ADR: ``adr/<NAME>_lo``, ``adr/<NAME>_hi`` and ``adr/probing_reach_rate`` from one non-blocking copy of
+        the observer's integers, here where the episode log's scalars are harvested (nothing inside the rollout waits)."""
+        adr = self._env_adr()
+        if adr is None or not self.writer:
+            return
+        for k, v in adr.scalars().items():
+            self.writer.add_scalar(k, v, self.frame)
 
     def write_stats(self, total_time, epoch_num, play_time, update_time, stats, curr_frames):
         if not self.writer:

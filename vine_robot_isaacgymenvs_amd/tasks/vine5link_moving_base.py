@@ -156,6 +156,7 @@ class Vine5LinkMovingBase(VecTask):
         self._handle = None
         from ..utils import env_params
         self._per_episode = env_params.per_episode(self.cfg["env"])      # (refused here, before anything is created)
+        self._adr = env_params.adr_config(self.cfg["env"], multi_gpu=int(os.getenv("WORLD_SIZE", "1")) > 1)
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -185,7 +186,9 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_trajectory()
         if self._on_rank0("EPISODE_LOG", "logged"):
             self._setup_episode_log()
-        if self._per_episode:                    # every rank: each redraws its own shard, by the global env id
+        if self._adr is not None:                # ENV_PARAMS_ADR: the redraw's place, with ranges that move
+            self._setup_env_adr()
+        elif self._per_episode:                  # every rank: each redraws its own shard, by the global env id
             self._setup_env_redraw()
 
     # ------------------------------------------------------------------ step observers (utils/observers.py)
@@ -347,6 +350,11 @@ class Vine5LinkMovingBase(VecTask):
         spec = self.cfg["env"].get("ENV_PARAMS") or {}
         self._env_redraw = env_redraw.EnvRedraw(self._lib, self._handle, self._vcfg, spec, self.reset_buf, self.env_params,
                                                 self.env_inertia, self.device)
+        self._attach_env_redraw()
+        self.logger.info(f"ENV_PARAMS_PER_EPISODE: the plants of {len(self._env_redraw.spec)} names are redrawn on the device "
+                         f"whenever an env's episode ends")
+
+    def _attach_env_redraw(self):
         self._env_params_host = self._env_inertia_host = None        # no host mirror: the device redraws
         for o in self._observers:
             if hasattr(o, "redraw"):
@@ -354,13 +362,32 @@ class Vine5LinkMovingBase(VecTask):
             if hasattr(o, "env_episode_of"):
                 o.env_episode_of = lambda envs: self._env_redraw.episodes_now()[list(envs)]
         self._add_observer(self._env_redraw)
-        self.logger.info(f"ENV_PARAMS_PER_EPISODE: the plants of {len(self._env_redraw.spec)} names are redrawn on the device "
-                         f"whenever an env's episode ends")
 
     @property
     def env_redraw(self):
-        """The ``EnvRedraw`` of this env (``None`` unless ``ENV_PARAMS_PER_EPISODE``)."""
+        """The ``EnvRedraw`` of this env (``None`` unless ``ENV_PARAMS_PER_EPISODE``; under ``ENV_PARAMS_ADR`` its ``EnvAdr``)."""
         return self._env_redraw
+
+    # ------------------------------------------------------------------ ENV_PARAMS_ADR (include/vine_env_adr.h)
+    def _setup_env_adr(self):
+        """The redraw's place is taken by two launches behind every step that also move the ranges of the names under
+        ``ENV_PARAMS_ADR.NAMES``: they begin at START (the tables bound in ``create_sim`` are START's), the ``[lo, hi]`` of
+        ``ENV_PARAMS`` are their limits.  The launches read the step's reward matrix, so one is bound here (arming
+        introspection) before anything is captured; one bound already is shared."""
+        from ..utils import env_adr
+        if self._reward_matrix is None:
+            self.bind_reward_matrix()
+        spec = self.cfg["env"].get("ENV_PARAMS") or {}
+        self._env_redraw = env_adr.EnvAdr(self._lib, self._handle, self._vcfg, spec, self._adr, self.reset_buf, self.env_params,
+                                          self.env_inertia, self.device, self.logger)
+        self._attach_env_redraw()
+        self.logger.info(f"ENV_PARAMS_ADR: the ranges of {', '.join(self._adr['NAMES'])} start at START and move on the device "
+                         f"by the reach rate of the episodes probing their boundaries")
+
+    @property
+    def env_adr(self):
+        """The ``EnvAdr`` of this env (``None`` unless ``ENV_PARAMS_ADR``)."""
+        return self._env_redraw if self._adr is not None else None
 
     # ------------------------------------------------------------------ MAT_FILE replay (V5:281-297, 947-982)
     def read_mat_file(self, filename):
@@ -416,6 +443,9 @@ class Vine5LinkMovingBase(VecTask):
         self._env_inertia_draws = {}             # LINK_MASS / TIP_LINK_MASS: the per-env factors the link rows were formed from
         spec = self.cfg["env"].get("ENV_PARAMS") or {}
         if len(spec):
+            if getattr(self, "_adr", None) is not None:      # ENV_PARAMS_ADR: episode 0 is drawn from START
+                from ..utils import env_params
+                spec = env_params.adr_start_spec(spec, self._adr)
             self._setup_env_params(spec)
             self._setup_env_inertia(spec)
 
@@ -640,6 +670,8 @@ class Vine5LinkMovingBase(VecTask):
                      self._lib)
         if self._episode_log is not None:        # EPISODE_LOG: their running episode is discarded without a row
             self._episode_log.reset_envs(ids)
+        if self.env_adr is not None:             # ENV_PARAMS_ADR: ... and is not counted at its boundary
+            self.env_adr.reset_envs(ids)
 
     # ------------------------------------------------------------------ metrics side channel (V5:1250-1322)
     def collect_stats(self):
@@ -753,8 +785,8 @@ class Vine5LinkMovingBase(VecTask):
     # ------------------------------------------------------------------ test / tooling hooks
     def bind_reward_matrix(self):
         """Ask the kernel to also write the [N,13] unweighted reward matrix (V5:1272) each step."""
-        if self._episode_log is not None:    # EPISODE_LOG reads the matrix it bound at set-up: that one is shared
-            return self._reward_matrix
+        if self._episode_log is not None or self.env_adr is not None:      # EPISODE_LOG and ENV_PARAMS_ADR read the matrix bound
+            return self._reward_matrix                                      # at set-up: that one is shared
         self._reward_matrix = torch.zeros((self.num_envs, abi.NUM_REWARDS), device=self.device)
         native.check(self._lib.vine_bind_reward_matrix(self._handle, self._reward_matrix.data_ptr()), self._lib)
         self._introspection = True           # the library arms VINE_FLAG_INTROSPECT together with the matrix

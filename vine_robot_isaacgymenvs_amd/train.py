@@ -2,6 +2,7 @@
 with the semantics of the reference's ``isaacgymenvs/train.py:35-183``: compose the config, rank -> device,
 seed (+rank twice), register the env creator, dump ``runs/<name>/config.yaml`` and the config pickle, run."""
 import datetime
+import logging
 import os
 import pickle
 import sys
@@ -19,6 +20,15 @@ def launch(cfg):
         cfg["checkpoint"] = os.path.abspath(cfg["checkpoint"])          # train.py:60-63
         cfg["train"]["params"]["load_path"] = cfg["checkpoint"]
     set_np_formatting()
+    env_cfg = cfg["task"]["env"]
+    if len(env_cfg.get("ENV_PARAMS_ADR") or {}):
+        from .utils import env_params
+        if cfg["test"]:                      # a player measures the policy on the whole of what it may meet
+            logging.getLogger(__name__).info("test=True: task.env.ENV_PARAMS_ADR is forced off, the plants are redrawn from "
+                                             "the full ENV_PARAMS limits")
+            env_cfg["ENV_PARAMS_ADR"] = {}
+        else:
+            env_params.adr_config(env_cfg, multi_gpu=bool(cfg["multi_gpu"]))      # (refused here, before a rank starts)
 
     rank = int(os.getenv("LOCAL_RANK", "0"))
     if cfg["multi_gpu"]:                                                 # train.py:71-75

@@ -164,6 +164,37 @@ def with_episode_params(rows, params, names, inertia=None):
     return out
 
 
+def drawn_at(env, episode, end_step):
+    """ENV_PARAMS_ADR: the index of the step whose launch drew every row's episode, int64 [R]: the end step of the SAME env's
+    row of the episode before it.  -1 for episode 0 (drawn by nobody: START's table) and where that row is not among the
+    rows (the ring dropped it): the range in force when the episode was drawn is then unknown."""
+    env = np.asarray(env, dtype=np.int64)
+    k = np.asarray(episode, dtype=np.int64)
+    end = np.asarray(end_step, dtype=np.int64)
+    out = np.full(len(env), -1, dtype=np.int64)
+    order = np.lexsort((k, env))
+    e, ks = env[order], k[order]
+    has = np.r_[False, (e[1:] == e[:-1]) & (ks[1:] == ks[:-1] + 1)] if len(e) else np.zeros(0, dtype=bool)
+    out[order[has]] = end[order[np.flatnonzero(has) - 1]]
+    return out
+
+
+def with_adr_params(rows, columns):
+    """ENV_PARAMS_ADR: ``rows`` (with ``episode``) with ``param_<NAME>`` per parameter that varies across the rows and the
+    ``probe`` column (the boundary ``2 * slot + side`` the episode was pinned to, -1: none, -2: unknown).  ``columns(envs,
+    episodes, drawn_at)`` -> ``(params, inertia or None, probe)``.  A row whose predecessor was dropped has NaN parameters;
+    ``(rows, unknown)`` with ``unknown`` their number."""
+    out = dict(rows)
+    if not len(np.asarray(rows["env"])):
+        out["probe"] = np.zeros(0, dtype=np.int64)
+        return out, 0
+    at = drawn_at(rows["env"], rows["episode"], rows["end_step"])
+    params, inertia, probe = columns(rows["env"], rows["episode"], at)
+    out = with_episode_params(rows, params, abi.ENV_PARAM_ROW_NAMES, inertia)
+    out["probe"] = probe
+    return out, int(np.count_nonzero(probe == -2))
+
+
 def value_rate(rows, column, of="reached_ever"):
     """The mean of the 0/1 column ``of`` over the episodes of each distinct value of ``column``: (values [V] ascending,
     rate [V], count [V])."""
@@ -175,14 +206,22 @@ def value_rate(rows, column, of="reached_ever"):
 
 
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
-         redraw=None):
+         redraw=None, adr=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
     bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
     dict of ``spec``, ``seed``, ``env_id_offset``, ``base``, ``inertia_base``, ``geometry``) the rows' ``episode`` column and
     what ``load_env_redraw`` needs to rebuild every episode's column without a device; the two tables are then the plants
-    at the moment of writing."""
+    at the moment of writing.  With ENV_PARAMS_ADR also ``adr``: a dict of ``config`` (``env_params.adr_config``'s result),
+    ``history`` [H, 4] (complete), ``history_dropped`` and ``widen0`` [VR_NAMES, 2] (the ``widen`` in force before the run's
+    first step: zeros, or a restored checkpoint's)."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if adr is not None:
+        import json
+        out["adr_config"] = np.array(json.dumps(adr["config"]))
+        out["adr_history"] = np.asarray(adr["history"], dtype=np.int64).reshape(-1, 4)
+        out["adr_history_dropped"] = np.array(int(adr["history_dropped"]), dtype=np.int64)
+        out["adr_widen0"] = np.asarray(adr.get("widen0", np.zeros((abi.VR_NAMES, 2))), dtype=np.int64).reshape(abi.VR_NAMES, 2)
     if redraw is not None:
         import json
         out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
@@ -233,27 +272,82 @@ def load_env_inertia(path):
         return z["env_inertia"], [str(n) for n in z["env_inertia_names"]]
 
 
-def load_env_redraw(path):
-    """Of a file written under ENV_PARAMS_PER_EPISODE: ``(episode [R], columns)`` with ``columns(envs, episodes)`` ->
-    ``(params [VP_COUNT, M], inertia [VI_COUNT, M] or None)``, ``env_params.draw_columns`` rebuilt from the stored spec, seed,
-    ``env_id_offset`` and base rows (host code of the library only, no device); else ``(None, None)``."""
+def _redraw_of(path):
+    """What ``load_env_redraw`` and ``load_env_adr`` read of a file written under ENV_PARAMS_PER_EPISODE, else ``None``."""
     import ctypes as C
     import json
     from . import env_params
     with np.load(path) as z:
         if "redraw_spec" not in z.files:
-            return None, None
-        spec, seed, offset = json.loads(str(z["redraw_spec"][()])), int(z["redraw_seed"]), int(z["redraw_env_id_offset"])
-        base, inertia_base, geometry, episode = z["redraw_base"], z["redraw_inertia_base"], z["redraw_geometry"], z["episode"]
+            return None
+        r = {"spec": json.loads(str(z["redraw_spec"][()])), "seed": int(z["redraw_seed"]), "offset": int(z["redraw_env_id_offset"]),
+             "base": z["redraw_base"], "inertia_base": z["redraw_inertia_base"], "episode": z["episode"], "adr": None}
+        geometry = z["redraw_geometry"]
+        if "adr_config" in z.files:
+            r.update(adr=json.loads(str(z["adr_config"][()])), history=z["adr_history"], dropped=int(z["adr_history_dropped"]),
+                     widen0=z["adr_widen0"] if "adr_widen0" in z.files else None)
 
-    def columns(envs, episodes_):
+    def derive(t):
         lib = native.load()
         vcfg = abi.VineConfig()
         native.check(lib.vine_config_default(C.byref(vcfg)), lib)
         vcfg.link_length, vcfg.link_com, vcfg.gravity = (float(g) for g in geometry)
-        return env_params.draw_columns(spec, base, inertia_base, lambda t: env_params.derive_inertia(lib, vcfg, t), seed,
-                                       np.asarray(envs, dtype=np.int64) + offset, episodes_)
-    return episode, columns
+        return env_params.derive_inertia(lib, vcfg, t)
+    r["derive"] = derive
+    return r
+
+
+def load_env_redraw(path):
+    """Of a file written under ENV_PARAMS_PER_EPISODE: ``(episode [R], columns)`` with ``columns(envs, episodes)`` ->
+    ``(params [VP_COUNT, M], inertia [VI_COUNT, M] or None)``, ``env_params.draw_columns`` rebuilt from the stored spec, seed,
+    ``env_id_offset`` and base rows (host code of the library only, no device); else ``(None, None)``.  A file written under
+    ENV_PARAMS_ADR gives its ``episode`` too, but its ``columns`` raises: a plant there also depends on the step that drew it,
+    and ``load_env_adr`` is its reader."""
+    from . import env_params
+    r = _redraw_of(path)
+    if r is None:
+        return None, None
+
+    def columns(envs, episodes_):
+        if r["adr"] is not None:
+            raise ValueError("%s was written under ENV_PARAMS_ADR: an episode's plant also depends on the range in force when it "
+                             "was drawn; read it with load_env_adr or load_rows_with_params" % path)
+        return env_params.draw_columns(r["spec"], r["base"], r["inertia_base"], r["derive"], r["seed"],
+                                       np.asarray(envs, dtype=np.int64) + r["offset"], episodes_)
+    return r["episode"], columns
+
+
+def load_env_adr(path):
+    """Of a file written under ENV_PARAMS_ADR: ``(config, history [H, 4], history_dropped, widen0 [VR_NAMES, 2], columns)`` with
+    ``columns(envs, episodes, drawn_at)`` -> ``(params [VP_COUNT, M], inertia [VI_COUNT, M] or None, probe [M])``,
+    ``env_params.adr_episode_columns`` rebuilt from what the file stores (float64, NaN and probe -2 where ``drawn_at`` is -1;
+    ``drawn_at``: this module's); else ``(None, None, 0, None, None)``."""
+    from . import env_params
+    r = _redraw_of(path)
+    if r is None or r["adr"] is None:
+        return None, None, 0, None, None
+    widen0 = r["widen0"] if r["widen0"] is not None else np.zeros((abi.VR_NAMES, 2), dtype=np.int64)
+
+    def columns(envs, episodes_, drawn_at_):
+        return env_params.adr_episode_columns(r["spec"], r["adr"], r["seed"], np.asarray(envs, dtype=np.int64) + r["offset"], episodes_,
+                                              drawn_at_, r["history"], base=r["base"], inertia_base=r["inertia_base"],
+                                              derive=r["derive"], widen0=widen0)
+    return r["adr"], r["history"], r["dropped"], widen0, columns
+
+
+def load_rows_with_params(path):
+    """The rows of a file written under ENV_PARAMS_PER_EPISODE with the ``param_<NAME>`` columns of every row's own episode
+    (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device."""
+    episode, columns = load_env_redraw(path)
+    rows = dict(load(path)[0])
+    if episode is None:
+        return rows
+    rows["episode"] = episode
+    adr_columns = load_env_adr(path)[4]
+    if adr_columns is not None:
+        return with_adr_params(rows, adr_columns)[0]
+    params, inertia = columns(rows["env"], episode) if len(episode) else (None, None)
+    return with_episode_params(rows, params, abi.ENV_PARAM_ROW_NAMES, inertia)
 
 
 class EpisodeLog:
@@ -295,6 +389,7 @@ class EpisodeLog:
         self.env_inertia_of, self.env_inertia_names = None, None   # ENV_INERTIA: likewise
         self.redraw = None           # ENV_PARAMS_PER_EPISODE: the task's ``env_redraw.EnvRedraw``; rows then carry ``episode``
         self.part_counters = []      # ... and every harvested part the device's episode_index at its harvest
+        self.unknown_plants = 0      # ENV_PARAMS_ADR: rows of the last rows_with_params() whose plant is unknown (NaN)
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -354,6 +449,8 @@ class EpisodeLog:
         self.parts.append(words.cpu().numpy())       # decoded and sorted when somebody asks for rows
         if self.redraw is not None:                  # the same stream point as the cursor: nothing was enqueued in between
             self.part_counters.append(self.redraw.episodes_now())
+            if hasattr(self.redraw, "harvest_history"):      # ENV_PARAMS_ADR: and the moves of the ranges up to here
+                self.redraw.harvest_history()
         self._rows = None
         return cursor - first
 
@@ -381,6 +478,13 @@ class EpisodeLog:
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
         (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env."""
         rows = self.rows()
+        if getattr(self.redraw, "adr", None) is not None:      # ENV_PARAMS_ADR: the range in force when the episode was drawn
+            self.redraw.harvest_history()
+            out, self.unknown_plants = with_adr_params(rows, self.redraw.episode_columns)
+            if self.unknown_plants:
+                self.logger.info(f"EPISODE_LOG: {self.unknown_plants} rows have no known plant (the row of the episode before "
+                                 f"them was dropped)")
+            return out
         if self.redraw is not None:
             params, inertia = self.redraw.columns(rows["env"], rows["episode"]) if len(rows["env"]) else (None, None)
             return with_episode_params(rows, params, self.env_param_names, inertia)
@@ -405,8 +509,12 @@ class EpisodeLog:
             redraw = {"spec": r.spec, "seed": r.seed, "env_id_offset": r.env_id_offset,
                       "base": env_params.config_row(r.lib, r.vcfg), "inertia_base": env_params.inertia_config_row(r.lib, r.vcfg),
                       "geometry": (r.vcfg.link_length, r.vcfg.link_com, r.vcfg.gravity)}
+        adr = None
+        if getattr(self.redraw, "adr", None) is not None:
+            adr = {"config": self.redraw.adr, "history": self.redraw.harvest_history(), "history_dropped": self.redraw.history_dropped,
+                   "widen0": self.redraw.widen0}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names, redraw)
+             self.env_inertia_names, redraw, adr)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -20,7 +20,9 @@ The observers: ``video.VideoCapture`` (CAPTURE_VIDEO), ``trajectory.TrajectoryRe
 ``WindowRing`` --, ``episodes.EpisodeLog`` (EPISODE_LOG), the SYSID node of utils/sysid.py, and, last in launch order,
 ``env_redraw.EnvRedraw`` (ENV_PARAMS_PER_EPISODE): the one observer that WRITES what the step reads -- the bound per-env
 tables and the delay rings of the envs the step has just flagged -- so it runs behind the others, which have then read what
-this step's plant produced.  Its ``live_tensors`` are the tables and its episode counters.
+this step's plant produced.  Its ``live_tensors`` are the tables and its episode counters.  Under ENV_PARAMS_ADR
+``env_adr.EnvAdr`` stands in its place: two launches that also move the ranges the plants are drawn from, whose integers
+(steps per boundary, counts, per-env flags, the history cursor) are live tensors too.
 
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer

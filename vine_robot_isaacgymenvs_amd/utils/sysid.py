@@ -199,6 +199,7 @@ FORCED = (
     ("env", "EPISODE_LOG", False),
     ("env", "MAT_FILE", ""),
     ("env", "ENV_PARAMS_PER_EPISODE", False),      # a candidate keeps its plant: the table IS the search's population
+    ("env", "ENV_PARAMS_ADR", {}),                 # ... and no range moves
 )
 
 
