@@ -15,7 +15,13 @@ With --adr: the same three cases for the two launches of ENV_PARAMS_ADR (include
 same run.  The ADR launches read the reward matrix, and a bound matrix makes the step itself write 52 more bytes per env, so
 their baseline is the step alone WITH a matrix bound: node cost = (step + launches) - (that step).
 
-usage: python scripts/ubench/env_params_bench.py [--redraw | --adr] [num_envs ...]        (default: 16384 1048576)"""
+With --sensor: the cost of the ENV_SENSOR launch (include/vine_env_sensor.h) behind every step of the default handle (no
+table: up to 16384 envs the four-lane kernel), beside the bare step in the same run: idle (delay, hold and noise 0 in every env,
+never a first frame: every lane still pushes its frame), with the step's own resets under delays 0..8 and holds, and with
+noise on every env (28 Philox calls per env and step).  Reported with the share of the 8 TB/s HBM peak the launch's bytes
+over its duration amount to (bytes: the passes over the observation block that case makes).
+
+usage: python scripts/ubench/env_params_bench.py [--redraw | --adr | --sensor] [num_envs ...]        (default: 16384 1048576)"""
 import os
 import statistics
 import sys
@@ -171,7 +177,82 @@ def main_redraw(sizes, adr=False):
         torch.cuda.empty_cache()
 
 
+SENSOR_CASES = {  # name -> (ENV_SENSOR keys, the progress the launch reads: "busy" = never 0, "own" = the step's, passes)
+    "idle": ({"DELAY": 0, "PER_EPISODE": True}, "busy", 2),                                        # read the buffer, write a slot
+    "the step's own resets": ({"DELAY": [0, 8], "HOLD": [0.0, 0.3], "PER_EPISODE": True}, "own", 4),
+    "noise on every env": ({"DELAY": [0, 8], "NOISE_STD": 0.01, "PER_EPISODE": True}, "own", 4)}
+HBM_PEAK = 8.0e12
+
+
+def make_sensor(n, case):
+    from vine_robot_isaacgymenvs_amd.utils import env_sensor
+    keys, which, _ = SENSOR_CASES[case]
+    cfg = base_cfg(n, 0, True)
+    env = type("H", (HipEnv,), {"kernel": None})(cfg)
+    env.set_introspection(False)
+    spec = env_sensor.sensor_config({"ENV_SENSOR": keys}, env.num_obs)
+    sspec = env_sensor.sensor_spec(env.lib, env.cfg, spec)
+    table = torch.as_tensor(env_sensor.draw_sensor(spec, int(env.cfg.seed), range(n), 0), dtype=torch.float32, device=env.dev).contiguous()
+    ring = torch.zeros((abi.SENSOR_SLOTS, n, env.num_obs), device=env.dev)
+    fresh = torch.ones(n, dtype=torch.uint8, device=env.dev)
+    episode = torch.zeros(n, dtype=torch.int32, device=env.dev)
+    progress = env.progress_t if which == "own" else torch.ones(n, dtype=torch.long, device=env.dev)
+    k = 100 if n <= 65536 else 20
+    g = torch.Generator(device=env.dev).manual_seed(0)
+    acts = [torch.rand((n, 2), device=env.dev, generator=g) * 2 - 1 for _ in range(8)]
+
+    def pair(a):
+        env.step_t(a, sync=False)
+        native.check(env.lib.vine_env_sensor_scheduled(env.h, sspec, env.obs_t.data_ptr(), env.reset_t.data_ptr(), progress.data_ptr(),
+                                                       table.data_ptr(), ring.data_ptr(), fresh.data_ptr(), episode.data_ptr(),
+                                                       torch.cuda.current_stream(env.dev).cuda_stream), env.lib)
+    for i in range(16):
+        pair(acts[i % 8])
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        for i in range(k):
+            pair(acts[i % 8])
+    graph.replay()
+    torch.cuda.synchronize()
+    env.keep = (sspec, table, ring, fresh, episode, progress)
+    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + " + sensor"
+
+
+def main_sensor(sizes):
+    for n in sizes:
+        envs = {"step alone": make(n, None, None)}
+        envs.update({"step + sensor, " + case: make_sensor(n, case) for case in SENSOR_CASES})
+        times = {name: [] for name in envs}
+        for _ in range(ROUNDS):
+            for name, (env, graph, k, _) in envs.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                times[name].append(e0.elapsed_time(e1) / k * 1e3)
+        print("num_envs %d (%s), %d rounds alternated, one graph replay of %d steps each (us per step: min / median / max)"
+              % (n, envs["step alone"][3], ROUNDS, envs["step alone"][2]))
+        for name in envs:
+            t = times[name]
+            print("  %-40s %8.1f %8.1f %8.1f" % (name, min(t), statistics.median(t), max(t)), flush=True)
+        base = statistics.median(times["step alone"])
+        block = n * envs["step alone"][0].num_obs * 4
+        for case, (_, _, passes) in SENSOR_CASES.items():
+            cost = statistics.median(times["step + sensor, " + case]) - base
+            share = passes * block / (cost * 1e-6) / HBM_PEAK if cost > 0 else float("nan")
+            print("  sensor, %s: %+.2f us per launch; %d passes over the %.2f MB observation block = %.1f %% of the HBM peak"
+                  % (case, cost, passes, block / 1e6, 100 * share))
+        for env, _, _, _ in envs.values():
+            env.close()
+        del envs
+        torch.cuda.empty_cache()
+
+
 def main():
+    if "--sensor" in sys.argv[1:]:
+        return main_sensor([int(a) for a in sys.argv[1:] if a != "--sensor"] or [16384, 1 << 20])
     args = [a for a in sys.argv[1:] if a not in ("--redraw", "--adr")]
     if "--redraw" in sys.argv[1:] or "--adr" in sys.argv[1:]:
         return main_redraw([int(a) for a in args] or [16384, 1 << 20], adr="--adr" in sys.argv[1:])

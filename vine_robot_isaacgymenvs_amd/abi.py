@@ -584,6 +584,49 @@ def declare_env_redraw(lib):
     return lib
 
 
+# ---- include/vine_env_sensor.h (product library only)
+ENV_SENSOR_ABI_VERSION = 1
+ENV_SENSOR_THREADS = 256
+SENSOR_MAX_DELAY = 8
+SENSOR_SLOTS = SENSOR_MAX_DELAY + 1
+SENSOR_RNG_NOISE, SENSOR_RNG_HOLD = 5, 6
+# VineEnvSensorSlot = the rows of the sensor table; the draw's name keys are those of "SENSOR_" + name
+ENV_SENSOR_NAMES = ["DELAY", "HOLD", "NOISE_STD"]
+VSN_DELAY, VSN_HOLD, VSN_NOISE_STD = range(3)
+VSN_NAMES = 3
+
+
+class VineEnvSensorSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_values", C.c_int32),
+        ("seed", C.c_uint64),
+        ("values", C.c_void_p),
+        ("name", VineEnvRedrawName * VSN_NAMES),
+        ("num_obs", C.c_int32),
+        ("column_mask", C.c_uint32),
+        ("clip_observations", C.c_float),
+        ("per_episode", C.c_int32),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+ENV_SENSOR_PROTOTYPES = {
+    "vine_env_sensor_spec_size": (C.c_int, []),
+    "vine_env_sensor_spec": (C.c_int, [_P(VineConfig), _P(VineEnvRedrawName), _VP, _VP, C.c_int, C.c_uint32, C.c_int,
+                                       _P(VineEnvSensorSpec)]),
+    "vine_env_sensor_scheduled": (C.c_int, [_H, _P(VineEnvSensorSpec)] + [_VP] * 8),
+}
+
+
+def declare_env_sensor(lib):
+    _attach(lib, ENV_SENSOR_PROTOTYPES)
+    if lib.vine_env_sensor_spec_size() != C.sizeof(VineEnvSensorSpec):
+        raise RuntimeError("VineEnvSensorSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_env_adr.h (product library only)
 ENV_ADR_ABI_VERSION = 1
 ENV_ADR_THREADS = 256
@@ -678,6 +721,6 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_env_adr, declare_sysid):
+                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_sysid):
         declare_one(lib)
     return lib

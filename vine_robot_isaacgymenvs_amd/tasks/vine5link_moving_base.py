@@ -149,6 +149,7 @@ class Vine5LinkMovingBase(VecTask):
         self._trajectory = None
         self._episode_log = None
         self._env_redraw = None
+        self._env_sensor = None
         self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log,
                                    # the per-episode redraw of the plants (last: it replaces what the others read)
 
@@ -157,6 +158,8 @@ class Vine5LinkMovingBase(VecTask):
         from ..utils import env_params
         self._per_episode = env_params.per_episode(self.cfg["env"])      # (refused here, before anything is created)
         self._adr = env_params.adr_config(self.cfg["env"], multi_gpu=int(os.getenv("WORLD_SIZE", "1")) > 1)
+        from ..utils import env_sensor
+        self._sensor_cfg = env_sensor.sensor_config(self.cfg["env"], self.cfg["env"]["numObservations"])
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -186,6 +189,8 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_trajectory()
         if self._on_rank0("EPISODE_LOG", "logged"):
             self._setup_episode_log()
+        if self._sensor_cfg is not None:         # every rank: each senses its own shard, by the global env id; in front of
+            self._setup_env_sensor()             # the redraw, which stays last
         if self._adr is not None:                # ENV_PARAMS_ADR: the redraw's place, with ranges that move
             self._setup_env_adr()
         elif self._per_episode:                  # every rank: each redraws its own shard, by the global env id
@@ -258,11 +263,15 @@ class Vine5LinkMovingBase(VecTask):
         for o in self._observers:
             (o.before if before else o.advance)(n_steps)
 
-    def _observe(self, actions):
+    def _observe(self, actions, obs_out=None):
         """Behind a step launch: every observer's launch on the same stream, then its host-side count.  ``actions``:
-        device address of the action buffer the step consumed."""
+        device address of the action buffer the step consumed; ``obs_out``: the observation tensor it wrote, handed to
+        the observers that ask for it (``wants_obs``)."""
         for o in self._observers:
-            o.enqueue(self._stream(), actions)
+            if getattr(o, "wants_obs", False):
+                o.enqueue(self._stream(), actions, obs=obs_out.data_ptr())
+            else:
+                o.enqueue(self._stream(), actions)
             o.advance(1)
 
     # ------------------------------------------------------------------ CAPTURE_VIDEO (V5:205-221, 1169-1207)
@@ -339,6 +348,26 @@ class Vine5LinkMovingBase(VecTask):
     def episode_log(self):
         """The ``EpisodeLog`` of this env (``None`` unless ``EPISODE_LOG``)."""
         return self._episode_log
+
+    # ------------------------------------------------------------------ ENV_SENSOR (include/vine_env_sensor.h)
+    def _setup_env_sensor(self):
+        """A launch behind every step rewrites the observation that step wrote: per-env delay, dropped frames and noise
+        (utils/env_sensor.py).  The step kernels are not touched: the four-lane kernel and the fused rollout step stay."""
+        from ..utils import env_sensor
+        self._env_sensor = self._add_observer(env_sensor.EnvSensor(
+            self._lib, self._handle, self._vcfg, self._sensor_cfg, self.reset_buf, self.progress_buf, self.num_envs, self.num_obs,
+            self.device))
+        if self._episode_log is not None:
+            self._episode_log.sensor = self._env_sensor
+        varying = env_sensor.varying_names(self._sensor_cfg)
+        self.logger.info(f"ENV_SENSOR: delay, dropped frames and noise on {len(self._sensor_cfg['COLUMNS'])} of {self.num_obs} "
+                         f"observation columns; {', '.join(varying) or 'nothing'} varies"
+                         f"{', redrawn at every reset' if self._sensor_cfg['PER_EPISODE'] else ''}")
+
+    @property
+    def env_sensor(self):
+        """The ``EnvSensor`` of this env (``None`` unless ``ENV_SENSOR``)."""
+        return self._env_sensor
 
     # ------------------------------------------------------------------ ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h)
     def _setup_env_redraw(self):
@@ -598,6 +627,7 @@ class Vine5LinkMovingBase(VecTask):
                 o.drain()
                 o.close()
             self._observers, self._video, self._trajectory, self._episode_log, self._env_redraw = [], None, None, None, None
+            self._env_sensor = None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -619,7 +649,7 @@ class Vine5LinkMovingBase(VecTask):
             o.before(1)
         native.check(fn(self._handle, first_arg, obs_out.data_ptr(), self.rew_buf.data_ptr(), self.reset_buf.data_ptr(),
                         self.progress_buf.data_ptr(), self.timeout_buf.data_ptr(), self._stream()), self._lib)
-        self._observe(actions_ptr)
+        self._observe(actions_ptr, obs_out)
         self.num_steps += 1
 
     def _rebind(self, obs_out):
@@ -672,6 +702,8 @@ class Vine5LinkMovingBase(VecTask):
             self._episode_log.reset_envs(ids)
         if self.env_adr is not None:             # ENV_PARAMS_ADR: ... and is not counted at its boundary
             self.env_adr.reset_envs(ids)
+        if self._env_sensor is not None:         # ENV_SENSOR: their next frame is an episode's first
+            self._env_sensor.reset_envs(ids)
 
     # ------------------------------------------------------------------ metrics side channel (V5:1250-1322)
     def collect_stats(self):

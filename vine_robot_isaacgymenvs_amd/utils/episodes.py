@@ -205,8 +205,20 @@ def value_rate(rows, column, of="reached_ever"):
     return values, hit / np.maximum(count, 1), count
 
 
+def with_sensor_params(rows, sensor_params):
+    """ENV_SENSOR: ``rows`` with ``param_SENSOR_DELAY`` / ``_HOLD`` / ``_NOISE_STD`` for the names that vary.
+    ``sensor_params(envs, episodes)`` -> ``{"SENSOR_<NAME>": values [R]}`` (``env_sensor.episode_params``: held values are
+    joined by env, per-episode ones by the row's ``episode``, the join ``param_<NAME>`` uses under ENV_PARAMS_PER_EPISODE)."""
+    out = dict(rows)
+    if len(np.asarray(rows["env"])):
+        episodes_ = rows["episode"] if "episode" in rows else np.zeros(len(rows["env"]), dtype=np.int64)
+        for name, values in sensor_params(rows["env"], episodes_).items():
+            out["param_" + name] = values
+    return out
+
+
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
-         redraw=None, adr=None):
+         redraw=None, adr=None, sensor=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
     bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
@@ -214,8 +226,17 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
     what ``load_env_redraw`` needs to rebuild every episode's column without a device; the two tables are then the plants
     at the moment of writing.  With ENV_PARAMS_ADR also ``adr``: a dict of ``config`` (``env_params.adr_config``'s result),
     ``history`` [H, 4] (complete), ``history_dropped`` and ``widen0`` [VR_NAMES, 2] (the ``widen`` in force before the run's
-    first step: zeros, or a restored checkpoint's)."""
+    first step: zeros, or a restored checkpoint's).  With ENV_SENSOR (``sensor``: a dict of ``spec``, ``seed`` and
+    ``env_id_offset``) what ``load_env_sensor`` needs to rebuild the ``param_SENSOR_*`` columns without a device, and, where
+    the rows carry one, their ``episode`` column."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if sensor is not None:
+        import json
+        out["sensor_spec"] = np.array(json.dumps(sensor["spec"]))
+        out["sensor_seed"] = np.array(int(sensor["seed"]), dtype=np.uint64)
+        out["sensor_env_id_offset"] = np.array(int(sensor["env_id_offset"]), dtype=np.int64)
+        if "episode" in rows:
+            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
     if adr is not None:
         import json
         out["adr_config"] = np.array(json.dumps(adr["config"]))
@@ -335,9 +356,37 @@ def load_env_adr(path):
     return r["adr"], r["history"], r["dropped"], widen0, columns
 
 
+def load_env_sensor(path):
+    """Of a file written under ENV_SENSOR: ``(spec, episode [R] or None, sensor_params)`` with ``sensor_params(envs,
+    episodes)`` -> ``env_sensor.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
+    ``(None, None, None)``."""
+    import json
+    from . import env_sensor
+    with np.load(path) as z:
+        if "sensor_spec" not in z.files:
+            return None, None, None
+        spec, seed, offset = json.loads(str(z["sensor_spec"][()])), int(z["sensor_seed"]), int(z["sensor_env_id_offset"])
+        episode = z["episode"] if "episode" in z.files else None
+
+    def sensor_params(envs, episodes_):
+        return env_sensor.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
+    return spec, episode, sensor_params
+
+
 def load_rows_with_params(path):
     """The rows of a file written under ENV_PARAMS_PER_EPISODE with the ``param_<NAME>`` columns of every row's own episode
-    (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device."""
+    (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device.  Under
+    ENV_SENSOR also the ``param_SENSOR_*`` columns."""
+    _, sensor_episode, sensor_params = load_env_sensor(path)
+    rows = _load_rows_with_plant_params(path)
+    if sensor_params is None:
+        return rows
+    if sensor_episode is not None:
+        rows["episode"] = sensor_episode
+    return with_sensor_params(rows, sensor_params)
+
+
+def _load_rows_with_plant_params(path):
     episode, columns = load_env_redraw(path)
     rows = dict(load(path)[0])
     if episode is None:
@@ -390,6 +439,7 @@ class EpisodeLog:
         self.redraw = None           # ENV_PARAMS_PER_EPISODE: the task's ``env_redraw.EnvRedraw``; rows then carry ``episode``
         self.part_counters = []      # ... and every harvested part the device's episode_index at its harvest
         self.unknown_plants = 0      # ENV_PARAMS_ADR: rows of the last rows_with_params() whose plant is unknown (NaN)
+        self.sensor = None           # ENV_SENSOR: the task's ``env_sensor.EnvSensor``; under its PER_EPISODE rows carry ``episode``
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -406,6 +456,15 @@ class EpisodeLog:
             self.timeouts.data_ptr(), self.episode.data_ptr(), self.totals.data_ptr(),
             self.table.data_ptr() if self.table is not None else None,
             self.cursor.data_ptr() if self.cursor is not None else None, stream), self.lib)
+
+    def _counters(self):
+        """Who counts the episodes of every env on the device: the redraw, else a sensor redrawn per episode (with both on
+        the two count alike), else nobody."""
+        if self.redraw is not None:
+            return self.redraw
+        if self.sensor is not None and self.sensor.spec["PER_EPISODE"]:
+            return self.sensor
+        return None
 
     def reset_envs(self, env_ids):
         """The envs were reset from outside the step: their running episode is discarded without a row."""
@@ -447,8 +506,8 @@ class EpisodeLog:
         a, b = first % self.capacity, (cursor - 1) % self.capacity + 1
         words = self.table[a:b] if a < b else torch.cat([self.table[a:], self.table[:b]])
         self.parts.append(words.cpu().numpy())       # decoded and sorted when somebody asks for rows
-        if self.redraw is not None:                  # the same stream point as the cursor: nothing was enqueued in between
-            self.part_counters.append(self.redraw.episodes_now())
+        if self._counters() is not None:             # the same stream point as the cursor: nothing was enqueued in between
+            self.part_counters.append(self._counters().episodes_now())
             if hasattr(self.redraw, "harvest_history"):      # ENV_PARAMS_ADR: and the moves of the ranges up to here
                 self.redraw.harvest_history()
         self._rows = None
@@ -456,7 +515,7 @@ class EpisodeLog:
 
     def rows(self):
         """Every harvested row so far, sorted by (end step, env)."""
-        if self._rows is None and self.redraw is not None:
+        if self._rows is None and self._counters() is not None:
             parts = []
             for words, counters in zip(self.parts, self.part_counters):      # ordinals count back from each harvest's counters
                 part = decode_rows(words)
@@ -476,7 +535,12 @@ class EpisodeLog:
 
     def rows_with_params(self):
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
-        (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env."""
+        (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env.  Under
+        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``)."""
+        out = self._rows_with_plant_params()
+        return with_sensor_params(out, self.sensor.episode_params) if self.sensor is not None else out
+
+    def _rows_with_plant_params(self):
         rows = self.rows()
         if getattr(self.redraw, "adr", None) is not None:      # ENV_PARAMS_ADR: the range in force when the episode was drawn
             self.redraw.harvest_history()
@@ -513,8 +577,11 @@ class EpisodeLog:
         if getattr(self.redraw, "adr", None) is not None:
             adr = {"config": self.redraw.adr, "history": self.redraw.harvest_history(), "history_dropped": self.redraw.history_dropped,
                    "widen0": self.redraw.widen0}
+        sensor = None
+        if self.sensor is not None:
+            sensor = {"spec": self.sensor.spec, "seed": self.sensor.seed, "env_id_offset": self.sensor.env_id_offset}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names, redraw, adr)
+             self.env_inertia_names, redraw, adr, sensor)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

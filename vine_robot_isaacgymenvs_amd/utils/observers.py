@@ -6,7 +6,10 @@ enqueued.  The task class (tasks/vine5link_moving_base.py) keeps its observers i
 
   before(n)                 ``n`` steps are about to be enqueued (or a graph holding them replayed)
   enqueue(stream, actions)  the observer's launch behind the step just enqueued on ``stream``; ``actions``: device address
-                            of the action buffer that step consumed
+                            of the action buffer that step consumed.  An observer whose class attribute ``wants_obs`` is
+                            true is called as ``enqueue(stream, actions, obs=address)`` with the device address of the
+                            observation buffer that step wrote; every other observer is called exactly as before, with the
+                            two positional arguments, and needs no ``obs`` parameter
   advance(n)                ``n`` steps, each with its launch behind it, have been enqueued (or replayed)
   set_steps(steps)          the device's step count was set from outside
   live_tensors()            what a caller that rolls steps back (the warm-up pass in front of a graph capture) must save
@@ -22,7 +25,9 @@ The observers: ``video.VideoCapture`` (CAPTURE_VIDEO), ``trajectory.TrajectoryRe
 tables and the delay rings of the envs the step has just flagged -- so it runs behind the others, which have then read what
 this step's plant produced.  Its ``live_tensors`` are the tables and its episode counters.  Under ENV_PARAMS_ADR
 ``env_adr.EnvAdr`` stands in its place: two launches that also move the ranges the plants are drawn from, whose integers
-(steps per boundary, counts, per-env flags, the history cursor) are live tensors too.
+(steps per boundary, counts, per-env flags, the history cursor) are live tensors too.  ``env_sensor.EnvSensor`` (ENV_SENSOR)
+rewrites the observation the step has just written (``wants_obs``); it reads the step's reset flags and nothing the redraw
+writes, and stands directly in front of the redraw, which stays last.
 
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer

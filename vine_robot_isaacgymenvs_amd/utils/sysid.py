@@ -200,6 +200,7 @@ FORCED = (
     ("env", "MAT_FILE", ""),
     ("env", "ENV_PARAMS_PER_EPISODE", False),      # a candidate keeps its plant: the table IS the search's population
     ("env", "ENV_PARAMS_ADR", {}),                 # ... and no range moves
+    ("env", "ENV_SENSOR", {}),                     # ... and the fit reads the state as it is: no sensor model
 )
 
 
