@@ -627,6 +627,49 @@ def declare_env_sensor(lib):
     return lib
 
 
+# ---- include/vine_env_push.h (product library only)
+ENV_PUSH_ABI_VERSION = 1
+ENV_PUSH_THREADS = 256
+PUSH_MAX_POINTS = 6
+PUSH_COMPOSITES = 20               # = VI_COUNT - VI_MTOT
+PUSH_RNG = 7
+# VineEnvPushSlot = the rows of the push table; the draw's name keys are those of "PUSH_" + name
+ENV_PUSH_NAMES = ["RATE", "IMPULSE"]
+VPU_RATE, VPU_IMPULSE = range(2)
+VPU_NAMES = 2
+
+
+class VineEnvPushSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_values", C.c_int32),
+        ("seed", C.c_uint64),
+        ("values", C.c_void_p),
+        ("name", VineEnvRedrawName * VPU_NAMES),
+        ("num_points", C.c_int32),
+        ("per_episode", C.c_int32),
+        ("points", C.c_int32 * PUSH_MAX_POINTS),
+        ("composites", C.c_float * PUSH_COMPOSITES),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+ENV_PUSH_PROTOTYPES = {
+    "vine_env_push_spec_size": (C.c_int, []),
+    "vine_env_push_spec": (C.c_int, [_P(VineConfig), _P(VineEnvRedrawName), _VP, _VP, C.c_int, _P(C.c_int32), C.c_int, C.c_int,
+                                     _P(VineEnvPushSpec)]),
+    "vine_env_push_scheduled": (C.c_int, [_H, _P(VineEnvPushSpec)] + [_VP] * 5),
+}
+
+
+def declare_env_push(lib):
+    _attach(lib, ENV_PUSH_PROTOTYPES)
+    if lib.vine_env_push_spec_size() != C.sizeof(VineEnvPushSpec):
+        raise RuntimeError("VineEnvPushSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_env_adr.h (product library only)
 ENV_ADR_ABI_VERSION = 1
 ENV_ADR_THREADS = 256
@@ -721,6 +764,6 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_sysid):
+                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid):
         declare_one(lib)
     return lib

@@ -122,8 +122,10 @@ class PpoPlayerContinuous(FastInferenceMixin):
         print(format_report(self.report))
         if getattr(env, "episode_log", None) is not None and env.episode_log.table is not None:
             print(self._binned_report(env))
-            # ENV_PARAMS: the same rate against every varying parameter; ENV_SENSOR: and against the sensor's values
-            if getattr(env, "env_params", None) is not None or getattr(env, "env_sensor", None) is not None:
+            # ENV_PARAMS: the same rate against every varying parameter; ENV_SENSOR: and against the sensor's values; ENV_PUSH:
+            # and against the push's (by impulse: how large a kick the checkpoint survives)
+            if (getattr(env, "env_params", None) is not None or getattr(env, "env_sensor", None) is not None
+                    or getattr(env, "env_push", None) is not None):
                 print(self._param_report(env))
         return mean_r, mean_l
 
@@ -156,8 +158,9 @@ class PpoPlayerContinuous(FastInferenceMixin):
         the envs: by exact value where the envs hold at most ``exact`` distinct ones (a ``values`` entry of ``ENV_PARAMS``),
         else by bin.  Also kept in ``self.report["by_param"]``: name -> (values or bin edges, rate, episode count)."""
         from ..utils import episodes
-        # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode; ENV_SENSOR: the log joins the sensor's values to its rows
-        if getattr(env, "env_redraw", None) is not None or getattr(env, "env_sensor", None) is not None:
+        # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode; ENV_SENSOR / ENV_PUSH: the log joins their values to its rows
+        if (getattr(env, "env_redraw", None) is not None or getattr(env, "env_sensor", None) is not None
+                or getattr(env, "env_push", None) is not None):
             rows = env.episode_log.rows_with_params()
             keep = rows["end_step"] >= self._episodes_start[1]
             rows = {k: v[keep] for k, v in rows.items()}

@@ -24,6 +24,10 @@ SOURCES = (SRC, SRC_PPO, SRC_RENDER, SRC_RECORD, SRC_EPISODES, SRC_SYSID, SRC_RE
 # tests/test_env_params_adr_cpu.py pins SOURCES to the eight units above, in this order; the ninth, the sensor's, follows them
 # in UNITS, which is what build() compiles and links
 UNITS = SOURCES + (SRC_SENSOR,)
+# tests/test_env_sensor_cpu.py pins UNITS to those nine in turn; the tenth, the push's, follows them in BUILD_UNITS, which is
+# what build() compiles and links
+SRC_PUSH = os.path.join(_HERE, "csrc", "vine_env_push.hip")
+BUILD_UNITS = UNITS + (SRC_PUSH,)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -37,16 +41,20 @@ _HEADERS = ([os.path.join(_INC, h) for h in ("vine.h", "vine_ppo.h", "vine_rende
 _COMPOSITES = os.path.join(_HERE, "csrc", "vine_inertia_composites.h")
 _REDRAW_HEADERS = [_COMPOSITES, os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
 _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
-                   SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")]}
+                   SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
+                   SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")]}
 # vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply
 # and an add (under -ffp-contract=fast hipcc fuses it on gfx950, a pragma in the source notwithstanding)
 # vine_env_adr.hip forms the same columns and the range in force: it switches contraction off itself, by a pragma in front of
 # everything it includes, which this spelling of the flag makes the compiler honour (plain "fast" ignores the pragma)
 # vine_env_sensor.hip adds noise to an observation, obs + z * c, that numpy must reproduce bit for bit: the pragma and the flag
 # of vine_env_adr.hip
+# vine_env_push.hip draws its two per-env values with the same statement, and its solve is the float32 statement numpy makes:
+# the same pragma and flag
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"]}
-DEPS = list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
+                 SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"]}
+DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
+        + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")])
 
 _lib = None
 
@@ -85,7 +93,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The nine translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The ten translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -98,7 +106,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in UNITS:
+    for src in BUILD_UNITS:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)

@@ -150,6 +150,7 @@ class Vine5LinkMovingBase(VecTask):
         self._episode_log = None
         self._env_redraw = None
         self._env_sensor = None
+        self._env_push = None
         self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log,
                                    # the per-episode redraw of the plants (last: it replaces what the others read)
 
@@ -160,6 +161,8 @@ class Vine5LinkMovingBase(VecTask):
         self._adr = env_params.adr_config(self.cfg["env"], multi_gpu=int(os.getenv("WORLD_SIZE", "1")) > 1)
         from ..utils import env_sensor
         self._sensor_cfg = env_sensor.sensor_config(self.cfg["env"], self.cfg["env"]["numObservations"])
+        from ..utils import env_push
+        self._push_cfg = env_push.push_config(self.cfg["env"])
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -191,6 +194,8 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_episode_log()
         if self._sensor_cfg is not None:         # every rank: each senses its own shard, by the global env id; in front of
             self._setup_env_sensor()             # the redraw, which stays last
+        if self._push_cfg is not None:           # every rank, by the global env id; behind the sensor (which has then sensed
+            self._setup_env_push()               # what the step wrote), in front of the redraw
         if self._adr is not None:                # ENV_PARAMS_ADR: the redraw's place, with ranges that move
             self._setup_env_adr()
         elif self._per_episode:                  # every rank: each redraws its own shard, by the global env id
@@ -368,6 +373,25 @@ class Vine5LinkMovingBase(VecTask):
     def env_sensor(self):
         """The ``EnvSensor`` of this env (``None`` unless ``ENV_SENSOR``)."""
         return self._env_sensor
+
+    # ------------------------------------------------------------------ ENV_PUSH (include/vine_env_push.h)
+    def _setup_env_push(self):
+        """A launch behind every step adds, for the envs its draw selects, what a random impulse at a point of the chain does
+        to the six generalised velocities (utils/env_push.py).  The step kernels are not touched: the four-lane kernel and
+        the fused rollout step stay."""
+        from ..utils import env_push
+        self._env_push = self._add_observer(env_push.EnvPush(
+            self._lib, self._handle, self._vcfg, self._push_cfg, self.reset_buf, self.num_envs, self.device))
+        if self._episode_log is not None:
+            self._episode_log.push = self._env_push
+        varying = env_push.varying_names(self._push_cfg)
+        self.logger.info(f"ENV_PUSH: impulses at point(s) {self._push_cfg['POINTS']}; {', '.join(varying) or 'nothing'} varies"
+                         f"{', redrawn at every reset' if self._push_cfg['PER_EPISODE'] else ''}")
+
+    @property
+    def env_push(self):
+        """The ``EnvPush`` of this env (``None`` unless ``ENV_PUSH``)."""
+        return self._env_push
 
     # ------------------------------------------------------------------ ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h)
     def _setup_env_redraw(self):
@@ -627,7 +651,7 @@ class Vine5LinkMovingBase(VecTask):
                 o.drain()
                 o.close()
             self._observers, self._video, self._trajectory, self._episode_log, self._env_redraw = [], None, None, None, None
-            self._env_sensor = None
+            self._env_sensor = self._env_push = None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)

@@ -217,8 +217,14 @@ def with_sensor_params(rows, sensor_params):
     return out
 
 
+def with_push_params(rows, push_params):
+    """ENV_PUSH: ``rows`` with ``param_PUSH_RATE`` / ``param_PUSH_IMPULSE`` for the names that vary, joined as
+    ``with_sensor_params`` joins the sensor's: held values by env, per-episode ones by the row's ``episode``."""
+    return with_sensor_params(rows, push_params)
+
+
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
-         redraw=None, adr=None, sensor=None):
+         redraw=None, adr=None, sensor=None, push=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
     bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
@@ -228,8 +234,16 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
     ``history`` [H, 4] (complete), ``history_dropped`` and ``widen0`` [VR_NAMES, 2] (the ``widen`` in force before the run's
     first step: zeros, or a restored checkpoint's).  With ENV_SENSOR (``sensor``: a dict of ``spec``, ``seed`` and
     ``env_id_offset``) what ``load_env_sensor`` needs to rebuild the ``param_SENSOR_*`` columns without a device, and, where
-    the rows carry one, their ``episode`` column."""
+    the rows carry one, their ``episode`` column.  With ENV_PUSH (``push``: a dict of the same three keys) the same for the
+    ``param_PUSH_*`` columns (``load_env_push``)."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if push is not None:
+        import json
+        out["push_spec"] = np.array(json.dumps(push["spec"]))
+        out["push_seed"] = np.array(int(push["seed"]), dtype=np.uint64)
+        out["push_env_id_offset"] = np.array(int(push["env_id_offset"]), dtype=np.int64)
+        if "episode" in rows:
+            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
     if sensor is not None:
         import json
         out["sensor_spec"] = np.array(json.dumps(sensor["spec"]))
@@ -378,12 +392,32 @@ def load_rows_with_params(path):
     (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device.  Under
     ENV_SENSOR also the ``param_SENSOR_*`` columns."""
     _, sensor_episode, sensor_params = load_env_sensor(path)
+    _, push_episode, push_params = load_env_push(path)
     rows = _load_rows_with_plant_params(path)
-    if sensor_params is None:
-        return rows
-    if sensor_episode is not None:
-        rows["episode"] = sensor_episode
-    return with_sensor_params(rows, sensor_params)
+    for episode, params, join in ((sensor_episode, sensor_params, with_sensor_params), (push_episode, push_params, with_push_params)):
+        if params is None:
+            continue
+        if episode is not None:
+            rows["episode"] = episode
+        rows = join(rows, params)
+    return rows
+
+
+def load_env_push(path):
+    """Of a file written under ENV_PUSH: ``(spec, episode [R] or None, push_params)`` with ``push_params(envs, episodes)`` ->
+    ``env_push.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
+    ``(None, None, None)``."""
+    import json
+    from . import env_push
+    with np.load(path) as z:
+        if "push_spec" not in z.files:
+            return None, None, None
+        spec, seed, offset = json.loads(str(z["push_spec"][()])), int(z["push_seed"]), int(z["push_env_id_offset"])
+        episode = z["episode"] if "episode" in z.files else None
+
+    def push_params(envs, episodes_):
+        return env_push.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
+    return spec, episode, push_params
 
 
 def _load_rows_with_plant_params(path):
@@ -440,6 +474,7 @@ class EpisodeLog:
         self.part_counters = []      # ... and every harvested part the device's episode_index at its harvest
         self.unknown_plants = 0      # ENV_PARAMS_ADR: rows of the last rows_with_params() whose plant is unknown (NaN)
         self.sensor = None           # ENV_SENSOR: the task's ``env_sensor.EnvSensor``; under its PER_EPISODE rows carry ``episode``
+        self.push = None             # ENV_PUSH: the task's ``env_push.EnvPush``; likewise
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -464,6 +499,8 @@ class EpisodeLog:
             return self.redraw
         if self.sensor is not None and self.sensor.spec["PER_EPISODE"]:
             return self.sensor
+        if self.push is not None and self.push.spec["PER_EPISODE"]:      # ENV_PUSH: likewise
+            return self.push
         return None
 
     def reset_envs(self, env_ids):
@@ -536,9 +573,11 @@ class EpisodeLog:
     def rows_with_params(self):
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
         (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env.  Under
-        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``)."""
+        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``), under ENV_PUSH ``param_PUSH_*`` (``with_push_params``)."""
         out = self._rows_with_plant_params()
-        return with_sensor_params(out, self.sensor.episode_params) if self.sensor is not None else out
+        if self.sensor is not None:
+            out = with_sensor_params(out, self.sensor.episode_params)
+        return with_push_params(out, self.push.episode_params) if self.push is not None else out
 
     def _rows_with_plant_params(self):
         rows = self.rows()
@@ -580,8 +619,11 @@ class EpisodeLog:
         sensor = None
         if self.sensor is not None:
             sensor = {"spec": self.sensor.spec, "seed": self.sensor.seed, "env_id_offset": self.sensor.env_id_offset}
+        push = None
+        if self.push is not None:
+            push = {"spec": self.push.spec, "seed": self.push.seed, "env_id_offset": self.push.env_id_offset}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names, redraw, adr, sensor)
+             self.env_inertia_names, redraw, adr, sensor, push)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -27,7 +27,11 @@ this step's plant produced.  Its ``live_tensors`` are the tables and its episode
 ``env_adr.EnvAdr`` stands in its place: two launches that also move the ranges the plants are drawn from, whose integers
 (steps per boundary, counts, per-env flags, the history cursor) are live tensors too.  ``env_sensor.EnvSensor`` (ENV_SENSOR)
 rewrites the observation the step has just written (``wants_obs``); it reads the step's reset flags and nothing the redraw
-writes, and stands directly in front of the redraw, which stays last.
+writes, and stands in front of the redraw, which stays last.  ``env_push.EnvPush`` (ENV_PUSH) adds impulses to the six
+generalised velocities of the state block the step has just written.  It stands behind every observer that reads that block
+-- the video, the recorder and the episode log account for the step as the plant left it -- and behind the sensor, and in
+front of the redraw: it reads the inertia table's column of the episode that has just run, which the redraw replaces.  So
+the order is: video, recorder, episode log, sensor, push, redraw / ADR.
 
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer

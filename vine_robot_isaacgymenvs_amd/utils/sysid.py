@@ -201,6 +201,7 @@ FORCED = (
     ("env", "ENV_PARAMS_PER_EPISODE", False),      # a candidate keeps its plant: the table IS the search's population
     ("env", "ENV_PARAMS_ADR", {}),                 # ... and no range moves
     ("env", "ENV_SENSOR", {}),                     # ... and the fit reads the state as it is: no sensor model
+    ("env", "ENV_PUSH", {}),                       # ... and nothing but the recorded commands moves a candidate
 )
 
 
