@@ -1,0 +1,50 @@
+#!/usr/bin/env python3
+"""Sampling-based predictive control of the plants on the device (vine_robot_isaacgymenvs_amd/utils/mpc.py).
+
+  python mpc.py task=Vine5LinkMovingBase plants=64 samples=256 horizon=20 steps=2000 task.env.EPISODE_LOG=True
+
+  python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True \\
+      'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1], LINK_MASS: [0.7, 1.4]}'          # such plants, the nominal model
+
+  python mpc.py plants=64 'model_params={DAMPING: [0.005, 0.1]}'                     # the nominal plant, such models
+
+``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
+``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
+spec, drawn once per plant and repeated over the plant's samples) and ``out`` (directory of the episode log's .npz; default
+``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT,
+in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
+import logging
+import sys
+
+OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
+       "model_params": None, "out": "runs/mpc"}
+
+
+def main(argv=None):
+    from vine_robot_isaacgymenvs_amd.utils import mpc
+    from vine_robot_isaacgymenvs_amd.utils.config import ConfigError, load_config, parse_scalar
+    argv = sys.argv[1:] if argv is None else list(argv)
+    own, overrides = dict(OWN), []
+    for arg in argv:
+        key, eq, val = arg.partition("=")
+        if eq and key in OWN:
+            own[key] = val if key == "out" else parse_scalar(val)
+        else:
+            overrides.append(arg)
+    for key in ("cost", "model_params"):
+        if own[key] is not None and not hasattr(own[key], "keys"):
+            raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    cfg = load_config("config", overrides=overrides)
+    seed = cfg.get("seed", 0)
+    task_cfg = cfg["task"]
+    task_cfg["seed"] = seed
+    if not task_cfg["env"].get("EPISODE_LOG_DIR"):
+        task_cfg["env"]["EPISODE_LOG_DIR"] = own["out"]
+    return mpc.play(task_cfg, plants=own["plants"], samples=own["samples"], horizon=own["horizon"], lam=own["lambda"],
+                    sigma=own["sigma"], steps=int(own["steps"]), cost=own["cost"], model_params=own["model_params"],
+                    seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"))
+
+
+if __name__ == "__main__":
+    main()

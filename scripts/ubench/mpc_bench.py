@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""MPC timings on one MI355X (profiles/mpc/timings.txt):  python scripts/ubench/mpc_bench.py [plants] [samples] [horizon] [free]
+
+Per-launch durations from replayed hipGraphs of `horizon` launches each, device events around the replays: the model's step
+alone, the step with the scoring node behind it (the difference is the node), the fork and the update; then the whole
+control step (fork, horizon x (step + node), update, plant step) as the Controller captures it, in control steps per second
+(host clock around replays that end in a synchronise), beside `horizon` bare model steps.  `free`: free space (the
+four-lane step kernel) instead of the task's pipe."""
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from vine_robot_isaacgymenvs_amd import load_task_config  # noqa: E402
+from vine_robot_isaacgymenvs_amd.utils import mpc  # noqa: E402
+
+M = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+H = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+FREE = len(sys.argv) > 4 and sys.argv[4] == "free"
+REPLAYS = 20
+
+
+def graph_of(body):
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        for _ in range(H):
+            body()
+    return g
+
+
+def per_launch_us(g, before=None):
+    for _ in range(3):
+        if before:
+            before()
+        g.replay()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(REPLAYS):
+        if before:
+            before()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        g.replay()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1000.0 / H)
+    return np.median(out), min(out), max(out)
+
+
+def main():
+    cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % M])
+    cfg["seed"] = 42
+    if FREE:
+        cfg["env"].update(CREATE_PIPE=False, CREATE_SHELF=False)
+    plant = mpc.make_task(cfg)
+    model = mpc.make_task(mpc.model_config(cfg, M, K))
+    ctl = mpc.Controller(plant, model, K, H)
+    print("%s, %d plants x %d samples = %d model envs, horizon %d, model step kernel %s" % (
+        torch.cuda.get_device_name(0), M, K, M * K, H, model.step_kernel_name))
+    plant.step_into(ctl.plant_actions, ctl.plant_obs)
+    ctl.control_step()                                   # (eager: every lazy initialisation done)
+    steps = graph_of(lambda: model.step_into(ctl.actions, ctl.model_obs))
+    both = graph_of(ctl.model_step)
+    forks = graph_of(ctl.fork)
+    updates = graph_of(ctl.update)
+    s = per_launch_us(steps, ctl.fork)
+    print("step alone                    median %.2f us per launch (min %.2f, max %.2f) over %d replays of %d" % (*s, REPLAYS, H))
+    b = per_launch_us(both, ctl.fork)                    # every replay scores a live window: k = 1 .. H
+    print("step + node                   median %.2f us per pair   (min %.2f, max %.2f): node = %.2f us" % (*b, b[0] - s[0]))
+    b = per_launch_us(both)                              # outside a window (k > H): the node returns at once
+    print("step + node outside a window  median %.2f us per pair   (min %.2f, max %.2f): node = %.2f us" % (*b, b[0] - s[0]))
+    f = per_launch_us(forks)
+    print("fork                          median %.2f us per launch (min %.2f, max %.2f)" % f)
+    u = per_launch_us(updates)
+    print("update                        median %.2f us per launch (min %.2f, max %.2f)" % u)
+    for graph in (True, False):
+        c = mpc.Controller(plant, model, K, H, graph=graph)
+        c.run(2)
+        best, n = 1e9, 50
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c.run(n)
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t0)
+        print("Controller.run (%s): %d control steps in %.2f ms (best of 5) = %.1f control steps/s, %.1f us per control step; "
+              "%d bare model steps = %.1f us; %.3g model env-steps/s"
+              % ("hipGraph replay" if c.use_graph else "eager launches", n, best * 1e3, n / best, best / n * 1e6, H, H * s[0],
+                 n * M * K * H / best))
+    model.close()
+    plant.close()
+
+
+if __name__ == "__main__":
+    main()

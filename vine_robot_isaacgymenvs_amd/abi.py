@@ -751,6 +751,41 @@ def declare_sysid(lib):
     return lib
 
 
+# ---- include/vine_mpc.h (product library only)
+MPC_ABI_VERSION = 1
+MPC_THREADS = 256
+MPC_MAX_HORIZON = 64
+MPC_RNG_NOISE = 8
+
+
+class VineMpcConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_plants", C.c_int32),
+        ("samples", C.c_int32),
+        ("horizon", C.c_int32),
+        ("lambda_", C.c_double),       # `lambda` in the header
+        ("sigma", C.c_float * 2),
+        ("seed", C.c_uint64),
+    ]
+
+
+MPC_PROTOTYPES = {
+    "vine_mpc_config_default": (C.c_int, [_P(VineMpcConfig)]),
+    "vine_mpc_config_size": (C.c_int, []),
+    "vine_mpc_fork": (C.c_int, [_H, _H, _P(VineMpcConfig)] + [_VP] * 12),
+    "vine_mpc_scheduled": (C.c_int, [_H, _P(VineMpcConfig)] + [_VP] * 9),
+    "vine_mpc_update": (C.c_int, [_H, _P(VineMpcConfig)] + [_VP] * 8),
+}
+
+
+def declare_mpc(lib):
+    _attach(lib, MPC_PROTOTYPES)
+    if lib.vine_mpc_config_size() != C.sizeof(VineMpcConfig):
+        raise RuntimeError("VineMpcConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -764,6 +799,6 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid):
+                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc):
         declare_one(lib)
     return lib

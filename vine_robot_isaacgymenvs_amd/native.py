@@ -28,6 +28,10 @@ UNITS = SOURCES + (SRC_SENSOR,)
 # what build() compiles and links
 SRC_PUSH = os.path.join(_HERE, "csrc", "vine_env_push.hip")
 BUILD_UNITS = UNITS + (SRC_PUSH,)
+# tests/test_env_push_cpu.py pins BUILD_UNITS to those ten in turn; the eleventh, the predictive controller's, follows them in
+# ALL_UNITS, which is what build() compiles and links
+SRC_MPC = os.path.join(_HERE, "csrc", "vine_mpc.hip")
+ALL_UNITS = BUILD_UNITS + (SRC_MPC,)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -42,7 +46,8 @@ _COMPOSITES = os.path.join(_HERE, "csrc", "vine_inertia_composites.h")
 _REDRAW_HEADERS = [_COMPOSITES, os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
 _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
                    SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
-                   SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")]}
+                   SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
+                   SRC_MPC: [os.path.join(_INC, "vine_mpc.h")]}
 # vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply
 # and an add (under -ffp-contract=fast hipcc fuses it on gfx950, a pragma in the source notwithstanding)
 # vine_env_adr.hip forms the same columns and the range in force: it switches contraction off itself, by a pragma in front of
@@ -51,10 +56,12 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # of vine_env_adr.hip
 # vine_env_push.hip draws its two per-env values with the same statement, and its solve is the float32 statement numpy makes:
 # the same pragma and flag
+# vine_mpc.hip forms a sample's action, nominal + z * c, that numpy must reproduce bit for bit: the same pragma and flag
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
+                 SRC_MPC: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
-        + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")])
+        + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")])
 
 _lib = None
 
@@ -93,7 +100,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The ten translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The eleven translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -106,7 +113,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in BUILD_UNITS:
+    for src in ALL_UNITS:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)
