@@ -133,6 +133,20 @@ typedef struct VineTrunkArgs {
     const void* wt0; int64_t ldw0; const void* wt1; int64_t ldw1; const void* wt2; int64_t ldw2; const void* a3; int64_t a3_stride;
     const void* a2; const void* a1;
     void* gz3; void* gz2; void* gz1; float* part3; float* part2; float* part1;
+    /* -- appended fields; all zero = the four-phase launch described above --
+     * bias2 (nullable): `bias` holds b_ih alone and bias2 is b_hh; the LSTM forward phase adds them (one fp32 add per
+     * element: the bits of a prepared b_ih + b_hh).
+     * mlp_w1 != NULL: the MLP forward runs first, as PHASE 0 of the launch (five phases): workgroup b carries rows
+     * [128 b, 128 b + 128) through vine_mlp3_elu_mfma's arithmetic (8 waves x 16 rows, bit-identical to that function at
+     * every n) and writes x (observation block in columns [64, 96), MLP block in [0, 64)), a1 and a2 for its own later
+     * phases; then x, a1 and a2 are OUTPUTS, a3 must be x with a3_stride == ldx.  mlp_* as the arguments of
+     * vine_mlp3_elu_mfma_prep (mlp_raw NULL: the observation block of x is already filled; mlp_ldw1 = 32 for a padded W1,
+     * else F_in); alpha is shared with the MLP backward phase.  No side job: every parameter-derived operand must exist
+     * before the launch (vine_adam_step_emit / vine_copy_batched). */
+    const float* bias2;
+    const float* mlp_raw; int64_t mlp_F_in; const double* mlp_mean; const double* mlp_var; float mlp_eps, mlp_clip;
+    const void* mlp_w1; int64_t mlp_ldw1; const float* mlp_b1; const void* mlp_w2; int64_t mlp_ldw2; const float* mlp_b2;
+    const void* mlp_w3; int64_t mlp_ldw3; const float* mlp_b3;
 } VineTrunkArgs;
 int vine_trunk_phases(const VineTrunkArgs* args, void* stream);
 int64_t vine_trunk_args_size(void);      /* sizeof(VineTrunkArgs): checked against the host mirror */
@@ -610,6 +624,28 @@ int vine_adam_step_clip(int64_t n, float* params, float* grads, float* exp_avg, 
                         float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
                         const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
                         float* found_inf, const double* sq_partial, int32_t nparts, float max_norm, float* clip_out,
+                        void* stream);
+
+/* vine_adam_step_amp (sq_partial == NULL) or vine_adam_step_clip (sq_partial != NULL) that also writes the operands the
+ * optimiser step's forward pass derives from the parameters: the thread that updates a weight stores its new 16-bit value
+ * (the very dword halves lp16_shadow receives) at its places in the LSTM weight tiles and the transposed MLP weights, and
+ * its fp32 value in the merged head weights -- no launch, and no side job of another launch, builds them afterwards.
+ * Up to 16 jobs; job k covers the tensor at [begin[k], end[k]) of the flat block (begin % 4 == 0, whole rows of cols[k]
+ * elements) and sends its element (row r, column c) to dst[k] by op[k], in the vocabulary of vine_copy_batched's scatter forms:
+ *   0   fp32 copy             dst[r * dst_stride + c]
+ *   8   forward LSTM tile     (row r of 4H, k = c + (aux & 0xffff)) of [w_ih | 0 | w_hh] with aux >> 16 columns in all; the zero
+ *                             pad columns are never written (the caller zeroes them once)
+ *   9   backward LSTM tile    w_hh^T fragments, r = k, c = unit
+ *   10  16-bit transpose      dst[c * dst_stride + r] for c < aux
+ * dst_elems[k] = elements dst[k] holds: every index a job can form is checked against it here (VINE_ERR_INVALID_ARG).  A
+ * tensor with several destinations has several jobs.  A skipped step writes none of them, as it leaves lp16_shadow alone.
+ * n % 4 == 0 and lp16_shadow are required when njobs > 0; njobs == 0 is the plain step. */
+int vine_adam_step_emit(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
+                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
+                        const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
+                        float* found_inf, const double* sq_partial, int32_t nparts, float max_norm, float* clip_out,
+                        int32_t njobs, const int32_t* op, const int64_t* begin, const int64_t* end, const int64_t* cols,
+                        void* const* dst, const int64_t* dst_stride, const int64_t* aux, const int64_t* dst_elems,
                         void* stream);
 
 /* rl_games' AdaptiveScheduler on device scalars (`schedule_type: legacy`, PY:64-66):

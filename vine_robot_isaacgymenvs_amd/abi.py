@@ -278,6 +278,9 @@ PPO_PROTOTYPES = {
     "vine_adam_step_clip": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_float, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP, _VP,
                                       _VP, C.c_int32, C.c_float, _VP, _VP]),
+    "vine_adam_step_emit": (C.c_int, [_I64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, _VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP, _VP,
+                                      _VP, C.c_int32, C.c_float, _VP, C.c_int32] + [_VP] * 8 + [_VP]),
     "vine_adaptive_lr": (C.c_int, [_VP, _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
 }
 
@@ -322,7 +325,12 @@ class TrunkArgs(C.Structure):
                                            "loss_scale", "found_inf", "w_hh_tiled", "dgates", "bias_partial")] +
                 [("wt0", C.c_void_p), ("ldw0", C.c_int64), ("wt1", C.c_void_p), ("ldw1", C.c_int64), ("wt2", C.c_void_p),
                  ("ldw2", C.c_int64), ("a3", C.c_void_p), ("a3_stride", C.c_int64), ("a2", C.c_void_p), ("a1", C.c_void_p)] +
-                [(k, C.c_void_p) for k in ("gz3", "gz2", "gz1", "part3", "part2", "part1")])
+                [(k, C.c_void_p) for k in ("gz3", "gz2", "gz1", "part3", "part2", "part1")] +
+                # appended (all zero: the four-phase launch): the second bias pointer, then phase 0 = the MLP forward
+                [("bias2", C.c_void_p), ("mlp_raw", C.c_void_p), ("mlp_F_in", C.c_int64), ("mlp_mean", C.c_void_p),
+                 ("mlp_var", C.c_void_p), ("mlp_eps", C.c_float), ("mlp_clip", C.c_float), ("mlp_w1", C.c_void_p),
+                 ("mlp_ldw1", C.c_int64), ("mlp_b1", C.c_void_p), ("mlp_w2", C.c_void_p), ("mlp_ldw2", C.c_int64),
+                 ("mlp_b2", C.c_void_p), ("mlp_w3", C.c_void_p), ("mlp_ldw3", C.c_int64), ("mlp_b3", C.c_void_p)])
 
 
 # ---- include/vine_render.h (product library only)

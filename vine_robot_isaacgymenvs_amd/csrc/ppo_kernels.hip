@@ -516,7 +516,8 @@ __device__ __forceinline__ void lstm_seq_fwd_body(
     int T, long long B, const lp16_t* __restrict__ x, long long ldx, lp16_t* hp, long long hp_stride,
     const uint4* __restrict__ Wt, const float* __restrict__ bias, const float* __restrict__ c0,
     const unsigned char* __restrict__ done, HT* __restrict__ h_out, CT* __restrict__ c_all,
-    lp16_t* __restrict__ gates, int ablate, float* __restrict__ c_last, const float* __restrict__ h0) {
+    lp16_t* __restrict__ gates, int ablate, float* __restrict__ c_last, const float* __restrict__ h0,
+    const float* __restrict__ bias2 = nullptr) {
     constexpr int H = SEQ_H, KSTEPS = KS1 + 8, KX = 32 * KS1, NF = KSTEPS * 8;
     // LDS operand rows (16-B row skew; both pitches put the 16 rows of a fragment read on distinct bank groups): the x
     // blocks of ALL T steps, staged once in the prologue, and the masked h_{t-1} in two buffers.  The x k-steps of a step
@@ -581,6 +582,14 @@ __device__ __forceinline__ void lstm_seq_fwd_body(
             *reinterpret_cast<uint4*>(&hl[0][r * HP + 8 * c8]) = hv;
         }
         for (int p = tid; p < H; p += 512) st4(&bias_l[4 * p], ld4(bias + 4 * p));
+        // bias2: `bias` is b_ih alone and this is b_hh -- one fp32 add per element, as copy op 4, on the elements this thread
+        // has just staged (a loop of its own: folded into the loop above it cost trunk_phases_kernel a second spilled VGPR)
+        if (bias2) {
+            for (int p = tid; p < H; p += 512) {
+                const float4 u = *reinterpret_cast<const float4*>(&bias_l[4 * p]), v = ld4(bias2 + 4 * p);
+                st4(&bias_l[4 * p], make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w));
+            }
+        }
     }
     float c[2][8];
     unsigned dmask[2];
@@ -1396,20 +1405,21 @@ __device__ __forceinline__ void obs_normalize8(const float (&rv)[8], const float
 #else
 #define MLPM_STAMP(i)
 #endif
-template <int C1, int C2, int C3, int NW>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2))) void mlp3_elu_mfma_kernel(long long n, lp16_t* x, long long ldx,
-                                                            const float* __restrict__ raw, int F_in,
-                                                            const double* __restrict__ mean, const double* __restrict__ var,
-                                                            float eps, float clip, const lp16_t* __restrict__ w1,
-                                                            const float* __restrict__ b1, const lp16_t* __restrict__ w2,
-                                                            long long ldw2, const float* __restrict__ b2,
-                                                            const lp16_t* __restrict__ w3, long long ldw3,
-                                                            const float* __restrict__ b3, float alpha,
-                                                            lp16_t* __restrict__ act1, lp16_t* __restrict__ act2,
-                                                            lp16_t* out, long long out_stride, int ldw1,
-                                                            const CopyBatchArgs side, int side_blocks) {
+// The body is shared by the kernel below (SIDE: with the side job in its prologue) and by phase 0 of trunk_phases_kernel
+// (no side job: `side` is never touched).  lds_raw: (C1 P1 + C2 P2 + C3 P3) 16-bit elements; stat_m / stat_sd: 32 floats each.
+template <int C1, int C2, int C3, int NW, bool SIDE>
+__device__ __forceinline__ void mlp3_elu_mfma_body(unsigned char* lds_raw, float* stat_m, float* stat_sd, lp16_t* x, long long ldx,
+                                                   const float* __restrict__ raw, int F_in,
+                                                   const double* __restrict__ mean, const double* __restrict__ var,
+                                                   float eps, float clip, const lp16_t* __restrict__ w1,
+                                                   const float* __restrict__ b1, const lp16_t* __restrict__ w2,
+                                                   long long ldw2, const float* __restrict__ b2,
+                                                   const lp16_t* __restrict__ w3, long long ldw3,
+                                                   const float* __restrict__ b3, float alpha,
+                                                   lp16_t* __restrict__ act1, lp16_t* __restrict__ act2,
+                                                   lp16_t* out, long long out_stride, int ldw1,
+                                                   const CopyBatchArgs* side, int side_blocks) {
     constexpr int P1 = 32 + LDS_SKEW, P2 = C1 + LDS_SKEW, P3 = C2 + LDS_SKEW;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     lp16_t* w1l = reinterpret_cast<lp16_t*>(lds_raw);            // [C1][P1], rows in tile order
     lp16_t* w2l = w1l + C1 * P1;                                 // [C2][P2], rows in tile order
     lp16_t* w3l = w2l + C2 * P2;                                 // [C3][P3], natural order (its output goes to memory)
@@ -1445,7 +1455,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
     }
     // ---- this lane's B fragment of layer 1: columns 8 q .. 8 q + 7 of its row (per-column `if`s around the observation
     // loads compile to one round trip per column -- clamped addresses instead)
-    __shared__ float stat_m[32], stat_sd[32];
     float rv[8];
     double stat_mean = 0.0, stat_var = 1.0;
     if (raw) {
@@ -1466,12 +1475,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
     }
     // ---- side job (vine_mlp3_elu_mfma_prep): this workgroup's share of the optimiser step's operand preparation, the
     // former copy_batched launch in front of this one (nothing this kernel reads)
-    CopyItem items[MLP3_SIDE_ITEMS];
+    CopyItem items[SIDE ? MLP3_SIDE_ITEMS : 1];
+    if constexpr (SIDE) {
 #pragma unroll
-    for (int k = 0; k < MLP3_SIDE_ITEMS; ++k) {
-        const int vb = ((int)blockIdx.x + k * (int)gridDim.x) * (TH / 256) + (tid >> 8);
-        items[k].mode = 0;
-        if (vb < side_blocks) copy_item_load(side, vb, tid & 255, items[k]);
+        for (int k = 0; k < MLP3_SIDE_ITEMS; ++k) {
+            const int vb = ((int)blockIdx.x + k * (int)gridDim.x) * (TH / 256) + (tid >> 8);
+            items[k].mode = 0;
+            if (vb < side_blocks) copy_item_load(*side, vb, tid & 255, items[k]);
+        }
     }
     lp16x8_t af1;
     if (raw) {
@@ -1485,9 +1496,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
     } else {
         af1 = *reinterpret_cast<const lp16x8_t*>(x + b * ldx + 8 * q);
     }
-    if (side_blocks > 0) {
+    if constexpr (SIDE) {
+        if (side_blocks > 0) {
 #pragma unroll
-        for (int k = 0; k < MLP3_SIDE_ITEMS; ++k) copy_item_store(items[k]);
+            for (int k = 0; k < MLP3_SIDE_ITEMS; ++k) copy_item_store(items[k]);
+        }
     }
 #pragma unroll
     for (int it = 0; it < N1; ++it) {
@@ -1564,6 +1577,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
             make_float4(elu1(a[0] + bb.x, alpha), elu1(a[1] + bb.y, alpha), elu1(a[2] + bb.z, alpha), elu1(a[3] + bb.w, alpha)));
     }
     MLPM_STAMP(5)
+}
+template <int C1, int C2, int C3, int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2))) void mlp3_elu_mfma_kernel(long long n, lp16_t* x, long long ldx,
+                                                            const float* __restrict__ raw, int F_in,
+                                                            const double* __restrict__ mean, const double* __restrict__ var,
+                                                            float eps, float clip, const lp16_t* __restrict__ w1,
+                                                            const float* __restrict__ b1, const lp16_t* __restrict__ w2,
+                                                            long long ldw2, const float* __restrict__ b2,
+                                                            const lp16_t* __restrict__ w3, long long ldw3,
+                                                            const float* __restrict__ b3, float alpha,
+                                                            lp16_t* __restrict__ act1, lp16_t* __restrict__ act2,
+                                                            lp16_t* out, long long out_stride, int ldw1,
+                                                            const CopyBatchArgs side, int side_blocks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    __shared__ float stat_m[32], stat_sd[32];
+    mlp3_elu_mfma_body<C1, C2, C3, NW, true>(lds_raw, stat_m, stat_sd, x, ldx, raw, F_in, mean, var, eps, clip, w1, b1, w2, ldw2, b2,
+                                             w3, ldw3, b3, alpha, act1, act2, out, out_stride, ldw1, &side, side_blocks);
 }
 
 // ---- backward of a Linear through the previous layer's ELU on the matrix cores:
@@ -3856,9 +3886,12 @@ __global__ __launch_bounds__(512) void ln_heads_loss_kernel(
 // kernels gives workgroup b the same 128 samples (sequences [32 b, 32 b + 32) x T = 4 = rows [128 b, 128 b + 128) of the
 // sequence-major order) and reads, from the phase before it, only what the SAME workgroup wrote (hidden states -> loss;
 // dh -> LSTM backward; dG -> MLP backward): a workgroup barrier is all that separates them -- three grid fills / drains
-// fewer per optimiser step, and each phase finds its predecessor's rows in the CU's L2.  (The one-launch MLP forward
-// stays in front as its own launch: its side job builds the weight operands ALL workgroups of this chain read, and the
-// weight-gradient kernels -- reductions over all rows -- stay behind it.)  LDS: one dynamic block used phase after phase.
+// fewer per optimiser step, and each phase finds its predecessor's rows in the CU's L2.  The one-launch MLP forward is
+// PHASE 0 of the chain when its pointers are given (mlp_w1): same rows per workgroup again (8 waves x 16), and x / a1 / a2
+// are read back only by the workgroup that wrote them.  That became possible when the weight operands ALL workgroups of
+// this chain read stopped being built by the MLP launch's side job: the Adam kernel writes them (vine_adam_step_emit), so
+// they are complete before the launch starts.  Without mlp_w1 the MLP forward is a launch of its own in front.  The
+// weight-gradient kernels -- reductions over all rows -- stay behind.  LDS: one dynamic block used phase after phase.
 struct TrunkPhasesArgs {
     long long B; int T;
     // LSTM forward
@@ -3878,12 +3911,30 @@ struct TrunkPhasesArgs {
     const lp16_t* wt0; long long ldw0; const lp16_t* wt1; long long ldw1; const lp16_t* wt2; long long ldw2;
     const lp16_t* a3; long long a3_stride; const lp16_t* a2; const lp16_t* a1; float alpha;
     lp16_t* gz3; lp16_t* gz2; lp16_t* gz1; float* part3; float* part2; float* part1;
+    // LSTM forward: the second half of the bias when `bias` is b_ih alone (nullable)
+    const float* bias2;
+    // phase 0, the MLP forward (mlp_w1 == nullptr: the four-phase launch, x / a2 / a1 are inputs)
+    const float* mlp_raw; int mlp_F_in; const double* mlp_mean; const double* mlp_var; float mlp_eps, mlp_clip;
+    const lp16_t* mlp_w1; int mlp_ldw1; const float* mlp_b1; const lp16_t* mlp_w2; long long mlp_ldw2; const float* mlp_b2;
+    const lp16_t* mlp_w3; long long mlp_ldw3; const float* mlp_b3;
 };
+constexpr size_t MLP3_LDS_BYTES = ((size_t)256 * (32 + LDS_SKEW) + 128 * (256 + LDS_SKEW) + 64 * (128 + LDS_SKEW)) * sizeof(lp16_t);
 __global__ __launch_bounds__(512) void trunk_phases_kernel(const TrunkPhasesArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char trunk_lds[];
     TRUNK_STAMP(0)
+    if (a.mlp_w1) {
+        // phase 0: this workgroup's 128 rows through the MLP (8 waves x 16 rows, the stand-alone kernel's arithmetic); it
+        // writes the rows of x, a1 and a2 that the LSTM forward phase and the MLP backward phase of THIS workgroup read
+        float* stat = reinterpret_cast<float*>(trunk_lds + MLP3_LDS_BYTES);
+        mlp3_elu_mfma_body<256, 128, 64, 8, false>(trunk_lds, stat, stat + 32, const_cast<lp16_t*>(a.x) + 64, a.ldx, a.mlp_raw,
+                                                   a.mlp_F_in, a.mlp_mean, a.mlp_var, a.mlp_eps, a.mlp_clip, a.mlp_w1, a.mlp_b1,
+                                                   a.mlp_w2, a.mlp_ldw2, a.mlp_b2, a.mlp_w3, a.mlp_ldw3, a.mlp_b3, a.alpha,
+                                                   const_cast<lp16_t*>(a.a1), const_cast<lp16_t*>(a.a2),
+                                                   const_cast<lp16_t*>(a.a3), a.a3_stride, a.mlp_ldw1, nullptr, 0);
+        __syncthreads();      // x, a1, a2 of this workgroup's rows are written; the LSTM forward phase takes the LDS over
+    }
     lstm_seq_fwd_body<3, 22, lp16_t, lp16_t, SEQ_FWD_NC>(a.T, a.B, a.x, a.ldx, nullptr, 0, a.w_tiled, a.bias, a.c0, a.done, a.h_out, a.c_all,
-                                                 a.gates, a.ablate, a.c_last, a.h0);
+                                                 a.gates, a.ablate, a.c_last, a.h0, a.bias2);
     __syncthreads();      // this workgroup's hidden states are written (h_out slots 1 .. T of its 32 sequences)
     TRUNK_STAMP(1)
     ln_heads_loss_body<3, 4, lp16_t, lp16_t>(reinterpret_cast<float*>(trunk_lds),
@@ -3979,13 +4030,83 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(long long n, const flo
     if (threadIdx.x == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 
+// ---- Parameter-derived operands written by the Adam kernel itself (vine_adam_step_emit).  The 16-bit operand layouts of
+// the optimiser step's forward pass -- the LSTM weight tiles, the transposed MLP weights -- and the fp32 merged heads are
+// re-laid copies of values this kernel has in registers when it writes `shadow`; written from here they need no launch (and
+// no side job of another launch) of their own.  A job = one tensor's range [begin, end) of the flat block (begin a multiple
+// of 4, so a thread's four elements belong to one tensor), the tensor's row length `cols`, a destination and an op in the
+// vocabulary of CopyJob, seen from the SOURCE element (row r, column c) as the scatter forms see it:
+//   op 0   fp32 copy            dst[r * dst_stride + c]
+//   op 8   forward LSTM tile    element (row r of 4H, k = c + (aux & 0xffff)) of the virtual [w_ih | 0 | w_hh] with K = aux >> 16
+//                               columns; four consecutive k (cols % 4 == 0) are 8 contiguous bytes
+//   op 9   backward LSTM tile   w_hh^T fragments: r = k, c = unit
+//   op 10  16-bit transpose     dst[c * dst_stride + r] for c < aux
+// A tensor with several destinations has several jobs.  Every 16-bit value stored is a half of the dword `shadow` receives.
+struct EmitJob {
+    long long begin, end;
+    void* dst;
+    long long dst_stride, aux;
+    int cols, op;
+};
+#define VINE_EMIT_MAX_JOBS 16
+struct EmitTable {
+    EmitJob job[VINE_EMIT_MAX_JOBS];
+    int njobs;
+};
+__device__ __forceinline__ long long lstm_tile_fwd_index(int row, int k, int ksteps) {      // (copy_item_load, op 8)
+    const int g = row >> 8, unit = row & 255;
+    const int wv = unit >> 5, u5 = unit & 31, lane15 = 4 * (u5 >> 3) + (u5 & 3), ut = (u5 >> 2) & 1;
+    const int kk = k >> 5, k5 = k & 31, lane = (k5 >> 3) * 16 + lane15, i = k5 & 7, jj = 2 * g + ut;
+    return ((((long long)wv * ksteps + kk) * 8 + jj) * 64 + lane) * 8 + i;
+}
+__device__ __forceinline__ long long lstm_tile_bwd_index(int k, int unit) {                 // (copy_item_load, op 9)
+    const int wv = unit >> 5, u5 = unit & 31, lane15 = 4 * (u5 >> 3) + (u5 & 3), ut = (u5 >> 2) & 1;
+    const int kk = k >> 5, k5 = k & 31, lane = (k5 >> 3) * 16 + lane15, i = k5 & 7;
+    return ((((long long)wv * (4 * SEQ_H / 32) + kk) * 2 + ut) * 64 + lane) * 8 + i;
+}
+// e0: flat index of the thread's first element; pa: its four new fp32 values; pk: the same four as `shadow` holds them
+__device__ __forceinline__ void adam_emit(const EmitTable& E, long long e0, const float (&pa)[4], uint2 pk) {
+    const unsigned short h[4] = {(unsigned short)(pk.x & 0xffffu), (unsigned short)(pk.x >> 16),
+                                 (unsigned short)(pk.y & 0xffffu), (unsigned short)(pk.y >> 16)};
+#pragma unroll 1
+    for (int j = 0; j < E.njobs; ++j) {      // (linear search as in copy_batched_body; a tensor may have several jobs)
+        const EmitJob& J = E.job[j];
+        if (e0 < J.begin || e0 >= J.end) continue;
+        const unsigned local = (unsigned)(e0 - J.begin), cols = (unsigned)J.cols;
+        const int nv = (int)(J.end - e0 < 4 ? J.end - e0 : 4);
+        unsigned r = local / cols, c = local - r * cols;
+        if (J.op == 8 && !(cols & 3u)) {     // (nv == 4: the range is whole rows)
+            const int koff = (int)(J.aux & 0xffff), ksteps = (int)(J.aux >> 16) / 32;
+            *reinterpret_cast<uint2*>(reinterpret_cast<lp16_t*>(J.dst) + lstm_tile_fwd_index((int)r, (int)c + koff, ksteps)) = pk;
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (q < nv) {
+                if (J.op == 0) {
+                    reinterpret_cast<float*>(J.dst)[(long long)r * J.dst_stride + c] = pa[q];
+                } else if (J.op == 8) {
+                    const int koff = (int)(J.aux & 0xffff), ksteps = (int)(J.aux >> 16) / 32;
+                    reinterpret_cast<lp16_t*>(J.dst)[lstm_tile_fwd_index((int)r, (int)c + koff, ksteps)] = h[q];
+                } else if (J.op == 9) {
+                    reinterpret_cast<lp16_t*>(J.dst)[lstm_tile_bwd_index((int)r, (int)c)] = h[q];
+                } else if ((long long)c < J.aux) {      // op 10
+                    reinterpret_cast<lp16_t*>(J.dst)[(long long)c * J.dst_stride + r] = h[q];
+                }
+                if (++c == cols) { c = 0; ++r; }
+            }
+        }
+    }
+}
+
 template <bool CLIP>
 __global__ void adam_kernel(long long n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, float* lr_p, float* step_p,
                             float beta1, float beta2, float eps, float wd, float gscale, lp16_t* __restrict__ shadow,
                             const float* kl, float kl_scale, float kl_thr, float min_lr, float max_lr,
                             float* amp, float* found_inf, unsigned int* ticket, unsigned int* sub,
-                            const double* __restrict__ sq_partial, int nparts, float max_norm, float* clip_out) {
+                            const double* __restrict__ sq_partial, int nparts, float max_norm, float* clip_out,
+                            const EmitTable emit) {
     const float loss_scale = amp ? amp[0] : 1.0f;
     bool skip = found_inf && *found_inf != 0.0f;
     if (amp) gscale = gscale / loss_scale;
@@ -4036,7 +4157,11 @@ __global__ void adam_kernel(long long n, float* __restrict__ p, float* __restric
         st4(m + 4 * i, make_float4(ma[0], ma[1], ma[2], ma[3]));
         st4(v + 4 * i, make_float4(va[0], va[1], va[2], va[3]));
         st4(g + 4 * i, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        if (shadow) st4(shadow + 4 * i, make_float4(pa[0], pa[1], pa[2], pa[3]));   // bf16 copy for the GEMM operands
+        if (shadow) {                        // 16-bit copy for the GEMM operands, formed once: flat, and as the operands read it
+            const uint2 pk = make_uint2(f2lp2(pa[0], pa[1]), f2lp2(pa[2], pa[3]));
+            *reinterpret_cast<uint2*>(shadow + 4 * i) = pk;
+            if (emit.njobs > 0) adam_emit(emit, 4 * i, pa, pk);
+        }
     }
     // tail (n not a multiple of 4)
     const long long t = ((n >> 2) << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5653,7 +5778,27 @@ int vine_trunk_phases(const VineTrunkArgs* p, void* stream) {
     a.ldw2 = q.ldw2; a.a3 = (const lp16_t*)q.a3; a.a3_stride = q.a3_stride; a.a2 = (const lp16_t*)q.a2; a.a1 = (const lp16_t*)q.a1;
     a.alpha = q.alpha; a.gz3 = (lp16_t*)q.gz3; a.gz2 = (lp16_t*)q.gz2; a.gz1 = (lp16_t*)q.gz1; a.part3 = q.part3; a.part2 = q.part2;
     a.part1 = q.part1;
-    const size_t lds = 160 * 1024;      // the LSTM forward phase with its weight cache: 63 + 96 KB (the other phases need less)
+    a.bias2 = q.bias2;
+    if ((uintptr_t)q.bias2 & 15) return VINE_ERR_INVALID_ARG;
+    a.mlp_w1 = nullptr;
+    if (q.mlp_w1) {
+        // phase 0: the checks of vine_mlp3_elu_mfma_prep; the MLP block is columns [0, 64) of x, the observation block [64, 96)
+        if (!q.mlp_b1 || !q.mlp_w2 || !q.mlp_b2 || !q.mlp_w3 || !q.mlp_b3 || (q.mlp_ldw2 & 7) || (q.mlp_ldw3 & 7) ||
+            q.mlp_ldw2 < 256 || q.mlp_ldw3 < 128 || ((uintptr_t)q.mlp_w1 & (q.mlp_ldw1 == 32 ? 15 : 3)) || q.mlp_ldw1 <= 0 ||
+            q.mlp_ldw1 > 32 || (q.mlp_ldw1 & 1) || ((uintptr_t)q.mlp_w2 & 15) || ((uintptr_t)q.mlp_w3 & 15) ||
+            ((uintptr_t)q.mlp_b1 & 15) || ((uintptr_t)q.mlp_b2 & 15) || ((uintptr_t)q.mlp_b3 & 15) ||
+            (q.mlp_raw && (!q.mlp_mean || !q.mlp_var || q.mlp_F_in <= 0 || q.mlp_F_in > 32)) || q.a3 != q.x || q.a3_stride != q.ldx)
+            return VINE_ERR_INVALID_ARG;
+        a.mlp_raw = q.mlp_raw; a.mlp_F_in = (int)q.mlp_F_in; a.mlp_mean = q.mlp_mean; a.mlp_var = q.mlp_var; a.mlp_eps = q.mlp_eps;
+        a.mlp_clip = q.mlp_clip; a.mlp_w1 = (const lp16_t*)q.mlp_w1; a.mlp_ldw1 = (int)q.mlp_ldw1; a.mlp_b1 = q.mlp_b1;
+        a.mlp_w2 = (const lp16_t*)q.mlp_w2; a.mlp_ldw2 = q.mlp_ldw2; a.mlp_b2 = q.mlp_b2; a.mlp_w3 = (const lp16_t*)q.mlp_w3;
+        a.mlp_ldw3 = q.mlp_ldw3; a.mlp_b3 = q.mlp_b3;
+    } else {
+        a.mlp_raw = nullptr; a.mlp_F_in = 0; a.mlp_mean = a.mlp_var = nullptr; a.mlp_eps = a.mlp_clip = 0.0f; a.mlp_ldw1 = 0;
+        a.mlp_b1 = a.mlp_b2 = a.mlp_b3 = nullptr; a.mlp_w2 = a.mlp_w3 = nullptr; a.mlp_ldw2 = a.mlp_ldw3 = 0;
+    }
+    static_assert(MLP3_LDS_BYTES + 64 * sizeof(float) <= 160 * 1024, "phase 0 fits the launch's LDS");
+    const size_t lds = 160 * 1024;     // the LSTM forward phase with its weight cache: 63 + 96 KB (the other phases need less)
     if (!ensure_dyn_lds(reinterpret_cast<const void*>(&trunk_phases_kernel), lds)) return VINE_ERR_DEVICE;
     hipLaunchKernelGGL(trunk_phases_kernel, dim3((unsigned)(q.B / SEQ_ROWS)), dim3(512), lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
@@ -6294,7 +6439,7 @@ static int adam_launch(bool clip, int64_t n, float* params, float* grads, float*
                        float* step, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                        void* lp16_shadow, const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr,
                        float* amp_state, float* found_inf, const double* sq_partial, int32_t nparts, float max_norm,
-                       float* clip_out, void* stream) {
+                       float* clip_out, void* stream, const EmitTable* emit = nullptr) {
     if (n <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || !lr || !step) return VINE_ERR_INVALID_ARG;
     if (clip && (!sq_partial || nparts < 1 || nparts > GRAD_SQNORM_MAX_PARTS || !(max_norm > 0.0f))) return VINE_ERR_INVALID_ARG;
     unsigned int* ticket = ticket_slot(stream, TICKET_ADAM);
@@ -6305,11 +6450,62 @@ static int adam_launch(bool clip, int64_t n, float* params, float* grads, float*
     // 4 KB of parameters.  Hence a two-level election (8 group words 128 B apart, then the common word) on the full grid
     const int blocks = grid_for((n + 3) / 4, threads);
     unsigned int* sub = ticket_sub_of(ticket);
+    EmitTable none;
+    none.njobs = 0;
     hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(blocks), dim3(threads), 0, (hipStream_t)stream,
                        (long long)n, params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay, grad_scale,
                        (lp16_t*)lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, ticket, sub,
-                       sq_partial, (int)nparts, max_norm, clip_out);
+                       sq_partial, (int)nparts, max_norm, clip_out, emit ? *emit : none);
     return hipGetLastError() == hipSuccess ? VINE_OK : VINE_ERR_DEVICE;
+}
+
+int vine_adam_step_emit(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,
+                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* lp16_shadow,
+                        const float* kl, float kl_scale, float kl_threshold, float min_lr, float max_lr, float* amp_state,
+                        float* found_inf, const double* sq_partial, int32_t nparts, float max_norm, float* clip_out,
+                        int32_t njobs, const int32_t* op, const int64_t* begin, const int64_t* end, const int64_t* cols,
+                        void* const* dst, const int64_t* dst_stride, const int64_t* aux, const int64_t* dst_elems,
+                        void* stream) {
+    if (njobs < 0 || njobs > VINE_EMIT_MAX_JOBS || (njobs > 0 && (!op || !begin || !end || !cols || !dst || !dst_stride || !aux ||
+                                                                  !dst_elems || !lp16_shadow || (n & 3))))
+        return VINE_ERR_INVALID_ARG;
+    EmitTable t;
+    t.njobs = njobs;
+    for (int k = 0; k < njobs; ++k) {
+        // every index a job can form stays inside its destination: checked here once, not in the kernel
+        const long long len = end[k] - begin[k];
+        if (!dst[k] || begin[k] < 0 || (begin[k] & 3) || len <= 0 || end[k] > n || len >= (1ll << 31) || cols[k] <= 0 ||
+            cols[k] >= (1ll << 31) || len % cols[k] || dst_elems[k] <= 0)
+            return VINE_ERR_INVALID_ARG;
+        const long long rows = len / cols[k];
+        bool ok;
+        switch (op[k]) {
+            case 0:
+                ok = dst_stride[k] >= cols[k] && (rows - 1) * dst_stride[k] + cols[k] <= dst_elems[k] && !((uintptr_t)dst[k] & 3);
+                break;
+            case 8: {
+                const long long koff = aux[k] & 0xffff, K = aux[k] >> 16;
+                ok = rows == 4 * SEQ_H && K > 0 && !(K & 31) && koff + cols[k] <= K && dst_elems[k] >= 4ll * SEQ_H * K &&
+                     !((uintptr_t)dst[k] & 7) && ((cols[k] & 3) || !(koff & 3));
+                break;
+            }
+            case 9:
+                ok = rows == 4 * SEQ_H && cols[k] == SEQ_H && dst_elems[k] >= 4ll * SEQ_H * SEQ_H && !((uintptr_t)dst[k] & 1);
+                break;
+            case 10:
+                ok = aux[k] > 0 && aux[k] <= cols[k] && dst_stride[k] >= rows && (aux[k] - 1) * dst_stride[k] + rows <= dst_elems[k] &&
+                     !((uintptr_t)dst[k] & 1);
+                break;
+            default:
+                return VINE_ERR_UNSUPPORTED;
+        }
+        if (!ok) return VINE_ERR_INVALID_ARG;
+        t.job[k] = EmitJob{(long long)begin[k], (long long)end[k], dst[k], (long long)dst_stride[k], (long long)aux[k],
+                           (int)cols[k], (int)op[k]};
+    }
+    return adam_launch(sq_partial != nullptr, n, params, grads, exp_avg, exp_avg_sq, lr, step, beta1, beta2, eps, weight_decay,
+                       grad_scale, lp16_shadow, kl, kl_scale, kl_threshold, min_lr, max_lr, amp_state, found_inf, sq_partial,
+                       nparts, max_norm, clip_out, stream, &t);
 }
 
 int vine_adam_step_amp(int64_t n, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* lr, float* step,

@@ -335,6 +335,12 @@ class A2CAgent(FastInferenceMixin):
             if self.fused_mixed:
                 self.optimizer.enable_lp16_shadow(self.amp_dtype)
                 self.model.a2c_network.op_weight_lookup = self.optimizer.shadow_of
+                if self.is_cuda and fused.MLP_PHASE:
+                    # the Adam launch writes the forward pass's parameter-derived operands itself (five launches per step)
+                    net = self.model.a2c_network
+                    self.optimizer.enable_operand_set([m.weight for m in net.actor_mlp if isinstance(m, torch.nn.Linear)],
+                                                      net.rnn.rnn.weight_ih_l0, net.rnn.rnn.weight_hh_l0, net.mu.weight,
+                                                      net.mu.bias, net.value.weight, net.value.bias)
                 if self.amp_dtype == torch.float16:      # fp16 operands: GradScaler semantics (PY:53 via rl_games)
                     self._amp = self.optimizer.enable_loss_scaling(
                         float(config.get("loss_scale_init", 65536.0)), int(config.get("loss_scale_growth_interval", 2000)))
@@ -912,7 +918,7 @@ class A2CAgent(FastInferenceMixin):
         ext = all(g is not None and g.is_cuda for g in hb)     # head-bias gradients straight from the loss kernel
         batch_dict = {"obs": mb["obs"] if obs_n is None else obs_n, "obs_is_normalized": obs_n is not None,
                       "rnn_states": mb["rnn_states"], "seq_length": self.seq_len, "dones": mb["dones"],
-                      "head_bias_external": ext}
+                      "head_bias_external": ext, "operands": getattr(self.optimizer, "operands", None)}
         if norm_stats is not None:
             batch_dict["obs_norm_stats"] = norm_stats
         pack = None

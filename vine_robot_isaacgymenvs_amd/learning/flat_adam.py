@@ -44,6 +44,7 @@ class FlatAdam:
         self.param_groups = [{"params": self.params, "lr": self.lr, "betas": betas, "eps": eps,
                               "weight_decay": weight_decay}]
         self.shadow = None          # 16-bit copy of flat_params (GEMM operands of the mixed-precision update)
+        self.operands = None        # fused.OperandSet: the operands derived from the shadow, written by the Adam launch too
         self.amp_state = None       # [loss scale, growth tracker, growth interval, -] (enable_loss_scaling)
         self.found_inf = self.aux[1:2]
         self.check_grads = False    # look for non-finite gradients here (set when the backward pass does not check itself)
@@ -66,6 +67,25 @@ class FlatAdam:
 
     enable_bf16_shadow = enable_lp16_shadow      # round-2 name
 
+    def offset_of(self, p):
+        """Where parameter ``p`` starts in the flat block (identity lookup)."""
+        for q, off in zip(self.params, self.offsets):
+            if q is p:
+                return off
+        raise KeyError("parameter is not managed by this optimiser")
+
+    def enable_operand_set(self, mlp_weights, w_ih, w_hh, mu_w, mu_b, v_w, v_b):
+        """Keep the forward pass's parameter-derived operands (LSTM weight tiles, transposed MLP weights, merged heads) as
+        persistent buffers next to the shadow (call this outside any capture, after ``enable_lp16_shadow``): every Adam
+        launch then writes them together with the shadow (``vine_adam_step_emit``), and ``refresh_shadow`` rebuilds them
+        with the ``vine_copy_batched`` moves -- the same bytes either way.  -> the ``fused.OperandSet`` to hand to the
+        trunk's forward, or None where the network is not the default one (nothing changes then)."""
+        from . import fused
+        if self._lib is None or self.shadow is None or self.numel % 4 or not fused.OperandSet.supported(list(mlp_weights), w_ih, w_hh):
+            return None
+        self.operands = fused.OperandSet(self.shadow_of, self.offset_of, list(mlp_weights), w_ih, w_hh, mu_w, mu_b, v_w, v_b)
+        return self.operands
+
     def enable_loss_scaling(self, init_scale=65536.0, growth_interval=2000):
         """torch.amp.GradScaler restated on the device (its defaults: scale 2^16, x2 after 2000 good steps, x0.5 and a
         skipped step on overflow) -- what rl_games wraps the reference's ``mixed_precision: True`` update in.  The
@@ -82,6 +102,8 @@ class FlatAdam:
     def refresh_shadow(self):
         if self.shadow is not None:
             self.shadow.copy_(self.flat_params)
+            if self.operands is not None:
+                self.operands.rebuild()
 
     def shadow_of(self, p):
         """The 16-bit view matching parameter ``p`` (identity lookup)."""
@@ -140,7 +162,21 @@ class FlatAdam:
                     self.weight_decay, float(grad_scale), self.shadow.data_ptr() if self.shadow is not None else None,
                     kl.data_ptr() if kl is not None else None, float(kscale), float(thr), float(lo), float(hi),
                     self.amp_state.data_ptr() if amp else None, self.found_inf.data_ptr() if amp else None)
-            if clip is None:
+            if self.operands is not None:
+                # the launch that also writes the derived operands; its clip half is chosen by the partial sums
+                partial, out = None, None
+                if clip is not None:
+                    self.enable_clip_buffers()
+                    out = self.clip_out if clip_out is None else clip_out
+                    partial = self._clip_partial
+                    rc = self._lib.vine_grad_sqnorm(self.numel, self.flat_grads.data_ptr(), partial.data_ptr(), stream)
+                    if rc != 0:
+                        raise RuntimeError("vine_grad_sqnorm failed with status %d" % rc)
+                name, rc = "vine_adam_step_emit", self._lib.vine_adam_step_emit(
+                    *args, partial.data_ptr() if partial is not None else None, partial.numel() if partial is not None else 0,
+                    float(clip) if clip is not None else 0.0, out.data_ptr() if out is not None else None,
+                    *self.operands.emit_jobs, stream)
+            elif clip is None:
                 name, rc = "vine_adam_step_amp", self._lib.vine_adam_step_amp(*args, stream)
             else:
                 self.enable_clip_buffers()

@@ -123,7 +123,10 @@ MLP3_F32_SPLIT = os.environ.get("VINE_MLP3_F32_SPLIT", "1") != "0"
 MLP3_F32_SPLIT_RT = int(os.environ.get("VINE_MLP3_F32_SPLIT_RT", "0"))
 MLP3_PREP = os.environ.get("VINE_MLP3_PREP", "1") != "0"      # the step's operand preparation rides in the MLP launch (A/B knob)
 COPY_SCATTER = os.environ.get("VINE_COPY_SCATTER", "1") != "0"  # coalesced-load / scattered-store forms of tiles and transposes
-RIDES = [0]      # forward passes whose operand preparation rode in the MLP launch (tests look at it)
+RIDES = [0]      # forward passes whose operand preparation rode in another launch (the MLP's or Adam's) (tests look at it)
+# the optimiser's Adam launch writes the parameter-derived operands itself (FlatAdam.enable_operand_set) and the MLP forward
+# runs as phase 0 of the trunk launch: five launches per optimiser step.  0: the side job in the MLP launch, six launches
+MLP_PHASE = os.environ.get("VINE_MLP_PHASE", "1") != "0"
 # LSTM backward + MLP backward as two phases of one launch (same rows per workgroup); 0: two launches (A/B knob)
 BWD_PHASES = os.environ.get("VINE_BWD_PHASES", "1") != "0"
 # LSTM forward + LayerNorm / heads / loss + LSTM backward + MLP backward as four phases of one launch; 0: separate launches
@@ -702,6 +705,78 @@ class CopyBatch:
         self.jobs, self.keep = [], []
 
 
+class OperandSet:
+    """The operands an optimiser step's forward pass derives from the parameters alone, as PERSISTENT buffers owned by the
+    optimiser (``FlatAdam.enable_operand_set``): the LSTM weight tiles, the transposed MLP weights, the merged fp32 heads.
+    Two writers keep them current and write the same bytes: ``emit_jobs`` is the table the Adam launch takes
+    (``vine_adam_step_emit``: the thread that updates a weight stores it at its places), ``rebuild`` runs the
+    ``vine_copy_batched`` moves the forward pass would otherwise queue, from the 16-bit shadow (after anything but Adam
+    touched the parameters).  b_ih + b_hh is not part of the set: two threads own its terms, the LSTM forward phase adds
+    them.  Default network only (``supported``)."""
+
+    @staticmethod
+    def supported(mlp_w, w_ih, w_hh):
+        U = mlp_w[-1].shape[0] if mlp_w else 0
+        return (len(mlp_w) == 3 and tuple(W.shape[0] for W in mlp_w) == (256, 128, 64) and mlp_w[1].shape[1] == 256
+                and mlp_w[2].shape[1] == 128 and tuple(w_hh.shape) == (1024, 256) and w_ih.shape[0] == 1024
+                and U < w_ih.shape[1] <= 96 and (w_ih.shape[1] + 15) // 16 * 16 == 96)
+
+    def __init__(self, shadow_of, offset_of, mlp_w, w_ih, w_hh, mu_w, mu_b, v_w, v_b):
+        assert self.supported(mlp_w, w_ih, w_hh)
+        dev, op = w_ih.device, lp_dtype()
+        H, U, width, wpad = 256, 64, w_ih.shape[1], 96
+        A_, NH = mu_w.shape[0], mu_w.shape[0] + v_w.shape[0]
+        self.params = (mlp_w[1], mlp_w[2], w_ih, w_hh, mu_w, mu_b, v_w, v_b)
+        self.ops = (shadow_of(mlp_w[1]), shadow_of(mlp_w[2]), shadow_of(w_ih), shadow_of(w_hh))
+        self.U, self.wpad, self.A = U, wpad, A_
+        self.wtile = torch.zeros(4 * H * (wpad + H), device=dev, dtype=op)      # (the pad columns stay zero)
+        self.w_hh_tiled = torch.zeros(4 * H * H, device=dev, dtype=op)
+        self.wts = [torch.zeros((U, 4 * H), device=dev, dtype=op), torch.zeros((256, 128), device=dev, dtype=op),
+                    torch.zeros((128, 64), device=dev, dtype=op)]
+        self.w_heads = torch.zeros((NH, H), device=dev, dtype=torch.float32)
+        self.b_heads = torch.zeros(NH, device=dev, dtype=torch.float32)
+        K = wpad + H
+
+        def job(opc, p, cols, dst, stride, aux):
+            o = offset_of(p)
+            return (opc, o, o + p.numel(), cols, dst.data_ptr(), stride, aux, dst.numel())
+        jobs = [job(CopyBatch.LSTM_TILE_FWD_S, w_ih, width, self.wtile, 0, K << 16),
+                job(CopyBatch.TRANSPOSE_S, w_ih, width, self.wts[0], 4 * H, U),
+                job(CopyBatch.LSTM_TILE_FWD_S, w_hh, H, self.wtile, 0, wpad | (K << 16)),
+                job(CopyBatch.LSTM_TILE_BWD_S, w_hh, H, self.w_hh_tiled, 0, 0),
+                job(CopyBatch.TRANSPOSE_S, mlp_w[1], 256, self.wts[1], 128, 256),
+                job(CopyBatch.TRANSPOSE_S, mlp_w[2], 128, self.wts[2], 64, 128),
+                job(CopyBatch.COPY, mu_w, H, self.w_heads[:A_], H, 0), job(CopyBatch.COPY, v_w, H, self.w_heads[A_:], H, 0),
+                job(CopyBatch.COPY, mu_b, A_, self.b_heads[:A_], A_, 0),
+                job(CopyBatch.COPY, v_b, NH - A_, self.b_heads[A_:], NH - A_, 0)]
+        cols = list(zip(*jobs))
+        i64 = lambda v: _carray(C.c_int64, v)      # noqa: E731
+        # (njobs, op, begin, end, cols, dst, dst stride, aux, dst elements) as vine_adam_step_emit takes them
+        self.emit_jobs = (len(jobs), _carray(C.c_int32, cols[0]), i64(cols[1]), i64(cols[2]), i64(cols[3]),
+                          _carray(C.c_void_p, cols[4]), i64(cols[5]), i64(cols[6]), i64(cols[7]))
+        self.rebuild()
+
+    def covers(self, W2, W3, w_ih, w_hh, mu_w, mu_b, v_w, v_b):
+        """Is this the set of exactly these parameters (same storage)?"""
+        return all(a.data_ptr() == b.data_ptr() and a.shape == b.shape
+                   for a, b in zip(self.params, (W2, W3, w_ih, w_hh, mu_w, mu_b, v_w, v_b)))
+
+    @torch.no_grad()
+    def rebuild(self):
+        W2o, W3o, w_ih_op, w_hh_op = self.ops
+        _, _, _, _, mu_w, mu_b, v_w, v_b = self.params
+        prep = CopyBatch()
+        prep.add_lstm_tiles(w_ih_op, w_hh_op, self.wpad, self.wtile, self.w_hh_tiled)
+        prep.add(CopyBatch.TRANSPOSE, self.wts[1], W2o)
+        prep.add(CopyBatch.TRANSPOSE, self.wts[2], W3o)
+        prep.add(CopyBatch.TRANSPOSE, self.wts[0], w_ih_op[:, :self.U])
+        prep.add(CopyBatch.COPY, self.w_heads[:self.A], mu_w.detach())
+        prep.add(CopyBatch.COPY, self.w_heads[self.A:], v_w.detach())
+        prep.add(CopyBatch.COPY, self.b_heads[:self.A], mu_b.detach())
+        prep.add(CopyBatch.COPY, self.b_heads[self.A:], v_b.detach())
+        prep.flush(self.wtile)
+
+
 def column_sums(src, out=None, out1=None, n0=0, dup=False, batch=None):
     """Sum over dim 0 of a [R, ...] fp32 tensor with the hand-written kernel (deterministic; unlike ATen's
     multi-block reductions it needs no memset-cleared scratch, so it is safe inside a captured hipGraph).
@@ -824,7 +899,8 @@ class _Trunk(torch.autograd.Function):
       * only the MLP columns of the LSTM input gradient are computed (the observation columns need none),
       * both heads share one forward GEMM, one input-gradient GEMM and one weight-gradient GEMM.
     Argument order: obs_n, h0, c0, dones, T, concat, n_mlp, op_weights (None, or the bfloat16 copies of
-    W_1..W_L, w_ih, w_hh for the mixed-precision update), then the parameters
+    W_1..W_L, w_ih, w_hh for the mixed-precision update), head_bias_external, norm, loss_pack, operands (None, or the
+    optimiser's ``OperandSet``: route entry ``emitted``), then the parameters
     (W_1, b_1, ..., W_L, b_L, w_ih, w_hh, b_ih, b_hh, ln_gamma, ln_beta, ln_eps, mu_w, mu_b, v_w, v_b).
     Which kernels run is decided ONCE, at the top of ``forward``, from the arguments and the module's switches: the
     route ``ctx.route``.  Three of its entries can still be overturned further down -- ``ride`` by the moves the prepared
@@ -832,7 +908,7 @@ class _Trunk(torch.autograd.Function):
     then record what actually ran.  It also carries what forward hands to backward outside ``saved_tensors``."""
 
     @staticmethod
-    def forward(ctx, obs_n, h0, c0, dones, T, concat, n_mlp, op_weights, head_bias_external, norm, loss_pack, *params):
+    def forward(ctx, obs_n, h0, c0, dones, T, concat, n_mlp, op_weights, head_bias_external, norm, loss_pack, operands, *params):
         lib = _lib()
         mlp = [(params[2 * i], params[2 * i + 1]) for i in range(n_mlp)]
         w_ih, w_hh, b_ih, b_hh, ln_g, ln_b, ln_eps, mu_w, mu_b, v_w, v_b = params[2 * n_mlp:]
@@ -907,6 +983,10 @@ class _Trunk(torch.autograd.Function):
         # it starts from and the saved cell states are 16-bit (heads_loss and lp) and the MLP phase has 128-row workgroups
         r.bwd_phases = (BWD_PHASES and r.mlp3b and r.seq and T == 4 and r.lp and r.heads_loss and n % 128 == 0
                         and n >= 32768 and B % 32 == 0)
+        # the optimiser's prebuilt operand set (its Adam launch wrote them): where the preparation would ride in the MLP
+        # launch there is nothing left to prepare, and the MLP forward joins the trunk launch as its phase 0
+        r.emitted = (operands is not None and r.ride and r.phases and n % 128 == 0 and wpad == operands.wpad and U == operands.U
+                     and operands.covers(mlp[1][0], mlp[2][0], w_ih, w_hh, mu_w, mu_b, v_w, v_b))
         # filled in below by the launches that produce them (A2CAgent reads ``loss_fused``: did this node run the loss?)
         r.loss_fin = r.loss_fused = r.phases_done = None
 
@@ -928,7 +1008,17 @@ class _Trunk(torch.autograd.Function):
         bias = torch.empty(4 * H, device=dev, dtype=torch.float32)
         wcat, wts, w_hh_t = None, [None] * n_mlp, None
         wtile = w_hh_tiled = w1p = c_last = lstm_buffers = side = None
-        if mixed:
+        if r.emitted:
+            # nothing to prepare: the set's buffers, and the two LSTM biases as they are (the forward phase adds them)
+            obs_c = obs_n.contiguous()
+            x0 = xfull[:, U:width]
+            wtile, w_hh_tiled, wts = operands.wtile, operands.w_hh_tiled, list(operands.wts)
+            w_heads, b_heads = operands.w_heads, operands.b_heads
+            c_last = torch.empty((B, H), device=dev, dtype=torch.float32)
+            lstm_buffers = _lstm_state_buffers(xfull, w_hh_op, h0, c0, dones, T, True, prep=None, copy_c0=False,
+                                               c_dtype=lp_dtype(), mask_h0=False, h_once=r.h_once)
+            RIDES[0] += 1
+        elif mixed:
             # every operand derived from the parameters or the observations, in ONE launch: bf16 cast of the
             # observations (layer-1 operand and the LSTM operand's obs block), zero pad columns, [w_ih | 0 | w_hh],
             # transposed MLP weights for the backward kernels, merged head weights, b_ih + b_hh
@@ -996,7 +1086,9 @@ class _Trunk(torch.autograd.Function):
         if r.mlp3:
             # the whole MLP in one launch, activations carried in registers (vine_mlp3_elu_mfma)
             acts = [torch.empty((n, 256), device=dev, dtype=op), torch.empty((n, 128), device=dev, dtype=op)]
-            if r.ride:
+            if r.emitted:
+                pass               # (phase 0 of vine_trunk_phases below)
+            elif r.ride:
                 rc = lib.vine_mlp3_elu_mfma_prep(n, xfull.data_ptr() + 2 * U, xfull.stride(0), raw.data_ptr(), F_in,
                                                  norm[0].data_ptr(), norm[1].data_ptr(), float(norm[2]), 5.0,
                                                  Wop[0].data_ptr(), F_in, mlp[0][1].data_ptr(), 256, Wop[1].data_ptr(),
@@ -1011,7 +1103,7 @@ class _Trunk(torch.autograd.Function):
                     _check(rc, "vine_mlp3_elu_mfma_prep")
                     prep.clear()
                     RIDES[0] += 1
-            if not r.ride:
+            if not r.ride and not r.emitted:
                 _check(lib.vine_mlp3_elu_mfma(n, xfull.data_ptr() + 2 * U, xfull.stride(0),
                                               raw.data_ptr() if raw is not None else None, F_in,
                                               norm[0].data_ptr() if raw is not None else None,
@@ -1082,7 +1174,16 @@ class _Trunk(torch.autograd.Function):
             ta.a3, ta.a3_stride, ta.a2, ta.a1 = xcat.data_ptr(), xcat.stride(0), acts[1].data_ptr(), acts[0].data_ptr()
             ta.gz3, ta.gz2, ta.gz1 = gzs[2].data_ptr(), gzs[1].data_ptr(), gzs[0].data_ptr()
             ta.part3, ta.part2, ta.part1 = parts[2].data_ptr(), parts[1].data_ptr(), parts[0].data_ptr()
+            if r.emitted:
+                ta.bias, ta.bias2 = b_ih.data_ptr(), b_hh.data_ptr()
+                ta.mlp_raw, ta.mlp_F_in, ta.mlp_mean, ta.mlp_var = raw.data_ptr(), F_in, norm[0].data_ptr(), norm[1].data_ptr()
+                ta.mlp_eps, ta.mlp_clip = float(norm[2]), 5.0
+                ta.mlp_w1, ta.mlp_ldw1, ta.mlp_b1 = Wop[0].data_ptr(), F_in, mlp[0][1].data_ptr()
+                ta.mlp_w2, ta.mlp_ldw2, ta.mlp_b2 = Wop[1].data_ptr(), Wop[1].stride(0), mlp[1][1].data_ptr()
+                ta.mlp_w3, ta.mlp_ldw3, ta.mlp_b3 = Wop[2].data_ptr(), Wop[2].stride(0), mlp[2][1].data_ptr()
             rc = lib.vine_trunk_phases(C.byref(ta), st)
+            if r.emitted:      # (the routes below need the MLP's output and a prepared bias: no fallback from here)
+                _check(rc, "vine_trunk_phases (five phases)")
             if rc == -2:       # VINE_ERR_UNSUPPORTED: nothing has run -- the separate launches below
                 r.phases = False
             else:
@@ -1341,7 +1442,7 @@ class _Trunk(torch.autograd.Function):
             if batch.bypassed and amp is not None:
                 r.loss_pack["amp_covered"] = False     # (coverage is per delivery, not per batch)
             batch.flush(out)
-        return (None, None, None, None, None, None, None, None, None, None, None, *grads)
+        return (None, None, None, None, None, None, None, None, None, None, None, None, *grads)
 
 
 def linear_elu_mfma_ok(n, N, K):
@@ -1362,7 +1463,7 @@ def trunk_supported(obs_n, mlp_units, activation_is_elu, H, has_ln, T):
 
 
 def trunk(obs_n, h0, c0, dones, T, concat, mlp_params, lstm_params, ln, heads, op_weights=None,
-          head_bias_external=False, norm=None, loss_pack=None):
+          head_bias_external=False, norm=None, loss_pack=None, operands=None):
     """-> (heads [n, A+1] = [mu | value], hT, cT).  ``mlp_params`` = [(W, b), ...]; ``lstm_params`` =
     (w_ih, w_hh, b_ih, b_hh); ``ln`` = (gamma, beta, eps); ``heads`` = (mu_w, mu_b, value_w, value_b).
     ``op_weights`` = bfloat16 copies of (W_1, ..., W_L, w_ih, w_hh) selects the mixed-precision update: those GEMMs
@@ -1374,13 +1475,16 @@ def trunk(obs_n, h0, c0, dones, T, concat, mlp_params, lstm_params, ln, heads, o
     and the trunk normalises them itself (inside the one-launch MLP kernel where that applies).
     ``loss_pack`` (``ppo_loss_pack``): the PPO loss and its gradient are computed inside the node (one launch for
     LayerNorm + heads + loss + their backward); ``heads`` is still returned, the statistics land in the pack's tensors,
-    and ``torch.autograd.backward([heads], [anything of the same shape])`` runs the rest of the backward pass."""
+    and ``torch.autograd.backward([heads], [anything of the same shape])`` runs the rest of the backward pass.
+    ``operands`` (``OperandSet``, the optimiser's): the parameter-derived operands exist already -- the Adam launch wrote
+    them -- so where the preparation would otherwise ride in the MLP launch nothing is prepared, and the MLP forward runs
+    as phase 0 of the trunk launch."""
     if dones is not None:
         dones = dones.to(torch.uint8).contiguous()
     flat = [p for wb in mlp_params for p in wb]
     return _Trunk.apply(obs_n, h0.contiguous(), c0.contiguous(), dones, T, bool(concat), len(mlp_params),
                         tuple(op_weights) if op_weights is not None else None, bool(head_bias_external),
-                        tuple(norm) if norm is not None else None, loss_pack, *flat,
+                        tuple(norm) if norm is not None else None, loss_pack, operands, *flat,
                         *lstm_params, ln[0], ln[1], float(ln[2]), *heads)
 
 

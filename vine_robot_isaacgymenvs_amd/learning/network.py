@@ -111,7 +111,8 @@ class A2CNetwork(nn.Module):
         z = torch.zeros((1, batch, self.rnn_units), device=device)
         return (z, z.clone())
 
-    def forward_heads(self, obs, states, seq_length, dones, head_bias_external=False, norm=None, loss_pack=None):
+    def forward_heads(self, obs, states, seq_length, dones, head_bias_external=False, norm=None, loss_pack=None,
+                      operands=None):
         """Training forward on the MI355X as one fused autograd node (learning/fused.py:_Trunk):
         -> (heads [n, A+1] = [mu | value], states).  Caller checks ``fused.trunk_supported`` first."""
         r = self.rnn.rnn
@@ -125,7 +126,7 @@ class A2CNetwork(nn.Module):
                                   (self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps),
                                   (self.mu.weight, self.mu.bias, self.value.weight, self.value.bias),
                                   op_weights=op_weights, head_bias_external=head_bias_external, norm=norm,
-                                  loss_pack=loss_pack)
+                                  loss_pack=loss_pack, operands=operands)
         return heads, (h.unsqueeze(0), c.unsqueeze(0))
 
     def trunk_supported(self, obs, seq_length):
@@ -201,7 +202,7 @@ class ModelA2CContinuousLogStd(nn.Module):
         if net.trunk_supported(obs, T):
             heads, states = net.forward_heads(obs, input_dict["rnn_states"], T, input_dict.get("dones", None),
                                               input_dict.get("head_bias_external", False), norm=norm,
-                                              loss_pack=input_dict.get("loss_pack"))
+                                              loss_pack=input_dict.get("loss_pack"), operands=input_dict.get("operands"))
             A = net.mu.weight.shape[0]
             return heads[:, :A], heads[:, A:], net.sigma, states, heads
         mu, _logstd, value, states = net(obs, input_dict["rnn_states"], T, input_dict.get("dones", None))
