@@ -1388,11 +1388,13 @@ def test_fused_update_equals_stock_update():
     """One optimiser step of the agent through the fused path and through the stock composition, from the same
     weights and minibatch: same loss statistics, same updated parameters (to fp32 reduction-order noise).  Adam's first
     step moves every parameter by about lr * sign(g) whatever the gradient's size, so the gradient blocks of the first
-    optimiser step are compared as well, tensor by tensor, before Adam consumes them."""
+    optimiser step are compared as well, tensor by tensor, before Adam consumes them.  Both runs must have moved (by more
+    than one learning rate somewhere) and by the same: ||dp_fused - dp_stock|| / ||dp_stock|| is 1 for an Adam that did
+    nothing and 2 for a wrong sign; measured on an MI355X: below 5e-5 (|p - p0|.max = 7.2e-4 in both runs)."""
     from vine_robot_isaacgymenvs_amd import load_config
     from vine_robot_isaacgymenvs_amd.learning.a2c_continuous import A2CAgent
     from vine_robot_isaacgymenvs_amd.tasks import isaacgym_task_map
-    outs, firsts = [], []
+    outs, firsts, starts = [], [], []
     for use_fused in (True, False):
         cfg = load_config(overrides=["num_envs=512", "minibatch_size=2048"])
         cfg["task"]["seed"] = 42
@@ -1403,6 +1405,8 @@ def test_fused_update_equals_stock_update():
                                 mini_epochs=1, mixed_precision=False)
         torch.manual_seed(0)
         agent = A2CAgent("t", params, vec_env=env)
+        starts.append(torch.cat([p.detach().flatten() for p in agent.model.parameters()]).clone())
+        lr0 = float(agent.lr)
         agent.init_tensors()
         agent.fused_rollout = False          # same (stock, torch.randn) rollout for both; only the update differs
         agent.game_rewards.mean, agent.game_rewards.current_size = torch.zeros(1, device="cuda:0"), torch.zeros((), device="cuda:0")
@@ -1426,6 +1430,15 @@ def test_fused_update_equals_stock_update():
     for k in s1:
         assert abs(s1[k] - s2[k]) < 2e-3 * (1 + abs(s2[k])), (k, s1[k], s2[k])
     assert float((p1 - p2).abs().max()) < 2e-3      # 4 Adam steps of 3e-4.. lr: identical sign pattern of the updates
+    # ... which an Adam that did nothing would meet as well (the parameters move by about 1.2e-3 in all): the movement
+    p0 = starts[0]
+    assert torch.equal(p0, starts[1])
+    m1, m2 = (p1 - p0).double(), (p2 - p0).double()
+    assert float(m1.abs().max()) > lr0 and float(m2.abs().max()) > lr0, (float(m1.abs().max()), float(m2.abs().max()), lr0)
+    moved = float((m1 - m2).norm() / m2.norm())         # a dead Adam gives 1, a wrong sign 2
+    print("\n[fused update vs stock update] |p - p0|.max = %.3e fused, %.3e stock; ||dp_fused - dp_stock|| / ||dp_stock|| = %.2e"
+          % (float(m1.abs().max()), float(m2.abs().max()), moved), flush=True)
+    assert moved < 0.5, moved
     g1, g2 = firsts
     assert set(g1) == set(g2) and len(g1) == len(list(agent.model.parameters()))
     for k in g2:

@@ -70,18 +70,20 @@ class _Spaces:
         self.action_space = Box(-np.ones(actions), np.ones(actions))
 
 
-def _agent(B, width, mixed, clip_value, entropy_coef):
+def _agent(B, width, mixed, clip_value, entropy_coef, minibatches=1, **conf):
+    """An agent whose minibatch is ``B`` sequences of 4 steps (``minibatches`` of them per mini-epoch; ``conf``: further
+    entries of the training configuration)."""
     from vine_robot_isaacgymenvs_amd import load_config
     from vine_robot_isaacgymenvs_amd.learning.a2c_continuous import A2CAgent
     n = 4 * B
-    cfg = load_config(overrides=["num_envs=%d" % (n // 16), "minibatch_size=%d" % n])
+    cfg = load_config(overrides=["num_envs=%d" % (minibatches * n // 16), "minibatch_size=%d" % n])
     params = cfg["train"]["params"]
     params["config"].update(write_files=False, print_stats=False, use_graphs=False, mixed_precision=mixed,
-                            clip_value=clip_value, entropy_coef=entropy_coef)
+                            clip_value=clip_value, entropy_coef=entropy_coef, **conf)
     torch.manual_seed(0)
     agent = A2CAgent("t", params, vec_env=_Spaces(width))
     assert agent.fused_mixed == mixed and agent.use_fused and not agent.mixed_precision and agent.seq_len == 4
-    assert agent.minibatch_size == n and agent.obs_shape == (width,)
+    assert agent.minibatch_size == n and agent.obs_shape == (width,) and agent.num_minibatches == minibatches
     return agent
 
 

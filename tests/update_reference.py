@@ -7,7 +7,11 @@ state zeroed wherever ``dones`` is set, LayerNorm, the two heads) and the loss i
 ``critic_loss`` / ``bound_loss`` (pinned to the reference text by golden F8) combined exactly as ``calc_gradients``
 combines them.  With ``dtype=torch.float32`` and ``autocast=torch.float16`` the same function is the reference's
 ``mixed_precision: True`` arithmetic (torch autocast, loss multiplied by a GradScaler's ``loss_scale`` before the
-backward pass and the gradients divided by it after), the yardstick of what 16-bit operands cost."""
+backward pass and the gradients divided by it after), the yardstick of what 16-bit operands cost.
+
+The step half, ``reference_optimizer_step``: what turns that gradient block into the next step's weights (GradScaler's
+unscale / skip / back-off / growth, the max-norm clip, Adam, rl_games' adaptive learning-rate schedule), written out in
+float64 from a snapshot of the optimiser's state; nothing of it comes from ``FlatAdam`` either."""
 import copy
 import math
 
@@ -31,7 +35,8 @@ def _forward(model, obs, h0, c0, dones, T):
     x0 = obs
     if model.normalize_input:
         rms = model.running_mean_std
-        rms.update(obs)                 # training mode: the statistics move first, the batch is normalised with them
+        if rms.training:                # training mode: the statistics move first, the batch is normalised with them
+            rms.update(obs)
         mean, var = rms.running_mean.to(obs.dtype), rms.running_var.to(obs.dtype)
         x0 = ((obs - mean) / torch.sqrt(var + rms.epsilon)).clamp(-5.0, 5.0)
     x = x0
@@ -58,15 +63,9 @@ def _forward(model, obs, h0, c0, dones, T):
     return F.linear(y, net.mu.weight, net.mu.bias), F.linear(y, net.value.weight, net.value.bias), net.sigma
 
 
-def reference_step(model, mb, seq_len, e_clip, clip_value, critic_coef, entropy_coef, bounds_loss_coef,
-                   dtype=torch.float64, device=None, autocast=None, loss_scale=1.0):
-    """One optimiser step's gradient of ``model`` on minibatch ``mb`` (the keys ``A2CAgent.get_minibatch`` returns).
-    ``model`` and ``mb`` are left untouched: a deep copy in training mode, parameters converted to ``dtype``, runs on
-    ``device`` (default: the minibatch's); the normaliser statistics stay float64 as in the product.
-    -> dict: ``grads`` {parameter name: unscaled gradient}, ``stats`` {a_loss, c_loss, entropy, b_loss, kl}, ``mu`` /
-    ``sigma`` (the new policy of every sample: what the update writes back into the dataset), ``running_mean`` /
-    ``running_var`` / ``count`` (the observation normaliser after the step)."""
-    device = torch.device(device) if device is not None else mb["obs"].device
+def _copy_of(model, device, keep_mode=False):
+    """A deep copy of ``model`` on ``device`` in training mode; ``keep_mode``: the observation normaliser keeps the
+    training flag the original module has now (the agent puts it into eval after the first mini-epoch)."""
     net = model.a2c_network
     lookup, net.op_weight_lookup = net.op_weight_lookup, None         # (a bound method of the optimiser: not copied)
     try:
@@ -74,6 +73,22 @@ def reference_step(model, mb, seq_len, e_clip, clip_value, critic_coef, entropy_
     finally:
         net.op_weight_lookup = lookup
     m = m.to(device).train()
+    if keep_mode and m.normalize_input:
+        m.running_mean_std.train(model.running_mean_std.training)
+    return m
+
+
+def reference_step(model, mb, seq_len, e_clip, clip_value, critic_coef, entropy_coef, bounds_loss_coef,
+                   dtype=torch.float64, device=None, autocast=None, loss_scale=1.0, keep_mode=False):
+    """One optimiser step's gradient of ``model`` on minibatch ``mb`` (the keys ``A2CAgent.get_minibatch`` returns).
+    ``model`` and ``mb`` are left untouched: a deep copy in training mode, parameters converted to ``dtype``, runs on
+    ``device`` (default: the minibatch's); the normaliser statistics stay float64 as in the product.  ``keep_mode``: the
+    observation normaliser keeps the module's own training flag (in eval its statistics do not move) instead of training.
+    -> dict: ``grads`` {parameter name: unscaled gradient}, ``stats`` {a_loss, c_loss, entropy, b_loss, kl}, ``mu`` /
+    ``sigma`` (the new policy of every sample: what the update writes back into the dataset), ``running_mean`` /
+    ``running_var`` / ``count`` (the observation normaliser after the step)."""
+    device = torch.device(device) if device is not None else mb["obs"].device
+    m = _copy_of(model, device, keep_mode)
     for p in m.parameters():
         p.grad = None
         p.data = p.data.to(dtype)
@@ -108,6 +123,86 @@ def reference_step(model, mb, seq_len, e_clip, clip_value, critic_coef, entropy_
     if m.normalize_input:
         rms = m.running_mean_std
         out.update(running_mean=rms.running_mean, running_var=rms.running_var, count=rms.count)
+    return out
+
+
+WRONG_STEPS = ("bias correction with the old step", "clip left out", "unscaled by the new scale",
+               "learning rate after the schedule", "eps inside the root")
+
+
+def adaptive_lr(lr, kl, kl_scale, thr, min_lr, max_lr):
+    """rl_games' AdaptiveScheduler on a float32 learning rate (the product keeps it in float32, and so does this: one
+    correctly rounded division or product and a clamp): / 1.5 where the KL is above 2 thr, x 1.5 where it is below
+    thr / 2.  -> the new learning rate, a Python float that holds a float32 value."""
+    f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)      # noqa: E731
+    lr, k = f32(lr), f32(kl) * f32(kl_scale)
+    new = lr
+    if bool(k > f32(2.0) * f32(thr)):
+        new = torch.maximum(lr / f32(1.5), f32(min_lr))
+    if bool(k < f32(0.5) * f32(thr)):
+        new = torch.minimum(lr * f32(1.5), f32(max_lr))
+    return float(new)
+
+
+def reference_optimizer_step(state, grads_scaled, found_inf=False, grad_scale=1.0, clip=None, betas=(0.9, 0.999), eps=1e-8,
+                             kl=None, schedule=None, wrong=None):
+    """The step half of one optimiser step in float64: ``GradScaler.unscale_`` + ``clip_grad_norm_`` +
+    ``scaler.step(Adam)`` + ``scaler.update()`` + rl_games' AdaptiveScheduler, written out.
+
+    ``state``: {``params``, ``exp_avg``, ``exp_avg_sq`` (flat tensors), ``step``, ``lr``, ``amp_state``: (loss scale, growth
+    tracker, growth interval) or None without loss scaling}; it is not modified.  ``grads_scaled``: the flat gradient block
+    as the device holds it, still multiplied by the loss scale; ``grad_scale``: a further factor on it (1 / world size).
+    ``found_inf``: the overflow flag as raised so far.  ``clip``: max-norm or None.  ``kl`` with ``schedule`` =
+    (kl_scale, thr, min_lr, max_lr): the schedule that acts on the learning rate AFTER the step used the old one.
+
+    The block is unscaled by the pre-step scale.  With loss scaling, a non-finite block or a raised flag skips the step:
+    nothing moves, the scale is halved and the tracker goes to 0.  Otherwise norm = ||block||, coef = min(1, clip /
+    (norm + 1e-6)), Adam with the bias corrections of the incremented step, the tracker gains 1 and the scale doubles
+    when it reaches the growth interval.
+    -> {``params``, ``exp_avg``, ``exp_avg_sq``, ``step``, ``lr``, ``amp_state``, ``norm``, ``coef``, ``skipped``}.
+
+    ``wrong`` (one of ``WRONG_STEPS``): the same step with one subtle mistake, for negative controls."""
+    assert wrong is None or wrong in WRONG_STEPS, wrong
+    f64 = lambda t: t.detach().double().cpu().reshape(-1)      # noqa: E731
+    p, m, v = f64(state["params"]), f64(state["exp_avg"]), f64(state["exp_avg_sq"])
+    step, lr, amp = int(state["step"]), float(state["lr"]), state["amp_state"]
+    b1, b2 = betas
+    scale = 1.0 if amp is None else float(amp[0])
+    new_amp = None
+    if amp is not None:                      # what scaler.update() will leave, decided by the flag below
+        tracker, interval = int(amp[1]), int(amp[2])
+    g = f64(grads_scaled) * float(grad_scale) / scale
+    skipped = amp is not None and (bool(found_inf) or not bool(torch.isfinite(g).all()))
+    norm = float(torch.linalg.vector_norm(g))
+    coef = 1.0 if clip is None else min(1.0, float(clip) / (norm + 1e-6))
+    if amp is not None:
+        if skipped:
+            new_amp = (scale * 0.5, 0, interval)
+        elif tracker + 1 >= interval:
+            new_amp = (scale * 2.0, 0, interval)
+        else:
+            new_amp = (scale, tracker + 1, interval)
+    new_lr = lr if (kl is None or schedule is None) else adaptive_lr(lr, float(kl), *schedule)
+    out = {"norm": norm, "coef": coef, "skipped": skipped, "amp_state": new_amp, "lr": new_lr}
+    if skipped:
+        out.update(params=p, exp_avg=m, exp_avg_sq=v, step=step)
+        return out
+    if wrong == "unscaled by the new scale":
+        g = g * scale / float(new_amp[0])
+    if wrong != "clip left out":
+        g = g * coef
+    if wrong == "learning rate after the schedule":
+        lr = new_lr
+    t = step + 1
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    tb = step if wrong == "bias correction with the old step" else t
+    bc1, bc2 = 1.0 - b1 ** tb, 1.0 - b2 ** tb
+    if wrong == "eps inside the root":
+        denom = torch.sqrt(v / bc2 + eps)
+    else:
+        denom = torch.sqrt(v) / math.sqrt(bc2) + eps
+    out.update(params=p - (lr / bc1) * m / denom, exp_avg=m, exp_avg_sq=v, step=t)
     return out
 
 
@@ -162,12 +257,7 @@ def synthetic_minibatch(model, B, T, seed=0, device="cpu", e_clip=0.2):
     d[(kind >= 4) & (kind < 8)] = False     # 40 %: no done in the sequence
     d[kind >= 8, 0] = False                 # 20 %: dones at random later steps
     dones = d.reshape(n).to(torch.uint8)
-    lookup, net.op_weight_lookup = net.op_weight_lookup, None
-    try:
-        m = copy.deepcopy(model)
-    finally:
-        net.op_weight_lookup = lookup
-    m = m.to(device).double().train()
+    m = _copy_of(model, device).double()
     with torch.no_grad():                    # (float64 on the device: the CPU would be slow at 10^5 rows)
         mu, value, logstd = _forward(m, obs.to(device).double(), h0[0].to(device).double(), c0[0].to(device).double(),
                                      dones.to(device), T)
@@ -175,42 +265,62 @@ def synthetic_minibatch(model, B, T, seed=0, device="cpu", e_clip=0.2):
         sigma = torch.exp(logstd).expand_as(mu)
         actions = (mu + sigma * torch.randn(n, A, generator=g).double()).float().double()
         nlp = m.neglogp(actions, mu, sigma, logstd.expand_as(mu))
-    # The clipped losses' gradients jump where a sample changes branch.  A 16-bit forward pass moves mu and the value by
-    # ~1e-3, so a sample within that distance of a branch edge can land on either side: a handful of such samples
-    # dominate the error of every gradient tensor and make it a lottery.  Keep every sample `margin` away from the edges.
-    margin = 0.02
-    log_ratio = _away(torch.randn(n, generator=g).double() * 0.2, (math.log(1 - e_clip), math.log(1 + e_clip)), margin)
-    dv = value - (value + torch.randn(n, 1, generator=g).double() * 0.3)                 # value - old_values
-    dv = torch.sign(dv) * _away(dv.abs(), (e_clip,), margin)
-    old_values = value - dv
-    returns = value + torch.randn(n, 1, generator=g).double()
-    clipped = dv.abs() > e_clip                   # critic: max((v - r)^2, (vc - r)^2) switches at r = (v + vc) / 2
-    mid = (value + old_values + torch.sign(dv) * e_clip) / 2
-    returns = torch.where(clipped, mid + _away(returns - mid, (0.0,), margin), returns)
+    # float64 until keep_margins has moved the samples near an edge (it works in the tensors' own precision)
     mb = {"obs": obs, "dones": dones, "rnn_states": [h0, c0],
           "actions": actions.float(),
-          "old_logp_actions": (nlp + log_ratio).float(),
+          "old_logp_actions": nlp + torch.randn(n, generator=g).double() * 0.2,
+          "old_values": value + torch.randn(n, 1, generator=g).double() * 0.3,
+          "returns": value + torch.randn(n, 1, generator=g).double(),
           "advantages": torch.randn(n, generator=g),
-          "old_values": old_values.float(),
-          "returns": returns.float(),
           "mu": (mu + torch.randn(n, A, generator=g).double() * 0.1).float(),
           "sigma": (sigma * torch.exp(torch.randn(n, A, generator=g).double() * 0.1)).float()}
+    keep_margins(model, mb, T, e_clip, 0.02, device=device)
+    for k in ("old_logp_actions", "old_values", "returns"):
+        mb[k] = mb[k].float()
     mb = {k: ([s.to(device).contiguous() for s in v] if isinstance(v, list) else v.to(device).contiguous())
           for k, v in mb.items()}
     mb["range"] = (0, n)
     return mb
 
 
+def keep_margins(model, mb, T, e_clip=0.2, margin=0.02, device=None, keep_mode=False):
+    """Rewrite ``old_logp_actions``, ``old_values`` and ``returns`` of minibatch ``mb`` IN PLACE so that, for the policy
+    ``model`` holds now (float64, after the step's running-statistics update; ``keep_mode``: only if the module's
+    normaliser is in training mode, see ``reference_step``), every sample is at least ``margin`` away from the edges
+    between the loss's branches.  The forward pass runs on ``device`` (default: the minibatch's).
+
+    The clipped losses' gradients jump where a sample changes branch.  A 16-bit forward pass moves mu and the value by
+    ~1e-3, so a sample within that distance of a branch edge can land on either side: a handful of such samples dominate
+    the error of every gradient tensor and make it a lottery.  A sample closer than ``margin`` to an edge is moved to
+    ``2 margin`` from it on the same side; the others keep their values.  Edges: the probability ratio at 1 +- e_clip,
+    |value - old_values| at e_clip, and for the samples beyond it the critic's max((v - r)^2, (vc - r)^2), which switches
+    at r = (v + vc) / 2."""
+    device = torch.device(device) if device is not None else mb["obs"].device
+    m = _copy_of(model, device, keep_mode).double()
+    f64 = lambda t: t.detach().to(device).double()      # noqa: E731
+    with torch.no_grad():
+        mu, value, logstd = _forward(m, f64(mb["obs"]), f64(mb["rnn_states"][0][0]), f64(mb["rnn_states"][1][0]),
+                                     mb["dones"].to(device), T)
+        mu, value, logstd = mu.cpu(), value.cpu(), logstd.cpu()
+        sigma = torch.exp(logstd).expand_as(mu)
+        nlp = m.neglogp(mb["actions"].detach().cpu().double(), mu, sigma, logstd.expand_as(mu))
+        log_ratio = _away(mb["old_logp_actions"].detach().cpu().double() - nlp,
+                          (math.log(1 - e_clip), math.log(1 + e_clip)), margin)
+        dv = value - mb["old_values"].detach().cpu().double().reshape(value.shape)
+        dv = torch.sign(dv) * _away(dv.abs(), (e_clip,), margin)
+        old_values = value - dv
+        returns = mb["returns"].detach().cpu().double().reshape(value.shape)
+        clipped = dv.abs() > e_clip
+        mid = (value + old_values + torch.sign(dv) * e_clip) / 2
+        returns = torch.where(clipped, mid + _away(returns - mid, (0.0,), margin), returns)
+        for k, v in (("old_logp_actions", nlp + log_ratio), ("old_values", old_values), ("returns", returns)):
+            mb[k].copy_(v.reshape(mb[k].shape).to(mb[k].dtype))
+
+
 def loss_branch_shares(model, mb, T, e_clip=0.2):
     """(share of ratios outside the clip range, share of value predictions outside it, share of |mu| > 1.1) of the
     minibatch's policy after the running-statistics update: what ``synthetic_minibatch`` promises."""
-    net = model.a2c_network
-    lookup, net.op_weight_lookup = net.op_weight_lookup, None
-    try:
-        m = copy.deepcopy(model)
-    finally:
-        net.op_weight_lookup = lookup
-    m = m.to(mb["obs"].device).double().train()
+    m = _copy_of(model, mb["obs"].device).double()
     with torch.no_grad():
         mu, value, logstd = _forward(m, mb["obs"].double(), mb["rnn_states"][0][0].double(),
                                      mb["rnn_states"][1][0].double(), mb["dones"], T)
