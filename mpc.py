@@ -8,16 +8,21 @@
 
   python mpc.py plants=64 'model_params={DAMPING: [0.005, 0.1]}'                     # the nominal plant, such models
 
+  python mpc.py plants=64 steps=2000 'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1]}' \\
+      'adapt={params: {DAMPING: [0.005, 0.1], FPAM_K: [0.7, 1.3]}, window: 8, every: 8}'   # the model follows each plant
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
-spec, drawn once per plant and repeated over the plant's samples) and ``out`` (directory of the episode log's .npz; default
+spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
+DESIGN.md section 25: ``params`` maps names of the ``ENV_PARAMS`` table to the range ``[lo, hi]`` the belief lives in; ``window``,
+``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``) and ``out`` (directory of the episode log's .npz; default
 ``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT,
 in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
-       "model_params": None, "out": "runs/mpc"}
+       "model_params": None, "adapt": None, "out": "runs/mpc"}
 
 
 def main(argv=None):
@@ -31,7 +36,7 @@ def main(argv=None):
             own[key] = val if key == "out" else parse_scalar(val)
         else:
             overrides.append(arg)
-    for key in ("cost", "model_params"):
+    for key in ("cost", "model_params", "adapt"):
         if own[key] is not None and not hasattr(own[key], "keys"):
             raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -43,7 +48,8 @@ def main(argv=None):
         task_cfg["env"]["EPISODE_LOG_DIR"] = own["out"]
     return mpc.play(task_cfg, plants=own["plants"], samples=own["samples"], horizon=own["horizon"], lam=own["lambda"],
                     sigma=own["sigma"], steps=int(own["steps"]), cost=own["cost"], model_params=own["model_params"],
-                    seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"))
+                    seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
+                    adapt=own["adapt"])
 
 
 if __name__ == "__main__":

@@ -1,11 +1,17 @@
 #!/usr/bin/env python3
 """MPC timings on one MI355X (profiles/mpc/timings.txt):  python scripts/ubench/mpc_bench.py [plants] [samples] [horizon] [free]
+                                   (profiles/mpc_adapt/timings.txt):  ... mpc_bench.py --adapt [plants] [samples] [horizon] [free]
 
 Per-launch durations from replayed hipGraphs of `horizon` launches each, device events around the replays: the model's step
 alone, the step with the scoring node behind it (the difference is the node), the fork and the update; then the whole
 control step (fork, horizon x (step + node), update, plant step) as the Controller captures it, in control steps per second
 (host clock around replays that end in a synchronise), beside `horizon` bare model steps.  `free`: free space (the
-four-lane step kernel) instead of the task's pipe."""
+four-lane step kernel) instead of the task's pipe.
+
+`--adapt`: the five launches of include/vine_mpc_adapt.h instead (W = E = 8, DAMPING adapted), each from a replayed graph of
+`horizon` launches, and one whole cycle of the AdaptiveController beside E control steps of a Controller without a table (what
+the commit before the feature runs) and of a Controller whose model has a table bound (the one-lane step kernel: the table's
+own price, which adaptation pays but does not cause)."""
 import os
 import sys
 import time
@@ -17,6 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from vine_robot_isaacgymenvs_amd import load_task_config  # noqa: E402
 from vine_robot_isaacgymenvs_amd.utils import mpc  # noqa: E402
 
+ADAPT = "--adapt" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--adapt"]
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 H = int(sys.argv[3]) if len(sys.argv) > 3 else 20
@@ -52,7 +60,75 @@ def per_launch_us(g, before=None):
     return np.median(out), min(out), max(out)
 
 
+def best_run_us(c, n, rounds=5):
+    """Microseconds per control step of c.run(n), best of `rounds` (host clock around runs that end in a synchronise)."""
+    best = 1e9
+    for _ in range(rounds):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        c.run(n)
+        torch.cuda.synchronize()
+        best = min(best, time.perf_counter() - t0)
+    return best / n * 1e6
+
+
+def adapt_main():
+    from vine_robot_isaacgymenvs_amd.utils import mpc_adapt
+    W = E = 8
+    spec = {"params": {"DAMPING": [0.005, 0.1]}, "window": W, "every": E}
+    cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % M])
+    cfg["seed"] = 42
+    if FREE:
+        cfg["env"].update(CREATE_PIPE=False, CREATE_SHELF=False)
+    plant = mpc.make_task(cfg)
+    bare_model = mpc.make_task(mpc.model_config(cfg, M, K))
+    tcfg = mpc.model_config(cfg, M, K)
+    tcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}
+    model = mpc.make_task(tcfg)
+    ctl = mpc_adapt.AdaptiveController(plant, model, K, spec, H)
+    print("%s, %d plants x %d samples = %d model envs, horizon %d, window %d, every %d; model step kernel %s (no table: %s)" % (
+        torch.cuda.get_device_name(0), M, K, M * K, H, W, E, model.step_kernel_name, bare_model.step_kernel_name))
+    plant.step_into(ctl.plant_actions, ctl.plant_obs)
+    ctl.run(2 * E)                                       # (two captured cycles: every lazy initialisation done)
+    ctl.cycle_graph = None
+    launches = (("anchor", ctl.anchor, None), ("trace node", ctl.trace, None), ("pin", ctl.pin, None),
+                ("score node in a window", ctl.score, "window"), ("score node outside one", ctl.score, None),
+                ("estimate", ctl.estimate, None))
+    for name, fn, mode in launches:
+        g = graph_of(fn)
+        if mode == "window":                             # every replay of H = 20 nodes must see k = 1 .. W: step the model too
+            def body():
+                model.step_into(ctl.actions, ctl.model_obs)
+                ctl.score()
+            steps = graph_of(lambda: model.step_into(ctl.actions, ctl.model_obs))
+            s = per_launch_us(steps, ctl.pin)
+            b = per_launch_us(graph_of(body), ctl.pin)
+            print("%-26s median %.2f us (step + node %.2f - step alone %.2f; k <= W in %d of %d launches of a replay)" % (
+                name, b[0] - s[0], b[0], s[0], min(W, H), H))
+            continue
+        print("%-26s median %.2f us per launch (min %.2f, max %.2f) over %d replays of %d" % (name, *per_launch_us(g), REPLAYS, H))
+    n = 10 * E
+    rows = []
+    for name, c in (("Controller, model without a table", mpc.Controller(plant, bare_model, K, H, graph_steps=E)),
+                    ("Controller, model with a table", mpc.Controller(plant, model, K, H, graph_steps=E)),
+                    ("AdaptiveController", mpc_adapt.AdaptiveController(plant, model, K, spec, H))):
+        c.run(2 * E)
+        us = best_run_us(c, n)
+        rows.append(us)
+        print("%-36s %d control steps (hipGraph of %d): %.1f us per control step, %.1f us per %d control steps" % (
+            name, n, E, us, us * E, E))
+    print("one cycle against E bare control steps: +%.1f us (+%.2f%%) over the model with a table, +%.1f us (+%.2f%%) over the "
+          "model without one; W / (E * H) = %.2f%% of the model steps are the candidates' replay" % (
+              (rows[2] - rows[1]) * E, (rows[2] / rows[1] - 1) * 100, (rows[2] - rows[0]) * E, (rows[2] / rows[0] - 1) * 100,
+              100.0 * W / (E * H)))
+    model.close()
+    bare_model.close()
+    plant.close()
+
+
 def main():
+    if ADAPT:
+        return adapt_main()
     cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % M])
     cfg["seed"] = 42
     if FREE:

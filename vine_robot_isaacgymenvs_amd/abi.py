@@ -794,6 +794,62 @@ def declare_mpc(lib):
     return lib
 
 
+# ---- include/vine_mpc_adapt.h (product library only)
+MPC_ADAPT_ABI_VERSION = 1
+MPC_ADAPT_MAX_WINDOW = 32
+MPC_ADAPT_MAX_DIMS = 8
+MPC_ADAPT_FIELDS = 12
+MPC_ADAPT_BASE_ROWS = 20
+MPC_ADAPT_RNG = 9
+
+
+class VineMpcAdaptDim(C.Structure):
+    _fields_ = [
+        ("first_row", C.c_int32),
+        ("num_rows", C.c_int32),
+        ("lo", C.c_double),
+        ("hi", C.c_double),
+        ("std_floor", C.c_double),
+    ]
+
+
+class VineMpcAdaptConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_plants", C.c_int32),
+        ("samples", C.c_int32),
+        ("window", C.c_int32),
+        ("every", C.c_int32),
+        ("num_dims", C.c_int32),
+        ("min_steps", C.c_int32),
+        ("forget_on_reset", C.c_int32),
+        ("temperature", C.c_double),
+        ("rate", C.c_double),
+        ("seed", C.c_uint64),
+        ("weights", C.c_float * MPC_ADAPT_FIELDS),
+        ("base_rows", C.c_float * MPC_ADAPT_BASE_ROWS),
+        ("dims", VineMpcAdaptDim * MPC_ADAPT_MAX_DIMS),
+    ]
+
+
+MPC_ADAPT_PROTOTYPES = {
+    "vine_mpc_adapt_config_default": (C.c_int, [_P(VineMpcAdaptConfig)]),
+    "vine_mpc_adapt_config_size": (C.c_int, []),
+    "vine_mpc_adapt_anchor": (C.c_int, [_H, _P(VineMpcAdaptConfig)] + [_VP] * 11),
+    "vine_mpc_adapt_trace": (C.c_int, [_H, _P(VineMpcAdaptConfig)] + [_VP] * 11),
+    "vine_mpc_adapt_pin": (C.c_int, [_H, _P(VineMpcAdaptConfig)] + [_VP] * 15),
+    "vine_mpc_adapt_scheduled": (C.c_int, [_H, _P(VineMpcAdaptConfig)] + [_VP] * 9),
+    "vine_mpc_adapt_estimate": (C.c_int, [_H, _P(VineMpcAdaptConfig)] + [_VP] * 10),
+}
+
+
+def declare_mpc_adapt(lib):
+    _attach(lib, MPC_ADAPT_PROTOTYPES)
+    if lib.vine_mpc_adapt_config_size() != C.sizeof(VineMpcAdaptConfig):
+        raise RuntimeError("VineMpcAdaptConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -807,6 +863,7 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc):
+                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc,
+                        declare_mpc_adapt):
         declare_one(lib)
     return lib

@@ -28,6 +28,8 @@
 #pragma clang fp contract(fast)
 #include "vine_task_shared.h"
 #pragma clang fp contract(off)
+// the column copy, the ring rebuild and the reduction's wave step: stated once for this unit and vine_mpc_adapt.hip
+#include "vine_mpc_shared.h"
 
 namespace {
 
@@ -35,12 +37,6 @@ constexpr int THREADS = VINE_MPC_THREADS;
 constexpr int WAVES = THREADS / 64;
 constexpr int HMAX = VINE_MPC_MAX_HORIZON;
 static_assert(THREADS == 256 && 2 * HMAX <= THREADS, "one lane of the update per nominal entry");
-static_assert(VF_PIPE_Y == VF_FIFO0 + 2 * VINE_MAX_DELAY, "the ring is the fields VF_FIFO0 .. VF_PIPE_Y - 1");
-
-// What task_new_command reads (vine_task_shared.h).
-struct CommandParams {
-    float clip_act, act_noise, rail_scale, fpam_span, fpam_min;
-};
 
 struct MpcParams {
     int n, m, K, H, glog, delay;           // model envs, plants, samples, horizon; the MODEL handle's counter shift and delay
@@ -64,9 +60,7 @@ __device__ __forceinline__ float2 mpc_action(const MpcParams& S, unsigned e, boo
             unsigned w[4];
             philox4x32_10(e, (unsigned)t, VINE_MPC_RNG_NOISE | ((unsigned)(t >> 32) << 8), (unsigned)(2 * k + a), S.seed_lo,
                           S.seed_hi, w);
-            const int sum = (int)((w[0] & 0xffffu) + (w[0] >> 16) + (w[1] & 0xffffu) + (w[1] >> 16) + (w[2] & 0xffffu) +
-                                  (w[2] >> 16) + (w[3] & 0xffffu) + (w[3] >> 16));
-            z[a] = (float)(2 * sum - 524280);
+            z[a] = (float)mpc_deviate_int(w);
         }
     }
     const float zc0 = z[0] * S.c[0], zc1 = z[1] * S.c[1];
@@ -90,8 +84,7 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_fork_kernel(const MpcParams 
     if (e == 0) window[0] = (long long)c;
     if (e >= n) return;
     const int p = e / S.K, j = e - p * S.K;
-    for (int f = 0; f < VF_FIFO0; ++f) st[(size_t)f * n + e] = pst[(size_t)f * m + p];
-    for (int f = VF_PIPE_Y; f < VF_COUNT; ++f) st[(size_t)f * n + e] = pst[(size_t)f * m + p];
+    MPC_COPY_COLUMN(pst, m, p, st, n, e);
     // the delay ring: this sample's delay and action -> command constants (the step's env_params_of, vine_hip.hip)
     CommandParams P = S.cmd;
     int d = S.delay;
@@ -99,17 +92,7 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_fork_kernel(const MpcParams 
         P.rail_scale = env_params[(size_t)VP_RAIL_VELOCITY_SCALE * n + e];
         d = min(max((int)env_params[(size_t)VP_ACTION_DELAY * n + e], 0), VINE_MAX_DELAY);
     }
-    if (d > 0) {
-        const int cm = (int)(c % (unsigned long long)d);
-        const float2* __restrict__ hist = reinterpret_cast<const float2*>(history) + (size_t)p * VINE_MAX_DELAY;
-        for (int k = 1; k <= d; ++k) {
-            float rail, fpam;
-            task_new_command<false>(P, hist[k - 1], 0.0f, 0.0f, rail, fpam);
-            const int slot = (cm + d - k) % d;                    // (c - k) mod d, k <= d
-            st[(size_t)(VF_FIFO0 + 2 * slot) * n + e] = rail;
-            st[(size_t)(VF_FIFO0 + 2 * slot + 1) * n + e] = fpam;
-        }
-    }
+    mpc_rebuild_ring(P, d, c, reinterpret_cast<const float2*>(history) + (size_t)p * VINE_MAX_DELAY, st, n, e);
     const float2 nom = reinterpret_cast<const float2*>(nominal)[(size_t)p * S.H];
     reinterpret_cast<float2*>(actions)[e] = mpc_action(S, (unsigned)e, j == 0, tick[p], 0, nom.x, nom.y);
     rew[e] = 0.0f;
@@ -147,19 +130,9 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_node_kernel(const MpcParams 
     }
 }
 
-// The sum (or the minimum) of one value per lane over the workgroup, in a fixed order: a butterfly over the 64 lanes of each
-// wave (every lane ends with the same bits: a + b == b + a), the four wave values through LDS, combined in wave order.
+// The sum (or the minimum) of one value per lane over the workgroup, in a fixed order: wave_sum / wave_min (vine_mpc_shared.h)
+// over the 64 lanes of each wave, the four wave values through LDS, combined in wave order.
 // part: WAVES doubles of LDS per call site; the caller's __syncthreads() stands between the write and the read.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 __global__ __launch_bounds__(THREADS) void vine_mpc_update_kernel(const MpcParams S, const double* __restrict__ cost,
                                                                   const long long* __restrict__ plant_reset,

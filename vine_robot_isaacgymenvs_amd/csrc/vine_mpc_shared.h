@@ -1,0 +1,63 @@
+// vine_mpc_shared.h — what vine_mpc.hip (the fork, the update) and vine_mpc_adapt.hip (the pin, the estimate) state once:
+// the copy of a plant's state-block column onto a sample, the rebuild of the sample's delay ring from an action history, and
+// the workgroup reduction's wave step.  Include it behind vine_task_shared.h (task_new_command, VF_*); that header keeps
+// the contraction it was included under, whatever holds here.
+#ifndef VINE_MPC_SHARED_H
+#define VINE_MPC_SHARED_H
+
+#include <hip/hip_runtime.h>
+
+static_assert(VF_PIPE_Y == VF_FIFO0 + 2 * VINE_MAX_DELAY, "the ring is the fields VF_FIFO0 .. VF_PIPE_Y - 1");
+
+// What task_new_command reads (vine_task_shared.h).
+struct CommandParams {
+    float clip_act, act_noise, rail_scale, fpam_span, fpam_min;
+};
+
+// Every field of column p of the block pst[VF_COUNT][m] but the delay ring, onto column e of st[VF_COUNT][n].  A macro, not a
+// function: through a function, forced inline or not, the compiler turns two branches of vine_mpc_fork_kernel round (the same
+// code, other words), and that kernel's code object is to stay what it was before this header existed.
+#define MPC_COPY_COLUMN(pst, m, p, st, n, e)                                                                       \
+    do {                                                                                                           \
+        for (int f_ = 0; f_ < VF_FIFO0; ++f_) (st)[(size_t)f_ * (n) + (e)] = (pst)[(size_t)f_ * (m) + (p)];         \
+        for (int f_ = VF_PIPE_Y; f_ < VF_COUNT; ++f_) (st)[(size_t)f_ * (n) + (e)] = (pst)[(size_t)f_ * (m) + (p)]; \
+    } while (0)
+
+// The delay ring of column e at step count c for a sample with delay d and command constants P: for k = 1 .. d the command of
+// hist[k - 1] (the action handed k steps ago) goes to slot (c - k) mod d.  Slots d .. VINE_MAX_DELAY - 1 are not touched.
+__device__ __forceinline__ void mpc_rebuild_ring(const CommandParams& P, int d, unsigned long long c,
+                                                 const float2* hist, float* st, int n, int e) {
+    if (d > 0) {
+        const int cm = (int)(c % (unsigned long long)d);
+        for (int k = 1; k <= d; ++k) {
+            float rail, fpam;
+            task_new_command<false>(P, hist[k - 1], 0.0f, 0.0f, rail, fpam);
+            const int slot = (cm + d - k) % d;                    // (c - k) mod d, k <= d
+            st[(size_t)(VF_FIFO0 + 2 * slot) * n + e] = rail;
+            st[(size_t)(VF_FIFO0 + 2 * slot + 1) * n + e] = fpam;
+        }
+    }
+}
+
+// The sum (or the minimum) of one value per lane over a wave: a butterfly over its 64 lanes (every lane ends with the same
+// bits: a + b == b + a).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+// The integer of the eight-uniform deviate (include/vine_env_sensor.h, step 1): 2 S - 524280, S the sum of the eight 16-bit
+// halves of one Philox call's words.
+__device__ __forceinline__ int mpc_deviate_int(const unsigned w[4]) {
+    const int sum = (int)((w[0] & 0xffffu) + (w[0] >> 16) + (w[1] & 0xffffu) + (w[1] >> 16) + (w[2] & 0xffffu) +
+                          (w[2] >> 16) + (w[3] & 0xffffu) + (w[3] >> 16));
+    return 2 * sum - 524280;
+}
+
+#endif

@@ -311,15 +311,17 @@ class Controller:
         self.launches["plant_step"] += 1
 
     # -- many of them ----------------------------------------------------------------------------------------------------
-    def _capture(self):
+    def _capture(self, body=None):
+        """``body`` (default: ``graph_steps`` control steps) captured as one hipGraph, with nothing of it left behind."""
         from ..learning import graph_capture
         plant, model = self.plant, self.model
         counted, steps = dict(self.launches), (plant.num_steps, model.num_steps)
 
-        def body():
+        def control_steps():
             for _ in range(self.graph_steps):
                 self.control_step()
 
+        body = body or control_steps
         live = self.tensors() + plant.live_tensors() + model.live_tensors()
         graph = graph_capture.capture_rolled_back(self.device, body, live, _Pair(plant, model))
         # the warm-up pass was rolled back and the capture pass executed nothing: what the capture pass enqueued is the graph
@@ -381,14 +383,19 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None):
+         logger=None, adapt=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
     the plant has ``ENV_PARAMS`` -- the numbers ``test=True`` prints for the policy.  ``model_params``: an ``ENV_PARAMS``-style
     spec for the MODEL, drawn once per plant and repeated over its samples (default: the model is the configuration's own
     plant).  Returns a dict: ``report`` (or ``None``), ``by_param``, ``path`` (the log's ``.npz``), ``control_steps_per_second``,
-    ``plant_return`` (float64 [M], the summed plant reward) and ``controller``'s launch counts."""
+    ``plant_return`` (float64 [M], the summed plant reward) and ``controller``'s launch counts.
+
+    ``adapt``: a spec of ``mpc_adapt.adapt_config`` -- the model follows each plant online (include/vine_mpc_adapt.h), with
+    ``forget_on_reset`` when the plant has ``ENV_PARAMS_PER_EPISODE``.  The result then holds ``adapt``: ``names``, the final
+    ``mean`` and ``std`` [M, D], ``prior_mean``, and, where the plant carries an ``ENV_PARAMS`` table, ``truth`` and per name
+    the mean absolute error of the prior and of the final belief (printed too).  Without it nothing of this is launched."""
     import torch
     from . import episodes
     logger = logger or logging.getLogger(__name__)
@@ -407,13 +414,24 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         logger.info("mpc: model env.ENV_PARAMS forced from %r to {} (the model is the configuration's own plant)",
                     mcfg["env"]["ENV_PARAMS"])
         mcfg["env"]["ENV_PARAMS"] = {}
+    if adapt is not None and not mcfg["env"].get("ENV_PARAMS"):
+        mcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}      # binds a table that holds the configuration's own row: what is adapted
     plant = make_task(cfg, device)
     model = None
     try:
         model = make_task(mcfg, device)
-        ctl = Controller(plant, model, samples, horizon, lam, sigma, seed, graph=graph)
-        if model_params:
-            ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
+        if adapt is None:
+            ctl = Controller(plant, model, samples, horizon, lam, sigma, seed, graph=graph)
+            if model_params:
+                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
+        else:                                            # the prior is the model's value when the controller is made
+            from . import mpc_adapt
+            if model_params:
+                model.set_env_params({k: np.repeat(v, int(samples)) for k, v in
+                                      draw_model_params(model_params, model._vcfg, model._lib, seed, M).items()})
+            ctl = mpc_adapt.AdaptiveController(plant, model, samples, adapt, horizon, lam, sigma, seed, graph=graph,
+                                               forget_on_reset=env_params.per_episode(cfg["env"]))
+            print("mpc: adapting %s every %d control steps over a window of %d" % (", ".join(ctl.names), ctl.E, ctl.W), flush=True)
         log = getattr(plant, "episode_log", None)
         start = None
         if log is not None:
@@ -425,9 +443,13 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         total = torch.zeros(M, dtype=torch.float64, device=plant.device)
         torch.cuda.synchronize(plant.device)
         t0 = time.perf_counter()
-        for _ in range(int(steps)):
-            ctl.run(1)
-            total += plant.rew_buf
+        if adapt is None:
+            for _ in range(int(steps)):
+                ctl.run(1)
+                total += plant.rew_buf
+        else:                                            # whole cycles replay from one graph: the trace node sums the reward
+            ctl.run(int(steps))
+            total += ctl.returns
         torch.cuda.synchronize(plant.device)
         seconds = time.perf_counter() - t0
         out = {"report": None, "by_param": {}, "path": None, "control_steps_per_second": int(steps) / max(seconds, 1e-9),
@@ -454,6 +476,19 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
                     print("    [%.4g, %.4g%s  %.4g  (%d episodes)" % (edges[i], edges[i + 1], "]" if i == len(rate) - 1 else ")",
                                                                       rate[i], count[i]), flush=True)
             out["path"] = log.path                       # (written when the plant is closed, below)
+        if adapt is not None:
+            mean, std = ctl.belief()
+            prior, truth = ctl.prior_mean.cpu().numpy(), ctl.truth()
+            out["adapt"] = {"names": list(ctl.names), "mean": mean, "std": std, "prior_mean": prior, "truth": truth,
+                            "passes": ctl.passes.cpu().numpy(), "prior_error": {}, "final_error": {}}
+            for d, name in enumerate(ctl.names):
+                if truth is None:
+                    print("  adapt %s: final mean %s" % (name, np.array2string(mean[:, d], precision=4)), flush=True)
+                    continue
+                out["adapt"]["prior_error"][name] = float(np.abs(prior[:, d] - truth[:, d]).mean())
+                out["adapt"]["final_error"][name] = float(np.abs(mean[:, d] - truth[:, d]).mean())
+                print("  adapt %s: mean |prior - truth| %.4g, mean |belief - truth| %.4g" % (
+                    name, out["adapt"]["prior_error"][name], out["adapt"]["final_error"][name]), flush=True)
         return out
     finally:
         if model is not None:
