@@ -185,10 +185,11 @@ def undecided(cfg, f32, f64):
 def oracle_steps(cfg, precision, snaps, actions):
     """One oracle step from each device snapshot (``state`` [VF_COUNT, N], ``reset``, ``progress``, ``step_count``: what
     the env held in front of the step) with that step's stored actions -> dict of obs [T, N, F], rew [T, N], reset [T, N],
-    timeouts [T, N] and, float64 only, margins [T, 4, N]."""
+    timeouts [T, N], progress [T, N], the state block behind the step [T, VF_COUNT, N] (float64) and, float64 only, margins
+    [T, 4, N]."""
     from oracle import vine_oracle as vo
     orc = vo.OracleEnv(cfg, precision)
-    out = {"obs": [], "rew": [], "reset": [], "timeouts": [], "margins": []}
+    out = {"obs": [], "rew": [], "reset": [], "timeouts": [], "progress": [], "state": [], "margins": []}
     for snap, a in zip(snaps, actions):
         orc.state[:] = snap["state"].astype(orc.real)
         orc.reset_buf[:] = snap["reset"]
@@ -197,6 +198,7 @@ def oracle_steps(cfg, precision, snaps, actions):
         orc.step(a)
         out["obs"].append(orc.obs.copy()); out["rew"].append(orc.rew.copy())
         out["reset"].append(orc.reset_buf.copy()); out["timeouts"].append(orc.timeouts.copy())
+        out["progress"].append(orc.progress.copy()); out["state"].append(np.array(orc.state, np.float64))
         if precision == "f64":
             out["margins"].append(reset_margins(cfg, orc.state))
     orc.close()

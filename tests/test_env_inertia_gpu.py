@@ -7,7 +7,6 @@ one wave; 12-step episodes, so that resets and time-outs occur inside every 40-s
 tensors are compared as 32-bit words."""
 import ctypes as C
 import glob
-import types
 
 import numpy as np
 import pytest
@@ -16,6 +15,7 @@ import torch
 from oracle import vine_oracle as vo
 from tests.env_inertia_sets import NUM_SETS, set_cfg, table_of
 from tests.helpers import base_cfg, random_state
+from tests.step_reference import composite
 from tests.test_env_params_gpu import (MAX_LEN, N, T, _make_env, actions_for, assert_bit_equal, bits, case_cfg, own_table, rollout,
                                        saw_resets_and_timeouts)
 from tests.test_hip_parity import QPOS, compare_step
@@ -137,11 +137,9 @@ def test_nine_plants_in_one_batch_equal_nine_uniform_handles(Lane):
 
 # ---------------------------------------------------------------------------------------------------------------- 3
 def _composite(oracles):
-    """Env e of oracle e % 9, as one oracle-like object for compare_step."""
-    pick = lambda get, axis: np.stack([np.take(get(oracles[e % NUM_SETS]), e, axis=axis) for e in range(N)], axis=axis)   # noqa: E731
-    return types.SimpleNamespace(reset_buf=pick(lambda o: o.reset_buf, 0), progress=pick(lambda o: o.progress, 0),
-                                 timeouts=pick(lambda o: o.timeouts, 0), obs=pick(lambda o: o.obs, 0), rew=pick(lambda o: o.rew, 0),
-                                 state=pick(lambda o: np.asarray(o.state, np.float64), 1))
+    """Env e of oracle e % 9, as one oracle-like object for compare_step (tests/step_reference.py)."""
+    assert len(oracles) == NUM_SETS
+    return composite(oracles, N)
 
 
 # single_step_case's tolerances for the one-lane kernel (tests/test_hip_parity.py holds them as literals inside the function,

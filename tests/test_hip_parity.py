@@ -3,9 +3,12 @@ identical seeded inputs, against the golden fixtures made from the reference's P
 BASELINE.json's full size -- through size-independent properties.
 
 Tolerances (north_star: "stated fp32 tolerance"): integer outputs (reset/progress/time_outs) bit-exact;
-single-step float outputs vs the float32 oracle (same formulation) 2e-5 abs on positions, 2e-3 on velocities
-(the 6x6 mass matrix of a chain of 5 g links carrying a 100 g link has condition number ~1e3-1e4, so float32
-accelerations carry ~1e-4 relative error whatever the instruction order); vs the float64 oracle 1e-4 / 1e-2.
+single-step float outputs vs the float32 oracle (same formulation) 2e-5 abs on positions, 2e-3 on velocities; vs the
+float64 oracle 1e-4 / 1e-2.  These are coarse: over one step the float32 oracle is within 2e-7 .. 1.2e-6 of the float64
+oracle, relative to each group's largest value (q 2.9e-7, qd 3.8e-7, tip velocity 6.2e-7, rail force 8.1e-7, obs 1.2e-6; at
+worst 3.5e-6, obs in the explicit-damping modes), despite the mass matrix's condition number of ~1e3-1e4, so 2e-3 on
+velocities of magnitude 3 - 10 is several hundred times float32 round-off and a constant wrong by 0.1 % passes.
+tests/test_step_dynamics_gpu.py holds both step kernels to that round-off (tests/step_reference.py).
 """
 import ctypes as C
 

@@ -13,7 +13,10 @@ the rollout counter, the dataset's returns / values / advantages -- held to the 
   across neighbouring envs below 0.02, no draw twice; the rollout counter advances by the horizon;
 * env: a CPU oracle loaded with the device's own state in front of every step and stepped with the stored actions gives the
   next observation, the reset / time-out / done flags (exactly) and the shaped reward with its time-out bootstrap, at the
-  single-step tolerances of tests/test_hip_parity.py (float32 oracle tight, float64 oracle loose);
+  single-step tolerances of tests/test_hip_parity.py (float32 oracle tight, float64 oracle loose); and every group of
+  tests/step_reference.py (the state block behind the step, the observation, the reward) within ``K_STEP`` times the float32
+  oracle's own error against the float64 oracle, per class and norm: the four-lane kernel's rollout instantiation
+  (``step_rollout_into``) and ``step_into``, which tests/test_step_dynamics_gpu.py does not reach;
 * bookkeeping, last values, GAE and the value normaliser's two updates in float64.
 
 Tolerance of the network tensors: the same model in plain float32 torch on the same teacher-forced inputs (the replay's
@@ -48,7 +51,9 @@ hence K = 5 (1.5 x 3.05 = 4.6).  The heads (mus, values, neglogpacs, last_values
 state at 1.0 - 1.35 on the split routes and at 2.0 - 3.05 on the native-fp32 and the generic route; |mus - float64| <= 8.5e-7.
 The negative controls (n512_fused) exceed the bound by a factor of 6.5e4 (value left normalised: shaped rewards) to 1.2e6
 (dones shifted: snap_c), far beyond CONTROL_MARGIN: against a bound of a few float32 round-offs any of these bugs is an
-error of order 0.1.  Each run prints the figures; profiles/rollout_record/ratios.txt has the whole table (every tensor, the
+error of order 0.1.  The env steps' groups (kernel error / max(float32 oracle's error, FLOOR), bounds K_JOINT = 8.7 for q, qd
+and obs, K_STEP = 5.1 for the others): 1.6 - 2.4 (qd) and 1.6 - 2.1 (th, w) over the six cases, every other group at most
+1.3; profiles/step_dynamics/ratios.txt has them.  Each run prints the figures; profiles/rollout_record/ratios.txt has the whole table (every tensor, the
 absolute errors, the resets and the noise statistics of every case).
 """
 import time
@@ -58,6 +63,7 @@ import pytest
 import torch
 
 from tests import rollout_reference as rr
+from tests import step_reference as sr
 from tests import update_reference as ur
 from tests.test_update_gradients import CONTROL_MARGIN, _errs
 
@@ -249,6 +255,44 @@ def _check_env(agent, env, recs, orc, report, value_normalised=False):
     return dev_rew, dev_reset
 
 
+def _check_step_groups(name, env, recs, orc, T, report):
+    """tests/step_reference.py's group ratios of every env step of the record: the device's state block, next observation
+    and reward behind each step against the float64 oracle's, bounded by K_STEP x the float32 oracle's error.  Classes from
+    the reset flags in front of the step; ``rollout_reference.undecided`` env-steps are left out; with an obstacle the envs
+    that report a contact are, and only the ``kept`` class is compared."""
+    cfg = env._vcfg
+    obstacle = cfg.has_flag(sr.abi.FLAG_CREATE_PIPE) or cfg.has_flag(sr.abi.FLAG_CREATE_SHELF)
+    before = [s for rec in recs for s in rec["snaps"][:T]]
+    after = [s for rec in recs for s in rec["snaps"][1:T + 1]]
+    obs_next = torch.cat([torch.cat([rec["obses"][1:], rec["obs_end"][None]]) for rec in recs]).cpu().numpy()
+    skip = rr.undecided(cfg, orc["f32"], orc["f64"])
+    tally = sr.Tally(("kept",) if obstacle else ("kept", "reset"))
+    for t in range(len(before)):
+        runs = {"dev": sr.snapshot(after[t]["state"], obs_next[t], after[t]["rew"], after[t]["reset"], after[t]["progress"],
+                                   after[t]["timeout"])}
+        for p in ("f32", "f64"):
+            o = orc[p]
+            runs[p] = sr.snapshot(o["state"][t], o["obs"][t], o["rew"][t], o["reset"][t], o["progress"][t], o["timeouts"][t])
+        contact = np.zeros_like(skip[t])
+        if obstacle:
+            contact = np.asarray(before[t]["state"])[sr.abi.VF_CONTACT] != 0
+            for s in runs.values():
+                contact = contact | (s.state[sr.abi.VF_CONTACT] != 0)
+        was_reset = before[t]["reset"] != 0
+        ok = ~skip[t] & ~contact
+        tally.add({"kept": ok & ~was_reset, "reset": ok & was_reset, "undecided": skip[t], "contact": ~skip[t] & contact}, runs)
+    ratios, _, base = sr.report(tally)
+    raw = sr.unscaled(ratios)
+    k, w = sr.worst(raw)
+    report["step_groups"] = {"worst": (k, round(w, 3)), "classes": dict(tally.count)}
+    print("\n" + sr.table("rollout record %s %s: kernel error / max(float32 oracle's error, FLOOR); classes %s"
+                          % (name, report["entry"], dict(tally.count)), raw), flush=True)
+    assert tally.count["kept"] >= sr.MIN_KEPT * tally.steps * before[0]["reset"].shape[0], tally.count
+    bad = {key: (round(v[0], 3), round(v[1], 3)) for key, v in ratios.items() if not max(v) <= 1.0}
+    assert not bad, ("env step error above K_STEP = %g (q, qd, obs: K_JOINT = %g) x max(float32 oracle's error, FLOOR): "
+                     "error / bound" % (sr.K_STEP, sr.K_JOINT), bad)
+
+
 def _check_books(agent, recs, dev_rew, dev_reset, report):
     """Episode accumulators and meters in float64 from the device's rewards and reset flags."""
     T, N = agent.horizon_length, agent.num_actors
@@ -377,6 +421,7 @@ def test_rollout_record_against_float64_replay(case, monkeypatch):
 
     # ---- env, bookkeeping, dataset
     dev_rew, dev_reset = _check_env(agent, env, recs, orc, report)
+    _check_step_groups(name, env, recs, orc, T, report)
     _check_books(agent, recs, dev_rew, dev_reset, report)
     _check_dataset(agent, recs, report)
     env.close()
