@@ -222,7 +222,11 @@ typedef struct Model {
      * (PhysX maxJointVelocity, 100 rad/s), joint efforts applied during the first substep of a simulate only */
     real armature, vmax_link, vmax_joint;
     int effort_first_substep_only;
+    /* contact probe of tests/contact_reference.py: scale factors of the obstacle contacts' constants (CS_*), all 1 by
+     * default (x 1 is exact: the unprobed arithmetic is unchanged) and never part of the product */
+    real cs[11];
 } Model;
+enum { CS_K, CS_C, CS_WALL, CS_OUTER, CS_LEN, CS_LINK_Y0, CS_LINK_Y1, CS_OVERHANG, CS_BOARD_HY, CS_BOARD_HZ, CS_STRIP, CS_COUNT };
 
 static void model_init(Model* M, const VineConfig* c) {
     M->mc = c->cart_mass; M->L = c->link_length; M->l = c->link_com; M->z1 = c->joint1_z;
@@ -230,6 +234,7 @@ static void model_init(Model* M, const VineConfig* c) {
     M->cad = c->link_angular_damping;
     M->implicit_damping = (c->flags & VINE_FLAG_IMPLICIT_JOINT_DAMPING) != 0;
     M->armature = 0; M->vmax_link = 0; M->vmax_joint = 0; M->effort_first_substep_only = 0;
+    for (int i = 0; i < CS_COUNT; ++i) M->cs[i] = 1;
     M->mtot = M->mc;
     for (int i = 0; i < NL; ++i) { M->m[i] = c->link_mass[i]; M->I[i] = c->link_inertia[i]; M->mtot += M->m[i]; }
     for (int i = 0; i < NL; ++i) {
@@ -596,18 +601,43 @@ int vine_oracle_simulate(const VineConfig* cfg, int form, double* q, double* qd,
  * Link rectangle in link-local (y, z): y in [-0.0381, +0.0719] (main cylinder r = 0.0381 + FPAM cylinder at
  * y = 0.055, r = 0.0169; URDF:95-115), z in [0, L] (link_0: length 0.1 centred at 0.04425 -> [-0.00575, 0.09425]).
  * Local z maps to d = (-sin phi, cos phi), local y to l = (cos phi, sin phi) in world (y, z). */
-#define CONTACT_K ((real)2000.0)  /* N/m   penalty stiffness */
-#define CONTACT_C ((real)2.0)     /* N s/m penalty damping   */
-#define LINK_Y0 ((real)-0.0381)
-#define LINK_Y1 ((real)0.0719)
+#define CONTACT_K ((real)2000.0 * M->cs[CS_K])  /* N/m   penalty stiffness */
+#define CONTACT_C ((real)2.0 * M->cs[CS_C])     /* N s/m penalty damping   */
+#define LINK_Y0 ((real)-0.0381 * M->cs[CS_LINK_Y0])
+#define LINK_Y1 ((real)0.0719 * M->cs[CS_LINK_Y1])
+#define LINK0_Z0 ((real)-0.00575 * M->cs[CS_OVERHANG])   /* link 0 reaches this far behind its joint */
 static const real BOARD[2][4] = {
     /* cy,      cz,   hy,     hz   in the shelf frame */
     {-0.001f, 0.0f, 0.1995f, 0.005f},
     {0.0f, 0.2f, 0.2f, 0.005f},
 };
 
+/* The margin of the discontinuous contact decisions (metres): how far the state is from deciding one of them the other
+ * way.  A point against a box: |min(ey, ez)| (in or out) and, inside, |ey - ez| (which face it leaves through); a corner
+ * against a link rectangle: |the smallest of the four depths| (in or out) and, inside, the second smallest minus the
+ * smallest (the nearest side).  The clamp f > 0 is continuous and is none of them.  ``margin`` NULL: not recorded. */
+static void margin_box(real* margin, real ey, real ez) {
+    if (!margin) return;
+    real lo = ey < ez ? ey : ez, m = lo < 0 ? -lo : lo;
+    if (lo > 0) { real d = ey < ez ? ez - ey : ey - ez; if (d < m) m = d; }
+    if (m < *margin) *margin = m;
+}
+static void margin_rect(real* margin, real d0, real d1, real d2, real d3) {
+    if (!margin) return;
+    real d[4] = {d0, d1, d2, d3}, lo = d0, next = 0;
+    int at = 0;
+    for (int i = 1; i < 4; ++i) if (d[i] < lo) { lo = d[i]; at = i; }
+    real m = lo < 0 ? -lo : lo;
+    if (lo > 0) {
+        next = d[at == 0 ? 1 : 0];
+        for (int i = 0; i < 4; ++i) if (i != at && d[i] < next) next = d[i];
+        if (next - lo < m) m = next - lo;
+    }
+    if (m < *margin) *margin = m;
+}
+
 /* Adds the contact generalised forces (relative coordinates) to Qc; returns |F| on the strip. */
-static real shelf_contact(const Model* M, const real* q, const real* qd, real shelf_y, real shelf_z, real* Qc) {
+static real shelf_contact(const Model* M, const real* q, const real* qd, real shelf_y, real shelf_z, real* Qc, real* margin) {
     real strip_fy = 0, strip_fz = 0;
     real ang = M->phi0, om = 0;
     real py[NL + 1], pz[NL + 1], pvy = qd[0], pvz = 0;
@@ -616,7 +646,7 @@ static real shelf_contact(const Model* M, const real* q, const real* qd, real sh
         ang += q[k + 1]; om += qd[k + 1];
         real s = (real)sin((double)ang), c = (real)cos((double)ang);
         real dy = -s, dz = c, ly = c, lz = s;
-        real z0 = (k == 0) ? (real)-0.00575 : 0, z1 = (k == 0) ? (real)0.09425 : M->L;
+        real z0 = (k == 0) ? LINK0_Z0 : 0, z1 = (k == 0) ? (real)0.09425 : M->L;
         real fy_tot = 0, fz_tot = 0;   /* applied to this link, with moments about every proximal joint */
         real mom[NL];
         for (int j = 0; j <= k; ++j) mom[j] = 0;
@@ -630,7 +660,9 @@ static real shelf_contact(const Model* M, const real* q, const real* qd, real sh
                 real vy = pvy - om * rz, vz = pvz + om * ry;
                 for (int bx = 0; bx < 2; ++bx) {
                     real ddy = wy - (shelf_y + BOARD[bx][0]), ddz = wz - (shelf_z + BOARD[bx][1]);
-                    real ey = BOARD[bx][2] - (real)fabs((double)ddy), ez = BOARD[bx][3] - (real)fabs((double)ddz);
+                    real ey = BOARD[bx][2] * M->cs[CS_BOARD_HY] - (real)fabs((double)ddy);
+                    real ez = BOARD[bx][3] * M->cs[CS_BOARD_HZ] - (real)fabs((double)ddz);
+                    margin_box(margin, ey, ez);
                     if (ey <= 0 || ez <= 0) continue;
                     real fy = 0, fz = 0;
                     if (ey < ez) {
@@ -648,9 +680,10 @@ static real shelf_contact(const Model* M, const real* q, const real* qd, real sh
             }
         /* (b) strip front corners vs this link's rectangle */
         for (int e = 0; e < 2; ++e) {
-            real wy = shelf_y + (real)0.2, wz = shelf_z + (e ? (real)0.005 : (real)-0.005);
+            real wy = shelf_y + (real)0.2 * M->cs[CS_STRIP], wz = shelf_z + (e ? (real)0.005 : (real)-0.005);
             real ry = wy - py[k], rz = wz - pz[k];
             real zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
+            margin_rect(margin, zl - z0, z1 - zl, yl - LINK_Y0, LINK_Y1 - yl);
             if (!(zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1)) continue;
             /* exit through the nearest face: outward normal n, depth dep */
             real dep = zl - z0, ny = -dy, nz = -dz;
@@ -679,7 +712,7 @@ double vine_oracle_shelf_contact(const VineConfig* cfg, const double* q, const d
     Model M; model_init(&M, cfg);
     real rq[ND], rqd[ND], Q[ND];
     for (int i = 0; i < ND; ++i) { rq[i] = (real)q[i]; rqd[i] = (real)qd[i]; Q[i] = 0; }
-    real f = shelf_contact(&M, rq, rqd, (real)shelf_y, (real)shelf_z, Q);
+    real f = shelf_contact(&M, rq, rqd, (real)shelf_y, (real)shelf_z, Q, NULL);
     for (int i = 0; i < ND; ++i) Qc[i] = Q[i];
     return f;
 }
@@ -691,11 +724,11 @@ double vine_oracle_shelf_contact(const VineConfig* cfg, const double* q, const d
  * rectangles in the pipe frame: y_l in [0, 0.00525] and [0.15015, 0.1554], z_l in [0, 0.34125].
  * Same penalty model as the shelf: (a) 6 points per link vs the two walls, (b) the 4 rim corners of the entrance
  * (z_l = 0) and of the far end vs every link rectangle.  No contact force is reported for the pipe (V5:1246). */
-#define PIPE_LEN ((real)0.34125)
-#define PIPE_WALL ((real)0.00525)
-#define PIPE_OUTER ((real)0.1554)
+#define PIPE_LEN ((real)0.34125 * M->cs[CS_LEN])
+#define PIPE_WALL ((real)0.00525 * M->cs[CS_WALL])
+#define PIPE_OUTER ((real)0.1554 * M->cs[CS_OUTER])
 static void pipe_contact(const Model* M, const real* q, const real* qd, real pipe_y, real pipe_z, real theta_prime,
-                         real* Qc) {
+                         real* Qc, real* margin) {
     const real th = theta_prime + (real)1.5707963267948966;
     const real ct = (real)cos((double)th), st = (real)sin((double)th);
     /* pipe-frame axes in world (y,z): e_y = (ct, st), e_z = (-st, ct) */
@@ -707,7 +740,7 @@ static void pipe_contact(const Model* M, const real* q, const real* qd, real pip
         ang += q[k + 1]; om += qd[k + 1];
         real s = (real)sin((double)ang), c = (real)cos((double)ang);
         real dy = -s, dz = c, ly = c, lz = s;
-        real z0 = (k == 0) ? (real)-0.00575 : 0, z1 = (k == 0) ? (real)0.09425 : M->L;
+        real z0 = (k == 0) ? LINK0_Z0 : 0, z1 = (k == 0) ? (real)0.09425 : M->L;
         real fy_tot = 0, mom[NL];
         for (int j = 0; j <= k; ++j) mom[j] = 0;
         for (int e = 0; e < 2; ++e)
@@ -725,6 +758,7 @@ static void pipe_contact(const Model* M, const real* q, const real* qd, real pip
                     real cy = wall_lo[w] + (real)0.5 * PIPE_WALL, cz = (real)0.5 * PIPE_LEN;
                     real ddy = pyl - cy, ddz = pzl - cz;
                     real ey = (real)0.5 * PIPE_WALL - (real)fabs((double)ddy), ez = (real)0.5 * PIPE_LEN - (real)fabs((double)ddz);
+                    margin_box(margin, ey, ez);
                     if (ey <= 0 || ez <= 0) continue;
                     real fyl = 0, fzl = 0;
                     if (ey < ez) {
@@ -748,6 +782,7 @@ static void pipe_contact(const Model* M, const real* q, const real* qd, real pip
                 real wy = pipe_y + pyl * ct - pzl * st, wz = pipe_z + pyl * st + pzl * ct;
                 real ry = wy - py[k], rz = wz - pz[k];
                 real zl = ry * dy + rz * dz, yl = ry * ly + rz * lz;
+                margin_rect(margin, zl - z0, z1 - zl, yl - LINK_Y0, LINK_Y1 - yl);
                 if (!(zl > z0 && zl < z1 && yl > LINK_Y0 && yl < LINK_Y1)) continue;
                 real dep = zl - z0, ny = -dy, nz = -dz;
                 if (z1 - zl < dep) { dep = z1 - zl; ny = dy; nz = dz; }
@@ -771,7 +806,7 @@ void vine_oracle_pipe_contact(const VineConfig* cfg, const double* q, const doub
     Model M; model_init(&M, cfg);
     real rq[ND], rqd[ND], Q[ND];
     for (int i = 0; i < ND; ++i) { rq[i] = (real)q[i]; rqd[i] = (real)qd[i]; Q[i] = 0; }
-    pipe_contact(&M, rq, rqd, (real)pipe_y, (real)pipe_z, (real)theta_prime, Q);
+    pipe_contact(&M, rq, rqd, (real)pipe_y, (real)pipe_z, (real)theta_prime, Q, NULL);
     for (int i = 0; i < ND; ++i) Qc[i] = Q[i];
 }
 
@@ -784,13 +819,13 @@ void vine_oracle_pipe_contact(const VineConfig* cfg, const double* q, const doub
  * over the substeps of |F| on the front-edge strip; 0 without a shelf).  Shared by the env step and by
  * ``vine_oracle_simulate_obstacles`` (the ``simulate`` of the golden generator's fake tensor API). */
 static real sim_step(const Model* M, int form, int substeps, const real* cj, real* q, real* qd, const real* eff, real hsub,
-                     int shelf, int pipe, real shelf_y, real shelf_z, real pipe_y, real pipe_z, real pipe_tp) {
+                     int shelf, int pipe, real shelf_y, real shelf_z, real pipe_y, real pipe_z, real pipe_tp, real* margin) {
     real csum = 0;
     for (int s = 0; s < substeps; ++s) {
         real effc[ND];
         for (int i = 0; i < ND; ++i) effc[i] = (i > 0 && s > 0 && M->effort_first_substep_only) ? 0 : eff[i];
-        if (shelf) csum += shelf_contact(M, q, qd, shelf_y, shelf_z, effc);
-        if (pipe) pipe_contact(M, q, qd, pipe_y, pipe_z, pipe_tp, effc);
+        if (shelf) csum += shelf_contact(M, q, qd, shelf_y, shelf_z, effc, margin);
+        if (pipe) pipe_contact(M, q, qd, pipe_y, pipe_z, pipe_tp, effc, margin);
         FLOP_BUCKET(0); FLOP_CALL(0);
         substep(M, form, cj, q, qd, effc, hsub);
         FLOP_BUCKET(2);
@@ -805,7 +840,7 @@ double vine_oracle_simulate_obstacles(const VineConfig* cfg, int form, double* q
     real rq[ND], rqd[ND], re[ND], cj[ND];
     for (int i = 0; i < ND; ++i) { rq[i] = (real)q[i]; rqd[i] = (real)qd[i]; re[i] = (real)eff[i]; cj[i] = cjoint ? (real)cjoint[i] : M.d; }
     real contact = sim_step(&M, form, n, cj, rq, rqd, re, (real)h, shelf, pipe, (real)obstacle[0], (real)obstacle[1],
-                            (real)obstacle[2], (real)obstacle[3], (real)obstacle[4]);
+                            (real)obstacle[2], (real)obstacle[3], (real)obstacle[4], NULL);
     for (int i = 0; i < ND; ++i) { q[i] = rq[i]; qd[i] = rqd[i]; }
     return contact;
 }
@@ -996,6 +1031,7 @@ struct VineHandle {
     int64_t step_count;
     const float* reset_values;
     float* reward_matrix;
+    double* margin;      /* [n] contact-decision margin of the last step (vine_oracle_contact_margin), NULL: not recorded */
 };
 #define ST(h, f, e) ((h)->st[(size_t)(f) * (h)->n + (e)])
 
@@ -1017,6 +1053,24 @@ void vine_oracle_set_probe(VineHandle* h, double armature, double vmax_link, dou
     h->model.effort_first_substep_only = effort_first_substep_only;
 }
 void vine_oracle_set_formulation(VineHandle* h, int form) { h->form = form; }
+/* contact probe: ``scale`` holds CS_COUNT factors on the obstacle contacts' constants (see Model); oracle-only, used by the
+ * negative controls of tests/contact_reference.py (vine_oracle_*_contact take a configuration and stay unprobed). */
+int vine_oracle_set_contact_probe(VineHandle* h, const double* scale, int count) {
+    if (!h || !scale || count != CS_COUNT) return fail(VINE_ERR_INVALID_ARG, "contact probe: CS_COUNT factors expected");
+    for (int i = 0; i < CS_COUNT; ++i) h->model.cs[i] = (real)scale[i];
+    return VINE_OK;
+}
+/* Per env, the minimum over all substeps of the last step of the margin of every discontinuous contact decision (metres;
+ * see margin_box): recorded from the first call on, which returns the buffer ([n] doubles, +inf until a step ran or
+ * where no obstacle is configured). */
+double* vine_oracle_contact_margin(VineHandle* h) {
+    if (!h) return NULL;
+    if (!h->margin) {
+        h->margin = (double*)malloc(sizeof(double) * (size_t)h->n);
+        if (h->margin) for (int e = 0; e < h->n; ++e) h->margin[e] = (double)INFINITY;
+    }
+    return h->margin;
+}
 
 static int validate(const VineConfig* c) {
     if (!c) return fail(VINE_ERR_INVALID_ARG, "cfg is NULL");
@@ -1066,6 +1120,7 @@ void vine_destroy(VineHandle* h) {
     if (!h) return;
     if (h->owns_st) free(h->st);
     if (h->owns_f32) free(h->st_f32);
+    free(h->margin);
     free(h);
 }
 float* vine_state_ptr(VineHandle* h) { return h ? h->st_f32 : NULL; }
@@ -1253,6 +1308,7 @@ static void step_env(VineHandle* h, int e, const float* actions, float* obs, flo
     real pipe_y = ST(h, VF_PIPE_Y, e), pipe_z = ST(h, VF_PIPE_Z, e), pipe_tp = ST(h, VF_OBJ_ANGLE, e);
     real u_used = (c->flags & VINE_FLAG_USE_SMOOTHED_FPAM) ? smoothed : u_fpam; /* V5:1059 */
     const real hsub = (real)c->dt / (real)c->substeps;
+    real margin = (real)INFINITY;
 
     /* ---- control_freq_inv x [refresh, actuation, contact norm, simulate] (VT:338-356) ---- */
     for (int it = 0; it < c->control_freq_inv; ++it) {
@@ -1279,10 +1335,12 @@ static void step_env(VineHandle* h, int e, const float* actions, float* obs, flo
         }
         if (shelf) contact_sum += contact;                           /* VT:348-351 */
         contact = sim_step(M, h->form, c->substeps, cj, q, qd, eff, hsub, shelf, pipe, shelf_y, shelf_z, pipe_y, pipe_z,
-                           pipe_tp);                                 /* gym.simulate, VT:356 */
+                           pipe_tp, h->margin ? &margin : NULL);     /* gym.simulate, VT:356 */
         tip_kinematics(M, q, qd, tip);                               /* refreshed rigid-body states */
         cart_y = q[0]; cart_vy = qd[0];
     }
+
+    if (h->margin) h->margin[e] = (double)margin;
 
     /* ---- post_physics_step (V5:1110-1120) ---- */
     int64_t prog = progress[e] + 1;                                  /* V5:1111 */

@@ -75,6 +75,10 @@ def load(precision="f64", omp=False):
     lib.vine_oracle_set_formulation.argtypes = [C.c_void_p, C.c_int]
     lib.vine_oracle_pull_mirror.argtypes = [C.c_void_p]
     lib.vine_oracle_set_probe.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
+    lib.vine_oracle_set_contact_probe.argtypes = [C.c_void_p, _D, C.c_int]
+    lib.vine_oracle_set_contact_probe.restype = C.c_int
+    lib.vine_oracle_contact_margin.argtypes = [C.c_void_p]
+    lib.vine_oracle_contact_margin.restype = _D
     _cache[key] = lib
     return lib
 
@@ -180,6 +184,11 @@ def energy(cfg, q, qd):
     return lib.vine_oracle_energy(C.byref(cfg), _dp(q), _dp(qd))
 
 
+# the factors of OracleEnv.set_contact_probe, in the order of oracle/vine_oracle.c's CS_*
+CONTACT_PROBE = ("contact_k", "contact_c", "pipe_wall", "pipe_outer", "pipe_len", "link_y0", "link_y1", "link0_overhang",
+                 "board_hy", "board_hz", "strip_offset")
+
+
 class OracleEnv:
     """The oracle behind the same C ABI as the product (device_id = -1), numpy buffers."""
 
@@ -207,6 +216,7 @@ class OracleEnv:
         self.timeouts = np.zeros(self.n, np.uint8)
         self.reward_matrix = None
         self._reset_values = None
+        self._margin = None
 
     def bind_reward_matrix(self):
         self.reward_matrix = np.zeros((self.n, abi.NUM_REWARDS), np.float32)
@@ -227,6 +237,26 @@ class OracleEnv:
     def set_probe(self, armature=0.0, vmax_link=0.0, vmax_joint=0.0, effort_first_substep_only=False):
         """Oracle-only physics probe switches (tests/test_oracle_physics.py: sweep of unverifiable PhysX defaults)."""
         self.lib.vine_oracle_set_probe(self.h, armature, vmax_link, vmax_joint, int(effort_first_substep_only))
+
+    def set_contact_probe(self, **factors):
+        """Oracle-only scale factors on the obstacle contacts' constants (``CONTACT_PROBE``; each 1 unless named): the
+        negative controls of tests/contact_reference.py."""
+        unknown = set(factors) - set(CONTACT_PROBE)
+        assert not unknown, unknown
+        scale = np.array([factors.get(k, 1.0) for k in CONTACT_PROBE], np.float64)
+        rc = self.lib.vine_oracle_set_contact_probe(self.h, _dp(scale), len(scale))
+        if rc:
+            raise RuntimeError(self.lib.vine_last_error().decode())
+
+    @property
+    def contact_margin(self):
+        """[n] float64: per env, the minimum over all substeps of the last step of the margin (metres) of every
+        discontinuous contact decision -- a point entering a wall or board, the face it leaves through, an obstacle corner
+        entering a link rectangle, its nearest side.  Recorded from the first read on (+inf before the next step)."""
+        if self._margin is None:
+            ptr = self.lib.vine_oracle_contact_margin(self.h)
+            self._margin = np.ctypeslib.as_array(ptr, shape=(self.n,))
+        return self._margin
 
     def stats(self, index_to_view=0):
         """vine_stats: the dashboard vector (abi.VS_*) of the state the last step left behind."""
@@ -263,6 +293,7 @@ class OracleEnv:
     def close(self):
         if self.h:
             self.state = None
+            self._margin = None
             self.lib.vine_destroy(self.h)
             self.h = None
 

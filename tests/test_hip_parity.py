@@ -25,8 +25,9 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module", params=["lane", "quad"])
 def HipEnv(request):
     """The product library through its C ABI, once per step kernel: "lane" = one env per lane (vine_step_kernel),
-    "quad" = four lanes per env (vine_step_quad_kernel) wherever that kernel applies (no obstacle, the two scalable
-    observation layouts; the library silently takes the one-lane kernel elsewhere)."""
+    "quad" = four lanes per env (vine_step_quad_kernel) wherever that kernel applies (control_freq_inv 4, implicit joint
+    damping without the stiffness / link-damping extras, the two scalable observation layouts, no per-env parameter
+    table; obstacles are covered; the library silently takes the one-lane kernel elsewhere)."""
     import torch
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X (the product has no CPU fallback)")

@@ -1211,7 +1211,7 @@ class A2CAgent(FastInferenceMixin):
             try:
                 g = torch.cuda.CUDAGraph()
                 torch.cuda.synchronize(self.device)
-                with torch.cuda.graph(g, pool=self._upd_pool, capture_error_mode="thread_local"):
+                with graph_capture.collector_at_rest(), torch.cuda.graph(g, pool=self._upd_pool, capture_error_mode="thread_local"):
                     self.optimizer.step(grad_scale=1.0 / self.rank_size, lr_schedule=self._lr_schedule_args(),
                                         **self._clip_args(self.optimizer.clip_out))
                 rec = self._upd_graphs["tail"] = {"G": g}
@@ -1318,7 +1318,7 @@ class A2CAgent(FastInferenceMixin):
                 keep = probe.clone()
                 torch.cuda.synchronize(self.device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with graph_capture.collector_at_rest(), torch.cuda.graph(g, capture_error_mode="thread_local"):
                     dist.all_reduce(probe, op=dist.ReduceOp.SUM)
                 return True, "captured", (g, probe, keep)
             except RuntimeError as err:
@@ -1433,7 +1433,7 @@ class A2CAgent(FastInferenceMixin):
         keep = []
         rms_training = bool(key[1])
         try:
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+            with graph_capture.collector_at_rest(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
                 for ep in range(n_epochs):
                     ahead = self._rms_updates_ahead(nb) if (rms_training and ep == 0) else None
                     for i in range(nb):
@@ -1469,7 +1469,7 @@ class A2CAgent(FastInferenceMixin):
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         pool = None if os.environ.get("VINE_UPD_POOL") == "separate" else self._upd_pool
-        with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
+        with graph_capture.collector_at_rest(), torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
             if lead:
                 # the step behind the previous all-reduce: the KL next to the gradients is the sum over the ranks by
                 # now, the schedule runs inside the Adam launch (the dataset's mu / sigma slices were refreshed by the

@@ -4,6 +4,8 @@ import time
 
 import torch
 
+from . import graph_capture
+
 
 def ppo_kernel_rooflines(device, B=8192, T=4, H=256, width=92, wpad=96, sets=4):
     """Stand-alone HIP-event timings of the two largest hand-written kernels of the mixed-precision update at its
@@ -348,7 +350,7 @@ def run_ppo_bench(env, cfg, args, steps, warmup, barrier, world, rank):
         try:
             gcap = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.cuda.graph(gcap, capture_error_mode="thread_local"):
+            with graph_capture.collector_at_rest(), torch.cuda.graph(gcap, capture_error_mode="thread_local"):
                 for i in range(64):
                     orig(pool[i % 16], env.obs_buf)
             gcap.replay()

@@ -6,8 +6,27 @@ rolled back, and the capture pass executes nothing.  So neither pass counts towa
 What is rolled back is the caller's own tensors and ``env.live_tensors()`` -- the env's buffers and what each of its
 observers says it needs --, the env's step count (the key of the random streams) and the device RNG state."""
 import contextlib
+import gc
 
 import torch
+
+
+@contextlib.contextmanager
+def collector_at_rest():
+    """Around a stream capture: dead reference cycles are collected in front of it and the cyclic collector rests during it.
+    A cycle may own an env handle or a ``torch.cuda.CUDAGraph`` (a closed-over agent of an earlier run in the same process),
+    and their finalisers synchronise the device and free device memory.  The collector starts wherever an allocation tips
+    it over, on whichever thread -- the autograd thread of a captured backward pass included --, and such a finaliser run
+    inside a capture ends the process (abort).  (``torch.cuda.graph`` itself collects on entry only under
+    ``torch.compiler.config.force_cudagraph_gc``, and never keeps the collector from starting later.)"""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def capture_rolled_back(device, body, live, env, pool=None):
@@ -29,7 +48,7 @@ def capture_rolled_back(device, body, live, env, pool=None):
     torch.cuda.synchronize(device)
     graph = torch.cuda.CUDAGraph()
     # thread_local: RCCL's watchdog thread may touch the HIP runtime while this thread captures
-    with torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local"), paused():
+    with collector_at_rest(), torch.cuda.graph(graph, pool=pool, capture_error_mode="thread_local"), paused():
         body()
     return graph
 

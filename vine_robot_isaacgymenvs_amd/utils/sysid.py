@@ -158,6 +158,7 @@ class Evaluator:
 
     def run_window(self):
         import torch
+        from ..learning.graph_capture import collector_at_rest
         if not self.use_graph:
             for _ in range(self.horizon):
                 self.step()
@@ -165,7 +166,7 @@ class Evaluator:
             if self.graph is None:
                 torch.cuda.synchronize(self.device)
                 self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                with collector_at_rest(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                     for _ in range(self.horizon):
                         self.step()
             self.graph.replay()
