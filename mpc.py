@@ -11,18 +11,23 @@
   python mpc.py plants=64 steps=2000 'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1]}' \\
       'adapt={params: {DAMPING: [0.005, 0.1], FPAM_K: [0.7, 1.3]}, window: 8, every: 8}'   # the model follows each plant
 
+  python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True policy=runs/Vine5LinkMovingBase/nn/Vine5LinkMovingBase.pth \\
+      terminal_value=1.0                                                             # the samples roll this policy
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
 DESIGN.md section 25: ``params`` maps names of the ``ENV_PARAMS`` table to the range ``[lo, hi]`` the belief lives in; ``window``,
-``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``) and ``out`` (directory of the episode log's .npz; default
-``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT,
-in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
+``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``), ``policy`` (a checkpoint of ``train.py``:
+the samples roll it and the planner's sequence is a residual on its mean; the network is the composed
+configuration's ``train.params``; plants * samples must be a multiple of 512), ``terminal_value`` (the weight of the critic's
+value behind the horizon; default 0) and ``out`` (directory of the episode log's .npz; default ``runs/mpc``) are this tool's own
+keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
-       "model_params": None, "adapt": None, "out": "runs/mpc"}
+       "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "out": "runs/mpc"}
 
 
 def main(argv=None):
@@ -33,7 +38,7 @@ def main(argv=None):
     for arg in argv:
         key, eq, val = arg.partition("=")
         if eq and key in OWN:
-            own[key] = val if key == "out" else parse_scalar(val)
+            own[key] = val if key in ("out", "policy") else parse_scalar(val)
         else:
             overrides.append(arg)
     for key in ("cost", "model_params", "adapt"):
@@ -49,7 +54,8 @@ def main(argv=None):
     return mpc.play(task_cfg, plants=own["plants"], samples=own["samples"], horizon=own["horizon"], lam=own["lambda"],
                     sigma=own["sigma"], steps=int(own["steps"]), cost=own["cost"], model_params=own["model_params"],
                     seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
-                    adapt=own["adapt"])
+                    adapt=own["adapt"], policy=own["policy"], terminal_value=own["terminal_value"],
+                    policy_params=cfg["train"]["params"] if own["policy"] else None)
 
 
 if __name__ == "__main__":

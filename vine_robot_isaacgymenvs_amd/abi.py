@@ -850,6 +850,40 @@ def declare_mpc_adapt(lib):
     return lib
 
 
+# ---- include/vine_mpc_policy.h (product library only)
+MPC_POLICY_ABI_VERSION = 1
+MPC_POLICY_UNITS = 256
+MPC_POLICY_ROWS = 512
+
+
+class VineMpcPolicyConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("obs_width", C.c_int32),
+        ("ln_eps", C.c_float),
+        ("value_eps", C.c_float),
+        ("terminal_value", C.c_double),
+    ]
+
+
+_MPC_POLICY_HEAD = [_H, _P(VineMpcConfig), _P(VineMpcPolicyConfig)]
+MPC_POLICY_PROTOTYPES = {
+    "vine_mpc_policy_config_default": (C.c_int, [_P(VineMpcPolicyConfig)]),
+    "vine_mpc_policy_config_size": (C.c_int, []),
+    "vine_mpc_policy_fork": (C.c_int, [_H] + _MPC_POLICY_HEAD + [_VP, C.c_int32, _VP, C.c_int32] + [_VP] * 5 + [_I64, _VP]),
+    "vine_mpc_policy_act": (C.c_int, _MPC_POLICY_HEAD + [_VP] * 13),
+    "vine_mpc_policy_terminal": (C.c_int, _MPC_POLICY_HEAD + [_VP] * 10),
+    "vine_mpc_policy_compose": (C.c_int, _MPC_POLICY_HEAD + [_VP] * 5),
+}
+
+
+def declare_mpc_policy(lib):
+    _attach(lib, MPC_POLICY_PROTOTYPES)
+    if lib.vine_mpc_policy_config_size() != C.sizeof(VineMpcPolicyConfig):
+        raise RuntimeError("VineMpcPolicyConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -864,6 +898,6 @@ def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc,
-                        declare_mpc_adapt):
+                        declare_mpc_adapt, declare_mpc_policy):
         declare_one(lib)
     return lib

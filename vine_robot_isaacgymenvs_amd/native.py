@@ -36,6 +36,10 @@ ALL_UNITS = BUILD_UNITS + (SRC_MPC,)
 # LIB_UNITS, which is what build() compiles and links
 SRC_MPC_ADAPT = os.path.join(_HERE, "csrc", "vine_mpc_adapt.hip")
 LIB_UNITS = ALL_UNITS + (SRC_MPC_ADAPT,)
+# tests/test_mpc_adapt_cpu.py pins LIB_UNITS to those twelve in turn; the thirteenth, the controller's policy proposal, follows
+# them in POLICY_UNITS, which is what build() compiles and links
+SRC_MPC_POLICY = os.path.join(_HERE, "csrc", "vine_mpc_policy.hip")
+POLICY_UNITS = LIB_UNITS + (SRC_MPC_POLICY,)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -53,7 +57,8 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
                    SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
                    SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
-                   SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]}
+                   SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
+                   SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")]}
 # vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply
 # and an add (under -ffp-contract=fast hipcc fuses it on gfx950, a pragma in the source notwithstanding)
 # vine_env_adr.hip forms the same columns and the range in force: it switches contraction off itself, by a pragma in front of
@@ -64,12 +69,15 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # the same pragma and flag
 # vine_mpc.hip forms a sample's action, nominal + z * c, that numpy must reproduce bit for bit: the same pragma and flag
 # vine_mpc_adapt.hip forms a candidate's value, mean + z * std, and the belief's update in float64 the same way: the same again
+# vine_mpc_policy.hip forms an action, mu + d, and a cost, cost - w * V, that numpy must reproduce bit for bit: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
+                 SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
-        + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED])
+        + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
+        + [SRC_MPC_POLICY, os.path.join(_INC, "vine_mpc_policy.h")])
 
 _lib = None
 
@@ -108,7 +116,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The twelve translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The thirteen translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -121,7 +129,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in LIB_UNITS:
+    for src in POLICY_UNITS:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)

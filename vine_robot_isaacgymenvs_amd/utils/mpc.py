@@ -383,7 +383,7 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None, adapt=None):
+         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -395,7 +395,13 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     ``adapt``: a spec of ``mpc_adapt.adapt_config`` -- the model follows each plant online (include/vine_mpc_adapt.h), with
     ``forget_on_reset`` when the plant has ``ENV_PARAMS_PER_EPISODE``.  The result then holds ``adapt``: ``names``, the final
     ``mean`` and ``std`` [M, D], ``prior_mean``, and, where the plant carries an ``ENV_PARAMS`` table, ``truth`` and per name
-    the mean absolute error of the prior and of the final belief (printed too).  Without it nothing of this is launched."""
+    the mean absolute error of the prior and of the final belief (printed too).  Without it nothing of this is launched.
+
+    ``policy``: a checkpoint of ``train.py`` -- the samples roll that policy and the planner's sequence is a residual on its
+    mean (include/vine_mpc_policy.h, ``mpc_policy.PolicyController``); ``policy_params`` is the ``train.params`` block of the
+    composed configuration the network is built from, as ``train.py test=True`` builds it; ``terminal_value``: the weight of
+    the critic's value behind the horizon (0: the extra inference and the terminal launch are not issued).  The result then
+    holds ``policy`` (the path).  ``policy`` together with ``adapt`` is refused.  Without it nothing of this is launched."""
     import torch
     from . import episodes
     logger = logger or logging.getLogger(__name__)
@@ -406,6 +412,16 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
+    if policy is None and terminal_value:
+        raise ConfigError("mpc: terminal_value needs policy=<checkpoint>: the critic is the policy's")
+    if policy is not None:
+        from . import mpc_policy
+        if adapt is not None:
+            raise ConfigError("mpc: policy= together with adapt= is refused: the adaptive controller does not roll the policy yet")
+        if policy_params is None:
+            raise ConfigError("mpc: policy= needs policy_params, the train.params block the network is built from")
+        mpc_policy.check_shape(M, samples)
+        mpc_policy._eps("terminal_value", terminal_value)
     mcfg = model_config(cfg, M, samples, cost, logger)
     if model_params:
         env_params.spec_forms(model_params)
@@ -420,7 +436,15 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     model = None
     try:
         model = make_task(mcfg, device)
-        if adapt is None:
+        if policy is not None:
+            proposal = mpc_policy.PolicyProposal(policy_params, M * int(samples), int(plant.num_obs), plant.device)
+            proposal.restore(policy)
+            ctl = mpc_policy.PolicyController(plant, model, samples, proposal, horizon, lam, sigma, seed, graph=graph,
+                                              terminal_value=terminal_value)
+            if model_params:
+                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
+            print("mpc: the samples roll the policy of %s; terminal_value %g" % (policy, float(terminal_value)), flush=True)
+        elif adapt is None:
             ctl = Controller(plant, model, samples, horizon, lam, sigma, seed, graph=graph)
             if model_params:
                 ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
@@ -455,6 +479,8 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         out = {"report": None, "by_param": {}, "path": None, "control_steps_per_second": int(steps) / max(seconds, 1e-9),
                "plant_return": total.cpu().numpy(), "launches": dict(ctl.launches), "graphed": ctl.use_graph,
                "model_step_kernel": model.step_kernel_name, "model_table_bound": model.env_params is not None}
+        if policy is not None:
+            out["policy"] = policy
         print("mpc: %d control steps in %.3f s (%.4g control steps/s, %.4g model env-steps/s)" % (
             int(steps), seconds, out["control_steps_per_second"], out["control_steps_per_second"] * M * ctl.K * ctl.H), flush=True)
         if log is not None:
