@@ -14,6 +14,9 @@
   python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True policy=runs/Vine5LinkMovingBase/nn/Vine5LinkMovingBase.pth \\
       terminal_value=1.0                                                             # the samples roll this policy
 
+  python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True \\
+      'observe={DELAY: 3, HOLD: 0.1, NOISE_Q: 0.002, COMPENSATE: True}'              # the planner's own delayed, noisy sensor
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
@@ -21,13 +24,15 @@ DESIGN.md section 25: ``params`` maps names of the ``ENV_PARAMS`` table to the r
 ``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``), ``policy`` (a checkpoint of ``train.py``:
 the samples roll it and the planner's sequence is a residual on its mean; the network is the composed
 configuration's ``train.params``; plants * samples must be a multiple of 512), ``terminal_value`` (the weight of the critic's
-value behind the horizon; default 0) and ``out`` (directory of the episode log's .npz; default ``runs/mpc``) are this tool's own
-keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
+value behind the horizon; default 0), ``observe`` (the planner sees its plants through a sensing path of its own, DESIGN.md
+section 27: ``DELAY``, ``HOLD``, ``NOISE_Q``, ``NOISE_QD`` as ``ENV_SENSOR`` takes them, ``COMPENSATE``, ``CATCHUP``) and ``out``
+(directory of the episode log's .npz; default ``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
-       "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "out": "runs/mpc"}
+       "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "observe": None,
+       "out": "runs/mpc"}
 
 
 def main(argv=None):
@@ -41,7 +46,7 @@ def main(argv=None):
             own[key] = val if key in ("out", "policy") else parse_scalar(val)
         else:
             overrides.append(arg)
-    for key in ("cost", "model_params", "adapt"):
+    for key in ("cost", "model_params", "adapt", "observe"):
         if own[key] is not None and not hasattr(own[key], "keys"):
             raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -55,7 +60,7 @@ def main(argv=None):
                     sigma=own["sigma"], steps=int(own["steps"]), cost=own["cost"], model_params=own["model_params"],
                     seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
                     adapt=own["adapt"], policy=own["policy"], terminal_value=own["terminal_value"],
-                    policy_params=cfg["train"]["params"] if own["policy"] else None)
+                    policy_params=cfg["train"]["params"] if own["policy"] else None, observe=own["observe"])
 
 
 if __name__ == "__main__":

@@ -884,6 +884,43 @@ def declare_mpc_policy(lib):
     return lib
 
 
+# ---- include/vine_mpc_observe.h (product library only)
+MPC_OBSERVE_ABI_VERSION = 1
+MPC_OBSERVE_THREADS = 256
+MPC_OBSERVE_SLOTS = MAX_DELAY + 1
+MPC_OBSERVE_LOG = 2 * MAX_DELAY
+MPC_OBSERVE_RNG_NOISE = 10
+MPC_OBSERVE_RNG_HOLD = 11
+MPC_OBSERVE_NAMES = ("DELAY", "HOLD", "NOISE_Q", "NOISE_QD")       # the rows of the per-plant table
+VMO_DELAY, VMO_HOLD, VMO_NOISE_Q, VMO_NOISE_QD, VMO_NAMES = 0, 1, 2, 3, 4
+
+
+class VineMpcObserveConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_plants", C.c_int32),
+        ("catchup", C.c_int32),
+        ("compensate", C.c_int32),
+        ("seed", C.c_uint64),
+    ]
+
+
+MPC_OBSERVE_PROTOTYPES = {
+    "vine_mpc_observe_config_default": (C.c_int, [_P(VineMpcObserveConfig)]),
+    "vine_mpc_observe_config_size": (C.c_int, []),
+    "vine_mpc_observe_measure": (C.c_int, [_H, _P(VineMpcObserveConfig)] + [_VP] * 8),
+    "vine_mpc_observe_pin": (C.c_int, [_H, _H, _P(VineMpcObserveConfig)] + [_VP] * 12),
+    "vine_mpc_observe_catchup": (C.c_int, [_H, _H, _P(VineMpcObserveConfig), C.c_int32] + [_VP] * 12),
+}
+
+
+def declare_mpc_observe(lib):
+    _attach(lib, MPC_OBSERVE_PROTOTYPES)
+    if lib.vine_mpc_observe_config_size() != C.sizeof(VineMpcObserveConfig):
+        raise RuntimeError("VineMpcObserveConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -898,6 +935,6 @@ def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc,
-                        declare_mpc_adapt, declare_mpc_policy):
+                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe):
         declare_one(lib)
     return lib

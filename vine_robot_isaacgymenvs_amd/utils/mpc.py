@@ -383,7 +383,7 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None):
+         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -401,7 +401,13 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     mean (include/vine_mpc_policy.h, ``mpc_policy.PolicyController``); ``policy_params`` is the ``train.params`` block of the
     composed configuration the network is built from, as ``train.py test=True`` builds it; ``terminal_value``: the weight of
     the critic's value behind the horizon (0: the extra inference and the terminal launch are not issued).  The result then
-    holds ``policy`` (the path).  ``policy`` together with ``adapt`` is refused.  Without it nothing of this is launched."""
+    holds ``policy`` (the path).  ``policy`` together with ``adapt`` is refused.  Without it nothing of this is launched.
+
+    ``observe``: a spec of ``mpc_observe.observe_config`` -- the planner sees each plant through a delayed, noisy sensor of
+    its own and predicts the delivered frame forward through a third task, the predictor (include/vine_mpc_observe.h,
+    ``mpc_observe.ObservingController``).  The result then holds ``observe``: the per-plant ``table`` [4, M], its ``names``,
+    ``catchup``, ``compensate`` and the mean ``lag``.  ``observe`` together with ``adapt`` or ``policy`` is refused.  Without
+    it nothing of this is constructed or launched."""
     import torch
     from . import episodes
     logger = logger or logging.getLogger(__name__)
@@ -412,6 +418,13 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
+    if observe is not None:
+        from . import mpc_observe
+        if adapt is not None:
+            raise ConfigError("mpc: observe= together with adapt= is refused: the adaptive controller traces the plant's exact state")
+        if policy is not None:
+            raise ConfigError("mpc: observe= together with policy= is refused: the policy's memory is forked from the plant's exact state")
+        mpc_observe.observe_config(observe)
     if policy is None and terminal_value:
         raise ConfigError("mpc: terminal_value needs policy=<checkpoint>: the critic is the policy's")
     if policy is not None:
@@ -433,10 +446,20 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     if adapt is not None and not mcfg["env"].get("ENV_PARAMS"):
         mcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}      # binds a table that holds the configuration's own row: what is adapted
     plant = make_task(cfg, device)
-    model = None
+    model = predictor = None
     try:
         model = make_task(mcfg, device)
-        if policy is not None:
+        if observe is not None:                          # the model's plant once more, one env per real plant
+            pcfg = copy.deepcopy(mcfg)
+            pcfg["env"]["numEnvs"] = M
+            predictor = make_task(pcfg, device)
+            ctl = mpc_observe.ObservingController(plant, model, predictor, samples, observe, horizon, lam, sigma, seed, graph=graph)
+            if model_params:
+                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
+            print("mpc: observing through DELAY %s, HOLD %s, NOISE_Q %s, NOISE_QD %s; %d catch-up steps, %s" % (
+                ctl.spec["DELAY"], ctl.spec["HOLD"], ctl.spec["NOISE_Q"], ctl.spec["NOISE_QD"], ctl.C,
+                "compensated" if ctl.spec["COMPENSATE"] else "not compensated"), flush=True)
+        elif policy is not None:
             proposal = mpc_policy.PolicyProposal(policy_params, M * int(samples), int(plant.num_obs), plant.device)
             proposal.restore(policy)
             ctl = mpc_policy.PolicyController(plant, model, samples, proposal, horizon, lam, sigma, seed, graph=graph,
@@ -481,6 +504,9 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
                "model_step_kernel": model.step_kernel_name, "model_table_bound": model.env_params is not None}
         if policy is not None:
             out["policy"] = policy
+        if observe is not None:
+            out["observe"] = {"names": list(mpc_observe.NAMES), "table": ctl.table_host.copy(), "catchup": ctl.C,
+                              "compensate": ctl.spec["COMPENSATE"], "lag": float(ctl.lag.double().mean())}
         print("mpc: %d control steps in %.3f s (%.4g control steps/s, %.4g model env-steps/s)" % (
             int(steps), seconds, out["control_steps_per_second"], out["control_steps_per_second"] * M * ctl.K * ctl.H), flush=True)
         if log is not None:
@@ -517,6 +543,8 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
                     name, out["adapt"]["prior_error"][name], out["adapt"]["final_error"][name]), flush=True)
         return out
     finally:
+        if predictor is not None:
+            predictor.close()
         if model is not None:
             model.close()
         plant.close()
