@@ -17,6 +17,9 @@
   python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True \\
       'observe={DELAY: 3, HOLD: 0.1, NOISE_Q: 0.002, COMPENSATE: True}'              # the planner's own delayed, noisy sensor
 
+  python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True 'observe={DELAY: 1, NOISE_Q: 0.01, NOISE_QD: 0.1}' \\
+      'filter={GAIN_Q: 0.3, GAIN_QD: {values: [0.1, 0.3, 1.0]}}'                     # ... averaged over successive frames
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
@@ -25,13 +28,14 @@ DESIGN.md section 25: ``params`` maps names of the ``ENV_PARAMS`` table to the r
 the samples roll it and the planner's sequence is a residual on its mean; the network is the composed
 configuration's ``train.params``; plants * samples must be a multiple of 512), ``terminal_value`` (the weight of the critic's
 value behind the horizon; default 0), ``observe`` (the planner sees its plants through a sensing path of its own, DESIGN.md
-section 27: ``DELAY``, ``HOLD``, ``NOISE_Q``, ``NOISE_QD`` as ``ENV_SENSOR`` takes them, ``COMPENSATE``, ``CATCHUP``) and ``out``
+section 27: ``DELAY``, ``HOLD``, ``NOISE_Q``, ``NOISE_QD`` as ``ENV_SENSOR`` takes them, ``COMPENSATE``, ``CATCHUP``), ``filter``
+(a fixed-gain corrector over those frames, DESIGN.md section 28: ``GAIN_Q``, ``GAIN_QD`` in [0, 1]; needs ``observe``) and ``out``
 (directory of the episode log's .npz; default ``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
-       "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "observe": None,
+       "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "observe": None, "filter": None,
        "out": "runs/mpc"}
 
 
@@ -46,7 +50,7 @@ def main(argv=None):
             own[key] = val if key in ("out", "policy") else parse_scalar(val)
         else:
             overrides.append(arg)
-    for key in ("cost", "model_params", "adapt", "observe"):
+    for key in ("cost", "model_params", "adapt", "observe", "filter"):
         if own[key] is not None and not hasattr(own[key], "keys"):
             raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -60,7 +64,8 @@ def main(argv=None):
                     sigma=own["sigma"], steps=int(own["steps"]), cost=own["cost"], model_params=own["model_params"],
                     seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
                     adapt=own["adapt"], policy=own["policy"], terminal_value=own["terminal_value"],
-                    policy_params=cfg["train"]["params"] if own["policy"] else None, observe=own["observe"])
+                    policy_params=cfg["train"]["params"] if own["policy"] else None, observe=own["observe"],
+                    filter=own["filter"])
 
 
 if __name__ == "__main__":

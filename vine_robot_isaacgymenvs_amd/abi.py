@@ -921,6 +921,26 @@ def declare_mpc_observe(lib):
     return lib
 
 
+# ---- include/vine_mpc_filter.h (product library only)
+MPC_FILTER_ABI_VERSION = 1
+MPC_FILTER_THREADS = 256
+MPC_FILTER_NAMES = ("GAIN_Q", "GAIN_QD")                          # the rows of the per-plant gain table
+VMF_GAIN_Q, VMF_GAIN_QD, VMF_NAMES = 0, 1, 2
+
+MPC_FILTER_PROTOTYPES = {
+    "vine_mpc_filter_abi_version": (C.c_int, []),
+    "vine_mpc_filter_pin": (C.c_int, [_H, _H, _P(VineMpcObserveConfig)] + [_VP] * 12),
+    "vine_mpc_filter_correct": (C.c_int, [_H, _H, _P(VineMpcObserveConfig)] + [_VP] * 9),
+}
+
+
+def declare_mpc_filter(lib):
+    _attach(lib, MPC_FILTER_PROTOTYPES)
+    if lib.vine_mpc_filter_abi_version() != MPC_FILTER_ABI_VERSION:
+        raise RuntimeError("vine_mpc_filter.h: the library's ABI version differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -935,6 +955,6 @@ def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc,
-                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe):
+                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter):
         declare_one(lib)
     return lib

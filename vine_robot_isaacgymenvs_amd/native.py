@@ -43,6 +43,9 @@ POLICY_UNITS = LIB_UNITS + (SRC_MPC_POLICY,)
 # tests/test_mpc_policy_cpu.py pins POLICY_UNITS to those thirteen in turn, and the loop of build() over them; the fourteenth, the
 # controller's sensing path, follows them there: build() compiles and links POLICY_UNITS + (SRC_MPC_OBSERVE,)
 SRC_MPC_OBSERVE = os.path.join(_HERE, "csrc", "vine_mpc_observe.hip")
+# tests/test_mpc_observe_cpu.py pins that spelling of the loop; the fifteenth, the corrector over the sensing path's frames,
+# follows it there: build() compiles and links POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,)
+SRC_MPC_FILTER = os.path.join(_HERE, "csrc", "vine_mpc_filter.hip")
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -62,7 +65,8 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
                    SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")],
-                   SRC_MPC_OBSERVE: [os.path.join(_INC, "vine_mpc_observe.h"), _MPC_SHARED]}
+                   SRC_MPC_OBSERVE: [os.path.join(_INC, "vine_mpc_observe.h"), _MPC_SHARED],
+                   SRC_MPC_FILTER: [os.path.join(_INC, "vine_mpc_observe.h"), os.path.join(_INC, "vine_mpc_filter.h"), _MPC_SHARED]}
 # vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply
 # and an add (under -ffp-contract=fast hipcc fuses it on gfx950, a pragma in the source notwithstanding)
 # vine_env_adr.hip forms the same columns and the range in force: it switches contraction off itself, by a pragma in front of
@@ -75,15 +79,18 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # vine_mpc_adapt.hip forms a candidate's value, mean + z * std, and the belief's update in float64 the same way: the same again
 # vine_mpc_policy.hip forms an action, mu + d, and a cost, cost - w * V, that numpy must reproduce bit for bit: the same again
 # vine_mpc_observe.hip forms a measured joint value, q + z * c, that numpy must reproduce bit for bit: the same again
+# vine_mpc_filter.hip forms a corrected joint value, x + g * (y - x), that numpy must reproduce bit for bit: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_OBSERVE: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_OBSERVE: ["-ffp-contract=fast-honor-pragmas"],
+                 SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
         + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
         + [SRC_MPC_POLICY, os.path.join(_INC, "vine_mpc_policy.h")]
-        + [SRC_MPC_OBSERVE, os.path.join(_INC, "vine_mpc_observe.h")])
+        + [SRC_MPC_OBSERVE, os.path.join(_INC, "vine_mpc_observe.h")]
+        + [SRC_MPC_FILTER, os.path.join(_INC, "vine_mpc_filter.h")])
 
 _lib = None
 
@@ -122,7 +129,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The fourteen translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The fifteen translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -135,7 +142,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,):
+    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)

@@ -383,7 +383,7 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None):
+         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -407,6 +407,13 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     its own and predicts the delivered frame forward through a third task, the predictor (include/vine_mpc_observe.h,
     ``mpc_observe.ObservingController``).  The result then holds ``observe``: the per-plant ``table`` [4, M], its ``names``,
     ``catchup``, ``compensate`` and the mean ``lag``.  ``observe`` together with ``adapt`` or ``policy`` is refused.  Without
+    it nothing of this is constructed or launched.
+
+    ``filter``: a spec of ``mpc_filter.filter_config`` -- a fixed-gain corrector over successive frames (include/vine_mpc_filter.h,
+    ``mpc_filter.FilteringController``): the pin and the catch-up are delivered its estimate instead of the raw frame.  It needs
+    ``observe=`` and is refused together with ``adapt`` or ``policy``, and where the largest ``DELAY`` plus the model's largest
+    ``ACTION_DELAY`` reaches beyond the action log.  The result then holds ``filter``: the per-plant ``gain`` [2, M], its
+    ``names`` and the mean ``innov`` [2]; the per-parameter report has ``param_FILTER_<NAME>`` for a gain that varies.  Without
     it nothing of this is constructed or launched."""
     import torch
     from . import episodes
@@ -418,13 +425,26 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
+    if filter is not None:
+        from . import mpc_filter
+        if observe is None:
+            raise ConfigError("mpc: filter= needs observe=: the frames it corrects are the sensing path's")
+        if adapt is not None:
+            raise ConfigError("mpc: filter= together with adapt= is refused: the adaptive controller traces the plant's exact state")
+        if policy is not None:
+            raise ConfigError("mpc: filter= together with policy= is refused: the policy's memory is forked from the plant's exact state")
+        mpc_filter.filter_config(filter)
     if observe is not None:
         from . import mpc_observe
         if adapt is not None:
             raise ConfigError("mpc: observe= together with adapt= is refused: the adaptive controller traces the plant's exact state")
         if policy is not None:
             raise ConfigError("mpc: observe= together with policy= is refused: the policy's memory is forked from the plant's exact state")
-        mpc_observe.observe_config(observe)
+        checked = mpc_observe.observe_config(observe)
+        if filter is not None:
+            if model_params:
+                env_params.spec_forms(model_params)
+            mpc_filter.largest_reach(checked, mpc_filter.model_action_delay(cfg["env"], model_params))
     if policy is None and terminal_value:
         raise ConfigError("mpc: terminal_value needs policy=<checkpoint>: the critic is the policy's")
     if policy is not None:
@@ -453,12 +473,18 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
             pcfg = copy.deepcopy(mcfg)
             pcfg["env"]["numEnvs"] = M
             predictor = make_task(pcfg, device)
-            ctl = mpc_observe.ObservingController(plant, model, predictor, samples, observe, horizon, lam, sigma, seed, graph=graph)
+            if filter is not None:
+                ctl = mpc_filter.FilteringController(plant, model, predictor, samples, observe, filter, horizon, lam, sigma, seed,
+                                                     graph=graph)
+            else:
+                ctl = mpc_observe.ObservingController(plant, model, predictor, samples, observe, horizon, lam, sigma, seed, graph=graph)
             if model_params:
                 ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
             print("mpc: observing through DELAY %s, HOLD %s, NOISE_Q %s, NOISE_QD %s; %d catch-up steps, %s" % (
                 ctl.spec["DELAY"], ctl.spec["HOLD"], ctl.spec["NOISE_Q"], ctl.spec["NOISE_QD"], ctl.C,
                 "compensated" if ctl.spec["COMPENSATE"] else "not compensated"), flush=True)
+            if filter is not None:
+                print("mpc: filtering with GAIN_Q %s, GAIN_QD %s" % (ctl.filter_spec["GAIN_Q"], ctl.filter_spec["GAIN_QD"]), flush=True)
         elif policy is not None:
             proposal = mpc_policy.PolicyProposal(policy_params, M * int(samples), int(plant.num_obs), plant.device)
             proposal.restore(policy)
@@ -507,6 +533,11 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         if observe is not None:
             out["observe"] = {"names": list(mpc_observe.NAMES), "table": ctl.table_host.copy(), "catchup": ctl.C,
                               "compensate": ctl.spec["COMPENSATE"], "lag": float(ctl.lag.double().mean())}
+        if filter is not None:
+            out["filter"] = {"names": list(mpc_filter.NAMES), "gain": ctl.gain_host.copy(),
+                             "innov": ctl.innov.double().mean(dim=1).cpu().numpy()}
+            print("mpc: mean lag %.3g, mean innovation (sum of squares) q %.4g, qd %.4g" % (
+                out["observe"]["lag"], out["filter"]["innov"][0], out["filter"]["innov"][1]), flush=True)
         print("mpc: %d control steps in %.3f s (%.4g control steps/s, %.4g model env-steps/s)" % (
             int(steps), seconds, out["control_steps_per_second"], out["control_steps_per_second"] * M * ctl.K * ctl.H), flush=True)
         if log is not None:
@@ -515,6 +546,10 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
             rows = log.rows_with_params() if plant.env_params is not None else log.rows()
             keep = rows["end_step"] >= start
             rows = {k: v[keep] for k, v in rows.items()}
+            if filter is not None:                       # a gain that varies over the plants is a parameter of the report
+                for slot, name in enumerate(mpc_filter.DRAW_NAMES):
+                    if len(np.unique(ctl.gain_host[slot])) > 1:
+                        rows["param_" + name] = ctl.gain_host[slot][rows["env"]]
             out["report"] = episodes.report(rows)
             print(format_report(out["report"]), flush=True)
             for column in [k for k in rows if k.startswith("param_")]:
