@@ -678,6 +678,53 @@ def declare_env_push(lib):
     return lib
 
 
+# ---- include/vine_env_target.h (product library only)
+ENV_TARGET_ABI_VERSION = 1
+ENV_TARGET_THREADS = 256
+# VineEnvTargetSlot = the rows of the target table; the draw's name keys are those of "TARGET_" + name
+ENV_TARGET_NAMES = ["VEL_ALONG", "VEL_ACROSS", "SPAN_ALONG", "SPAN_ACROSS"]
+VTG_VEL_ALONG, VTG_VEL_ACROSS, VTG_SPAN_ALONG, VTG_SPAN_ACROSS = range(4)
+VTG_NAMES = 4
+# VineEnvTargetRow = the rows of the observer's own per-env state
+(VTM_ANCHOR_Y, VTM_ANCHOR_Z, VTM_DEPTH0, VTM_AXIS_C, VTM_AXIS_S, VTM_OFF_ALONG, VTM_OFF_ACROSS, VTM_VEL_ALONG,
+ VTM_VEL_ACROSS) = range(9)
+VTM_COUNT = 9
+TARGET_FREE, TARGET_SHELF, TARGET_PIPE = range(3)
+
+
+class VineEnvTargetSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_values", C.c_int32),
+        ("seed", C.c_uint64),
+        ("values", C.c_void_p),
+        ("name", VineEnvRedrawName * VTG_NAMES),
+        ("mode", C.c_int32),
+        ("num_obs", C.c_int32),
+        ("vel_column", C.c_int32),
+        ("per_episode", C.c_int32),
+        ("cdt", C.c_float),
+        ("clip_observations", C.c_float),
+        ("inv_obs_scale", C.c_float * 2),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+ENV_TARGET_PROTOTYPES = {
+    "vine_env_target_spec_size": (C.c_int, []),
+    "vine_env_target_spec": (C.c_int, [_P(VineConfig), _P(VineEnvRedrawName), _VP, _VP, C.c_int, C.c_int, _P(VineEnvTargetSpec)]),
+    "vine_env_target_scheduled": (C.c_int, [_H, _P(VineEnvTargetSpec)] + [_VP] * 8),
+}
+
+
+def declare_env_target(lib):
+    _attach(lib, ENV_TARGET_PROTOTYPES)
+    if lib.vine_env_target_spec_size() != C.sizeof(VineEnvTargetSpec):
+        raise RuntimeError("VineEnvTargetSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_env_adr.h (product library only)
 ENV_ADR_ABI_VERSION = 1
 ENV_ADR_THREADS = 256
@@ -954,7 +1001,7 @@ def declare(lib):
 def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
-                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_sysid, declare_mpc,
+                        declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
                         declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter):
         declare_one(lib)
     return lib

@@ -35,6 +35,11 @@ Deviations from the reference's defaults (each documented in DESIGN.md / INTEGRA
     impulse at one of POINTS (0 the cart, m the distal end of link m - 1, 5 the tip; default [5]), applied on the device
     behind the step to the six generalised velocities through the step's own mass matrix; PER_EPISODE redraws the two values
     at every reset; the step kernels are untouched; utils/env_push.py),
+  task.env.ENV_TARGET {} (not a reference key; VEL_ALONG, VEL_ACROSS, SPAN_ALONG, SPAN_ACROSS -- each a number, [lo, hi] or
+    {values: [...]} -- give every env a target that moves during the episode: at VEL m/s along +y / +z in free space, or along
+    the depth axis of the shelf or the pipe, turning round SPAN m either side of where the reset put it; advanced on the device
+    behind the step, which also puts the target's velocity into the observation; PER_EPISODE redraws the four values at every
+    reset; the step kernels are untouched; utils/env_target.py),
   train.params.config.mixed_precision_dtype (not an rl_games key): fp16 (the reference's autocast dtype) = the hand-written
     mixed-precision update with device-side loss scaling; train.params.config.rollout_precision: fp32 (the reference's),
   task.env.physicsModel.* (switches of the built-in articulation solver; not reference keys),
@@ -121,6 +126,7 @@ TASK = {
          'ENV_PARAMS_ADR': {},
          'ENV_SENSOR': {},
          'ENV_PUSH': {},
+         'ENV_TARGET': {},
          'CREATE_SHELF': False,
          'CREATE_PIPE': True,
          'CREATE_HISTOGRAMS_PERIODICALLY': False,

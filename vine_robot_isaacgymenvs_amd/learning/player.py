@@ -123,9 +123,10 @@ class PpoPlayerContinuous(FastInferenceMixin):
         if getattr(env, "episode_log", None) is not None and env.episode_log.table is not None:
             print(self._binned_report(env))
             # ENV_PARAMS: the same rate against every varying parameter; ENV_SENSOR: and against the sensor's values; ENV_PUSH:
-            # and against the push's (by impulse: how large a kick the checkpoint survives)
+            # and against the push's (by impulse: how large a kick the checkpoint survives); ENV_TARGET: and against the target's (by
+            # velocity: how fast a target the checkpoint still reaches)
             if (getattr(env, "env_params", None) is not None or getattr(env, "env_sensor", None) is not None
-                    or getattr(env, "env_push", None) is not None):
+                    or getattr(env, "env_push", None) is not None or getattr(env, "env_target", None) is not None):
                 print(self._param_report(env))
         return mean_r, mean_l
 
@@ -158,9 +159,10 @@ class PpoPlayerContinuous(FastInferenceMixin):
         the envs: by exact value where the envs hold at most ``exact`` distinct ones (a ``values`` entry of ``ENV_PARAMS``),
         else by bin.  Also kept in ``self.report["by_param"]``: name -> (values or bin edges, rate, episode count)."""
         from ..utils import episodes
-        # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode; ENV_SENSOR / ENV_PUSH: the log joins their values to its rows
+        # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode; ENV_SENSOR / ENV_PUSH / ENV_TARGET: the log joins their values
+        # to its rows
         if (getattr(env, "env_redraw", None) is not None or getattr(env, "env_sensor", None) is not None
-                or getattr(env, "env_push", None) is not None):
+                or getattr(env, "env_push", None) is not None or getattr(env, "env_target", None) is not None):
             rows = env.episode_log.rows_with_params()
             keep = rows["end_step"] >= self._episodes_start[1]
             rows = {k: v[keep] for k, v in rows.items()}

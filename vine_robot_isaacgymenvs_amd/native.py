@@ -46,6 +46,9 @@ SRC_MPC_OBSERVE = os.path.join(_HERE, "csrc", "vine_mpc_observe.hip")
 # tests/test_mpc_observe_cpu.py pins that spelling of the loop; the fifteenth, the corrector over the sensing path's frames,
 # follows it there: build() compiles and links POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,)
 SRC_MPC_FILTER = os.path.join(_HERE, "csrc", "vine_mpc_filter.hip")
+# tests/test_mpc_filter_cpu.py pins that spelling in turn; the sixteenth, the moving target's, follows it there: build() compiles
+# and links POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,)
+SRC_TARGET = os.path.join(_HERE, "csrc", "vine_env_target.hip")
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -62,6 +65,7 @@ _MPC_SHARED = os.path.join(_HERE, "csrc", "vine_mpc_shared.h")      # the fork's
 _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
                    SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
                    SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
+                   SRC_TARGET: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h")],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
                    SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")],
@@ -80,17 +84,20 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # vine_mpc_policy.hip forms an action, mu + d, and a cost, cost - w * V, that numpy must reproduce bit for bit: the same again
 # vine_mpc_observe.hip forms a measured joint value, q + z * c, that numpy must reproduce bit for bit: the same again
 # vine_mpc_filter.hip forms a corrected joint value, x + g * (y - x), that numpy must reproduce bit for bit: the same again
+# vine_env_target.hip forms an offset, off + vel * cdt, a target, ay - off * c, and an observation column, obs + w * inv, that
+# numpy must reproduce bit for bit: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_OBSERVE: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"], SRC_TARGET: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
         + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
         + [SRC_MPC_POLICY, os.path.join(_INC, "vine_mpc_policy.h")]
         + [SRC_MPC_OBSERVE, os.path.join(_INC, "vine_mpc_observe.h")]
-        + [SRC_MPC_FILTER, os.path.join(_INC, "vine_mpc_filter.h")])
+        + [SRC_MPC_FILTER, os.path.join(_INC, "vine_mpc_filter.h")]
+        + [SRC_TARGET, os.path.join(_INC, "vine_env_target.h")])
 
 _lib = None
 
@@ -129,7 +136,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The fifteen translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The sixteen translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -142,7 +149,7 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,):
+    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)

@@ -151,6 +151,7 @@ class Vine5LinkMovingBase(VecTask):
         self._env_redraw = None
         self._env_sensor = None
         self._env_push = None
+        self._env_target = None
         self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log,
                                    # the per-episode redraw of the plants (last: it replaces what the others read)
 
@@ -163,6 +164,9 @@ class Vine5LinkMovingBase(VecTask):
         self._sensor_cfg = env_sensor.sensor_config(self.cfg["env"], self.cfg["env"]["numObservations"])
         from ..utils import env_push
         self._push_cfg = env_push.push_config(self.cfg["env"])
+        from ..utils import env_target
+        self._target_cfg = env_target.target_config(self.cfg["env"], env_target.control_period(
+            self.cfg["sim"]["dt"], self.cfg["env"].get("controlFrequencyInv", 1)))
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -192,6 +196,8 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_trajectory()
         if self._on_rank0("EPISODE_LOG", "logged"):
             self._setup_episode_log()
+        if self._target_cfg is not None:         # every rank, by the global env id; behind the observers that account for the
+            self._setup_env_target()             # step as the plant left it, in front of the sensor, which senses its velocity
         if self._sensor_cfg is not None:         # every rank: each senses its own shard, by the global env id; in front of
             self._setup_env_sensor()             # the redraw, which stays last
         if self._push_cfg is not None:           # every rank, by the global env id; behind the sensor (which has then sensed
@@ -392,6 +398,29 @@ class Vine5LinkMovingBase(VecTask):
     def env_push(self):
         """The ``EnvPush`` of this env (``None`` unless ``ENV_PUSH``)."""
         return self._env_push
+
+    # ------------------------------------------------------------------ ENV_TARGET (include/vine_env_target.h)
+    def _setup_env_target(self):
+        """A launch behind every step carries each env's target one control step along its bounded path in the state block
+        the next step reads, and adds the target's velocity to the observation the step wrote (utils/env_target.py).  The
+        step kernels are not touched: the four-lane kernel and the fused rollout step stay."""
+        from ..utils import env_target
+        if self.mat is not None:
+            raise NotImplementedError("ENV_TARGET with MAT_FILE: the replay overwrites the target before every step")
+        self._env_target = self._add_observer(env_target.EnvTarget(
+            self._lib, self._handle, self._vcfg, self._target_cfg, self.reset_buf, self.progress_buf, self.num_envs, self.num_obs,
+            self.device))
+        if self._episode_log is not None:
+            self._episode_log.target = self._env_target
+        varying = env_target.varying_names(self._target_cfg)
+        self.logger.info(f"ENV_TARGET: targets move in {env_target.MODES[self._target_cfg['MODE']]} mode; "
+                         f"{', '.join(varying) or 'nothing'} varies"
+                         f"{', redrawn at every reset' if self._target_cfg['PER_EPISODE'] else ''}")
+
+    @property
+    def env_target(self):
+        """The ``EnvTarget`` of this env (``None`` unless ``ENV_TARGET``)."""
+        return self._env_target
 
     # ------------------------------------------------------------------ ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h)
     def _setup_env_redraw(self):
@@ -651,7 +680,7 @@ class Vine5LinkMovingBase(VecTask):
                 o.drain()
                 o.close()
             self._observers, self._video, self._trajectory, self._episode_log, self._env_redraw = [], None, None, None, None
-            self._env_sensor = self._env_push = None
+            self._env_sensor = self._env_push = self._env_target = None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -728,6 +757,8 @@ class Vine5LinkMovingBase(VecTask):
             self.env_adr.reset_envs(ids)
         if self._env_sensor is not None:         # ENV_SENSOR: their next frame is an episode's first
             self._env_sensor.reset_envs(ids)
+        if self._env_target is not None:         # ENV_TARGET: ... and their target starts from where this reset put it
+            self._env_target.reset_envs(ids)
 
     # ------------------------------------------------------------------ metrics side channel (V5:1250-1322)
     def collect_stats(self):

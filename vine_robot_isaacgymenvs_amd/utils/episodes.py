@@ -223,8 +223,14 @@ def with_push_params(rows, push_params):
     return with_sensor_params(rows, push_params)
 
 
+def with_target_params(rows, target_params):
+    """ENV_TARGET: ``rows`` with ``param_TARGET_VEL_ALONG`` .. ``param_TARGET_SPAN_ACROSS`` for the names that vary, joined as
+    ``with_sensor_params`` joins the sensor's: held values by env, per-episode ones by the row's ``episode``."""
+    return with_sensor_params(rows, target_params)
+
+
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
-         redraw=None, adr=None, sensor=None, push=None):
+         redraw=None, adr=None, sensor=None, push=None, target=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
     bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
@@ -235,8 +241,16 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
     first step: zeros, or a restored checkpoint's).  With ENV_SENSOR (``sensor``: a dict of ``spec``, ``seed`` and
     ``env_id_offset``) what ``load_env_sensor`` needs to rebuild the ``param_SENSOR_*`` columns without a device, and, where
     the rows carry one, their ``episode`` column.  With ENV_PUSH (``push``: a dict of the same three keys) the same for the
-    ``param_PUSH_*`` columns (``load_env_push``)."""
+    ``param_PUSH_*`` columns (``load_env_push``), with ENV_TARGET (``target``) for the ``param_TARGET_*`` columns
+    (``load_env_target``)."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
+    if target is not None:
+        import json
+        out["target_spec"] = np.array(json.dumps(target["spec"]))
+        out["target_seed"] = np.array(int(target["seed"]), dtype=np.uint64)
+        out["target_env_id_offset"] = np.array(int(target["env_id_offset"]), dtype=np.int64)
+        if "episode" in rows:
+            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
     if push is not None:
         import json
         out["push_spec"] = np.array(json.dumps(push["spec"]))
@@ -393,8 +407,10 @@ def load_rows_with_params(path):
     ENV_SENSOR also the ``param_SENSOR_*`` columns."""
     _, sensor_episode, sensor_params = load_env_sensor(path)
     _, push_episode, push_params = load_env_push(path)
+    _, target_episode, target_params = load_env_target(path)
     rows = _load_rows_with_plant_params(path)
-    for episode, params, join in ((sensor_episode, sensor_params, with_sensor_params), (push_episode, push_params, with_push_params)):
+    for episode, params, join in ((sensor_episode, sensor_params, with_sensor_params), (push_episode, push_params, with_push_params),
+                                  (target_episode, target_params, with_target_params)):
         if params is None:
             continue
         if episode is not None:
@@ -418,6 +434,23 @@ def load_env_push(path):
     def push_params(envs, episodes_):
         return env_push.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
     return spec, episode, push_params
+
+
+def load_env_target(path):
+    """Of a file written under ENV_TARGET: ``(spec, episode [R] or None, target_params)`` with ``target_params(envs, episodes)``
+    -> ``env_target.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
+    ``(None, None, None)``."""
+    import json
+    from . import env_target
+    with np.load(path) as z:
+        if "target_spec" not in z.files:
+            return None, None, None
+        spec, seed, offset = json.loads(str(z["target_spec"][()])), int(z["target_seed"]), int(z["target_env_id_offset"])
+        episode = z["episode"] if "episode" in z.files else None
+
+    def target_params(envs, episodes_):
+        return env_target.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
+    return spec, episode, target_params
 
 
 def _load_rows_with_plant_params(path):
@@ -475,6 +508,7 @@ class EpisodeLog:
         self.unknown_plants = 0      # ENV_PARAMS_ADR: rows of the last rows_with_params() whose plant is unknown (NaN)
         self.sensor = None           # ENV_SENSOR: the task's ``env_sensor.EnvSensor``; under its PER_EPISODE rows carry ``episode``
         self.push = None             # ENV_PUSH: the task's ``env_push.EnvPush``; likewise
+        self.target = None           # ENV_TARGET: the task's ``env_target.EnvTarget``; likewise
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -501,6 +535,8 @@ class EpisodeLog:
             return self.sensor
         if self.push is not None and self.push.spec["PER_EPISODE"]:      # ENV_PUSH: likewise
             return self.push
+        if self.target is not None and self.target.spec["PER_EPISODE"]:  # ENV_TARGET: likewise
+            return self.target
         return None
 
     def reset_envs(self, env_ids):
@@ -573,11 +609,14 @@ class EpisodeLog:
     def rows_with_params(self):
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
         (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env.  Under
-        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``), under ENV_PUSH ``param_PUSH_*`` (``with_push_params``)."""
+        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``), under ENV_PUSH ``param_PUSH_*`` (``with_push_params``), under
+        ENV_TARGET ``param_TARGET_*`` (``with_target_params``)."""
         out = self._rows_with_plant_params()
         if self.sensor is not None:
             out = with_sensor_params(out, self.sensor.episode_params)
-        return with_push_params(out, self.push.episode_params) if self.push is not None else out
+        if self.push is not None:
+            out = with_push_params(out, self.push.episode_params)
+        return with_target_params(out, self.target.episode_params) if self.target is not None else out
 
     def _rows_with_plant_params(self):
         rows = self.rows()
@@ -622,8 +661,11 @@ class EpisodeLog:
         push = None
         if self.push is not None:
             push = {"spec": self.push.spec, "seed": self.push.seed, "env_id_offset": self.push.env_id_offset}
+        target = None
+        if self.target is not None:
+            target = {"spec": self.target.spec, "seed": self.target.seed, "env_id_offset": self.target.env_id_offset}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names, redraw, adr, sensor, push)
+             self.env_inertia_names, redraw, adr, sensor, push, target)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -80,6 +80,7 @@ FORCED = (
     ("env", "ENV_PARAMS_ADR", {}),
     ("env", "ENV_SENSOR", {}),                     # the planner reads the state as it is
     ("env", "ENV_PUSH", {}),                       # ... and nothing but its own actions moves a sample
+    ("env", "ENV_TARGET", {}),                     # ... and no target moves by itself
 )
 
 

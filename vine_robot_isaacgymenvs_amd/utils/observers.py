@@ -30,8 +30,11 @@ rewrites the observation the step has just written (``wants_obs``); it reads the
 writes, and stands in front of the redraw, which stays last.  ``env_push.EnvPush`` (ENV_PUSH) adds impulses to the six
 generalised velocities of the state block the step has just written.  It stands behind every observer that reads that block
 -- the video, the recorder and the episode log account for the step as the plant left it -- and behind the sensor, and in
-front of the redraw: it reads the inertia table's column of the episode that has just run, which the redraw replaces.  So
-the order is: video, recorder, episode log, sensor, push, redraw / ADR.
+front of the redraw: it reads the inertia table's column of the episode that has just run, which the redraw replaces.
+``env_target.EnvTarget`` (ENV_TARGET) moves the target in the state block for the NEXT step and adds the target's velocity to
+the observation the step has just written (``wants_obs``).  It stands behind the video, the recorder and the episode log,
+which must see the target the step used, and in front of the sensor, which then delays and perturbs the velocity columns
+with the rest of the frame.  So the order is: video, recorder, episode log, target, sensor, push, redraw / ADR.
 
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer
