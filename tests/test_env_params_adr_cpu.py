@@ -73,9 +73,12 @@ def test_header_equals_the_mirror_and_the_struct_size(lib):
     assert flags.index("-ffp-contract=fast-honor-pragmas") > flags.index("-ffp-contract=fast")      # (the later one wins)
     source = open(native.SRC_ADR).read()
     assert source.index("#pragma clang fp contract(off)") < source.index("#include")
-    draw = open(os.path.join(os.path.dirname(native.SRC_ADR), "vine_env_redraw_draw.h")).read()
-    for function in ("mix64", "redraw_u", "redraw_value", "redraw_column", "names_inertia"):      # stated once, in the header
-        assert re.search(r"inline \w[\w ]* %s\(" % function, draw), function
+    csrc = os.path.dirname(native.SRC_ADR)
+    draw = open(os.path.join(csrc, "vine_env_redraw_draw.h")).read()
+    assert '#include "vine_named_draw.h"' in draw and any(d.endswith("vine_named_draw.h") for d in native.DEPS)
+    draw += open(os.path.join(csrc, "vine_named_draw.h")).read()      # (the named draw itself: what the column header includes)
+    for function in ("mix64", "redraw_u", "redraw_value", "redraw_column", "names_inertia"):      # stated once, in the headers
+        assert len(re.findall(r"inline \w[\w ]* %s\(" % function, draw)) == 1, function
         assert not re.search(r"inline \w[\w ]* %s\(" % function, open(native.SRC_REDRAW).read()), function
 
 

@@ -99,7 +99,7 @@ def test_header_equals_the_mirror_the_struct_size_and_the_build_wiring(lib):
     assert native.BUILD_UNITS == native.UNITS + (native.SRC_PUSH,) and len(native.BUILD_UNITS) == 10 and len(native.UNITS) == 9
     assert native.SRC_PUSH in native.DEPS and any(d.endswith("vine_env_push.h") for d in native.DEPS)
     headers = native._SOURCE_HEADERS[native.SRC_PUSH]
-    assert any(d.endswith("vine_env_push.h") for d in headers) and any(d.endswith("vine_env_redraw_draw.h") for d in headers)
+    assert any(d.endswith("vine_env_push.h") for d in headers) and any(d.endswith("vine_named_draw.h") for d in headers)
     flags = native._flags(native.SRC_PUSH)
     assert flags.index("-ffp-contract=fast-honor-pragmas") > flags.index("-ffp-contract=fast") and "-ffp-contract=off" not in flags
     source = open(native.SRC_PUSH).read()

@@ -83,7 +83,7 @@ def test_header_equals_the_mirror_the_struct_size_and_the_build_wiring(lib):
     assert os.path.basename(native.SRC_TARGET) == "vine_env_target.hip" and os.path.exists(native.SRC_TARGET)
     assert native.SRC_TARGET in native.DEPS and any(d.endswith("vine_env_target.h") for d in native.DEPS)
     headers = native._SOURCE_HEADERS[native.SRC_TARGET]
-    assert any(d.endswith("vine_env_target.h") for d in headers) and any(d.endswith("vine_env_redraw_draw.h") for d in headers)
+    assert any(d.endswith("vine_env_target.h") for d in headers) and any(d.endswith("vine_named_draw.h") for d in headers)
     assert native._SOURCE_FLAGS[native.SRC_TARGET] == ["-ffp-contract=fast-honor-pragmas"]
     flags = native._flags(native.SRC_TARGET)
     assert flags.index("-ffp-contract=fast-honor-pragmas") > flags.index("-ffp-contract=fast") and "-ffp-contract=off" not in flags
@@ -317,7 +317,7 @@ def test_sysid_and_mpc_force_it_off_and_the_test_entry_keeps_it_on(caplog, monke
 
 # ----------------------------------------------------------------------------------------------------------- the draw
 def redraw_value64(form, key_name, seed, g, k, radix=1):
-    """``redraw_value`` of csrc/vine_env_redraw_draw.h in Python integers and floats, one (g, k) at a time."""
+    """``redraw_value`` of csrc/vine_named_draw.h in Python integers and floats, one (g, k) at a time."""
     m64 = (1 << 64) - 1
 
     def mix(x):

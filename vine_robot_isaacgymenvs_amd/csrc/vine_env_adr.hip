@@ -29,10 +29,6 @@ constexpr int BOUNDARIES = 2 * VR_NAMES;
 static_assert(BOUNDARIES <= 64, "decide is one wave, one lane per boundary");
 static_assert(2 * BOUNDARIES <= THREADS, "the workgroup's counts are flushed by its first 2 * BOUNDARIES lanes");
 
-const char* const kNames[VR_NAMES] = {
-    "DAMPING", "SMOOTHING_ALPHA_INFLATE", "SMOOTHING_ALPHA_DEFLATE", "RAIL_VELOCITY_SCALE", "RAIL_P_GAIN", "RAIL_D_GAIN",
-    "RAIL_ACCELERATION", "ACTION_DELAY", "FPAM_K", "FPAM_C", "FPAM_b", "FPAM_B", "CART_MASS", "LINK_MASS", "TIP_LINK_MASS"};
-
 // the boundary of slot s, side 0 = lo / 1 = hi, after w steps outward
 __host__ __device__ inline double adr_bound(const VineEnvAdrSpec& A, int s, int side, int w) {
     const VineEnvAdrName& a = A.name[s];
@@ -164,11 +160,7 @@ __global__ __launch_bounds__(THREADS) void vine_env_adr_redraw_kernel(const Vine
     }
 }
 
-int bad_name(int s, const char* why) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "env adr spec: %s: %s", kNames[s], why);
-    return vine_invalid_arg(msg);
-}
+int bad_name(int s, const char* why) { return named_refusal("env adr spec", kRedrawNames[s], why); }
 
 }  // namespace
 

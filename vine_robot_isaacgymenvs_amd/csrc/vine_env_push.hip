@@ -8,7 +8,7 @@
 // and stores six velocities.  The launch is latency-bound at rollout sizes (profiles/env_sensor/node_cost.txt), not byte-bound.
 //
 // CONTRACTION IS OFF FOR THIS WHOLE TRANSLATION UNIT, by the pragma in front of everything it includes (native.py compiles it
-// with -ffp-contract=fast-honor-pragmas; plain "fast" ignores the pragma): the draw of vine_env_redraw_draw.h must hold the
+// with -ffp-contract=fast-honor-pragmas; plain "fast" ignores the pragma): the draw of vine_named_draw.h must hold the
 // host's bits, and the solve is then the float32 statement numpy makes, product by product.
 #pragma clang fp contract(off)
 
@@ -18,14 +18,15 @@
 #include <cstring>
 
 #include "../../include/vine_env_push.h"
-#include "vine_env_redraw_draw.h"
+#include "vine_named_draw.h"
 #include "vine_observer.h"
 #include "vine_policy_head.h"
 
 namespace {
 
 constexpr int THREADS = VINE_ENV_PUSH_THREADS;
-constexpr int ND = VINE_NUM_LINKS + 1;
+constexpr int NL = VINE_NUM_LINKS;
+constexpr int ND = NL + 1;
 constexpr int NC = VINE_PUSH_COMPOSITES;
 static_assert(VI_COUNT - VI_MTOT == NC && VI_B0 == VI_MTOT + 1 && VI_GB0 == VI_B0 + NL && VI_ADIAG0 == VI_GB0 + NL &&
                   VI_AOFF1 == VI_ADIAG0 + NL,
@@ -128,23 +129,12 @@ __global__ __launch_bounds__(THREADS) void vine_env_push_kernel(const VineEnvPus
         }
     }
 
-    if (S.per_episode && flagged) {
-        const int k = episode_index[e] + 1;
-        episode_index[e] = k;
-        const unsigned long long gg = (unsigned long long)env_off + (unsigned long long)e;
-#pragma unroll
-        for (int q = 0; q < VPU_NAMES; ++q)
-            table[(size_t)q * n + e] = (float)redraw_value(S.name[q], false, S.values, S.seed, gg, (unsigned long long)(long long)k);
-    }
+    if (S.per_episode && flagged) VINE_NAMED_REDRAW_ROWS(VPU_NAMES, S.name, 0u, S.values, S.seed, env_off, e, n, table, episode_index);
 }
 
 const char* const kNames[VPU_NAMES] = {"PUSH_RATE", "PUSH_IMPULSE"};
 
-int bad_name(int s, const char* why) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "env push spec: %s: %s", kNames[s], why);
-    return vine_invalid_arg(msg);
-}
+int bad_name(int s, const char* why) { return named_refusal("env push spec", kNames[s], why); }
 
 // is v a value the name may take?  (what the kernel would write into the table: the float32 of it)
 const char* bad_value(int s, double v) {
@@ -188,33 +178,9 @@ int vine_env_push_spec(const VineConfig* cfg, const VineEnvRedrawName names[VPU_
     for (int s = 0; s < VPU_NAMES; ++s) {
         const VineEnvRedrawName& nm = names[s];
         S.name[s] = nm;
-        bool zero = false;
-        if (nm.reserved != 0) return bad_name(s, "reserved must be 0");
-        if (nm.form == VINE_REDRAW_NUMBER) {
-            if (!std::isfinite(nm.lo)) return bad_name(s, "the number is not finite");
-            if (const char* why = bad_value(s, nm.lo)) return bad_name(s, why);
-            zero = nm.lo == 0.0;
-        } else if (nm.form == VINE_REDRAW_RANGE) {
-            if (!std::isfinite(nm.lo) || !std::isfinite(nm.hi) || nm.lo > nm.hi) return bad_name(s, "a range needs finite lo <= hi");
-            if (const char* why = bad_value(s, nm.lo)) return bad_name(s, why);
-            if (const char* why = bad_value(s, nm.hi)) return bad_name(s, why);
-            zero = nm.hi == 0.0;
-        } else if (nm.form == VINE_REDRAW_VALUES) {
-            if (nm.values_count < 1 || nm.values_first < 0 || (long long)nm.values_first + nm.values_count > num_values)
-                return bad_name(s, "the extent of the value list lies outside the values array");
-            if (nm.radix < 1) return bad_name(s, "radix must be at least 1");
-            zero = true;
-            for (int i = 0; i < nm.values_count; ++i) {
-                const double v = host_values[nm.values_first + i];
-                if (!std::isfinite(v)) return bad_name(s, "a listed value is not finite");
-                if (const char* why = bad_value(s, v)) return bad_name(s, why);
-                zero = zero && v == 0.0;
-            }
-        } else if (nm.form == VINE_REDRAW_ABSENT) {
-            return bad_name(s, "absent: every name needs a number, a range or a value list");
-        } else {
-            return bad_name(s, "unknown form");
-        }
+        const NamedCheck c = named_check(nm, host_values, num_values, false, [s](double v) { return bad_value(s, v); });
+        if (c.why) return bad_name(s, c.why);
+        const bool zero = c.hi == 0.0;           // (no value is negative: the largest is zero where all are)
         if (zero && !S.per_episode) return bad_name(s, "constant zero: nothing to do");
     }
     S.checked = 1u;

@@ -70,14 +70,7 @@ __global__ __launch_bounds__(THREADS) void vine_env_redraw_kernel(const VineEnvR
     }
 }
 
-int bad_name(int s, const char* why) {
-    static const char* const kNames[VR_NAMES] = {
-        "DAMPING", "SMOOTHING_ALPHA_INFLATE", "SMOOTHING_ALPHA_DEFLATE", "RAIL_VELOCITY_SCALE", "RAIL_P_GAIN", "RAIL_D_GAIN",
-        "RAIL_ACCELERATION", "ACTION_DELAY", "FPAM_K", "FPAM_C", "FPAM_b", "FPAM_B", "CART_MASS", "LINK_MASS", "TIP_LINK_MASS"};
-    char msg[200];
-    snprintf(msg, sizeof msg, "env redraw spec: %s: %s", kNames[s], why);
-    return vine_invalid_arg(msg);
-}
+int bad_name(int s, const char* why) { return named_refusal("env redraw spec", kRedrawNames[s], why); }
 
 // a refusal of the table checks, which saw candidate column i as a table of one env: "of env 0" -> "of candidate i"
 int refused_candidate(int rc, int i) {
@@ -117,25 +110,16 @@ int vine_env_redraw_spec(const VineConfig* cfg, const VineEnvRedrawName names[VR
     for (int s = 0; s < VR_NAMES; ++s) {
         const VineEnvRedrawName& nm = names[s];
         S.name[s] = nm;
-        if (nm.reserved != 0) return bad_name(s, "reserved must be 0");
+        const NamedCheck c = named_check(nm, host_values, num_values, true, any_value);
+        if (c.why) return bad_name(s, c.why);
         if (nm.form == VINE_REDRAW_ABSENT) continue;
         any = true;
-        if (nm.form == VINE_REDRAW_NUMBER) {
-            if (!std::isfinite(nm.lo)) return bad_name(s, "the number is not finite");
-        } else if (nm.form == VINE_REDRAW_RANGE) {
-            if (!std::isfinite(nm.lo) || !std::isfinite(nm.hi) || nm.lo > nm.hi) return bad_name(s, "a range needs finite lo <= hi");
+        if (nm.form == VINE_REDRAW_RANGE) {
             if (s == VR_ACTION_DELAY && (nm.lo != std::floor(nm.lo) || nm.hi != std::floor(nm.hi)))
                 return bad_name(s, "an integer parameter takes an integer range");
             if (width < 2) width = 2;
-        } else if (nm.form == VINE_REDRAW_VALUES) {
-            if (nm.values_count < 1 || nm.values_first < 0 || (long long)nm.values_first + nm.values_count > num_values)
-                return bad_name(s, "the extent of the value list lies outside the values array");
-            if (nm.radix < 1) return bad_name(s, "radix must be at least 1");
-            for (int i = 0; i < nm.values_count; ++i)
-                if (!std::isfinite(host_values[nm.values_first + i])) return bad_name(s, "a listed value is not finite");
-            if (width < nm.values_count) width = nm.values_count;
-        } else {
-            return bad_name(s, "unknown form");
+        } else if (nm.form == VINE_REDRAW_VALUES && width < nm.values_count) {
+            width = nm.values_count;
         }
     }
     if (!any) return vine_invalid_arg("env redraw spec: no name is present, nothing to redraw");

@@ -1,20 +1,17 @@
-// vine_env_redraw_draw.h — the draw of ENV_PARAMS_PER_EPISODE, stated once for the two translation units that form table
-// columns on the device: vine_env_redraw.hip (include/vine_env_redraw.h) and vine_env_adr.hip (include/vine_env_adr.h).
+// vine_env_redraw_draw.h — what the two translation units that form table COLUMNS on the device share beyond the named draw
+// itself (vine_named_draw.h, which this includes): vine_env_redraw.hip (include/vine_env_redraw.h) and vine_env_adr.hip
+// (include/vine_env_adr.h).
 //
 // BOTH ARE COMPILED WITHOUT FLOATING-POINT CONTRACTION (native.py): `a + b * c` must stay a multiply and an add, each rounded,
 // as numpy and the host pass form it.
 //
-// `redraw_value` and `redraw_column` are host and device functions: the spec functions form the candidates they check with
+// `redraw_column` is a host and device function, as `redraw_value` is: the spec functions form the candidates they check with
 // the statements the kernels form their columns with.
 #ifndef VINE_ENV_REDRAW_DRAW_H
 #define VINE_ENV_REDRAW_DRAW_H
 
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-
-#include "../../include/vine_env_redraw.h"
 #include "vine_inertia_composites.h"
+#include "vine_named_draw.h"
 
 namespace {
 
@@ -22,41 +19,10 @@ constexpr int NL = VINE_NUM_LINKS;
 static_assert(VR_NAMES == 15 && VR_FPAM_K == 8 && VR_CART_MASS == 12, "slots 0..7 are rows 0..7, 8..11 the FPAM vectors");
 static_assert(VP_FPAM_K0 == 8 && VP_FPAM_C0 == 13 && VP_FPAM_b0 == 18 && VP_FPAM_B0 == 23 && VP_COUNT == 28, "FPAM rows");
 
-__host__ __device__ inline unsigned long long mix64(unsigned long long x) {      // splitmix64's finaliser
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// u in [0, 1) of (seed, key, global env id g, episode k); k == 0 gives utils/env_params.py uniform01
-__host__ __device__ inline double redraw_u(unsigned long long seed, unsigned long long key, unsigned long long g,
-                                           unsigned long long k) {
-    const unsigned long long pre = mix64(seed ^ key) + g * 0x9E3779B97F4A7C15ull;
-    const unsigned long long h = mix64(pre ^ mix64(k));
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// the value of one name (present: form != ABSENT) for env g in episode k
-__host__ __device__ inline double redraw_value(const VineEnvRedrawName& nm, bool integer, const double* values,
-                                               unsigned long long seed, unsigned long long g, unsigned long long k) {
-    if (nm.form == VINE_REDRAW_NUMBER) return nm.lo;
-    if (nm.form == VINE_REDRAW_VALUES) {
-        const unsigned long long count = (unsigned long long)nm.values_count;
-        unsigned long long i;
-        if (k == 0ull) {
-            i = (g / nm.radix) % count;
-        } else {
-            const double u = redraw_u(seed, nm.key, g, k);
-            i = (unsigned long long)floor(u * (double)nm.values_count);
-            if (i > count - 1ull) i = count - 1ull;
-        }
-        return values[(size_t)nm.values_first + i];
-    }
-    const double u = redraw_u(seed, nm.key, g, k);
-    const double lo = nm.lo, hi = nm.hi;
-    if (integer) return fmin(lo + floor(u * (hi - lo + 1.0)), hi);
-    return lo + (hi - lo) * u;
-}
+// the names of a spec's slots (VineEnvRedrawSlot), as a refusal words them
+const char* const kRedrawNames[VR_NAMES] = {
+    "DAMPING", "SMOOTHING_ALPHA_INFLATE", "SMOOTHING_ALPHA_DEFLATE", "RAIL_VELOCITY_SCALE", "RAIL_P_GAIN", "RAIL_D_GAIN",
+    "RAIL_ACCELERATION", "ACTION_DELAY", "FPAM_K", "FPAM_C", "FPAM_b", "FPAM_B", "CART_MASS", "LINK_MASS", "TIP_LINK_MASS"};
 
 // the two columns of an env from the per-name values v (read where the name is present): pcol = the parameter table's 28
 // rows (the base's where a name is absent), icol = the inertia table's 31, the derived rows from the primary ones

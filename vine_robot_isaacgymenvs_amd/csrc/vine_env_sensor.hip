@@ -9,7 +9,7 @@
 //
 // CONTRACTION IS OFF FOR THIS WHOLE TRANSLATION UNIT, by the pragma in front of everything it includes (native.py compiles it
 // with -ffp-contract=fast-honor-pragmas; plain "fast" ignores the pragma): `obs + z * c` must stay a multiply and an add,
-// each rounded, as numpy forms it, and the draw of vine_env_redraw_draw.h likewise.
+// each rounded, as numpy forms it, and the draw of vine_named_draw.h likewise.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -18,7 +18,7 @@
 #include <cstring>
 
 #include "../../include/vine_env_sensor.h"
-#include "vine_env_redraw_draw.h"
+#include "vine_named_draw.h"
 #include "vine_observer.h"
 #include "vine_policy_head.h"
 
@@ -40,7 +40,7 @@ __device__ __forceinline__ float2 pack(const float (&o)[2]) { return make_float2
 // 1 / sqrt(32 * (65536^2 - 1) / 12): the deviate's scale, in float64 (host and device form it by the same statement)
 __host__ __device__ inline double sensor_noise_scale() { return 1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0); }
 
-__host__ __device__ inline bool sensor_integer(int s) { return s == VSN_DELAY; }
+constexpr unsigned INTEGER_NAMES = 1u << VSN_DELAY;      // the names whose range is over the integers
 
 template <int NOBS>
 __global__ __launch_bounds__(THREADS) void vine_env_sensor_kernel(const VineEnvSensorSpec S, const int n, const unsigned env_off,
@@ -141,23 +141,12 @@ __global__ __launch_bounds__(THREADS) void vine_env_sensor_kernel(const VineEnvS
     }
     if (is_fresh) fresh[e] = 0;
 
-    if (S.per_episode && reset[e] != 0) {
-        const int k = episode_index[e] + 1;
-        episode_index[e] = k;
-        const unsigned long long gg = (unsigned long long)env_off + (unsigned long long)e;
-#pragma unroll
-        for (int q = 0; q < VSN_NAMES; ++q)
-            table[(size_t)q * n + e] = (float)redraw_value(S.name[q], sensor_integer(q), S.values, S.seed, gg, (unsigned long long)(long long)k);
-    }
+    if (S.per_episode && reset[e] != 0) VINE_NAMED_REDRAW_ROWS(VSN_NAMES, S.name, INTEGER_NAMES, S.values, S.seed, env_off, e, n, table, episode_index);
 }
 
 const char* const kNames[VSN_NAMES] = {"SENSOR_DELAY", "SENSOR_HOLD", "SENSOR_NOISE_STD"};
 
-int bad_name(int s, const char* why) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "env sensor spec: %s: %s", kNames[s], why);
-    return vine_invalid_arg(msg);
-}
+int bad_name(int s, const char* why) { return named_refusal("env sensor spec", kNames[s], why); }
 
 // is v a value the name may take?  (what the kernel would write into the table: the float32 of it)
 const char* bad_value(int s, double v) {
@@ -207,31 +196,9 @@ int vine_env_sensor_spec(const VineConfig* cfg, const VineEnvRedrawName names[VS
     for (int s = 0; s < VSN_NAMES; ++s) {
         const VineEnvRedrawName& nm = names[s];
         S.name[s] = nm;
-        if (nm.reserved != 0) return bad_name(s, "reserved must be 0");
-        if (nm.form == VINE_REDRAW_NUMBER) {
-            if (!std::isfinite(nm.lo)) return bad_name(s, "the number is not finite");
-            if (const char* why = bad_value(s, nm.lo)) return bad_name(s, why);
-            all_zero = all_zero && nm.lo == 0.0;
-        } else if (nm.form == VINE_REDRAW_RANGE) {
-            if (!std::isfinite(nm.lo) || !std::isfinite(nm.hi) || nm.lo > nm.hi) return bad_name(s, "a range needs finite lo <= hi");
-            if (const char* why = bad_value(s, nm.lo)) return bad_name(s, why);
-            if (const char* why = bad_value(s, nm.hi)) return bad_name(s, why);
-            all_zero = all_zero && nm.hi == 0.0;
-        } else if (nm.form == VINE_REDRAW_VALUES) {
-            if (nm.values_count < 1 || nm.values_first < 0 || (long long)nm.values_first + nm.values_count > num_values)
-                return bad_name(s, "the extent of the value list lies outside the values array");
-            if (nm.radix < 1) return bad_name(s, "radix must be at least 1");
-            for (int i = 0; i < nm.values_count; ++i) {
-                const double v = host_values[nm.values_first + i];
-                if (!std::isfinite(v)) return bad_name(s, "a listed value is not finite");
-                if (const char* why = bad_value(s, v)) return bad_name(s, why);
-                all_zero = all_zero && v == 0.0;
-            }
-        } else if (nm.form == VINE_REDRAW_ABSENT) {
-            return bad_name(s, "absent: every name needs a number, a range or a value list");
-        } else {
-            return bad_name(s, "unknown form");
-        }
+        const NamedCheck c = named_check(nm, host_values, num_values, false, [s](double v) { return bad_value(s, v); });
+        if (c.why) return bad_name(s, c.why);
+        all_zero = all_zero && c.hi == 0.0;      // (no value is negative: the largest is zero where all are)
     }
     if (all_zero && !S.per_episode)
         return vine_invalid_arg("env sensor spec: SENSOR_DELAY, SENSOR_HOLD and SENSOR_NOISE_STD are all constant zero: nothing to do");

@@ -9,7 +9,7 @@
 //
 // CONTRACTION IS OFF FOR THIS WHOLE TRANSLATION UNIT, by the pragma in front of everything it includes (native.py compiles it
 // with -ffp-contract=fast-honor-pragmas; plain "fast" ignores the pragma): `obs + w * inv`, `off + vel * cdt` and
-// `ay - off * c` must stay a multiply and an add, each rounded, as numpy forms them, and the draw of vine_env_redraw_draw.h
+// `ay - off * c` must stay a multiply and an add, each rounded, as numpy forms them, and the draw of vine_named_draw.h
 // must hold the host's bits.
 #pragma clang fp contract(off)
 
@@ -19,7 +19,7 @@
 #include <cstring>
 
 #include "../../include/vine_env_target.h"
-#include "vine_env_redraw_draw.h"
+#include "vine_named_draw.h"
 #include "vine_observer.h"
 
 namespace {
@@ -128,25 +128,14 @@ __global__ __launch_bounds__(THREADS) void vine_env_target_kernel(const VineEnvT
         MO(VTM_VEL_ACROSS) = vc;
     }
 
-    if (S.per_episode && flagged) {
-        const int k = episode_index[e] + 1;
-        episode_index[e] = k;
-        const unsigned long long gg = (unsigned long long)env_off + (unsigned long long)e;
-#pragma unroll
-        for (int q = 0; q < VTG_NAMES; ++q)
-            table[(size_t)q * n + e] = (float)redraw_value(S.name[q], false, S.values, S.seed, gg, (unsigned long long)(long long)k);
-    }
+    if (S.per_episode && flagged) VINE_NAMED_REDRAW_ROWS(VTG_NAMES, S.name, 0u, S.values, S.seed, env_off, e, n, table, episode_index);
 #undef ST
 #undef MO
 }
 
 const char* const kNames[VTG_NAMES] = {"TARGET_VEL_ALONG", "TARGET_VEL_ACROSS", "TARGET_SPAN_ALONG", "TARGET_SPAN_ACROSS"};
 
-int bad_name(int s, const char* why) {
-    char msg[240];
-    snprintf(msg, sizeof msg, "env target spec: %s: %s", kNames[s], why);
-    return vine_invalid_arg(msg);
-}
+int bad_name(int s, const char* why) { return named_refusal("env target spec", kNames[s], why); }
 
 bool is_span(int s) { return s == VTG_SPAN_ALONG || s == VTG_SPAN_ACROSS; }
 
@@ -211,31 +200,9 @@ int vine_env_target_spec(const VineConfig* cfg, const VineEnvRedrawName names[VT
     for (int s = 0; s < VTG_NAMES; ++s) {
         const VineEnvRedrawName& nm = names[s];
         S.name[s] = nm;
-        if (nm.reserved != 0) return bad_name(s, "reserved must be 0");
-        double lo, hi;
-        if (nm.form == VINE_REDRAW_NUMBER) {
-            if (!std::isfinite(nm.lo)) return bad_name(s, "the number is not finite");
-            lo = hi = nm.lo;
-        } else if (nm.form == VINE_REDRAW_RANGE) {
-            if (!std::isfinite(nm.lo) || !std::isfinite(nm.hi) || nm.lo > nm.hi) return bad_name(s, "a range needs finite lo <= hi");
-            lo = nm.lo;
-            hi = nm.hi;
-        } else if (nm.form == VINE_REDRAW_VALUES) {
-            if (nm.values_count < 1 || nm.values_first < 0 || (long long)nm.values_first + nm.values_count > num_values)
-                return bad_name(s, "the extent of the value list lies outside the values array");
-            if (nm.radix < 1) return bad_name(s, "radix must be at least 1");
-            lo = hi = host_values[nm.values_first];
-            for (int i = 0; i < nm.values_count; ++i) {
-                const double v = host_values[nm.values_first + i];
-                if (!std::isfinite(v)) return bad_name(s, "a listed value is not finite");
-                lo = v < lo ? v : lo;
-                hi = v > hi ? v : hi;
-            }
-        } else if (nm.form == VINE_REDRAW_ABSENT) {
-            return bad_name(s, "absent: every name needs a number, a range or a value list");
-        } else {
-            return bad_name(s, "unknown form");
-        }
+        const NamedCheck c = named_check(nm, host_values, num_values, false, any_value);
+        if (c.why) return bad_name(s, c.why);
+        const double lo = c.lo, hi = c.hi;
         if (is_span(s) && !(lo >= 0.0)) return bad_name(s, "must not be negative");
         if (!std::isfinite((float)lo) || !std::isfinite((float)hi)) return bad_name(s, "does not fit a float32");
         max_abs[s] = fmaxf(fabsf((float)lo), fabsf((float)hi));

@@ -4,7 +4,7 @@
 // handle, a host-derived column and a device-derived column of the same float32 masses hold the same bits -- PROVIDED the
 // translation unit that runs this on the device is compiled without floating-point contraction (native.py gives
 // vine_env_redraw.hip -ffp-contract=off; the host pass targets baseline x86-64, which has no fused multiply-add).
-// Also the hidden accessor of what a redraw needs of a handle.  Not part of the C ABI.
+// Not part of the C ABI.
 #ifndef VINE_INERTIA_COMPOSITES_H
 #define VINE_INERTIA_COMPOSITES_H
 
@@ -31,9 +31,5 @@ __host__ __device__ inline void inertia_composites(float cart_mass, const float*
         o.aoff[i] = L * o.b[i];
     }
 }
-
-// The tables bound to a handle and the global id of its env 0 (vine_hip.hip).
-extern "C" __attribute__((visibility("hidden"))) int vine_env_tables_of(VineHandle* h, const float** params, const float** inertia,
-                                                                        unsigned* env_id_offset);
 
 #endif

@@ -26,6 +26,9 @@ extern "C" {
 __attribute__((visibility("hidden"))) int vine_handle_info(VineHandle* h, VineHandleInfo* out);
 __attribute__((visibility("hidden"))) const float* vine_reward_matrix_of(VineHandle* h);   // the bound [N,13] matrix, or NULL
 __attribute__((visibility("hidden"))) void vine_set_error(const char* msg);    // sets vine_last_error()'s thread-local text
+// the tables bound to a handle (NULL where none is) and the global id of its env 0
+__attribute__((visibility("hidden"))) int vine_env_tables_of(VineHandle* h, const float** params, const float** inertia,
+                                                             unsigned* env_id_offset);
 }
 
 // The steps completed, from the handle's counter pair (vine_hip.hip step_of says why it has this form): what the step kernels

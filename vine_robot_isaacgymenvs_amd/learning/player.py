@@ -53,6 +53,14 @@ def format_report(report):
     return "\n".join("  " + line for line in lines)
 
 
+DRAW_OBSERVERS = ("env_sensor", "env_push", "env_target")      # whose named draws the episode log joins to its rows
+
+
+def _has_any(env, *names):
+    """Is one of the env's properties ``names`` there and not ``None``?"""
+    return any(getattr(env, name, None) is not None for name in names)
+
+
 class PpoPlayerContinuous(FastInferenceMixin):
     def __init__(self, params, vec_env=None):
         self.config = config = params["config"]
@@ -125,8 +133,7 @@ class PpoPlayerContinuous(FastInferenceMixin):
             # ENV_PARAMS: the same rate against every varying parameter; ENV_SENSOR: and against the sensor's values; ENV_PUSH:
             # and against the push's (by impulse: how large a kick the checkpoint survives); ENV_TARGET: and against the target's (by
             # velocity: how fast a target the checkpoint still reaches)
-            if (getattr(env, "env_params", None) is not None or getattr(env, "env_sensor", None) is not None
-                    or getattr(env, "env_push", None) is not None or getattr(env, "env_target", None) is not None):
+            if _has_any(env, "env_params", *DRAW_OBSERVERS):
                 print(self._param_report(env))
         return mean_r, mean_l
 
@@ -161,8 +168,7 @@ class PpoPlayerContinuous(FastInferenceMixin):
         from ..utils import episodes
         # ENV_PARAMS_PER_EPISODE: the plant of every row's own episode; ENV_SENSOR / ENV_PUSH / ENV_TARGET: the log joins their values
         # to its rows
-        if (getattr(env, "env_redraw", None) is not None or getattr(env, "env_sensor", None) is not None
-                or getattr(env, "env_push", None) is not None or getattr(env, "env_target", None) is not None):
+        if _has_any(env, "env_redraw", *DRAW_OBSERVERS):
             rows = env.episode_log.rows_with_params()
             keep = rows["end_step"] >= self._episodes_start[1]
             rows = {k: v[keep] for k, v in rows.items()}

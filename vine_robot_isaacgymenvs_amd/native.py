@@ -60,12 +60,15 @@ _HEADERS = ([os.path.join(_INC, h) for h in ("vine.h", "vine_ppo.h", "vine_rende
                                                         "vine_policy_head.h", "vine_ppo_formulas.h")])
 # what only some translation units include and compile with: the others' objects do not depend on it
 _COMPOSITES = os.path.join(_HERE, "csrc", "vine_inertia_composites.h")
-_REDRAW_HEADERS = [_COMPOSITES, os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
+# the named draw (csrc/vine_named_draw.h): what the sensor, the push and the target include of it; the redraw and ADR also
+# form table columns (csrc/vine_env_redraw_draw.h, which needs the composites)
+_NAMED_DRAW_HEADERS = [os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HERE, "csrc", "vine_named_draw.h")]
+_REDRAW_HEADERS = [_COMPOSITES] + _NAMED_DRAW_HEADERS + [os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
 _MPC_SHARED = os.path.join(_HERE, "csrc", "vine_mpc_shared.h")      # the fork's and the pin's column copy and ring rebuild
 _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
-                   SRC_SENSOR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
-                   SRC_PUSH: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
-                   SRC_TARGET: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h")],
+                   SRC_SENSOR: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
+                   SRC_PUSH: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
+                   SRC_TARGET: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h")],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
                    SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")],

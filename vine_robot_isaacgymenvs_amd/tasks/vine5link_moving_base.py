@@ -360,20 +360,27 @@ class Vine5LinkMovingBase(VecTask):
         """The ``EpisodeLog`` of this env (``None`` unless ``EPISODE_LOG``)."""
         return self._episode_log
 
+    # ------------------------------------------------------------------ the three observers with a table of named draws
+    def _add_table_observer(self, key, observer, what):
+        """What ENV_SENSOR, ENV_PUSH and ENV_TARGET do alike with their observer: into the launch order, onto the episode log
+        (whose attribute ``key.lower()`` it becomes), and one log line: ``what``, then which names vary."""
+        from ..utils import named_draw
+        self._add_observer(observer)
+        if self._episode_log is not None:
+            setattr(self._episode_log, key.lower(), observer)
+        varying = ", ".join(named_draw.varying(observer.NAMES, observer.spec))
+        self.logger.info(f"ENV_{key}: {what}; {varying or 'nothing'} varies"
+                         f"{', redrawn at every reset' if observer.spec['PER_EPISODE'] else ''}")
+        return observer
+
     # ------------------------------------------------------------------ ENV_SENSOR (include/vine_env_sensor.h)
     def _setup_env_sensor(self):
         """A launch behind every step rewrites the observation that step wrote: per-env delay, dropped frames and noise
         (utils/env_sensor.py).  The step kernels are not touched: the four-lane kernel and the fused rollout step stay."""
         from ..utils import env_sensor
-        self._env_sensor = self._add_observer(env_sensor.EnvSensor(
+        self._env_sensor = self._add_table_observer("SENSOR", env_sensor.EnvSensor(
             self._lib, self._handle, self._vcfg, self._sensor_cfg, self.reset_buf, self.progress_buf, self.num_envs, self.num_obs,
-            self.device))
-        if self._episode_log is not None:
-            self._episode_log.sensor = self._env_sensor
-        varying = env_sensor.varying_names(self._sensor_cfg)
-        self.logger.info(f"ENV_SENSOR: delay, dropped frames and noise on {len(self._sensor_cfg['COLUMNS'])} of {self.num_obs} "
-                         f"observation columns; {', '.join(varying) or 'nothing'} varies"
-                         f"{', redrawn at every reset' if self._sensor_cfg['PER_EPISODE'] else ''}")
+            self.device), f"delay, dropped frames and noise on {len(self._sensor_cfg['COLUMNS'])} of {self.num_obs} observation columns")
 
     @property
     def env_sensor(self):
@@ -386,13 +393,9 @@ class Vine5LinkMovingBase(VecTask):
         to the six generalised velocities (utils/env_push.py).  The step kernels are not touched: the four-lane kernel and
         the fused rollout step stay."""
         from ..utils import env_push
-        self._env_push = self._add_observer(env_push.EnvPush(
-            self._lib, self._handle, self._vcfg, self._push_cfg, self.reset_buf, self.num_envs, self.device))
-        if self._episode_log is not None:
-            self._episode_log.push = self._env_push
-        varying = env_push.varying_names(self._push_cfg)
-        self.logger.info(f"ENV_PUSH: impulses at point(s) {self._push_cfg['POINTS']}; {', '.join(varying) or 'nothing'} varies"
-                         f"{', redrawn at every reset' if self._push_cfg['PER_EPISODE'] else ''}")
+        self._env_push = self._add_table_observer("PUSH", env_push.EnvPush(
+            self._lib, self._handle, self._vcfg, self._push_cfg, self.reset_buf, self.num_envs, self.device),
+            f"impulses at point(s) {self._push_cfg['POINTS']}")
 
     @property
     def env_push(self):
@@ -407,15 +410,9 @@ class Vine5LinkMovingBase(VecTask):
         from ..utils import env_target
         if self.mat is not None:
             raise NotImplementedError("ENV_TARGET with MAT_FILE: the replay overwrites the target before every step")
-        self._env_target = self._add_observer(env_target.EnvTarget(
+        self._env_target = self._add_table_observer("TARGET", env_target.EnvTarget(
             self._lib, self._handle, self._vcfg, self._target_cfg, self.reset_buf, self.progress_buf, self.num_envs, self.num_obs,
-            self.device))
-        if self._episode_log is not None:
-            self._episode_log.target = self._env_target
-        varying = env_target.varying_names(self._target_cfg)
-        self.logger.info(f"ENV_TARGET: targets move in {env_target.MODES[self._target_cfg['MODE']]} mode; "
-                         f"{', '.join(varying) or 'nothing'} varies"
-                         f"{', redrawn at every reset' if self._target_cfg['PER_EPISODE'] else ''}")
+            self.device), f"targets move in {env_target.MODES[self._target_cfg['MODE']]} mode")
 
     @property
     def env_target(self):

@@ -20,29 +20,20 @@ link masses and on their inertias about the COM (the geometry is unchanged, so t
 What env ``g`` gets depends on ``(seed, name, g)`` with ``g`` the GLOBAL env id (``env_id_offset`` + local index), never on
 the batch size: a rank's shard equals its slice of the whole batch, the rule the step's own random streams follow."""
 import ctypes as C
-import hashlib
 
 import numpy as np
 
 from .. import abi
+from . import named_draw
 from .config import ConfigError
+from .named_draw import name_key, uniform01_episode  # noqa: F401  (the hash is stated in named_draw; callers find it here too)
 
-def _mix(x):
-    """splitmix64's finaliser on uint64 arrays."""
-    x = np.asarray(x, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
+INTEGER = ("ACTION_DELAY",)      # the names whose range is over the integers
 
 
 def uniform01(seed, name, gids):
-    """One float64 in [0, 1) per global env id, a pure function of ``(seed, name, id)``."""
-    key = int.from_bytes(hashlib.sha256(name.encode()).digest()[:8], "little")
-    g = np.asarray(gids, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        h = _mix(_mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(key)) + g * np.uint64(0x9E3779B97F4A7C15))
-    return (h >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    """One float64 in [0, 1) per global env id, a pure function of ``(seed, name, id)``: episode 0 of ``uniform01_episode``."""
+    return uniform01_episode(seed, name, gids, 0)
 
 
 def config_row(lib, vcfg):
@@ -100,28 +91,7 @@ def check_inertia_table(lib, vcfg, table):
 
 
 def _number(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ConfigError("ENV_PARAMS.%s: %r is not a number" % (name, v))
-    return float(v)
-
-
-def _form(name, entry):
-    """('scalar', v) / ('range', lo, hi) / ('values', [..])."""
-    if hasattr(entry, "keys"):
-        if list(entry.keys()) != ["values"]:
-            raise ConfigError("ENV_PARAMS.%s: a mapping must hold the one key 'values', not %s" % (name, sorted(entry.keys())))
-        vals = entry["values"]
-        if not isinstance(vals, (list, tuple)) or len(vals) == 0:
-            raise ConfigError("ENV_PARAMS.%s: 'values' must be a non-empty list" % name)
-        return ("values", [_number(name, v) for v in vals])
-    if isinstance(entry, (list, tuple)):
-        if len(entry) != 2:
-            raise ConfigError("ENV_PARAMS.%s: a range is [lo, hi], not %r" % (name, list(entry)))
-        lo, hi = _number(name, entry[0]), _number(name, entry[1])
-        if lo > hi:
-            raise ConfigError("ENV_PARAMS.%s: lo > hi in [%g, %g]" % (name, lo, hi))
-        return ("range", lo, hi)
-    return ("scalar", _number(name, entry))
+    return named_draw.number("ENV_PARAMS.%s" % name, v, finite=False)       # (an infinite end is the table checks' to refuse)
 
 
 def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
@@ -135,8 +105,8 @@ def build_table(spec, vcfg, seed, num_envs, env_id_offset=0, lib=None):
 
 
 def spec_forms(spec):
-    """``{name: ('scalar', v) / ('range', lo, hi) / ('values', [..])}`` of a spec, in its order; raises ``ConfigError`` for an
-    unknown name or a malformed entry."""
+    """``{name: v / [lo, hi] / {"values": [..]}}`` of a spec, in its order (``named_draw.form``: the spec as plain numbers
+    and lists, what the episode file stores as JSON); raises ``ConfigError`` for an unknown name or a malformed entry."""
     spec = spec or {}
     if not hasattr(spec, "keys"):
         raise ConfigError("ENV_PARAMS must be a mapping of parameter names, not %r" % (spec,))
@@ -144,10 +114,11 @@ def spec_forms(spec):
         if name not in abi.ENV_PARAM_ROWS and name not in abi.ENV_INERTIA_NAMES:
             raise ConfigError("ENV_PARAMS: unknown parameter %r (known: %s)" % (
                 name, ", ".join(abi.ENV_PARAM_NAMES + abi.ENV_INERTIA_NAMES)))
-    forms = {name: _form(name, spec[name]) for name in spec.keys()}
-    f = forms.get("ACTION_DELAY")
-    if f is not None and f[0] == "range" and (f[1] != np.floor(f[1]) or f[2] != np.floor(f[2])):
-        raise ConfigError("ENV_PARAMS.ACTION_DELAY: an integer parameter takes an integer range, not [%g, %g]" % (f[1], f[2]))
+    forms = {name: named_draw.form("ENV_PARAMS.%s" % name, spec[name], finite=False) for name in spec.keys()}
+    for name in INTEGER:
+        f = forms.get(name)
+        if isinstance(f, list) and (f[0] != np.floor(f[0]) or f[1] != np.floor(f[1])):
+            raise ConfigError("ENV_PARAMS.%s: an integer parameter takes an integer range, not [%g, %g]" % (name, f[0], f[1]))
     return forms
 
 
@@ -179,29 +150,7 @@ def set_inertia_rows(table, base, draws):
 
 def _candidates(forms):
     """What a spec CAN give an env, per name: both ends of a range, every listed value, the number."""
-    return {name: list(f[1]) if f[0] == "values" else list(f[1:]) for name, f in forms.items()}
-
-
-def _draw(forms, seed, gids):
-    """name -> float64 [N], the per-env value of every name of a spec: the ``values`` entries count the global env id in
-    one mixed radix over ALL names of the spec, in its order, whichever table a name fills."""
-    out, radix = {}, 1
-    for name, form in forms.items():
-        if form[0] == "scalar":
-            v = np.full(len(gids), form[1], dtype=np.float64)
-        elif form[0] == "range":
-            lo, hi = form[1], form[2]
-            u = uniform01(seed, name, gids)
-            if name == "ACTION_DELAY":
-                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
-            else:
-                v = lo + (hi - lo) * u
-        else:
-            vals = np.asarray(form[1], dtype=np.float64)
-            v = vals[(gids // radix) % len(vals)]
-            radix *= len(vals)
-        out[name] = v
-    return out
+    return {name: named_draw.candidates(f) for name, f in forms.items()}
 
 
 def draw_inertia_table(spec, base, seed, num_envs, derive, env_id_offset=0, check=None, draws=None):
@@ -226,7 +175,7 @@ def draw_inertia_table(spec, base, seed, num_envs, derive, env_id_offset=0, chec
             check(derive(probe))
         except ValueError as e:
             raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
-    drawn = {name: v for name, v in _draw(forms, seed, gids).items() if name in abi.ENV_INERTIA_NAMES}
+    drawn = {name: v for name, v in _draw_episode(forms, seed, gids, 0).items() if name in abi.ENV_INERTIA_NAMES}
     table = np.repeat(base[:, None], num_envs, axis=1)
     set_inertia_rows(table, base, drawn)
     if draws is not None:
@@ -278,7 +227,7 @@ def draw_table(spec, base, seed, num_envs, env_id_offset=0, check=None, draws=No
             check(probe)
         except ValueError as e:
             raise ValueError("ENV_PARAMS: %s" % str(e).replace(" of env ", " of candidate ")) from None
-    for name, v in _draw(forms, seed, gids).items():
+    for name, v in _draw_episode(forms, seed, gids, 0).items():
         if name in abi.ENV_PARAM_ROWS:
             set_rows(table, base, name, v)
         if draws is not None:
@@ -308,47 +257,10 @@ def per_episode(env_cfg):
     return True
 
 
-def name_key(name):
-    """The 64-bit key of a parameter name: the first 8 bytes of its SHA-256, little endian."""
-    return int.from_bytes(hashlib.sha256(name.encode()).digest()[:8], "little")
-
-
-def uniform01_episode(seed, name, gids, episodes):
-    """One float64 in [0, 1) per (global env id, episode) pair, a pure function of ``(seed, name, id, episode)``; episode 0
-    is ``uniform01``, because ``_mix(0) == 0``."""
-    g = np.asarray(gids, dtype=np.uint64)
-    k = np.asarray(episodes, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        pre = _mix(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ np.uint64(name_key(name))) + g * np.uint64(0x9E3779B97F4A7C15)
-        h = _mix(pre ^ _mix(k))
-    return (h >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
-
-
 def _draw_episode(forms, seed, gids, episodes):
-    """``_draw`` for (global env id, episode) pairs: episode 0 is ``_draw``'s value; from episode 1 on a ``values`` entry
-    takes ``values[min(floor(u * len), len - 1)]`` with its own ``u`` (the mixed-radix count of the id alone would repeat the
-    same combination for ever)."""
-    gids = np.asarray(gids, dtype=np.int64)
-    k = np.asarray(episodes, dtype=np.int64)
-    out, radix = {}, 1
-    for name, form in forms.items():
-        if form[0] == "scalar":
-            v = np.full(len(gids), form[1], dtype=np.float64)
-        elif form[0] == "range":
-            lo, hi = form[1], form[2]
-            u = uniform01_episode(seed, name, gids, k)
-            if name == "ACTION_DELAY":
-                v = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi)
-            else:
-                v = lo + (hi - lo) * u
-        else:
-            vals = np.asarray(form[1], dtype=np.float64)
-            u = uniform01_episode(seed, name, gids, k)
-            later = np.minimum(np.floor(u * float(len(vals))).astype(np.int64), len(vals) - 1)
-            v = vals[np.where(k == 0, (gids // radix) % len(vals), later)]
-            radix *= len(vals)
-        out[name] = v
-    return out
+    """name -> float64 [M], the value of every name of a spec for (global env id, episode) pairs: ``named_draw.draw`` over
+    ALL names of the spec, in its order, whichever table a name fills.  Episode 0 is what the tables are set up from."""
+    return dict(zip(forms, named_draw.draw(list(forms.items()), seed, gids, episodes, INTEGER, who="draw_columns")))
 
 
 def draw_columns(spec, base, inertia_base, derive, seed, gids, episodes):
@@ -393,24 +305,9 @@ def build_columns(spec, vcfg, gids, episodes, lib=None, seed=None):
 
 
 def redraw_names(spec):
-    """``(abi.VineEnvRedrawName * VR_NAMES, values float64 [V])`` of a spec: per name its form, ends, key, the extent of its
-    list in ``values`` and its place in the mixed radix."""
-    forms = spec_forms(spec)
-    names = (abi.VineEnvRedrawName * abi.VR_NAMES)()
-    values, radix = [], 1
-    for name, form in forms.items():
-        nm = names[abi.ENV_REDRAW_NAMES.index(name)]
-        nm.key = name_key(name)
-        nm.radix = 1
-        if form[0] == "scalar":
-            nm.form, nm.lo, nm.hi = abi.REDRAW_NUMBER, form[1], form[1]
-        elif form[0] == "range":
-            nm.form, nm.lo, nm.hi = abi.REDRAW_RANGE, form[1], form[2]
-        else:
-            nm.form, nm.values_first, nm.values_count, nm.radix = abi.REDRAW_VALUES, len(values), len(form[1]), radix
-            values += form[1]
-            radix *= len(form[1])
-    return names, np.asarray(values, dtype=np.float64)
+    """``(abi.VineEnvRedrawName * VR_NAMES, values float64 [V])`` of a spec (``named_draw.pack``), every name in its slot of
+    ``abi.ENV_REDRAW_NAMES``; a name the spec does not hold stays ABSENT."""
+    return named_draw.pack(list(spec_forms(spec).items()), abi.VR_NAMES, abi.ENV_REDRAW_NAMES.index)
 
 
 def redraw_spec(lib, vcfg, spec, device_values=None):
@@ -458,7 +355,7 @@ def adr_config(env_cfg, multi_gpu=False):
             continue
         entry, where = names[name], "%s.NAMES.%s" % (_ADR, name)
         form = forms.get(name)
-        if form is None or form[0] != "range":
+        if not isinstance(form, list):
             raise ConfigError("%s: the name must be a [lo, hi] range in task.env.ENV_PARAMS, its limits" % where)
         if not hasattr(entry, "keys") or sorted(entry.keys()) != ["START", "STEP"]:
             raise ConfigError("%s must hold START and STEP" % where)
@@ -468,8 +365,8 @@ def adr_config(env_cfg, multi_gpu=False):
         lo, hi, step = _number(where + ".START", start[0]), _number(where + ".START", start[1]), _number(where + ".STEP", entry["STEP"])
         if not (np.isfinite(lo) and np.isfinite(hi)) or lo > hi:
             raise ConfigError("%s.START: lo > hi in [%g, %g]" % (where, lo, hi))
-        if lo < form[1] or hi > form[2]:
-            raise ConfigError("%s.START [%g, %g] lies outside the limits [%g, %g]" % (where, lo, hi, form[1], form[2]))
+        if lo < form[0] or hi > form[1]:
+            raise ConfigError("%s.START [%g, %g] lies outside the limits [%g, %g]" % (where, lo, hi, form[0], form[1]))
         if not np.isfinite(step) or not step > 0.0:
             raise ConfigError("%s.STEP must be positive, not %g" % (where, step))
         if name == "ACTION_DELAY" and (lo != np.floor(lo) or hi != np.floor(hi) or step != np.floor(step)):
@@ -508,9 +405,9 @@ def adr_max_widen(spec, adr):
     for name, a in adr["NAMES"].items():
         s = abi.ENV_REDRAW_NAMES.index(name)
         lo, hi, step = np.float64(a["START"][0]), np.float64(a["START"][1]), np.float64(a["STEP"])
-        m_lo, m_hi = np.ceil((lo - forms[name][1]) / step), np.ceil((forms[name][2] - hi) / step)
-        out[s, 0] = int(m_lo) + (1 if lo - m_lo * step > forms[name][1] else 0)      # (the last step arrives AT the limit, not
-        out[s, 1] = int(m_hi) + (1 if hi + m_hi * step < forms[name][2] else 0)      # an ulp inside it)
+        m_lo, m_hi = np.ceil((lo - forms[name][0]) / step), np.ceil((forms[name][1] - hi) / step)
+        out[s, 0] = int(m_lo) + (1 if lo - m_lo * step > forms[name][0] else 0)      # (the last step arrives AT the limit, not
+        out[s, 1] = int(m_hi) + (1 if hi + m_hi * step < forms[name][1] else 0)      # an ulp inside it)
     return out
 
 
@@ -523,8 +420,8 @@ def adr_ranges(spec, adr, widen):
     for name, a in adr["NAMES"].items():
         s = abi.ENV_REDRAW_NAMES.index(name)
         step = np.float64(a["STEP"])
-        lo = max(np.float64(forms[name][1]), np.float64(a["START"][0]) - np.float64(widen[s, 0]) * step)
-        hi = min(np.float64(forms[name][2]), np.float64(a["START"][1]) + np.float64(widen[s, 1]) * step)
+        lo = max(np.float64(forms[name][0]), np.float64(a["START"][0]) - np.float64(widen[s, 0]) * step)
+        hi = min(np.float64(forms[name][1]), np.float64(a["START"][1]) + np.float64(widen[s, 1]) * step)
         out[name] = (float(lo), float(hi))
     return out
 
@@ -538,7 +435,7 @@ def adr_draw(spec, adr, seed, gids, episodes, widen):
     forms = dict(spec_forms(spec))
     ranges = adr_ranges(spec, adr, widen)
     for name, (lo, hi) in ranges.items():
-        forms[name] = ("range", lo, hi)
+        forms[name] = [lo, hi]
     drawn = _draw_episode(forms, seed, gids, k)
     slots = [abi.ENV_REDRAW_NAMES.index(name) for name in adr["NAMES"]]
     count = 2 * len(slots)

@@ -11,16 +11,17 @@ are stated once, in include/vine_env_push.h.
                    5 the tip (default ``[5]``)
   ``PER_EPISODE``  False: every env's two values are drawn once and held; True: redrawn on the device at every reset
 
-What env ``g`` gets in episode ``k`` is ``env_params``'s draw under the names ``PUSH_RATE`` and ``PUSH_IMPULSE``, keyed by
-the GLOBAL env id: a rank's shard draws what the whole batch would."""
+What env ``g`` gets in episode ``k`` is the named draw (utils/named_draw.py) under the names ``PUSH_RATE`` and
+``PUSH_IMPULSE``, keyed by the GLOBAL env id: a rank's shard draws what the whole batch would."""
 import ctypes as C
 
 import numpy as np
 
 from .. import abi, native
-from . import env_params
+from . import env_params, named_draw
 from .config import ConfigError
-from .env_sensor import _candidates, _form, philox4x32_10
+from .named_draw import candidates, philox4x32_10
+from .observers import TableObserver
 
 _KEY = "task.env.ENV_PUSH"
 NAMES = tuple(abi.ENV_PUSH_NAMES)                    # the table's rows, the order of the mixed radix
@@ -32,7 +33,7 @@ ND = NL + 1
 # ---- configuration
 def _check_values(name, form):
     where = "%s.%s" % (_KEY, name)
-    for v in _candidates(form):
+    for v in candidates(form):
         if name == "RATE" and not 0.0 <= v <= 1.0:
             raise ConfigError("%s: %g lies outside [0, 1]" % (where, v))
         if name == "IMPULSE" and not v >= 0.0:
@@ -54,7 +55,7 @@ def push_config(env_cfg):
         raise ConfigError("%s: unknown key(s) %s" % (_KEY, ", ".join(str(k) for k in unknown)))
     out = {}
     for name in NAMES:
-        out[name] = _form("%s.%s" % (_KEY, name), cfg.get(name, 0))
+        out[name] = named_draw.form("%s.%s" % (_KEY, name), cfg.get(name, 0))
         _check_values(name, out[name])
     points = cfg.get("POINTS", [abi.PUSH_MAX_POINTS - 1])
     if not isinstance(points, (list, tuple)) or len(points) == 0:
@@ -69,63 +70,29 @@ def push_config(env_cfg):
             raise ConfigError("%s.POINTS: point %d is listed twice" % (_KEY, m))
         seen.append(int(m))
     out["POINTS"] = seen
-    per_episode = cfg.get("PER_EPISODE", False)
-    if not isinstance(per_episode, (bool, np.bool_)):
-        raise ConfigError("%s.PER_EPISODE must be a bool, not %r" % (_KEY, per_episode))
-    out["PER_EPISODE"] = bool(per_episode)
+    out["PER_EPISODE"] = named_draw.flag("%s.PER_EPISODE" % _KEY, cfg.get("PER_EPISODE", False))
     if not out["PER_EPISODE"]:
         for name in NAMES:
-            if max(_candidates(out[name])) == 0.0:
+            if max(candidates(out[name])) == 0.0:
                 raise ConfigError("%s.%s is constant zero: nothing to do" % (_KEY, name))
     return out
 
 
 def varying_names(spec):
     """The names of ``NAMES`` whose value can differ between envs or episodes."""
-    return [n for n in NAMES if len(set(_candidates(spec[n]))) > 1]
+    return named_draw.varying(NAMES, spec)
 
 
 # ---- the draw
 def draw_push(spec, seed, gids, episodes):
-    """float64 [2, M]: RATE and IMPULSE of M ``(global env id, episode)`` pairs, ``redraw_value`` of
-    csrc/vine_env_redraw_draw.h on the host.  Episode 0 of a value list counts the id in the mixed radix of the two names."""
-    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
-    k = np.broadcast_to(np.asarray(episodes, dtype=np.int64), gids.shape)
-    if np.any(gids < 0) or np.any(k < 0):
-        raise ValueError("draw_push: env ids and episodes are non-negative")
-    out, radix = np.zeros((len(NAMES), len(gids)), dtype=np.float64), 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        form = spec[name]
-        if isinstance(form, dict):
-            vals = np.asarray(form["values"], dtype=np.float64)
-            u = env_params.uniform01_episode(seed, draw_name, gids, k)
-            later = np.minimum(np.floor(u * float(len(vals))).astype(np.int64), len(vals) - 1)
-            out[s] = vals[np.where(k == 0, (gids // radix) % len(vals), later)]
-            radix *= len(vals)
-        elif isinstance(form, list):
-            lo, hi = np.float64(form[0]), np.float64(form[1])
-            out[s] = lo + (hi - lo) * env_params.uniform01_episode(seed, draw_name, gids, k)
-        else:
-            out[s] = np.float64(form)
-    return out
+    """float64 [2, M]: RATE and IMPULSE of M ``(global env id, episode)`` pairs: ``named_draw.draw``, the host's statement of
+    ``redraw_value`` (csrc/vine_named_draw.h)."""
+    return named_draw.draw(named_draw.named(NAMES, DRAW_NAMES, spec), seed, gids, episodes, who="draw_push")
 
 
 def push_names(spec):
     """``(abi.VineEnvRedrawName * VPU_NAMES, values float64 [V])`` of a spec."""
-    names = (abi.VineEnvRedrawName * abi.VPU_NAMES)()
-    values, radix = [], 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        nm, form = names[s], spec[name]
-        nm.key, nm.radix = env_params.name_key(draw_name), 1
-        if isinstance(form, dict):
-            nm.form, nm.values_first, nm.values_count, nm.radix = abi.REDRAW_VALUES, len(values), len(form["values"]), radix
-            values += list(form["values"])
-            radix *= len(form["values"])
-        elif isinstance(form, list):
-            nm.form, nm.lo, nm.hi = abi.REDRAW_RANGE, form[0], form[1]
-        else:
-            nm.form, nm.lo, nm.hi = abi.REDRAW_NUMBER, form, form
-    return names, np.asarray(values, dtype=np.float64)
+    return named_draw.pack(named_draw.named(NAMES, DRAW_NAMES, spec))
 
 
 def push_spec(lib, vcfg, spec, device_values=None):
@@ -300,65 +267,31 @@ def push_replay(state, reset, spec, seed, gids, steps, geometry, inertia=None, t
 
 # ---- the episode log's columns
 def episode_params(spec, seed, gids, episodes):
-    """``{"PUSH_<NAME>": float32 [M]}`` of the names that vary: what the ``param_PUSH_*`` columns of the episode log hold for
-    rows of global envs ``gids`` in ``episodes`` (zeros where the values are held: episode 0's draw)."""
-    drawn = draw_push(spec, seed, gids, episodes if spec["PER_EPISODE"] else 0).astype(np.float32)
-    return {DRAW_NAMES[NAMES.index(n)]: drawn[NAMES.index(n)] for n in varying_names(spec)}
+    """``{"PUSH_<NAME>": float32 [M]}`` of the names that vary: ``named_draw.episode_params``."""
+    return named_draw.episode_params(NAMES, DRAW_NAMES, spec, seed, gids, episodes)
 
 
-class EnvPush:
+class EnvPush(TableObserver):
     """A step observer (the protocol: utils/observers.py) that adds impulses to the velocities of the state block the step
-    has just written.  In launch order it stands behind ``EnvSensor`` and in front of ``EnvRedraw`` / ``EnvAdr``."""
+    has just written.  In launch order it stands behind ``EnvSensor`` and in front of ``EnvRedraw`` / ``EnvAdr``.  The draw
+    follows the device's count."""
+
+    NAMES, DRAW_NAMES = NAMES, DRAW_NAMES
 
     def __init__(self, lib, handle, vcfg, spec, reset, num_envs, device):
         """``spec``: ``push_config``'s result; ``reset``: the step's buffer."""
         import torch
-        self.lib, self.handle, self.vcfg, self.device = lib, handle, vcfg, device
-        self.spec = spec
-        self.seed, self.env_id_offset = int(vcfg.seed), int(vcfg.env_id_offset)
-        self.num_envs = int(num_envs)
+        super().__init__(lib, handle, vcfg, spec, num_envs, device)
         self.reset = reset
-        _, values = push_names(spec)
-        self.values = torch.as_tensor(values, dtype=torch.float64, device=device) if len(values) else None
-        self.pspec = push_spec(lib, vcfg, spec, self.values.data_ptr() if self.values is not None else None)
-        gids = np.arange(self.num_envs, dtype=np.int64) + self.env_id_offset
-        self.table = torch.as_tensor(draw_push(spec, self.seed, gids, 0).astype(np.float32), device=device).contiguous()
-        self.episode_index = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+        self.pspec = push_spec(lib, vcfg, spec, self.values_ptr)
         self.push_count = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
-        self.paused = 0
-        self.copy_done = None
-
-    # -- the observer protocol ---------------------------------------------------------------------------------------------
-    def before(self, n_steps):
-        pass
 
     def enqueue(self, stream, actions=None):
         native.check(self.lib.vine_env_push_scheduled(
             self.handle, self.pspec, self.reset.data_ptr(), self.table.data_ptr(), self.episode_index.data_ptr(),
             self.push_count.data_ptr(), stream), self.lib)
 
-    def advance(self, n_steps):
-        pass
-
-    def set_steps(self, steps):
-        pass                         # the draw follows the device's count
-
     def live_tensors(self):
         """A rolled-back pass has counted pushes and, per episode, redrawn values and counted episodes.  The velocities it
         wrote are in the state block, which is the env's own live tensor."""
         return [self.table, self.episode_index, self.push_count]
-
-    def drain(self):
-        pass
-
-    def close(self):
-        pass
-
-    # -- which push --------------------------------------------------------------------------------------------------------
-    def episodes_now(self):
-        """A host copy of ``episode_index`` at this point of the current stream (synchronises)."""
-        return self.episode_index.cpu().numpy().astype(np.int64)
-
-    def episode_params(self, envs, episodes):
-        """``episode_params`` of local env indices ``envs``."""
-        return episode_params(self.spec, self.seed, np.asarray(envs, dtype=np.int64) + self.env_id_offset, episodes)

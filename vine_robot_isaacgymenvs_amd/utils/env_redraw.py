@@ -11,52 +11,35 @@ import torch
 
 from .. import native
 from . import env_params
+from .observers import StepObserver
 
 
-class EnvRedraw:
+class EnvRedraw(StepObserver):
     """A step observer (the protocol: utils/observers.py), last in launch order: the step's other observers have read what
     the step wrote before the next step's plant replaces this one's."""
 
     def __init__(self, lib, handle, vcfg, spec, reset, params, inertia, device):
         """``reset``: the step's reset buffer; ``params`` / ``inertia``: the device tensors bound to ``handle`` (``inertia``
         ``None`` when the spec names no mass)."""
+        super().__init__()
         self.lib, self.handle, self.vcfg, self.device = lib, handle, vcfg, device
-        # the spec as plain numbers and lists: what the episode file stores as JSON
-        self.spec = {name: f[1] if f[0] == "scalar" else [f[1], f[2]] if f[0] == "range" else {"values": list(f[1])}
-                     for name, f in env_params.spec_forms(spec).items()}
+        self.spec = env_params.spec_forms(spec)      # as plain numbers and lists: what the episode file stores as JSON
         self.seed, self.env_id_offset = int(vcfg.seed), int(vcfg.env_id_offset)
         self.reset, self.params, self.inertia = reset, params, inertia
         _, values = env_params.redraw_names(self.spec)
         self.values = torch.as_tensor(values, dtype=torch.float64, device=device) if len(values) else None
         self.rspec = env_params.redraw_spec(lib, vcfg, self.spec, self.values.data_ptr() if self.values is not None else None)
+        # (an episode's ordinal does not depend on the step count: set_steps means nothing here)
         self.episode_index = torch.zeros(params.shape[1], dtype=torch.int32, device=device)
-        self.paused = 0
-        self.copy_done = None
-
-    # -- the observer protocol ---------------------------------------------------------------------------------------------
-    def before(self, n_steps):
-        pass
 
     def enqueue(self, stream, actions=None):
         native.check(self.lib.vine_env_redraw_scheduled(
             self.handle, self.rspec, self.reset.data_ptr(), self.params.data_ptr(),
             self.inertia.data_ptr() if self.inertia is not None else None, self.episode_index.data_ptr(), stream), self.lib)
 
-    def advance(self, n_steps):
-        pass
-
-    def set_steps(self, steps):
-        pass                         # an episode's ordinal does not depend on the step count
-
     def live_tensors(self):
         """A rolled-back pass has redrawn columns and counted episodes: the tables and the counters go back with the state."""
         return [self.params] + ([self.inertia] if self.inertia is not None else []) + [self.episode_index]
-
-    def drain(self):
-        pass
-
-    def close(self):
-        pass
 
     # -- which plant -------------------------------------------------------------------------------------------------------
     def columns(self, envs, episodes):
@@ -64,7 +47,3 @@ class EnvRedraw:
         None)``, float32, no device involved."""
         gids = np.asarray(envs, dtype=np.int64) + self.env_id_offset
         return env_params.build_columns(self.spec, self.vcfg, gids, episodes, lib=self.lib, seed=self.seed)
-
-    def episodes_now(self):
-        """A host copy of ``episode_index`` at this point of the current stream (synchronises)."""
-        return self.episode_index.cpu().numpy().astype(np.int64)

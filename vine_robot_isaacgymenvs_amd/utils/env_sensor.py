@@ -11,57 +11,31 @@ launch behind every step (``sensor_replay``: what every GPU test compares agains
   ``COLUMNS``      ``all`` or a list of observation column indices the model applies to
   ``PER_EPISODE``  False: every env's three values are drawn once and held; True: redrawn on the device at every reset
 
-What env ``g`` gets in episode ``k`` is ``env_params``'s draw under the names ``SENSOR_DELAY``, ``SENSOR_HOLD`` and
-``SENSOR_NOISE_STD``, keyed by the GLOBAL env id: a rank's shard draws what the whole batch would."""
+What env ``g`` gets in episode ``k`` is the named draw (utils/named_draw.py) under the names ``SENSOR_DELAY``, ``SENSOR_HOLD``
+and ``SENSOR_NOISE_STD``, keyed by the GLOBAL env id: a rank's shard draws what the whole batch would."""
 import ctypes as C
 
 import numpy as np
 
 from .. import abi, native
-from . import env_params
+from . import named_draw
 from .config import ConfigError
+from .named_draw import candidates, philox4x32_10
+from .observers import FirstFrameObserver
 
 _KEY = "task.env.ENV_SENSOR"
 NAMES = tuple(abi.ENV_SENSOR_NAMES)                  # the table's rows, the order of the mixed radix
 DRAW_NAMES = tuple("SENSOR_" + n for n in NAMES)     # the names the draw is keyed by, and of the log's param_ columns
+INTEGER = ("SENSOR_DELAY",)                          # the draw names whose range is over the integers
 SLOTS = abi.SENSOR_SLOTS
 # the scale of the eight-uniform deviate, 1 / sqrt(32 * (65536^2 - 1) / 12), in float64
 NOISE_SCALE = np.float64(1.0) / np.sqrt(np.float64(32.0) * (np.float64(65536.0) * np.float64(65536.0) - np.float64(1.0)) / np.float64(12.0))
 
 
 # ---- configuration
-def _number(where, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-        raise ConfigError("%s: %r is not a finite number" % (where, v))
-    return float(v)
-
-
-def _form(where, entry):
-    """A plain number, ``[lo, hi]`` or ``{"values": [..]}`` of floats."""
-    if hasattr(entry, "keys"):
-        if list(entry.keys()) != ["values"]:
-            raise ConfigError("%s: a mapping must hold the one key 'values', not %s" % (where, sorted(entry.keys())))
-        vals = entry["values"]
-        if not isinstance(vals, (list, tuple)) or len(vals) == 0:
-            raise ConfigError("%s: 'values' must be a non-empty list" % where)
-        return {"values": [_number(where, v) for v in vals]}
-    if isinstance(entry, (list, tuple)):
-        if len(entry) != 2:
-            raise ConfigError("%s: a range is [lo, hi], not %r" % (where, list(entry)))
-        lo, hi = _number(where, entry[0]), _number(where, entry[1])
-        if lo > hi:
-            raise ConfigError("%s: lo > hi in [%g, %g]" % (where, lo, hi))
-        return [lo, hi]
-    return _number(where, entry)
-
-
-def _candidates(form):
-    return list(form["values"]) if isinstance(form, dict) else list(form) if isinstance(form, list) else [form]
-
-
 def _check_values(name, form):
     where = "%s.%s" % (_KEY, name)
-    for v in _candidates(form):
+    for v in candidates(form):
         if name == "DELAY" and (v != np.floor(v) or not 0 <= v <= abi.SENSOR_MAX_DELAY):
             raise ConfigError("%s: %g is not an integer in 0 .. %d" % (where, v, abi.SENSOR_MAX_DELAY))
         if name == "HOLD" and not (v >= 0.0 and np.float32(v) < np.float32(1.0)):
@@ -84,7 +58,7 @@ def sensor_config(env_cfg, num_obs):
         raise ConfigError("%s: unknown key(s) %s" % (_KEY, ", ".join(str(k) for k in unknown)))
     out = {}
     for name in NAMES:
-        out[name] = _form("%s.%s" % (_KEY, name), cfg.get(name, 0))
+        out[name] = named_draw.form("%s.%s" % (_KEY, name), cfg.get(name, 0))
         _check_values(name, out[name])
     columns = cfg.get("COLUMNS", "all")
     num_obs = int(num_obs)
@@ -104,11 +78,8 @@ def sensor_config(env_cfg, num_obs):
             raise ConfigError("%s.COLUMNS: column %d is listed twice" % (_KEY, j))
         seen.add(int(j))
     out["COLUMNS"] = sorted(seen)
-    per_episode = cfg.get("PER_EPISODE", False)
-    if not isinstance(per_episode, (bool, np.bool_)):
-        raise ConfigError("%s.PER_EPISODE must be a bool, not %r" % (_KEY, per_episode))
-    out["PER_EPISODE"] = bool(per_episode)
-    if not out["PER_EPISODE"] and all(max(_candidates(out[n])) == 0.0 for n in NAMES):
+    out["PER_EPISODE"] = named_draw.flag("%s.PER_EPISODE" % _KEY, cfg.get("PER_EPISODE", False))
+    if not out["PER_EPISODE"] and all(max(candidates(out[n])) == 0.0 for n in NAMES):
         raise ConfigError("%s: DELAY, HOLD and NOISE_STD are all constant zero: nothing to do" % _KEY)
     return out
 
@@ -119,51 +90,19 @@ def column_mask(spec):
 
 def varying_names(spec):
     """The names of ``NAMES`` whose value can differ between envs or episodes."""
-    return [n for n in NAMES if len(set(_candidates(spec[n]))) > 1]
+    return named_draw.varying(NAMES, spec)
 
 
 # ---- the draw
 def draw_sensor(spec, seed, gids, episodes):
-    """float64 [3, M]: DELAY, HOLD and NOISE_STD of M ``(global env id, episode)`` pairs, ``redraw_value`` of
-    csrc/vine_env_redraw_draw.h on the host.  Episode 0 of a value list counts the id in the mixed radix of the three names."""
-    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
-    k = np.broadcast_to(np.asarray(episodes, dtype=np.int64), gids.shape)
-    if np.any(gids < 0) or np.any(k < 0):
-        raise ValueError("draw_sensor: env ids and episodes are non-negative")
-    out, radix = np.zeros((len(NAMES), len(gids)), dtype=np.float64), 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        form = spec[name]
-        if isinstance(form, dict):
-            vals = np.asarray(form["values"], dtype=np.float64)
-            u = env_params.uniform01_episode(seed, draw_name, gids, k)
-            later = np.minimum(np.floor(u * float(len(vals))).astype(np.int64), len(vals) - 1)
-            out[s] = vals[np.where(k == 0, (gids // radix) % len(vals), later)]
-            radix *= len(vals)
-        elif isinstance(form, list):
-            lo, hi = np.float64(form[0]), np.float64(form[1])
-            u = env_params.uniform01_episode(seed, draw_name, gids, k)
-            out[s] = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi) if name == "DELAY" else lo + (hi - lo) * u
-        else:
-            out[s] = np.float64(form)
-    return out
+    """float64 [3, M]: DELAY, HOLD and NOISE_STD of M ``(global env id, episode)`` pairs: ``named_draw.draw``, the host's
+    statement of ``redraw_value`` (csrc/vine_named_draw.h)."""
+    return named_draw.draw(named_draw.named(NAMES, DRAW_NAMES, spec), seed, gids, episodes, INTEGER, who="draw_sensor")
 
 
 def sensor_names(spec):
     """``(abi.VineEnvRedrawName * VSN_NAMES, values float64 [V])`` of a spec."""
-    names = (abi.VineEnvRedrawName * abi.VSN_NAMES)()
-    values, radix = [], 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        nm, form = names[s], spec[name]
-        nm.key, nm.radix = env_params.name_key(draw_name), 1
-        if isinstance(form, dict):
-            nm.form, nm.values_first, nm.values_count, nm.radix = abi.REDRAW_VALUES, len(values), len(form["values"]), radix
-            values += list(form["values"])
-            radix *= len(form["values"])
-        elif isinstance(form, list):
-            nm.form, nm.lo, nm.hi = abi.REDRAW_RANGE, form[0], form[1]
-        else:
-            nm.form, nm.lo, nm.hi = abi.REDRAW_NUMBER, form, form
-    return names, np.asarray(values, dtype=np.float64)
+    return named_draw.pack(named_draw.named(NAMES, DRAW_NAMES, spec))
 
 
 def sensor_spec(lib, vcfg, spec, device_values=None):
@@ -179,18 +118,6 @@ def sensor_spec(lib, vcfg, spec, device_values=None):
 
 
 # ---- the launch, in numpy
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox-4x32-10 on uint32 arrays (broadcast against each other): the four output words."""
-    m32 = np.uint64(0xFFFFFFFF)
-    c = [np.asarray(x, dtype=np.uint64) & m32 for x in np.broadcast_arrays(c0, c1, c2, c3)]
-    k0, k1 = np.uint64(int(k0) & 0xFFFFFFFF), np.uint64(int(k1) & 0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & m32]
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
-    return [x.astype(np.uint32) for x in c]
-
-
 def noise_deviate(seed, gids, step, columns):
     """float32 [M, C]: the deviate z of global envs ``gids`` [M] in ``columns`` [C] behind step ``step``: ``2 * S - 524280``
     with S the sum of the eight 16-bit halves of the Philox call (exact in float32)."""
@@ -271,42 +198,28 @@ def sensor_replay(spec, seed, gids, steps, raw_obs, progress, resets, external_r
 
 # ---- the episode log's columns
 def episode_params(spec, seed, gids, episodes):
-    """``{"SENSOR_<NAME>": float32 [M]}`` of the names that vary: what the ``param_SENSOR_*`` columns of the episode log hold
-    for rows of global envs ``gids`` in ``episodes`` (zeros where the values are held: episode 0's draw)."""
-    drawn = draw_sensor(spec, seed, gids, episodes if spec["PER_EPISODE"] else 0).astype(np.float32)
-    return {DRAW_NAMES[NAMES.index(n)]: drawn[NAMES.index(n)] for n in varying_names(spec)}
+    """``{"SENSOR_<NAME>": float32 [M]}`` of the names that vary: ``named_draw.episode_params``."""
+    return named_draw.episode_params(NAMES, DRAW_NAMES, spec, seed, gids, episodes, INTEGER)
 
 
-class EnvSensor:
+class EnvSensor(FirstFrameObserver):
     """A step observer (the protocol: utils/observers.py) that asks for the observation buffer of the step it rides behind
-    (``wants_obs``) and rewrites it in place.  In launch order it stands in front of ``EnvRedraw`` / ``EnvAdr``."""
+    (``wants_obs``) and rewrites it in place.  In launch order it stands in front of ``EnvRedraw`` / ``EnvAdr``.  The ring's
+    slots follow the device's count; a frame never leaves its episode."""
 
     wants_obs = True
+    NAMES, DRAW_NAMES, INTEGER = NAMES, DRAW_NAMES, INTEGER
 
     def __init__(self, lib, handle, vcfg, spec, reset, progress, num_envs, num_obs, device):
         """``spec``: ``sensor_config``'s result; ``reset`` / ``progress``: the step's buffers."""
         import torch
-        self.lib, self.handle, self.vcfg, self.device = lib, handle, vcfg, device
-        self.spec = spec
-        self.seed, self.env_id_offset = int(vcfg.seed), int(vcfg.env_id_offset)
-        self.num_envs, self.num_obs = int(num_envs), int(num_obs)
+        super().__init__(lib, handle, vcfg, spec, num_envs, device)
+        self.num_obs = int(num_obs)
         self.reset, self.progress = reset, progress
-        _, values = sensor_names(spec)
-        self.values = torch.as_tensor(values, dtype=torch.float64, device=device) if len(values) else None
-        self.sspec = sensor_spec(lib, vcfg, spec, self.values.data_ptr() if self.values is not None else None)
+        self.sspec = sensor_spec(lib, vcfg, spec, self.values_ptr)
         if self.sspec.num_obs != self.num_obs:
             raise ValueError("ENV_SENSOR: the configuration has %d observation columns, the task %d" % (self.sspec.num_obs, self.num_obs))
-        gids = np.arange(self.num_envs, dtype=np.int64) + self.env_id_offset
-        self.table = torch.as_tensor(draw_sensor(spec, self.seed, gids, 0).astype(np.float32), device=device).contiguous()
         self.ring = torch.zeros((SLOTS, self.num_envs, self.num_obs), dtype=torch.float32, device=device)
-        self.fresh = torch.ones(self.num_envs, dtype=torch.uint8, device=device)
-        self.episode_index = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
-        self.paused = 0
-        self.copy_done = None
-
-    # -- the observer protocol ---------------------------------------------------------------------------------------------
-    def before(self, n_steps):
-        pass
 
     def enqueue(self, stream, actions=None, obs=None):
         if obs is None:
@@ -315,32 +228,6 @@ class EnvSensor:
             self.handle, self.sspec, int(obs), self.reset.data_ptr(), self.progress.data_ptr(), self.table.data_ptr(),
             self.ring.data_ptr(), self.fresh.data_ptr(), self.episode_index.data_ptr(), stream), self.lib)
 
-    def advance(self, n_steps):
-        pass
-
-    def set_steps(self, steps):
-        pass                         # the ring's slots follow the device's count; a frame never leaves its episode
-
     def live_tensors(self):
         """A rolled-back pass has pushed frames, cleared ``fresh`` and, per episode, redrawn values and counted episodes."""
         return [self.ring, self.table, self.fresh, self.episode_index]
-
-    def drain(self):
-        pass
-
-    def close(self):
-        pass
-
-    # -- which sensor ------------------------------------------------------------------------------------------------------
-    def reset_envs(self, env_ids):
-        """The envs were reset from outside the step: the next frame of each is its episode's first."""
-        self.fresh[env_ids] = 1
-
-    def episodes_now(self):
-        """A host copy of ``episode_index`` at this point of the current stream (synchronises)."""
-        return self.episode_index.cpu().numpy().astype(np.int64)
-
-    def episode_params(self, envs, episodes):
-        """``episode_params`` of local env indices ``envs``."""
-        return episode_params(self.spec, self.seed, np.asarray(envs, dtype=np.int64) + self.env_id_offset, episodes)
-

@@ -12,16 +12,17 @@ behind every step (``target_replay``: what every GPU test compares against, bit 
                    each a number, ``[lo, hi]`` or ``{values: [...]}``
   ``PER_EPISODE``  False: every env's four values are drawn once and held; True: redrawn on the device at every reset
 
-What env ``g`` gets in episode ``k`` is ``env_params``'s draw under the names ``TARGET_VEL_ALONG`` .. ``TARGET_SPAN_ACROSS``,
+What env ``g`` gets in episode ``k`` is the named draw (utils/named_draw.py) under the names ``TARGET_VEL_ALONG`` .. ``TARGET_SPAN_ACROSS``,
 keyed by the GLOBAL env id: a rank's shard draws what the whole batch would."""
 import ctypes as C
 
 import numpy as np
 
 from .. import abi, native
-from . import env_params
+from . import named_draw
 from .config import ConfigError
-from .env_sensor import _candidates, _form
+from .named_draw import candidates
+from .observers import FirstFrameObserver
 
 _KEY = "task.env.ENV_TARGET"
 NAMES = tuple(abi.ENV_TARGET_NAMES)                  # the table's rows, the order of the mixed radix
@@ -59,20 +60,17 @@ def target_config(env_cfg, cdt):
         raise ConfigError("%s: unknown key(s) %s" % (_KEY, ", ".join(str(k) for k in unknown)))
     out = {}
     for name in NAMES:
-        out[name] = _form("%s.%s" % (_KEY, name), cfg.get(name, 0))
-        for v in _candidates(out[name]):
+        out[name] = named_draw.form("%s.%s" % (_KEY, name), cfg.get(name, 0))
+        for v in candidates(out[name]):
             if name.startswith("SPAN") and not v >= 0.0:
                 raise ConfigError("%s.%s: %g is negative" % (_KEY, name, v))
             if abs(v) > float(np.finfo(np.float32).max):
                 raise ConfigError("%s.%s: %g does not fit a float32" % (_KEY, name, v))
-    per_episode = cfg.get("PER_EPISODE", False)
-    if not isinstance(per_episode, (bool, np.bool_)):
-        raise ConfigError("%s.PER_EPISODE must be a bool, not %r" % (_KEY, per_episode))
-    out["PER_EPISODE"] = bool(per_episode)
+    out["PER_EPISODE"] = named_draw.flag("%s.PER_EPISODE" % _KEY, cfg.get("PER_EPISODE", False))
     out["MODE"] = int(mode_of(env_cfg))
     if float(env_cfg.get("VELOCITY_SUCCESS_REWARD_WEIGHT", 0)) != 0.0:
         raise ConfigError("%s: task.env.VELOCITY_SUCCESS_REWARD_WEIGHT must be 0: the step's term assumes a resting target" % _KEY)
-    largest = {n: max(abs(np.float32(v)) for v in _candidates(out[n])) for n in NAMES}
+    largest = {n: max(abs(np.float32(v)) for v in candidates(out[n])) for n in NAMES}
     if out["MODE"] != abi.TARGET_FREE:
         for name in ("VEL_ACROSS", "SPAN_ACROSS"):
             if largest[name] != 0.0:
@@ -84,7 +82,7 @@ def target_config(env_cfg, cdt):
     for axis in ("ALONG", "ACROSS"):
         if largest["VEL_" + axis] == 0.0:
             continue
-        room = min(np.float32(v) for v in _candidates(out["SPAN_" + axis]))
+        room = min(np.float32(v) for v in candidates(out["SPAN_" + axis]))
         if np.float32(largest["VEL_" + axis]) * cdt > np.float32(2.0) * room or not room > 0.0:
             raise ConfigError("%s.VEL_%s: max|VEL| * cdt = %g exceeds 2 * min SPAN_%s = %g: one reflection would not keep the "
                               "target on its path" % (_KEY, axis, np.float32(largest["VEL_" + axis]) * cdt, axis, 2.0 * room))
@@ -95,50 +93,19 @@ def target_config(env_cfg, cdt):
 
 def varying_names(spec):
     """The names of ``NAMES`` whose value can differ between envs or episodes."""
-    return [n for n in NAMES if len(set(_candidates(spec[n]))) > 1]
+    return named_draw.varying(NAMES, spec)
 
 
 # ---- the draw
 def draw_target(spec, seed, gids, episodes):
-    """float64 [4, M]: the four values of M ``(global env id, episode)`` pairs, ``redraw_value`` of
-    csrc/vine_env_redraw_draw.h on the host.  Episode 0 of a value list counts the id in the mixed radix of the four names."""
-    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
-    k = np.broadcast_to(np.asarray(episodes, dtype=np.int64), gids.shape)
-    if np.any(gids < 0) or np.any(k < 0):
-        raise ValueError("draw_target: env ids and episodes are non-negative")
-    out, radix = np.zeros((len(NAMES), len(gids)), dtype=np.float64), 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        form = spec[name]
-        if isinstance(form, dict):
-            vals = np.asarray(form["values"], dtype=np.float64)
-            u = env_params.uniform01_episode(seed, draw_name, gids, k)
-            later = np.minimum(np.floor(u * float(len(vals))).astype(np.int64), len(vals) - 1)
-            out[s] = vals[np.where(k == 0, (gids // radix) % len(vals), later)]
-            radix *= len(vals)
-        elif isinstance(form, list):
-            lo, hi = np.float64(form[0]), np.float64(form[1])
-            out[s] = lo + (hi - lo) * env_params.uniform01_episode(seed, draw_name, gids, k)
-        else:
-            out[s] = np.float64(form)
-    return out
+    """float64 [4, M]: the four values of M ``(global env id, episode)`` pairs: ``named_draw.draw``, the host's statement of
+    ``redraw_value`` (csrc/vine_named_draw.h)."""
+    return named_draw.draw(named_draw.named(NAMES, DRAW_NAMES, spec), seed, gids, episodes, who="draw_target")
 
 
 def target_names(spec):
     """``(abi.VineEnvRedrawName * VTG_NAMES, values float64 [V])`` of a spec."""
-    names = (abi.VineEnvRedrawName * abi.VTG_NAMES)()
-    values, radix = [], 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        nm, form = names[s], spec[name]
-        nm.key, nm.radix = env_params.name_key(draw_name), 1
-        if isinstance(form, dict):
-            nm.form, nm.values_first, nm.values_count, nm.radix = abi.REDRAW_VALUES, len(values), len(form["values"]), radix
-            values += list(form["values"])
-            radix *= len(form["values"])
-        elif isinstance(form, list):
-            nm.form, nm.lo, nm.hi = abi.REDRAW_RANGE, form[0], form[1]
-        else:
-            nm.form, nm.lo, nm.hi = abi.REDRAW_NUMBER, form, form
-    return names, np.asarray(values, dtype=np.float64)
+    return named_draw.pack(named_draw.named(NAMES, DRAW_NAMES, spec))
 
 
 def target_spec(lib, vcfg, spec, device_values=None):
@@ -260,50 +227,36 @@ def target_replay(spec, seed, gids, layout, state, obs, progress, resets, axis=N
 
 # ---- the episode log's columns
 def episode_params(spec, seed, gids, episodes):
-    """``{"TARGET_<NAME>": float32 [M]}`` of the names that vary: what the ``param_TARGET_*`` columns of the episode log hold
-    for rows of global envs ``gids`` in ``episodes`` (zeros where the values are held: episode 0's draw)."""
-    drawn = draw_target(spec, seed, gids, episodes if spec["PER_EPISODE"] else 0).astype(np.float32)
-    return {DRAW_NAMES[NAMES.index(n)]: drawn[NAMES.index(n)] for n in varying_names(spec)}
+    """``{"TARGET_<NAME>": float32 [M]}`` of the names that vary: ``named_draw.episode_params``."""
+    return named_draw.episode_params(NAMES, DRAW_NAMES, spec, seed, gids, episodes)
 
 
-class EnvTarget:
+class EnvTarget(FirstFrameObserver):
     """A step observer (the protocol: utils/observers.py) that moves each env's target in the state block the step reads and
     adds the target's velocity to the observation the step has just written (``wants_obs``).  In launch order it stands
-    behind the video, the recorder and the episode log and in front of ``EnvSensor``."""
+    behind the video, the recorder and the episode log and in front of ``EnvSensor``.  The path is a function of the env's
+    own state, not of the step count."""
 
     wants_obs = True
+    NAMES, DRAW_NAMES = NAMES, DRAW_NAMES
 
     def __init__(self, lib, handle, vcfg, spec, reset, progress, num_envs, num_obs, device):
         """``spec``: ``target_config``'s result; ``reset`` / ``progress``: the step's buffers."""
         import torch
-        self.lib, self.handle, self.vcfg, self.device = lib, handle, vcfg, device
-        self.spec = spec
-        self.seed, self.env_id_offset = int(vcfg.seed), int(vcfg.env_id_offset)
-        self.num_envs, self.num_obs = int(num_envs), int(num_obs)
+        super().__init__(lib, handle, vcfg, spec, num_envs, device)
+        self.num_obs = int(num_obs)
         self.reset, self.progress = reset, progress
-        _, values = target_names(spec)
-        self.values = torch.as_tensor(values, dtype=torch.float64, device=device) if len(values) else None
-        self.tspec = target_spec(lib, vcfg, spec, self.values.data_ptr() if self.values is not None else None)
+        self.tspec = target_spec(lib, vcfg, spec, self.values_ptr)
         if self.tspec.num_obs != self.num_obs:
             raise ValueError("ENV_TARGET: the configuration has %d observation columns, the task %d" % (self.tspec.num_obs, self.num_obs))
         if self.tspec.mode != spec["MODE"]:
             raise ValueError("ENV_TARGET: the configuration's obstacle flags give mode %d, the spec %d" % (self.tspec.mode, spec["MODE"]))
-        gids = np.arange(self.num_envs, dtype=np.int64) + self.env_id_offset
-        self.table = torch.as_tensor(draw_target(spec, self.seed, gids, 0).astype(np.float32), device=device).contiguous()
         self.motion = torch.zeros((abi.VTM_COUNT, self.num_envs), dtype=torch.float32, device=device)
         self.anchor = self.motion[abi.VTM_ANCHOR_Y:abi.VTM_ANCHOR_Z + 1]       # views of the one block the launch takes
         self.depth0 = self.motion[abi.VTM_DEPTH0]
         self.axis = self.motion[abi.VTM_AXIS_C:abi.VTM_AXIS_S + 1]
         self.off = self.motion[abi.VTM_OFF_ALONG:abi.VTM_OFF_ACROSS + 1]
         self.vel = self.motion[abi.VTM_VEL_ALONG:abi.VTM_VEL_ACROSS + 1]
-        self.fresh = torch.ones(self.num_envs, dtype=torch.uint8, device=device)
-        self.episode_index = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
-        self.paused = 0
-        self.copy_done = None
-
-    # -- the observer protocol ---------------------------------------------------------------------------------------------
-    def before(self, n_steps):
-        pass
 
     def enqueue(self, stream, actions=None, obs=None):
         if obs is None:
@@ -312,33 +265,8 @@ class EnvTarget:
             self.handle, self.tspec, int(obs), self.reset.data_ptr(), self.progress.data_ptr(), self.table.data_ptr(),
             self.motion.data_ptr(), self.fresh.data_ptr(), self.episode_index.data_ptr(), stream), self.lib)
 
-    def advance(self, n_steps):
-        pass
-
-    def set_steps(self, steps):
-        pass                         # the path is a function of the env's own state, not of the step count
-
     def live_tensors(self):
         """A rolled-back pass has moved offsets, flipped velocities, taken anchors, cleared ``fresh`` and, per episode, redrawn
         values and counted episodes: ``motion`` holds ``anchor``, ``depth0``, ``axis``, ``off`` and ``vel``.  The target it wrote
         is in the state block, which is the env's own live tensor."""
         return [self.motion, self.table, self.fresh, self.episode_index]
-
-    def drain(self):
-        pass
-
-    def close(self):
-        pass
-
-    # -- which target ------------------------------------------------------------------------------------------------------
-    def reset_envs(self, env_ids):
-        """The envs were reset from outside the step: the next frame of each is its episode's first."""
-        self.fresh[env_ids] = 1
-
-    def episodes_now(self):
-        """A host copy of ``episode_index`` at this point of the current stream (synchronises)."""
-        return self.episode_index.cpu().numpy().astype(np.int64)
-
-    def episode_params(self, envs, episodes):
-        """``episode_params`` of local env indices ``envs``."""
-        return episode_params(self.spec, self.seed, np.asarray(envs, dtype=np.int64) + self.env_id_offset, episodes)

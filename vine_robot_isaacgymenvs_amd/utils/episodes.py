@@ -10,6 +10,7 @@ the task class the ring can therefore never lap unharvested rows; ``dropped`` is
 
 One file per run, ``<dir>/<time_str>_episodes.npz``: the rows sorted by (end step, env) as named columns, the folded
 totals, ``dropped`` and the config keys that define the task.  ``load`` / ``report`` / ``binned_rate`` read it back."""
+import functools
 import logging
 import math
 import os
@@ -205,28 +206,21 @@ def value_rate(rows, column, of="reached_ever"):
     return values, hit / np.maximum(count, 1), count
 
 
-def with_sensor_params(rows, sensor_params):
-    """ENV_SENSOR: ``rows`` with ``param_SENSOR_DELAY`` / ``_HOLD`` / ``_NOISE_STD`` for the names that vary.
-    ``sensor_params(envs, episodes)`` -> ``{"SENSOR_<NAME>": values [R]}`` (``env_sensor.episode_params``: held values are
-    joined by env, per-episode ones by the row's ``episode``, the join ``param_<NAME>`` uses under ENV_PARAMS_PER_EPISODE)."""
+DRAW_OBSERVERS = ("sensor", "push", "target")      # the observers with a table of named draws, in the order their columns join
+
+
+def with_draw_params(rows, draw_params):
+    """``rows`` with the ``param_<DRAW NAME>`` columns of one observer's named draws (ENV_SENSOR: ``param_SENSOR_DELAY`` / ``_HOLD``
+    / ``_NOISE_STD``; ENV_PUSH: ``param_PUSH_RATE`` / ``_IMPULSE``; ENV_TARGET: ``param_TARGET_VEL_ALONG`` .. ``_SPAN_ACROSS``) for
+    the names that vary.  ``draw_params(envs, episodes)`` -> ``{DRAW NAME: values [R]}`` (``named_draw.episode_params``: held
+    values are joined by env, per-episode ones by the row's ``episode``, the join ``param_<NAME>`` uses under
+    ENV_PARAMS_PER_EPISODE)."""
     out = dict(rows)
     if len(np.asarray(rows["env"])):
         episodes_ = rows["episode"] if "episode" in rows else np.zeros(len(rows["env"]), dtype=np.int64)
-        for name, values in sensor_params(rows["env"], episodes_).items():
+        for name, values in draw_params(rows["env"], episodes_).items():
             out["param_" + name] = values
     return out
-
-
-def with_push_params(rows, push_params):
-    """ENV_PUSH: ``rows`` with ``param_PUSH_RATE`` / ``param_PUSH_IMPULSE`` for the names that vary, joined as
-    ``with_sensor_params`` joins the sensor's: held values by env, per-episode ones by the row's ``episode``."""
-    return with_sensor_params(rows, push_params)
-
-
-def with_target_params(rows, target_params):
-    """ENV_TARGET: ``rows`` with ``param_TARGET_VEL_ALONG`` .. ``param_TARGET_SPAN_ACROSS`` for the names that vary, joined as
-    ``with_sensor_params`` joins the sensor's: held values by env, per-episode ones by the row's ``episode``."""
-    return with_sensor_params(rows, target_params)
 
 
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
@@ -238,33 +232,18 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
     what ``load_env_redraw`` needs to rebuild every episode's column without a device; the two tables are then the plants
     at the moment of writing.  With ENV_PARAMS_ADR also ``adr``: a dict of ``config`` (``env_params.adr_config``'s result),
     ``history`` [H, 4] (complete), ``history_dropped`` and ``widen0`` [VR_NAMES, 2] (the ``widen`` in force before the run's
-    first step: zeros, or a restored checkpoint's).  With ENV_SENSOR (``sensor``: a dict of ``spec``, ``seed`` and
-    ``env_id_offset``) what ``load_env_sensor`` needs to rebuild the ``param_SENSOR_*`` columns without a device, and, where
-    the rows carry one, their ``episode`` column.  With ENV_PUSH (``push``: a dict of the same three keys) the same for the
-    ``param_PUSH_*`` columns (``load_env_push``), with ENV_TARGET (``target``) for the ``param_TARGET_*`` columns
-    (``load_env_target``)."""
+    first step: zeros, or a restored checkpoint's).  With ENV_SENSOR, ENV_PUSH or ENV_TARGET (``sensor``, ``push``, ``target``: each a
+    dict of ``spec``, ``seed`` and ``env_id_offset``) what ``load_env_draw`` needs to rebuild the ``param_SENSOR_*``,
+    ``param_PUSH_*`` and ``param_TARGET_*`` columns without a device, and, where the rows carry one, their ``episode`` column."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
-    if target is not None:
-        import json
-        out["target_spec"] = np.array(json.dumps(target["spec"]))
-        out["target_seed"] = np.array(int(target["seed"]), dtype=np.uint64)
-        out["target_env_id_offset"] = np.array(int(target["env_id_offset"]), dtype=np.int64)
-        if "episode" in rows:
-            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
-    if push is not None:
-        import json
-        out["push_spec"] = np.array(json.dumps(push["spec"]))
-        out["push_seed"] = np.array(int(push["seed"]), dtype=np.uint64)
-        out["push_env_id_offset"] = np.array(int(push["env_id_offset"]), dtype=np.int64)
-        if "episode" in rows:
-            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
-    if sensor is not None:
-        import json
-        out["sensor_spec"] = np.array(json.dumps(sensor["spec"]))
-        out["sensor_seed"] = np.array(int(sensor["seed"]), dtype=np.uint64)
-        out["sensor_env_id_offset"] = np.array(int(sensor["env_id_offset"]), dtype=np.int64)
-        if "episode" in rows:
-            out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
+    for prefix, draw in (("target", target), ("push", push), ("sensor", sensor)):
+        if draw is not None:
+            import json
+            out[prefix + "_spec"] = np.array(json.dumps(draw["spec"]))
+            out[prefix + "_seed"] = np.array(int(draw["seed"]), dtype=np.uint64)
+            out[prefix + "_env_id_offset"] = np.array(int(draw["env_id_offset"]), dtype=np.int64)
+            if "episode" in rows:
+                out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
     if adr is not None:
         import json
         out["adr_config"] = np.array(json.dumps(adr["config"]))
@@ -384,73 +363,44 @@ def load_env_adr(path):
     return r["adr"], r["history"], r["dropped"], widen0, columns
 
 
-def load_env_sensor(path):
-    """Of a file written under ENV_SENSOR: ``(spec, episode [R] or None, sensor_params)`` with ``sensor_params(envs,
-    episodes)`` -> ``env_sensor.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
-    ``(None, None, None)``."""
+def load_env_draw(path, prefix):
+    """Of a file written under ENV_SENSOR, ENV_PUSH or ENV_TARGET (``prefix``: one of ``DRAW_OBSERVERS``): ``(spec, episode [R]
+    or None, draw_params)`` with ``draw_params(envs, episodes)`` -> the ``episode_params`` of utils/env_<prefix>.py rebuilt
+    from the stored spec, seed and ``env_id_offset`` (no device); else ``(None, None, None)``."""
+    import importlib
     import json
-    from . import env_sensor
+    module = importlib.import_module(".env_" + prefix, __package__)
     with np.load(path) as z:
-        if "sensor_spec" not in z.files:
+        if prefix + "_spec" not in z.files:
             return None, None, None
-        spec, seed, offset = json.loads(str(z["sensor_spec"][()])), int(z["sensor_seed"]), int(z["sensor_env_id_offset"])
+        spec, seed, offset = json.loads(str(z[prefix + "_spec"][()])), int(z[prefix + "_seed"]), int(z[prefix + "_env_id_offset"])
         episode = z["episode"] if "episode" in z.files else None
 
-    def sensor_params(envs, episodes_):
-        return env_sensor.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
-    return spec, episode, sensor_params
+    def draw_params(envs, episodes_):
+        return module.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
+    return spec, episode, draw_params
+
+
+# the names the join and the loader had while each of the three observers had its own: files and callers written then still work
+with_sensor_params = with_push_params = with_target_params = with_draw_params
+load_env_sensor = functools.partial(load_env_draw, prefix="sensor")
+load_env_push = functools.partial(load_env_draw, prefix="push")
+load_env_target = functools.partial(load_env_draw, prefix="target")
 
 
 def load_rows_with_params(path):
     """The rows of a file written under ENV_PARAMS_PER_EPISODE with the ``param_<NAME>`` columns of every row's own episode
     (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device.  Under
-    ENV_SENSOR also the ``param_SENSOR_*`` columns."""
-    _, sensor_episode, sensor_params = load_env_sensor(path)
-    _, push_episode, push_params = load_env_push(path)
-    _, target_episode, target_params = load_env_target(path)
+    ENV_SENSOR, ENV_PUSH and ENV_TARGET also the ``param_SENSOR_*``, ``param_PUSH_*`` and ``param_TARGET_*`` columns."""
     rows = _load_rows_with_plant_params(path)
-    for episode, params, join in ((sensor_episode, sensor_params, with_sensor_params), (push_episode, push_params, with_push_params),
-                                  (target_episode, target_params, with_target_params)):
+    for prefix in DRAW_OBSERVERS:
+        _, episode, params = load_env_draw(path, prefix)
         if params is None:
             continue
         if episode is not None:
             rows["episode"] = episode
-        rows = join(rows, params)
+        rows = with_draw_params(rows, params)
     return rows
-
-
-def load_env_push(path):
-    """Of a file written under ENV_PUSH: ``(spec, episode [R] or None, push_params)`` with ``push_params(envs, episodes)`` ->
-    ``env_push.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
-    ``(None, None, None)``."""
-    import json
-    from . import env_push
-    with np.load(path) as z:
-        if "push_spec" not in z.files:
-            return None, None, None
-        spec, seed, offset = json.loads(str(z["push_spec"][()])), int(z["push_seed"]), int(z["push_env_id_offset"])
-        episode = z["episode"] if "episode" in z.files else None
-
-    def push_params(envs, episodes_):
-        return env_push.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
-    return spec, episode, push_params
-
-
-def load_env_target(path):
-    """Of a file written under ENV_TARGET: ``(spec, episode [R] or None, target_params)`` with ``target_params(envs, episodes)``
-    -> ``env_target.episode_params`` rebuilt from the stored spec, seed and ``env_id_offset`` (no device); else
-    ``(None, None, None)``."""
-    import json
-    from . import env_target
-    with np.load(path) as z:
-        if "target_spec" not in z.files:
-            return None, None, None
-        spec, seed, offset = json.loads(str(z["target_spec"][()])), int(z["target_seed"]), int(z["target_env_id_offset"])
-        episode = z["episode"] if "episode" in z.files else None
-
-    def target_params(envs, episodes_):
-        return env_target.episode_params(spec, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_)
-    return spec, episode, target_params
 
 
 def _load_rows_with_plant_params(path):
@@ -508,7 +458,7 @@ class EpisodeLog:
         self.unknown_plants = 0      # ENV_PARAMS_ADR: rows of the last rows_with_params() whose plant is unknown (NaN)
         self.sensor = None           # ENV_SENSOR: the task's ``env_sensor.EnvSensor``; under its PER_EPISODE rows carry ``episode``
         self.push = None             # ENV_PUSH: the task's ``env_push.EnvPush``; likewise
-        self.target = None           # ENV_TARGET: the task's ``env_target.EnvTarget``; likewise
+        self.target = None           # ENV_TARGET: the task's ``env_target.EnvTarget``; likewise (the three of DRAW_OBSERVERS)
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -527,16 +477,13 @@ class EpisodeLog:
             self.cursor.data_ptr() if self.cursor is not None else None, stream), self.lib)
 
     def _counters(self):
-        """Who counts the episodes of every env on the device: the redraw, else a sensor redrawn per episode (with both on
-        the two count alike), else nobody."""
+        """Who counts the episodes of every env on the device: the redraw, else the first of the sensor, the push and the
+        target that is redrawn per episode (all that are on count alike), else nobody."""
         if self.redraw is not None:
             return self.redraw
-        if self.sensor is not None and self.sensor.spec["PER_EPISODE"]:
-            return self.sensor
-        if self.push is not None and self.push.spec["PER_EPISODE"]:      # ENV_PUSH: likewise
-            return self.push
-        if self.target is not None and self.target.spec["PER_EPISODE"]:  # ENV_TARGET: likewise
-            return self.target
+        for observer in (self.sensor, self.push, self.target):
+            if observer is not None and observer.spec["PER_EPISODE"]:
+                return observer
         return None
 
     def reset_envs(self, env_ids):
@@ -609,14 +556,13 @@ class EpisodeLog:
     def rows_with_params(self):
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
         (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env.  Under
-        ENV_SENSOR also ``param_SENSOR_*`` (``with_sensor_params``), under ENV_PUSH ``param_PUSH_*`` (``with_push_params``), under
-        ENV_TARGET ``param_TARGET_*`` (``with_target_params``)."""
+        ENV_SENSOR also ``param_SENSOR_*``, under ENV_PUSH ``param_PUSH_*``, under ENV_TARGET ``param_TARGET_*``
+        (``with_draw_params``)."""
         out = self._rows_with_plant_params()
-        if self.sensor is not None:
-            out = with_sensor_params(out, self.sensor.episode_params)
-        if self.push is not None:
-            out = with_push_params(out, self.push.episode_params)
-        return with_target_params(out, self.target.episode_params) if self.target is not None else out
+        for observer in (self.sensor, self.push, self.target):
+            if observer is not None:
+                out = with_draw_params(out, observer.episode_params)
+        return out
 
     def _rows_with_plant_params(self):
         rows = self.rows()
@@ -655,15 +601,8 @@ class EpisodeLog:
         if getattr(self.redraw, "adr", None) is not None:
             adr = {"config": self.redraw.adr, "history": self.redraw.harvest_history(), "history_dropped": self.redraw.history_dropped,
                    "widen0": self.redraw.widen0}
-        sensor = None
-        if self.sensor is not None:
-            sensor = {"spec": self.sensor.spec, "seed": self.sensor.seed, "env_id_offset": self.sensor.env_id_offset}
-        push = None
-        if self.push is not None:
-            push = {"spec": self.push.spec, "seed": self.push.seed, "env_id_offset": self.push.env_id_offset}
-        target = None
-        if self.target is not None:
-            target = {"spec": self.target.spec, "seed": self.target.seed, "env_id_offset": self.target.env_id_offset}
+        sensor, push, target = (None if o is None else {"spec": o.spec, "seed": o.seed, "env_id_offset": o.env_id_offset}
+                                for o in (self.sensor, self.push, self.target))
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
              self.env_inertia_names, redraw, adr, sensor, push, target)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")

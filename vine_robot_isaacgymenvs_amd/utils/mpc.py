@@ -23,7 +23,7 @@ DEFAULT_COST = {"POSITION_REWARD_WEIGHT": 1.0}
 
 
 # ---------------------------------------------------------------------------------------------------------- configuration
-def _integer(key, v, lo, hi=None):
+def check_integer(key, v, lo, hi=None):
     if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
         raise ConfigError("mpc: %s must be an integer, not %r" % (key, v))
     if v < lo or (hi is not None and v > hi):
@@ -31,7 +31,7 @@ def _integer(key, v, lo, hi=None):
     return int(v)
 
 
-def _real(key, v):
+def check_real(key, v):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
         raise ConfigError("mpc: %s: %r is not a finite number" % (key, v))
     return float(v)
@@ -44,12 +44,12 @@ def mpc_config(num_plants, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     components, or two."""
     c = abi.VineMpcConfig()
     c.abi_version = abi.MPC_ABI_VERSION
-    c.num_plants = _integer("plants", num_plants, 1)
-    c.samples = _integer("samples", samples, 2)
-    c.horizon = _integer("horizon", horizon, 1, abi.MPC_MAX_HORIZON)
+    c.num_plants = check_integer("plants", num_plants, 1)
+    c.samples = check_integer("samples", samples, 2)
+    c.horizon = check_integer("horizon", horizon, 1, abi.MPC_MAX_HORIZON)
     if c.num_plants * c.samples > 0x7FFFFFFF:
         raise ConfigError("mpc: plants * samples = %d does not fit an int32" % (c.num_plants * c.samples))
-    lam = _real("lambda", lam)
+    lam = check_real("lambda", lam)
     if not lam > 0.0:
         raise ConfigError("mpc: lambda must be positive, not %g" % lam)
     c.lambda_ = lam
@@ -57,7 +57,7 @@ def mpc_config(num_plants, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     if len(pair) != 2:
         raise ConfigError("mpc: sigma is one number or two, not %r" % (sigma,))
     for a, s in enumerate(pair):
-        s = _real("sigma", s)
+        s = check_real("sigma", s)
         if s < 0.0 or s > float(np.finfo(np.float32).max):
             raise ConfigError("mpc: sigma must not be negative (and fit a float32), not %g" % s)
         c.sigma[a] = s
@@ -106,7 +106,7 @@ def model_config(cfg, num_plants, samples, cost=None, logger=None):
     for key, value in cost.items():
         if not str(key).endswith("_REWARD_WEIGHT") or key not in cfg["env"]:
             raise ConfigError("mpc: cost: %r is not a reward weight of the task (a *_REWARD_WEIGHT key of task.env)" % (key,))
-        value = _real("cost." + str(key), value)
+        value = check_real("cost." + str(key), value)
         if cfg["env"][key] != value:
             logger.info("mpc: model env.%s set from %r to %r", key, cfg["env"][key], value)
         cfg["env"][key] = value
@@ -421,7 +421,7 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     logger = logger or logging.getLogger(__name__)
     cfg = copy.deepcopy(cfg)
     if plants is not None:
-        cfg["env"]["numEnvs"] = _integer("plants", plants, 1)
+        cfg["env"]["numEnvs"] = check_integer("plants", plants, 1)
     M = int(cfg["env"]["numEnvs"])
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
@@ -455,7 +455,7 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         if policy_params is None:
             raise ConfigError("mpc: policy= needs policy_params, the train.params block the network is built from")
         mpc_policy.check_shape(M, samples)
-        mpc_policy._eps("terminal_value", terminal_value)
+        mpc_policy.check_eps("terminal_value", terminal_value)
     mcfg = model_config(cfg, M, samples, cost, logger)
     if model_params:
         env_params.spec_forms(model_params)

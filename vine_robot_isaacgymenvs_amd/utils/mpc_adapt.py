@@ -13,7 +13,7 @@ from .. import abi
 from . import env_sensor
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
-from .mpc import Controller, _integer, _real
+from .mpc import Controller, check_integer, check_real
 
 # temperature, rate, spread and floor: see DESIGN.md section 25 ("The four constants") for what they were checked against
 DEFAULTS = {"window": 8, "every": 8, "min_steps": 4, "temperature": 0.1, "rate": 0.5, "spread": 0.25, "floor": 0.01}
@@ -45,22 +45,22 @@ def adapt_config(spec, num_plants, samples, base_row, seed=0, forget_on_reset=Fa
         raise ConfigError("mpc adapt: params must be a non-empty mapping {NAME: [lo, hi]}, not %r" % (params,))
     c = abi.VineMpcAdaptConfig()
     c.abi_version = abi.MPC_ADAPT_ABI_VERSION
-    c.num_plants = _integer("adapt plants", num_plants, 1)
-    c.samples = _integer("adapt samples", samples, 2)
-    c.window = _integer("adapt.window", spec.get("window", DEFAULTS["window"]), 1, abi.MPC_ADAPT_MAX_WINDOW)
-    c.every = _integer("adapt.every", spec.get("every", max(DEFAULTS["every"], c.window)), 1)
+    c.num_plants = check_integer("adapt plants", num_plants, 1)
+    c.samples = check_integer("adapt samples", samples, 2)
+    c.window = check_integer("adapt.window", spec.get("window", DEFAULTS["window"]), 1, abi.MPC_ADAPT_MAX_WINDOW)
+    c.every = check_integer("adapt.every", spec.get("every", max(DEFAULTS["every"], c.window)), 1)
     if c.every < c.window:
         raise ConfigError("mpc adapt: every = %d must be at least window = %d (a cycle traces its first `window` steps)" % (
             c.every, c.window))
-    c.min_steps = _integer("adapt.min_steps", spec.get("min_steps", min(DEFAULTS["min_steps"], c.window)), 1, c.window)
-    c.temperature = _real("adapt.temperature", spec.get("temperature", DEFAULTS["temperature"]))
+    c.min_steps = check_integer("adapt.min_steps", spec.get("min_steps", min(DEFAULTS["min_steps"], c.window)), 1, c.window)
+    c.temperature = check_real("adapt.temperature", spec.get("temperature", DEFAULTS["temperature"]))
     if not c.temperature > 0.0:
         raise ConfigError("mpc adapt: temperature must be positive, not %g" % c.temperature)
-    c.rate = _real("adapt.rate", spec.get("rate", DEFAULTS["rate"]))
+    c.rate = check_real("adapt.rate", spec.get("rate", DEFAULTS["rate"]))
     if not 0.0 < c.rate <= 1.0:
         raise ConfigError("mpc adapt: rate must be in (0, 1], not %g" % c.rate)
-    spread = _real("adapt.spread", spec.get("spread", DEFAULTS["spread"]))
-    floor = _real("adapt.floor", spec.get("floor", DEFAULTS["floor"]))
+    spread = check_real("adapt.spread", spec.get("spread", DEFAULTS["spread"]))
+    floor = check_real("adapt.floor", spec.get("floor", DEFAULTS["floor"]))
     if spread < 0.0 or floor < 0.0:
         raise ConfigError("mpc adapt: spread and floor must not be negative, not %g and %g" % (spread, floor))
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed <= 0xFFFFFFFFFFFFFFFF:
@@ -75,7 +75,7 @@ def adapt_config(spec, num_plants, samples, base_row, seed=0, forget_on_reset=Fa
     for name, w in weights.items():
         if name not in FIELD_NAMES:
             raise ConfigError("mpc adapt: weights: unknown field %r (known: %s)" % (name, ", ".join(FIELD_NAMES)))
-        w = _real("adapt.weights." + name, w)
+        w = check_real("adapt.weights." + name, w)
         if w < 0.0 or w > float(np.finfo(np.float32).max):
             raise ConfigError("mpc adapt: weights.%s must not be negative (and fit a float32), not %g" % (name, w))
         c.weights[FIELD_NAMES.index(name)] = w
@@ -95,7 +95,7 @@ def adapt_config(spec, num_plants, samples, base_row, seed=0, forget_on_reset=Fa
         entry = params[name]
         if not isinstance(entry, (list, tuple)) or len(entry) != 2:
             raise ConfigError("mpc adapt: params.%s must be a range [lo, hi], not %r" % (name, entry))
-        lo, hi = _real("adapt.params." + name, entry[0]), _real("adapt.params." + name, entry[1])
+        lo, hi = check_real("adapt.params." + name, entry[0]), check_real("adapt.params." + name, entry[1])
         if lo > hi:
             raise ConfigError("mpc adapt: params.%s: lo > hi in [%g, %g]" % (name, lo, hi))
         first, count = abi.ENV_PARAM_ROWS[name]

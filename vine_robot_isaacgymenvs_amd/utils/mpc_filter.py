@@ -15,7 +15,7 @@ frame.  The semantics are stated once, in include/vine_mpc_filter.h.  What is le
 import numpy as np
 
 from .. import abi
-from . import env_params, env_sensor
+from . import env_params, named_draw
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
 from .mpc_observe import LOG, NOT_RING, RING, SLOTS, ObservingController, hold_uniform
@@ -42,32 +42,17 @@ def filter_config(spec):
     out = {}
     for name in NAMES:
         where = "%s.%s" % (_KEY, name)
-        out[name] = env_sensor._form(where, spec.get(name, DEFAULT_GAIN))
-        for v in env_sensor._candidates(out[name]):
+        out[name] = named_draw.form(where, spec.get(name, DEFAULT_GAIN))
+        for v in named_draw.candidates(out[name]):
             if not 0.0 <= v <= 1.0:
                 raise ConfigError("%s: %g lies outside [0, 1]" % (where, v))
     return out
 
 
 def draw_gains(spec, seed, gids):
-    """float64 [2, M]: GAIN_Q and GAIN_QD of the plants with global ids ``gids``: the draw of ``mpc_observe.draw_observe``
-    under the names ``FILTER_<NAME>``; a value list counts the id in the mixed radix of the two names."""
-    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
-    if np.any(gids < 0):
-        raise ValueError("draw_gains: plant ids are non-negative")
-    out, radix = np.zeros((len(NAMES), len(gids)), dtype=np.float64), 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        form = spec[name]
-        if isinstance(form, dict):
-            vals = np.asarray(form["values"], dtype=np.float64)
-            out[s] = vals[(gids // radix) % len(vals)]
-            radix *= len(vals)
-        elif isinstance(form, list):
-            lo, hi = np.float64(form[0]), np.float64(form[1])
-            out[s] = lo + (hi - lo) * env_params.uniform01_episode(seed, draw_name, gids, 0)
-        else:
-            out[s] = np.float64(form)
-    return out
+    """float64 [2, M]: GAIN_Q and GAIN_QD of the plants with global ids ``gids``: episode 0 of ``named_draw.draw`` under the
+    names ``FILTER_<NAME>``."""
+    return named_draw.draw(named_draw.named(NAMES, DRAW_NAMES, spec), seed, gids, 0, who="draw_gains")
 
 
 def check_gains(gain, num_plants):
@@ -83,7 +68,7 @@ def check_gains(gain, num_plants):
 def largest_reach(observe_spec, action_delay):
     """The deepest entry of ``act_log`` the filter's pin can read: the largest ``DELAY`` of the checked ``observe=`` spec plus
     the model's largest ``ACTION_DELAY``.  A ``ConfigError`` naming both when it lies beyond the log's last entry."""
-    delay = int(max(env_sensor._candidates(observe_spec["DELAY"])))
+    delay = int(max(named_draw.candidates(observe_spec["DELAY"])))
     reach = delay + int(action_delay)
     if reach > LOG - 1:
         raise ConfigError("%s: the largest observe.DELAY, %d, plus the model's largest ACTION_DELAY, %d, exceeds %d: the action "
@@ -97,8 +82,7 @@ def model_action_delay(env_cfg, model_params=None):
     entry = (model_params or {}).get("ACTION_DELAY")
     if entry is None:
         return int(env_cfg.get("ACTION_DELAY", 0))
-    form = env_params.spec_forms({"ACTION_DELAY": entry})["ACTION_DELAY"]
-    return int(max(form[1] if form[0] == "values" else form[1:]))
+    return int(max(named_draw.candidates(env_params.spec_forms({"ACTION_DELAY": entry})["ACTION_DELAY"])))
 
 
 # ---------------------------------------------------------------------------------------------------- the launches, in numpy

@@ -21,7 +21,7 @@ import contextlib
 import numpy as np
 
 from .. import abi
-from . import env_params, env_sensor
+from . import env_sensor, named_draw
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
 from .mpc import Controller
@@ -29,6 +29,7 @@ from .mpc import Controller
 _KEY = "mpc: observe"
 NAMES = tuple(abi.MPC_OBSERVE_NAMES)                  # the table's rows, the order of the mixed radix
 DRAW_NAMES = tuple("OBSERVE_" + n for n in NAMES)     # the names the draw is keyed by
+INTEGER = ("OBSERVE_DELAY",)                          # the draw names whose range is over the integers
 SLOTS, LOG = abi.MPC_OBSERVE_SLOTS, abi.MPC_OBSERVE_LOG
 NOISE_SCALE = env_sensor.NOISE_SCALE
 RING = slice(abi.VF_FIFO0, abi.VF_PIPE_Y)             # the fields of a column no frame holds
@@ -38,7 +39,7 @@ NOT_RING = np.array([f for f in range(abi.VF_COUNT) if not abi.VF_FIFO0 <= f < a
 # ---------------------------------------------------------------------------------------------------------- configuration
 def _check_values(name, form):
     where = "%s.%s" % (_KEY, name)
-    for v in env_sensor._candidates(form):
+    for v in named_draw.candidates(form):
         if name == "DELAY" and (v != np.floor(v) or not 0 <= v <= abi.MAX_DELAY):
             raise ConfigError("%s: %g is not an integer in 0 .. %d" % (where, v, abi.MAX_DELAY))
         if name == "HOLD" and not (v >= 0.0 and np.float32(v) < np.float32(1.0)):
@@ -58,13 +59,10 @@ def observe_config(spec):
         raise ConfigError("%s: unknown key(s) %s" % (_KEY, ", ".join(unknown)))
     out = {}
     for name in NAMES:
-        out[name] = env_sensor._form("%s.%s" % (_KEY, name), spec.get(name, 0))
+        out[name] = named_draw.form("%s.%s" % (_KEY, name), spec.get(name, 0))
         _check_values(name, out[name])
-    compensate = spec.get("COMPENSATE", True)
-    if not isinstance(compensate, (bool, np.bool_)):
-        raise ConfigError("%s.COMPENSATE must be a bool, not %r" % (_KEY, compensate))
-    out["COMPENSATE"] = bool(compensate)
-    largest = int(max(env_sensor._candidates(out["DELAY"])))
+    out["COMPENSATE"] = named_draw.flag("%s.COMPENSATE" % _KEY, spec.get("COMPENSATE", True))
+    largest = int(max(named_draw.candidates(out["DELAY"])))
     catchup = spec.get("CATCHUP", largest)
     if isinstance(catchup, bool) or not isinstance(catchup, (int, np.integer)) or not 0 <= catchup <= abi.MAX_DELAY:
         raise ConfigError("%s.CATCHUP must be an integer in 0 .. %d, not %r" % (_KEY, abi.MAX_DELAY, catchup))
@@ -76,26 +74,9 @@ def observe_config(spec):
 
 
 def draw_observe(spec, seed, gids):
-    """float64 [4, M]: DELAY, HOLD, NOISE_Q and NOISE_QD of the plants with global ids ``gids``: the sensor's draw
-    (``env_sensor.draw_sensor``, episode 0) under the names ``OBSERVE_<NAME>``; a value list counts the id in the mixed radix
-    of the four names."""
-    gids = np.asarray(gids, dtype=np.int64).reshape(-1)
-    if np.any(gids < 0):
-        raise ValueError("draw_observe: plant ids are non-negative")
-    out, radix = np.zeros((len(NAMES), len(gids)), dtype=np.float64), 1
-    for s, (name, draw_name) in enumerate(zip(NAMES, DRAW_NAMES)):
-        form = spec[name]
-        if isinstance(form, dict):
-            vals = np.asarray(form["values"], dtype=np.float64)
-            out[s] = vals[(gids // radix) % len(vals)]
-            radix *= len(vals)
-        elif isinstance(form, list):
-            lo, hi = np.float64(form[0]), np.float64(form[1])
-            u = env_params.uniform01_episode(seed, draw_name, gids, 0)
-            out[s] = np.minimum(lo + np.floor(u * (hi - lo + 1.0)), hi) if name == "DELAY" else lo + (hi - lo) * u
-        else:
-            out[s] = np.float64(form)
-    return out
+    """float64 [4, M]: DELAY, HOLD, NOISE_Q and NOISE_QD of the plants with global ids ``gids``: episode 0 of
+    ``named_draw.draw`` under the names ``OBSERVE_<NAME>``."""
+    return named_draw.draw(named_draw.named(NAMES, DRAW_NAMES, spec), seed, gids, 0, INTEGER, who="draw_observe")
 
 
 def observe_cconfig(num_plants, catchup=0, compensate=True, seed=0, table=None):
@@ -132,7 +113,7 @@ def noise_deviate(seed, gids, step, fields):
     step ``step``: ``2 * S - 524280`` with S the sum of the eight 16-bit halves of the Philox call (exact in float32)."""
     seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)
     g = (np.asarray(gids, dtype=np.int64).reshape(-1, 1) & 0xFFFFFFFF)
-    w = env_sensor.philox4x32_10(g, step & 0xFFFFFFFF, abi.MPC_OBSERVE_RNG_NOISE | (((step >> 32) << 8) & 0xFFFFFFFF),
+    w = named_draw.philox4x32_10(g, step & 0xFFFFFFFF, abi.MPC_OBSERVE_RNG_NOISE | (((step >> 32) << 8) & 0xFFFFFFFF),
                                  np.asarray(fields, dtype=np.int64).reshape(1, -1), seed & 0xFFFFFFFF, seed >> 32)
     total = sum((x & np.uint32(0xFFFF)).astype(np.int64) + (x >> np.uint32(16)).astype(np.int64) for x in w)
     return (2 * total - 524280).astype(np.float32)
@@ -142,7 +123,7 @@ def hold_uniform(seed, gids, step):
     """float32 [M]: u = (w >> 8) * 2^-24 of the hold stream behind step ``step``."""
     seed, step = int(seed) & 0xFFFFFFFFFFFFFFFF, int(step)
     g = np.asarray(gids, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
-    w = env_sensor.philox4x32_10(g, step & 0xFFFFFFFF, abi.MPC_OBSERVE_RNG_HOLD | (((step >> 32) << 8) & 0xFFFFFFFF), 0,
+    w = named_draw.philox4x32_10(g, step & 0xFFFFFFFF, abi.MPC_OBSERVE_RNG_HOLD | (((step >> 32) << 8) & 0xFFFFFFFF), 0,
                                  seed & 0xFFFFFFFF, seed >> 32)
     return (w[0] >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
 

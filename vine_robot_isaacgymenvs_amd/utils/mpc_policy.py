@@ -19,7 +19,7 @@ UNITS = abi.MPC_POLICY_UNITS
 
 
 # ---------------------------------------------------------------------------------------------------------- configuration
-def _eps(key, v):
+def check_eps(key, v):
     if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
         raise ConfigError("mpc policy: %s must be a finite number that is not negative, not %r" % (key, v))
     return float(v)
@@ -34,9 +34,9 @@ def policy_config(obs_width, ln_eps=DEFAULTS["ln_eps"], value_eps=DEFAULTS["valu
     if isinstance(obs_width, bool) or not isinstance(obs_width, (int, np.integer)) or not 1 <= obs_width <= abi.MAX_OBS:
         raise ConfigError("mpc policy: obs_width must be an integer in 1 .. %d, not %r" % (abi.MAX_OBS, obs_width))
     c.obs_width = int(obs_width)
-    c.ln_eps = _eps("ln_eps", ln_eps)
-    c.value_eps = _eps("value_eps", value_eps)
-    c.terminal_value = _eps("terminal_value", terminal_value)
+    c.ln_eps = check_eps("ln_eps", ln_eps)
+    c.value_eps = check_eps("value_eps", value_eps)
+    c.terminal_value = check_eps("terminal_value", terminal_value)
     return c
 
 

@@ -36,6 +36,10 @@ the observation the step has just written (``wants_obs``).  It stands behind the
 which must see the target the step used, and in front of the sensor, which then delays and perturbs the velocity columns
 with the rest of the frame.  So the order is: video, recorder, episode log, target, sensor, push, redraw / ADR.
 
+Those last observers keep no host account of the steps: ``StepObserver`` states the protocol's names that mean nothing to
+them once, and ``TableObserver`` what the target, the sensor and the push share -- a per-env table of named draws
+(utils/named_draw.py) that their launch redraws at a reset.
+
 The host never asks the device where it is: it counts the steps it has enqueued, and ``capture_schedule`` tells it which
 windows those steps completed.  A completed window is copied to pinned host memory on a side stream and handed to a writer
 thread; the training loop never waits for the encoder or the disk."""
@@ -45,7 +49,10 @@ import queue
 import threading
 import time
 
+import numpy as np
 import torch
+
+from . import named_draw
 
 
 KEEP = 256       # entries of a windowed observer's bookkeeping lists
@@ -199,3 +206,79 @@ class WindowRing:
             self.jobs.put(None)
             self.writer.join()
             self.writer = None
+
+
+class StepObserver:
+    """An observer whose launch follows the device's own counters: the host has nothing to count, wait for or write, so the
+    protocol's ``before``, ``advance``, ``set_steps``, ``drain`` and ``close`` do nothing.  A subclass gives ``enqueue`` and
+    ``live_tensors`` and owns ``episode_index`` (int32 [N] on the device)."""
+
+    def __init__(self):
+        self.paused = 0
+        self.copy_done = None
+
+    def before(self, n_steps):
+        pass
+
+    def advance(self, n_steps):
+        pass
+
+    def set_steps(self, steps):
+        pass
+
+    def drain(self):
+        pass
+
+    def close(self):
+        pass
+
+    def episodes_now(self):
+        """A host copy of ``episode_index`` at this point of the current stream (synchronises)."""
+        return self.episode_index.cpu().numpy().astype(np.int64)
+
+
+class TableObserver(StepObserver):
+    """A step observer with a float32 ``table`` [len(NAMES), N] of named draws (utils/named_draw.py), one row per name of the
+    checked ``spec``: episode 0's draw, which the observer's launch replaces per env at a reset when the spec says
+    ``PER_EPISODE`` (counting the env's episodes in ``episode_index``).  A subclass states ``NAMES`` (the spec's keys, the
+    table's rows), ``DRAW_NAMES`` (what the draw is keyed by, and the log's ``param_`` columns) and ``INTEGER`` (the draw
+    names whose range is over the integers), checks the spec against ``values_ptr`` and adds its own buffers."""
+
+    NAMES = DRAW_NAMES = INTEGER = ()
+
+    def __init__(self, lib, handle, vcfg, spec, num_envs, device):
+        super().__init__()
+        self.lib, self.handle, self.vcfg, self.device = lib, handle, vcfg, device
+        self.spec = spec
+        self.seed, self.env_id_offset = int(vcfg.seed), int(vcfg.env_id_offset)
+        self.num_envs = int(num_envs)
+        named = named_draw.named(self.NAMES, self.DRAW_NAMES, spec)
+        values = named_draw.pack(named)[1]
+        self.values = torch.as_tensor(values, dtype=torch.float64, device=device) if len(values) else None
+        gids = np.arange(self.num_envs, dtype=np.int64) + self.env_id_offset
+        self.table = torch.as_tensor(named_draw.draw(named, self.seed, gids, 0, self.INTEGER).astype(np.float32),
+                                     device=device).contiguous()
+        self.episode_index = torch.zeros(self.num_envs, dtype=torch.int32, device=device)
+
+    @property
+    def values_ptr(self):
+        """The device address of the value lists, ``None`` when the spec has none."""
+        return self.values.data_ptr() if self.values is not None else None
+
+    def episode_params(self, envs, episodes):
+        """``named_draw.episode_params`` of local env indices ``envs``."""
+        return named_draw.episode_params(self.NAMES, self.DRAW_NAMES, self.spec, self.seed,
+                                         np.asarray(envs, dtype=np.int64) + self.env_id_offset, episodes, self.INTEGER)
+
+
+class FirstFrameObserver(TableObserver):
+    """A ``TableObserver`` whose launch treats the first frame of an episode specially and so must hear of a reset from
+    outside the step: ``fresh`` (uint8 [N]), set here, cleared by the launch."""
+
+    def __init__(self, lib, handle, vcfg, spec, num_envs, device):
+        super().__init__(lib, handle, vcfg, spec, num_envs, device)
+        self.fresh = torch.ones(self.num_envs, dtype=torch.uint8, device=device)
+
+    def reset_envs(self, env_ids):
+        """The envs were reset from outside the step: the next frame of each is its episode's first."""
+        self.fresh[env_ids] = 1

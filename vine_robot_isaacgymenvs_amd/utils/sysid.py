@@ -288,9 +288,9 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
         ibase, iderive, icheck = np.asarray(inertia[0], dtype=np.float32), inertia[1], inertia[2]
     itable, best_icol = None, None
     gids = np.arange(N, dtype=np.int64)
-    initial = {name: (f[1], f[2]) for name, f in forms.items() if f[0] == "range" and name != "ACTION_DELAY"}
+    initial = {name: (f[0], f[1]) for name, f in forms.items() if isinstance(f, list) and name != "ACTION_DELAY"}
     ranges = dict(initial)
-    discrete = [name for name, f in forms.items() if f[0] == "values" or (name == "ACTION_DELAY" and f[0] == "range")]
+    discrete = [name for name, f in forms.items() if isinstance(f, dict) or (name == "ACTION_DELAY" and isinstance(f, list))]
     draws = {}
     table = env_params.draw_table(spec, base, seed, N, check=check, draws=draws)
     if masses:
@@ -304,8 +304,8 @@ def cem(evaluate, spec, base_row, num_envs, iterations, seed, elite_fraction=0.1
             s = _seed_of(seed, it)
             for name, f in forms.items():
                 u = env_params.uniform01(s, name, gids)
-                if f[0] == "scalar":
-                    v = np.full(N, f[1], dtype=np.float64)
+                if not isinstance(f, (list, dict)):
+                    v = np.full(N, f, dtype=np.float64)
                 elif name in ranges:
                     lo, hi = ranges[name]
                     v = lo + (hi - lo) * u
