@@ -20,6 +20,10 @@
   python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True 'observe={DELAY: 1, NOISE_Q: 0.01, NOISE_QD: 0.1}' \\
       'filter={GAIN_Q: 0.3, GAIN_QD: {values: [0.1, 0.3, 1.0]}}'                     # ... averaged over successive frames
 
+  python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True \\
+      'task.env.ENV_TARGET={VEL_ALONG: {values: [0, 0.1, -0.1]}, SPAN_ALONG: 0.05}' \\
+      'track={PATH: exact}'                                                          # the samples' targets move as the plant's will
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
@@ -29,14 +33,16 @@ the samples roll it and the planner's sequence is a residual on its mean, DESIGN
 configuration's ``train.params``; plants * samples must be a multiple of 512), ``terminal_value`` (the weight of the critic's
 value behind the horizon; default 0), ``observe`` (the planner sees its plants through a sensing path of its own, DESIGN.md
 section 27: ``DELAY``, ``HOLD``, ``NOISE_Q``, ``NOISE_QD`` as ``ENV_SENSOR`` takes them, ``COMPENSATE``, ``CATCHUP``), ``filter``
-(a fixed-gain corrector over those frames, DESIGN.md section 28: ``GAIN_Q``, ``GAIN_QD`` in [0, 1]; needs ``observe``) and ``out``
+(a fixed-gain corrector over those frames, DESIGN.md section 28: ``GAIN_Q``, ``GAIN_QD`` in [0, 1]; needs ``observe``), ``track``
+(the samples' targets follow their plant's ``task.env.ENV_TARGET`` path over the horizon, DESIGN.md section 30: ``PATH`` is
+``exact``, ``linear`` or ``held``; refused with ``policy``, ``adapt``, ``observe`` and ``filter``) and ``out``
 (directory of the episode log's .npz; default ``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
        "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "observe": None, "filter": None,
-       "out": "runs/mpc"}
+       "track": None, "out": "runs/mpc"}
 
 
 def main(argv=None):
@@ -50,7 +56,7 @@ def main(argv=None):
             own[key] = val if key in ("out", "policy") else parse_scalar(val)
         else:
             overrides.append(arg)
-    for key in ("cost", "model_params", "adapt", "observe", "filter"):
+    for key in ("cost", "model_params", "adapt", "observe", "filter", "track"):
         if own[key] is not None and not hasattr(own[key], "keys"):
             raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -65,7 +71,7 @@ def main(argv=None):
                     seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
                     adapt=own["adapt"], policy=own["policy"], terminal_value=own["terminal_value"],
                     policy_params=cfg["train"]["params"] if own["policy"] else None, observe=own["observe"],
-                    filter=own["filter"])
+                    filter=own["filter"], track=own["track"])
 
 
 if __name__ == "__main__":

@@ -8,6 +8,10 @@ control step (fork, horizon x (step + node), update, plant step) as the Controll
 (host clock around replays that end in a synchronise), beside `horizon` bare model steps.  `free`: free space (the
 four-lane step kernel) instead of the task's pipe.
 
+`--track` (profiles/mpc_track/node_cost.txt): plants with a moving target (VEL_ALONG 0, +-0.1, +-0.4 over a SPAN of 0.05 m); the
+whole control step from replayed graphs, without `track=` and with `held`, `linear` and `exact` on the same tree, each as
+the median, minimum and maximum over rounds of 50 replays; and the plan and the track node alone, per launch.
+
 `--adapt`: the five launches of include/vine_mpc_adapt.h instead (W = E = 8, DAMPING adapted), each from a replayed graph of
 `horizon` launches, and one whole cycle of the AdaptiveController beside E control steps of a Controller without a table (what
 the commit before the feature runs) and of a Controller whose model has a table bound (the one-lane step kernel: the table's
@@ -24,7 +28,8 @@ from vine_robot_isaacgymenvs_amd import load_task_config  # noqa: E402
 from vine_robot_isaacgymenvs_amd.utils import mpc  # noqa: E402
 
 ADAPT = "--adapt" in sys.argv
-sys.argv = [a for a in sys.argv if a != "--adapt"]
+TRACK = "--track" in sys.argv
+sys.argv = [a for a in sys.argv if a not in ("--adapt", "--track")]
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 H = int(sys.argv[3]) if len(sys.argv) > 3 else 20
@@ -126,9 +131,49 @@ def adapt_main():
     plant.close()
 
 
+def track_main():
+    from vine_robot_isaacgymenvs_amd.utils import mpc_track
+    cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % M])
+    cfg["seed"] = 42
+    if FREE:
+        cfg["env"].update(CREATE_PIPE=False, CREATE_SHELF=False)
+    cfg["env"]["ENV_TARGET"] = {"VEL_ALONG": {"values": [0.0, 0.1, -0.1, 0.4, -0.4]}, "SPAN_ALONG": 0.05}
+    plant = mpc.make_task(cfg)
+    model = mpc.make_task(mpc.model_config(cfg, M, K))
+    print("%s, %d plants x %d samples = %d model envs, horizon %d, model step kernel %s; ENV_TARGET %s" % (
+        torch.cuda.get_device_name(0), M, K, M * K, H, model.step_kernel_name, cfg["env"]["ENV_TARGET"]))
+    rounds, n = 9, 50
+    for kind in (None,) + mpc_track.PATHS[::-1]:
+        c = mpc.Controller(plant, model, K, H) if kind is None else mpc_track.TrackingController(plant, model, K, {"PATH": kind}, H)
+        c.run(4)
+        us = []
+        for _ in range(rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            c.run(n)
+            torch.cuda.synchronize()
+            us.append((time.perf_counter() - t0) / n * 1e6)
+        print("%-22s %d rounds of %d replayed control steps: median %.1f us per control step (min %.1f, max %.1f)%s" % (
+            "without track=" if kind is None else "track={PATH: %s}" % kind, rounds, n, np.median(us), min(us), max(us),
+            "" if kind is None else "; live %.2f of the plants" % float(c.live.float().mean())))
+    ctl = mpc_track.TrackingController(plant, model, K, {"PATH": "exact"}, H, graph=False)
+    ctl.control_step()
+    print("plan                   median %.2f us per launch (min %.2f, max %.2f) over %d replays of %d" % (
+        *per_launch_us(graph_of(ctl.plan)), REPLAYS, H))
+    print("track node, no window  median %.2f us per launch (min %.2f, max %.2f)" % per_launch_us(graph_of(ctl.track_node)))
+    steps = graph_of(lambda: mpc.Controller.model_step(ctl))
+    both = graph_of(ctl.model_step)
+    s, b = per_launch_us(steps, ctl.fork), per_launch_us(both, ctl.fork)
+    print("step + node %.2f us, step + node + track node %.2f us inside a window: track node = %.2f us" % (s[0], b[0], b[0] - s[0]))
+    model.close()
+    plant.close()
+
+
 def main():
     if ADAPT:
         return adapt_main()
+    if TRACK:
+        return track_main()
     cfg = load_task_config("Vine5LinkMovingBase", overrides=["num_envs=%d" % M])
     cfg["seed"] = 42
     if FREE:

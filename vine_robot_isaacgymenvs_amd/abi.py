@@ -988,6 +988,43 @@ def declare_mpc_filter(lib):
     return lib
 
 
+# ---- include/vine_mpc_track.h (product library only)
+MPC_TRACK_ABI_VERSION = 1
+MPC_TRACK_THREADS = 256
+MPC_TRACK_WORDS = 3                                                # TY, TZ, DEPTH of a path entry
+MPC_TRACK_PATHS = ("exact", "linear", "held")                      # by VineMpcTrackPath
+TRACK_EXACT, TRACK_LINEAR, TRACK_HELD = range(3)
+
+
+class VineMpcTrackSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_plants", C.c_int32),
+        ("samples", C.c_int32),
+        ("horizon", C.c_int32),
+        ("mode", C.c_int32),
+        ("path", C.c_int32),
+        ("cdt", C.c_float),
+        ("checked", C.c_uint32),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+MPC_TRACK_PROTOTYPES = {
+    "vine_mpc_track_spec_size": (C.c_int, []),
+    "vine_mpc_track_spec": (C.c_int, [_P(VineEnvTargetSpec), _P(VineMpcConfig), C.c_int, _P(VineMpcTrackSpec)]),
+    "vine_mpc_track_plan": (C.c_int, [_H, _P(VineMpcTrackSpec)] + [_VP] * 7),
+    "vine_mpc_track_scheduled": (C.c_int, [_H, _P(VineMpcTrackSpec)] + [_VP] * 5),
+}
+
+
+def declare_mpc_track(lib):
+    _attach(lib, MPC_TRACK_PROTOTYPES)
+    if lib.vine_mpc_track_spec_size() != C.sizeof(VineMpcTrackSpec):
+        raise RuntimeError("VineMpcTrackSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -1002,6 +1039,6 @@ def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
-                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter):
+                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track):
         declare_one(lib)
     return lib

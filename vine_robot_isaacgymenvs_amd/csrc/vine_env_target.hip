@@ -10,7 +10,8 @@
 // CONTRACTION IS OFF FOR THIS WHOLE TRANSLATION UNIT, by the pragma in front of everything it includes (native.py compiles it
 // with -ffp-contract=fast-honor-pragmas; plain "fast" ignores the pragma): `obs + w * inv`, `off + vel * cdt` and
 // `ay - off * c` must stay a multiply and an add, each rounded, as numpy forms them, and the draw of vine_named_draw.h
-// must hold the host's bits.
+// must hold the host's bits.  The path step and the words of a point of the path are stated in vine_target_path.h, which
+// vine_mpc_track.hip includes too.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -21,24 +22,11 @@
 #include "../../include/vine_env_target.h"
 #include "vine_named_draw.h"
 #include "vine_observer.h"
+#include "vine_target_path.h"
 
 namespace {
 
 constexpr int THREADS = VINE_ENV_TARGET_THREADS;
-
-// one control step along an axis of half-length S, reflected at its ends (one reflection suffices: the spec check)
-__device__ __forceinline__ void advance(float& off, float& vel, const float S, const float cdt) {
-    const float step = vel * cdt;
-    float nx = off + step;
-    if (nx > S) {
-        nx = S - (nx - S);
-        vel = -vel;
-    } else if (nx < -S) {
-        nx = -S - (nx + S);
-        vel = -vel;
-    }
-    off = nx;
-}
 
 template <int MODE>
 __global__ __launch_bounds__(THREADS) void vine_env_target_kernel(const VineEnvTargetSpec S, const int n, const unsigned env_off,
@@ -106,20 +94,13 @@ __global__ __launch_bounds__(THREADS) void vine_env_target_kernel(const VineEnvT
             o[0] = fminf(fmaxf(xy, -S.clip_observations), S.clip_observations);
             o[1] = fminf(fmaxf(xz, -S.clip_observations), S.clip_observations);
         }
-        advance(oa, va, table[(size_t)VTG_SPAN_ALONG * n + e], S.cdt);
-        if (MODE == VINE_TARGET_FREE) advance(oc, vc, table[(size_t)VTG_SPAN_ACROSS * n + e], S.cdt);
-        if (MODE == VINE_TARGET_FREE) {
-            ST(VF_TARGET_Y) = ay + oa;
-            ST(VF_TARGET_Z) = az + oc;
-        } else if (MODE == VINE_TARGET_SHELF) {
-            ST(VF_TARGET_Y) = ay - oa;
-            ST(VF_OBJ_DEPTH) = d0 + oa;
-        } else {
-            const float py = oa * c, pz = oa * s;
-            ST(VF_TARGET_Y) = ay - py;
-            ST(VF_TARGET_Z) = az - pz;
-            ST(VF_OBJ_DEPTH) = d0 + oa;
-        }
+        target_path_advance(oa, va, table[(size_t)VTG_SPAN_ALONG * n + e], S.cdt);
+        if (MODE == VINE_TARGET_FREE) target_path_advance(oc, vc, table[(size_t)VTG_SPAN_ACROSS * n + e], S.cdt);
+        float ty = 0.0f, tz = 0.0f, depth = 0.0f;
+        target_path_words<MODE>(ay, az, d0, c, s, oa, oc, ty, tz, depth);
+        ST(VF_TARGET_Y) = ty;
+        if (MODE != VINE_TARGET_SHELF) ST(VF_TARGET_Z) = tz;
+        if (MODE != VINE_TARGET_FREE) ST(VF_OBJ_DEPTH) = depth;
     }
     if (first || moving) {
         MO(VTM_OFF_ALONG) = oa;
@@ -148,9 +129,7 @@ void launch(const VineEnvTargetSpec& S, const VineHandleInfo& info, unsigned env
                        episode_index);
 }
 
-int mode_of(unsigned flags) {
-    return (flags & VINE_FLAG_CREATE_PIPE) ? VINE_TARGET_PIPE : (flags & VINE_FLAG_CREATE_SHELF) ? VINE_TARGET_SHELF : VINE_TARGET_FREE;
-}
+int mode_of(unsigned flags) { return target_path_mode_of(flags); }
 
 }  // namespace
 

@@ -49,6 +49,9 @@ SRC_MPC_FILTER = os.path.join(_HERE, "csrc", "vine_mpc_filter.hip")
 # tests/test_mpc_filter_cpu.py pins that spelling in turn; the sixteenth, the moving target's, follows it there: build() compiles
 # and links POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,)
 SRC_TARGET = os.path.join(_HERE, "csrc", "vine_env_target.hip")
+# tests/test_env_target_cpu.py pins that spelling, colon included; the seventeenth, the controller's target tracking, cannot join
+# the expression: build() hands it to the loop's body (a local helper) once more behind the loop
+SRC_MPC_TRACK = os.path.join(_HERE, "csrc", "vine_mpc_track.hip")
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -65,10 +68,13 @@ _COMPOSITES = os.path.join(_HERE, "csrc", "vine_inertia_composites.h")
 _NAMED_DRAW_HEADERS = [os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HERE, "csrc", "vine_named_draw.h")]
 _REDRAW_HEADERS = [_COMPOSITES] + _NAMED_DRAW_HEADERS + [os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
 _MPC_SHARED = os.path.join(_HERE, "csrc", "vine_mpc_shared.h")      # the fork's and the pin's column copy and ring rebuild
+_TARGET_PATH = os.path.join(_HERE, "csrc", "vine_target_path.h")    # the target's path step and the words of a point of it
 _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
                    SRC_SENSOR: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
                    SRC_PUSH: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
-                   SRC_TARGET: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h")],
+                   SRC_TARGET: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h"), _TARGET_PATH],
+                   SRC_MPC_TRACK: [os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_INC, "vine_env_target.h"),
+                                   os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
                    SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")],
@@ -89,18 +95,21 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # vine_mpc_filter.hip forms a corrected joint value, x + g * (y - x), that numpy must reproduce bit for bit: the same again
 # vine_env_target.hip forms an offset, off + vel * cdt, a target, ay - off * c, and an observation column, obs + w * inv, that
 # numpy must reproduce bit for bit: the same again
+# vine_mpc_track.hip forms the same offsets and targets H - 1 steps ahead, bit for bit those of vine_env_target.hip: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_OBSERVE: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"], SRC_TARGET: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"], SRC_TARGET: ["-ffp-contract=fast-honor-pragmas"],
+                 SRC_MPC_TRACK: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
         + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
         + [SRC_MPC_POLICY, os.path.join(_INC, "vine_mpc_policy.h")]
         + [SRC_MPC_OBSERVE, os.path.join(_INC, "vine_mpc_observe.h")]
         + [SRC_MPC_FILTER, os.path.join(_INC, "vine_mpc_filter.h")]
-        + [SRC_TARGET, os.path.join(_INC, "vine_env_target.h")])
+        + [SRC_TARGET, os.path.join(_INC, "vine_env_target.h")]
+        + [SRC_MPC_TRACK, os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH])
 
 _lib = None
 
@@ -139,7 +148,7 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The sixteen translation units are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The seventeen translation units are
     compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
@@ -152,7 +161,8 @@ def build(force=False, verbose=False):
     if os.path.exists(FINGERPRINT):
         os.remove(FINGERPRINT)
     jobs, objs = [], []
-    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,):
+
+    def compile_unit(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
         fp = _object_fingerprint(src)
@@ -161,13 +171,17 @@ def build(force=False, verbose=False):
         except OSError:
             fresh = False
         if fresh:
-            continue
+            return
         cmd = [hipcc] + _flags(src) + ["-c", "-o", obj, src]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         if os.path.exists(obj + ".fingerprint"):
             os.remove(obj + ".fingerprint")
         jobs.append((subprocess.Popen(cmd), cmd, obj, fp))
+
+    for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,):
+        compile_unit(src)
+    compile_unit(SRC_MPC_TRACK)      # the seventeenth: started before any of the sixteen is waited for
     for proc, cmd, obj, fp in jobs:
         if proc.wait() != 0:
             raise subprocess.CalledProcessError(proc.returncode, cmd)

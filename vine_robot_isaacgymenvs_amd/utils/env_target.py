@@ -136,6 +136,9 @@ def _advance(off, vel, span, cdt):
     return n.astype(np.float32), np.where(over | under, -vel, vel).astype(np.float32), over | under
 
 
+advance = _advance                    # the one statement of the path step, for utils/mpc_track.py plan_replay too
+
+
 def target_replay(spec, seed, gids, layout, state, obs, progress, resets, axis=None, external_resets=None, table=None):
     """The launch behind T steps, on the host, in float32, bit for bit.  ``spec``: ``target_config``'s result; ``gids`` [N]:
     global env ids; ``layout``: ``layout_of``'s result (or the same keys by hand); ``state`` [T, VF_COUNT, N] float32: the state

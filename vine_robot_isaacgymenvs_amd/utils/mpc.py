@@ -384,7 +384,7 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None):
+         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None, track=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -415,7 +415,15 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     ``observe=`` and is refused together with ``adapt`` or ``policy``, and where the largest ``DELAY`` plus the model's largest
     ``ACTION_DELAY`` reaches beyond the action log.  The result then holds ``filter``: the per-plant ``gain`` [2, M], its
     ``names`` and the mean ``innov`` [2]; the per-parameter report has ``param_FILTER_<NAME>`` for a gain that varies.  Without
-    it nothing of this is constructed or launched."""
+    it nothing of this is constructed or launched.
+
+    ``track``: a spec of ``mpc_track.track_config``, ``{PATH: exact | linear | held}`` -- the samples' targets move over the
+    horizon along their plant's ``ENV_TARGET`` path (include/vine_mpc_track.h, ``mpc_track.TrackingController``).  It needs a
+    plant with ``task.env.ENV_TARGET`` and is refused together with ``policy`` (the samples' observation would need the
+    velocity columns) and with ``adapt``, ``observe`` or ``filter`` (their third handles and traces were built for a resting
+    target).  The result then holds ``track``: ``PATH`` and ``live_fraction``, the share of (plant, control step) pairs whose
+    samples followed a path; the per-parameter report has the plant's varying ``param_TARGET_*`` columns.  Without it nothing
+    of this is constructed or launched."""
     import torch
     from . import episodes
     logger = logger or logging.getLogger(__name__)
@@ -426,6 +434,17 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
+    if track is not None:
+        from . import mpc_track
+        track = mpc_track.track_config(track)
+        if not (cfg["env"].get("ENV_TARGET") or {}):
+            raise ConfigError("mpc: track= needs a plant with task.env.ENV_TARGET: there is no path to follow")
+        if policy is not None:
+            raise ConfigError("mpc: track= together with policy= is refused: the samples' observation would need the target's velocity columns")
+        if adapt is not None:
+            raise ConfigError("mpc: track= together with adapt= is refused: the adaptive controller's traces were built for a resting target")
+        if observe is not None or filter is not None:
+            raise ConfigError("mpc: track= together with observe= or filter= is refused: the predictor was built for a resting target")
     if filter is not None:
         from . import mpc_filter
         if observe is None:
@@ -494,6 +513,11 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
             if model_params:
                 ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
             print("mpc: the samples roll the policy of %s; terminal_value %g" % (policy, float(terminal_value)), flush=True)
+        elif track is not None:
+            ctl = mpc_track.TrackingController(plant, model, samples, track, horizon, lam, sigma, seed, graph=graph)
+            if model_params:
+                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
+            print("mpc: the samples' targets follow the %s path of their plant's ENV_TARGET" % track["PATH"], flush=True)
         elif adapt is None:
             ctl = Controller(plant, model, samples, horizon, lam, sigma, seed, graph=graph)
             if model_params:
@@ -515,12 +539,15 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
             M, ctl.K, ctl.H, float(lam), sigma, "hipGraph replay" if ctl.use_graph else "eager launches",
             model.step_kernel_name), flush=True)
         total = torch.zeros(M, dtype=torch.float64, device=plant.device)
+        lived = torch.zeros((), dtype=torch.int64, device=plant.device) if track is not None else None
         torch.cuda.synchronize(plant.device)
         t0 = time.perf_counter()
         if adapt is None:
             for _ in range(int(steps)):
                 ctl.run(1)
                 total += plant.rew_buf
+                if lived is not None:
+                    lived += ctl.live.sum()
         else:                                            # whole cycles replay from one graph: the trace node sums the reward
             ctl.run(int(steps))
             total += ctl.returns
@@ -531,6 +558,10 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
                "model_step_kernel": model.step_kernel_name, "model_table_bound": model.env_params is not None}
         if policy is not None:
             out["policy"] = policy
+        if track is not None:
+            out["track"] = {"PATH": track["PATH"], "live_fraction": float(lived) / max(1, int(steps) * M)}
+            print("mpc: tracked along the %s path on %.4g of the (plant, control step) pairs" % (
+                track["PATH"], out["track"]["live_fraction"]), flush=True)
         if observe is not None:
             out["observe"] = {"names": list(mpc_observe.NAMES), "table": ctl.table_host.copy(), "catchup": ctl.C,
                               "compensate": ctl.spec["COMPENSATE"], "lag": float(ctl.lag.double().mean())}
@@ -544,7 +575,7 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         if log is not None:
             from ..learning.player import format_report
             log.harvest()
-            rows = log.rows_with_params() if plant.env_params is not None else log.rows()
+            rows = log.rows_with_params() if plant.env_params is not None or track is not None else log.rows()
             keep = rows["end_step"] >= start
             rows = {k: v[keep] for k, v in rows.items()}
             if filter is not None:                       # a gain that varies over the plants is a parameter of the report
