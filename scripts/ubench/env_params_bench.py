@@ -15,13 +15,17 @@ With --adr: the same three cases for the two launches of ENV_PARAMS_ADR (include
 same run.  The ADR launches read the reward matrix, and a bound matrix makes the step itself write 52 more bytes per env, so
 their baseline is the step alone WITH a matrix bound: node cost = (step + launches) - (that step).
 
+With --draw-adr: --adr, and beside its pair in the same run the two launches of ENV_DRAW_ADR (include/vine_env_draw_adr.h) on the
+same handle and against the same baseline: four names under ADR (SENSOR_DELAY, SENSOR_NOISE_STD, PUSH_IMPULSE, TARGET_VEL_ALONG),
+the three observers' tables present but their launches not issued, so that the difference is the pair's alone.
+
 With --sensor: the cost of the ENV_SENSOR launch (include/vine_env_sensor.h) behind every step of the default handle (no
 table: up to 16384 envs the four-lane kernel), beside the bare step in the same run: idle (delay, hold and noise 0 in every env,
 never a first frame: every lane still pushes its frame), with the step's own resets under delays 0..8 and holds, and with
 noise on every env (28 Philox calls per env and step).  Reported with the share of the 8 TB/s HBM peak the launch's bytes
 over its duration amount to (bytes: the passes over the observation block that case makes).
 
-usage: python scripts/ubench/env_params_bench.py [--redraw | --adr | --sensor] [num_envs ...]        (default: 16384 1048576)"""
+usage: python scripts/ubench/env_params_bench.py [--redraw | --adr | --draw-adr | --sensor] [num_envs ...]        (default: 16384 1048576)"""
 import os
 import statistics
 import sys
@@ -83,10 +87,39 @@ def make(n, kern, table, inertia=None, matrix=False, **over):
     return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode()
 
 
-def make_redraw(n, which, adr=False):
+DRAW_ADR_ENV = {"ENV_SENSOR": {"DELAY": [0, 8], "NOISE_STD": [0.0, 0.02], "PER_EPISODE": True},
+                "ENV_PUSH": {"RATE": 0.05, "IMPULSE": [0.0, 0.01], "PER_EPISODE": True},
+                "ENV_TARGET": {"VEL_ALONG": [-0.3, 0.3], "SPAN_ALONG": 0.05, "PER_EPISODE": True},
+                "ENV_DRAW_ADR": {"NAMES": {"SENSOR_DELAY": {"START": [0, 0], "STEP": 1}, "SENSOR_NOISE_STD": {"START": [0.0, 0.0], "STEP": 0.002},
+                                           "PUSH_IMPULSE": {"START": [0.0, 0.0], "STEP": 0.002},
+                                           "TARGET_VEL_ALONG": {"START": [0.0, 0.0], "STEP": 0.05}}}}
+
+
+def draw_adr_node(env, n, flags):
+    """The arguments of ``vine_env_draw_adr_scheduled`` on ``env``: the checked spec, the three tables at START, zeroed state."""
+    import ctypes as C
+
+    import numpy as np
+
+    from vine_robot_isaacgymenvs_amd.utils import env_draw_adr, env_push, env_sensor, env_target
+    cfgs = (env_sensor.sensor_config(DRAW_ADR_ENV, env.num_obs), env_push.push_config(DRAW_ADR_ENV),
+            env_target.target_config(DRAW_ADR_ENV, np.float32(env.cfg.dt) * np.float32(env.cfg.control_freq_inv)))
+    acfg = env_draw_adr.draw_adr_config(DRAW_ADR_ENV, *cfgs)
+    aspec = env_draw_adr.draw_adr_spec(env.lib, env.cfg, acfg, env_sensor.sensor_spec(env.lib, env.cfg, cfgs[0]),
+                                       env_push.push_spec(env.lib, env.cfg, cfgs[1]), env_target.target_spec(env.lib, env.cfg, cfgs[2]))
+    tables = [torch.zeros((rows, n), device=env.dev) for rows in (abi.VSN_NAMES, abi.VPU_NAMES, abi.VTG_NAMES)]
+    i32 = dict(dtype=torch.int32, device=env.dev)
+    state = [torch.zeros(18, **i32), torch.zeros(36, **i32), torch.zeros(n, **i32), torch.full((n,), -1, **i32), torch.zeros(n, **i32),
+             torch.zeros((acfg["HISTORY_CAPACITY"], 4), **i32), torch.zeros(1, dtype=torch.int64, device=env.dev)]
+    pointers = (C.c_void_p * 3)(*[t.data_ptr() for t in tables])
+    env.keep_draw_adr = (aspec, tables, state, pointers)
+    return [env.h, aspec, flags.data_ptr(), pointers, None] + [t.data_ptr() for t in state]
+
+
+def make_redraw(n, which, adr=False, draw=False):
     """The handle of ``lane+het_table+het_inertia`` with the redraw node behind every captured step; ``which``: the flags the
     node reads -- "none" (zeros), "own" (the step's reset buffer), "all" (ones).  ``adr``: the two ADR launches in the node's
-    place, a reward matrix bound."""
+    place, a reward matrix bound; ``draw``: the two ENV_DRAW_ADR launches in their place."""
     cfg = base_cfg(n, 0, True)
     env = type("H", (HipEnv,), {"kernel": "lane"})(cfg)
     env.set_introspection(False)
@@ -114,8 +147,13 @@ def make_redraw(n, which, adr=False):
                  torch.zeros((acfg["HISTORY_CAPACITY"], 4), **i32), torch.zeros(1, dtype=torch.int64, device=env.dev)]
         env.keep_adr = (aspec, state)
 
+    if draw:
+        draw_args = draw_adr_node(env, n, flags)
+
     def pair(a):
         env.step_t(a, sync=False)
+        if draw:
+            return native.check(env.lib.vine_env_draw_adr_scheduled(*(draw_args + [torch.cuda.current_stream(env.dev).cuda_stream])), env.lib)
         if adr:
             return native.check(env.lib.vine_env_adr_scheduled(
                 env.h, aspec, flags.data_ptr(), env.table_t.data_ptr(), env.inertia_t.data_ptr(), episode.data_ptr(),
@@ -134,10 +172,10 @@ def make_redraw(n, which, adr=False):
     env.keep = (rspec, episode, flags)
     torch.cuda.synchronize()
     env.reset_share = float((env.reset_t != 0).float().mean())
-    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + (" + adr" if adr else " + redraw")
+    return env, graph, k, env.lib.vine_step_kernel_name(env.h).decode() + (" + draw adr" if draw else " + adr" if adr else " + redraw")
 
 
-def main_redraw(sizes, adr=False):
+def main_redraw(sizes, adr=False, draw=False):
     for n in sizes:
         envs = {"step alone (both het tables)": make(n, "lane", "het", "het"),
                 "step + node, no env resetting": make_redraw(n, "none"),
@@ -148,6 +186,10 @@ def main_redraw(sizes, adr=False):
                          "step + adr, no env resetting": make_redraw(n, "none", True),
                          "step + adr, the step's own resets": make_redraw(n, "own", True),
                          "step + adr, every env resetting": make_redraw(n, "all", True)})
+        if draw:
+            envs.update({"step + draw adr, no env resetting": make_redraw(n, "none", True, True),
+                         "step + draw adr, the step's own resets": make_redraw(n, "own", True, True),
+                         "step + draw adr, every env resetting": make_redraw(n, "all", True, True)})
         times = {name: [] for name in envs}
         for _ in range(ROUNDS):
             for name, (env, graph, k, _) in envs.items():
@@ -170,7 +212,8 @@ def main_redraw(sizes, adr=False):
             base = statistics.median(times["step alone, reward matrix bound"])
             for name in list(envs)[5:]:
                 own = " (%.1f %% of the envs flagged after the last step)" % (100 * envs[name][0].reset_share) if "own" in name else ""
-                print("  adr launches, %s: %+.2f us per pair%s" % (name.split(", ")[1], statistics.median(times[name]) - base, own))
+                print("  %s launches, %s: %+.2f us per pair%s" % ("draw adr" if "draw adr" in name else "adr", name.split(", ")[1],
+                                                                 statistics.median(times[name]) - base, own))
         for env, _, _, _ in envs.values():
             env.close()
         del envs
@@ -253,9 +296,10 @@ def main_sensor(sizes):
 def main():
     if "--sensor" in sys.argv[1:]:
         return main_sensor([int(a) for a in sys.argv[1:] if a != "--sensor"] or [16384, 1 << 20])
-    args = [a for a in sys.argv[1:] if a not in ("--redraw", "--adr")]
-    if "--redraw" in sys.argv[1:] or "--adr" in sys.argv[1:]:
-        return main_redraw([int(a) for a in args] or [16384, 1 << 20], adr="--adr" in sys.argv[1:])
+    args = [a for a in sys.argv[1:] if a not in ("--redraw", "--adr", "--draw-adr")]
+    if "--redraw" in sys.argv[1:] or "--adr" in sys.argv[1:] or "--draw-adr" in sys.argv[1:]:
+        draw = "--draw-adr" in sys.argv[1:]
+        return main_redraw([int(a) for a in args] or [16384, 1 << 20], adr=draw or "--adr" in sys.argv[1:], draw=draw)
     for n in [int(a) for a in args] or [16384, 1 << 20]:
         envs = {name: make(n, *v) for name, v in VARIANTS.items()}
         times = {name: [] for name in VARIANTS}

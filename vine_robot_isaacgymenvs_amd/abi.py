@@ -1025,6 +1025,65 @@ def declare_mpc_track(lib):
     return lib
 
 
+# ---- include/vine_env_draw_adr.h (product library only)
+ENV_DRAW_ADR_ABI_VERSION = 1
+ENV_DRAW_ADR_THREADS = 256
+ENV_DRAW_ADR_HISTORY_WORDS = 4
+ENV_DRAW_ADR_KEY_PROBE = 0x13605cadb5285d5e      # named_draw.name_key("DRAW_ADR_PROBE")
+ENV_DRAW_ADR_KEY_WHICH = 0x5ce5f9cbbb3b47a7      # named_draw.name_key("DRAW_ADR_WHICH")
+VDA_SENSOR, VDA_PUSH, VDA_TARGET = range(3)      # VineEnvDrawAdrGroup: whose table a name's row lies in
+VDA_GROUPS = 3
+# VineEnvDrawAdrSlotIndex: the draw names of the three observers, one group behind the other
+ENV_DRAW_ADR_NAMES = (["SENSOR_" + n for n in ENV_SENSOR_NAMES] + ["PUSH_" + n for n in ENV_PUSH_NAMES]
+                      + ["TARGET_" + n for n in ENV_TARGET_NAMES])
+VDA_NAMES = 9
+ENV_DRAW_ADR_INTEGER = ("SENSOR_DELAY",)
+
+
+class VineEnvDrawAdrSlot(C.Structure):
+    _fields_ = [
+        ("adr", VineEnvAdrName),
+        ("max_widen", C.c_int32 * 2),
+        ("group", C.c_int32),
+        ("row", C.c_int32),
+        ("integer", C.c_int32),
+        ("reserved", C.c_int32),
+        ("limits", VineEnvRedrawName),
+    ]
+
+
+class VineEnvDrawAdrSpec(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_adr", C.c_int32),
+        ("queue", C.c_int32),
+        ("history_capacity", C.c_int32),
+        ("boundary_fraction", C.c_double),
+        ("widen_at", C.c_double),
+        ("narrow_at", C.c_double),
+        ("seed", C.c_uint64),
+        ("slot", VineEnvDrawAdrSlot * VDA_NAMES),
+        ("adr_slot", C.c_int32 * VDA_NAMES),
+        ("checked", C.c_uint32),
+    ]
+
+
+ENV_DRAW_ADR_PROTOTYPES = {
+    "vine_env_draw_adr_spec_size": (C.c_int, []),
+    "vine_env_draw_adr_spec": (C.c_int, [_P(VineConfig), _P(VineEnvSensorSpec), _P(VineEnvPushSpec), _P(VineEnvTargetSpec),
+                                         _P(VineEnvAdrName), C.c_double, C.c_int, C.c_double, C.c_double, C.c_int,
+                                         _P(VineEnvDrawAdrSpec)]),
+    "vine_env_draw_adr_scheduled": (C.c_int, [_H, _P(VineEnvDrawAdrSpec), _VP, _P(C.c_void_p)] + [_VP] * 9),
+}
+
+
+def declare_env_draw_adr(lib):
+    _attach(lib, ENV_DRAW_ADR_PROTOTYPES)
+    if lib.vine_env_draw_adr_spec_size() != C.sizeof(VineEnvDrawAdrSpec):
+        raise RuntimeError("VineEnvDrawAdrSpec: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 def declare_ppo(lib):
     _attach(lib, PPO_PROTOTYPES)
     return lib
@@ -1039,6 +1098,7 @@ def declare_all(lib):
     """Every prototype of the library, and the struct-size checks of the observers' configurations."""
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
-                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track):
+                        declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track,
+                        declare_env_draw_adr):
         declare_one(lib)
     return lib

@@ -40,6 +40,9 @@ Deviations from the reference's defaults (each documented in DESIGN.md / INTEGRA
     the depth axis of the shelf or the pipe, turning round SPAN m either side of where the reset put it; advanced on the device
     behind the step, which also puts the target's velocity into the observation; PER_EPISODE redraws the four values at every
     reset; the step kernels are untouched; utils/env_target.py),
+  task.env.ENV_DRAW_ADR {} (not a reference key; NAMES: {DRAW NAME: {START: [lo, hi], STEP: s}} over the PER_EPISODE [lo, hi] draws
+    of ENV_SENSOR, ENV_PUSH and ENV_TARGET (SENSOR_DELAY .. TARGET_SPAN_ACROSS) makes those ranges begin at START and widen on the
+    device towards their limits as ENV_PARAMS_ADR's do; utils/env_draw_adr.py),
   train.params.config.mixed_precision_dtype (not an rl_games key): fp16 (the reference's autocast dtype) = the hand-written
     mixed-precision update with device-side loss scaling; train.params.config.rollout_precision: fp32 (the reference's),
   task.env.physicsModel.* (switches of the built-in articulation solver; not reference keys),
@@ -127,6 +130,7 @@ TASK = {
          'ENV_SENSOR': {},
          'ENV_PUSH': {},
          'ENV_TARGET': {},
+         'ENV_DRAW_ADR': {},
          'CREATE_SHELF': False,
          'CREATE_PIPE': True,
          'CREATE_HISTOGRAMS_PERIODICALLY': False,

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "../../include/vine_env_adr.h"
+#include "vine_adr_shared.h"
 #include "vine_env_redraw_draw.h"
 #include "vine_observer.h"
 
@@ -26,6 +27,7 @@ namespace {
 
 constexpr int THREADS = VINE_ENV_ADR_THREADS;
 constexpr int BOUNDARIES = 2 * VR_NAMES;
+static_assert(ADR_HISTORY_WORDS == VINE_ENV_ADR_HISTORY_WORDS, "the history row of vine_adr_shared.h is the header's");
 static_assert(BOUNDARIES <= 64, "decide is one wave, one lane per boundary");
 static_assert(2 * BOUNDARIES <= THREADS, "the workgroup's counts are flushed by its first 2 * BOUNDARIES lanes");
 
@@ -33,42 +35,16 @@ static_assert(2 * BOUNDARIES <= THREADS, "the workgroup's counts are flushed by 
 __host__ __device__ inline double adr_bound(const VineEnvAdrSpec& A, int s, int side, int w) {
     const VineEnvAdrName& a = A.name[s];
     const VineEnvRedrawName& lim = A.redraw.name[s];
-    if (side == 0) return fmax(lim.lo, a.start_lo - (double)w * a.step);
-    return fmin(lim.hi, a.start_hi + (double)w * a.step);
+    if (side == 0) return adr_bound_lo(lim.lo, a.start_lo, a.step, w);
+    return adr_bound_hi(lim.hi, a.start_hi, a.step, w);
 }
 
 __global__ __launch_bounds__(64) void vine_env_adr_decide_kernel(const VineEnvAdrSpec A, const unsigned long long* __restrict__ counters,
                                                                  const int glog, int* __restrict__ widen, int* __restrict__ counts,
                                                                  int* __restrict__ history, unsigned long long* __restrict__ cursor) {
-    const int b = (int)threadIdx.x;
-    bool changed = false;
-    int w_new = 0;
-    if (b < BOUNDARIES && A.name[b >> 1].on) {
-        const int n = counts[2 * b], r = counts[2 * b + 1];
-        if (n >= A.queue) {
-            const int w = widen[b];
-            w_new = w;
-            if ((double)r >= A.widen_at * (double)n) w_new = min(w + 1, A.max_widen[b >> 1][b & 1]);
-            else if ((double)r <= A.narrow_at * (double)n) w_new = max(w - 1, 0);
-            changed = w_new != w;
-            if (changed) widen[b] = w_new;
-            counts[2 * b] = 0;
-            counts[2 * b + 1] = 0;
-        }
-    }
-    const unsigned long long ballot = __ballot(changed);
-    if (ballot == 0ull) return;
-    const unsigned long long base = cursor[0];
-    if (changed) {
-        const unsigned long long k = base + (unsigned long long)__popcll(ballot & ((1ull << b) - 1ull));
-        int* row = history + (size_t)(k % (unsigned long long)A.history_capacity) * VINE_ENV_ADR_HISTORY_WORDS;
-        row[0] = (int)(long long)vine_steps_completed(counters, glog) - 1;
-        row[1] = b;
-        row[2] = w_new;
-        row[3] = 0;
-    }
-    __syncthreads();      // every lane has read the cursor
-    if (b == 0) cursor[0] = base + (unsigned long long)__popcll(ballot);
+    adr_decide_lane((int)threadIdx.x, BOUNDARIES, A.queue, A.widen_at, A.narrow_at, A.history_capacity,
+                    [&A](int b) { return A.name[b >> 1].on != 0; }, [&A](int b) { return A.max_widen[b >> 1][b & 1]; }, counters, glog,
+                    widen, counts, history, cursor);
 }
 
 __global__ __launch_bounds__(THREADS) void vine_env_adr_redraw_kernel(const VineEnvAdrSpec A, const int n, const unsigned env_off,

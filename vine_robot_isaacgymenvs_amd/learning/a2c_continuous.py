@@ -1489,11 +1489,17 @@ class A2CAgent(FastInferenceMixin):
         """The env's ``EnvAdr`` (ENV_PARAMS_ADR), else ``None``."""
         return getattr(getattr(self.vec_env, "env", self.vec_env), "env_adr", None)
 
+    def _env_draw_adr(self):
+        """The env's ``EnvDrawAdr`` (ENV_DRAW_ADR), else ``None``."""
+        return getattr(getattr(self.vec_env, "env", self.vec_env), "env_draw_adr", None)
+
     def get_full_state_weights(self):
         state = {"model": self.model.state_dict(), "epoch": self.epoch_num, "optimizer": self.optimizer.state_dict(),
                  "frame": self.frame, "last_mean_rewards": self.last_mean_rewards, "last_lr": float(self.lr)}
         if self._env_adr() is not None:          # ENV_PARAMS_ADR: how far every boundary has moved
             state["adr"] = self._env_adr().state_dict()
+        if self._env_draw_adr() is not None:     # ENV_DRAW_ADR: likewise, for the sensor's, the push's and the target's ranges
+            state["draw_adr"] = self._env_draw_adr().state_dict()
         return state
 
     def save(self, fn):
@@ -1515,6 +1521,8 @@ class A2CAgent(FastInferenceMixin):
             self.lr.fill_(ckpt["last_lr"])
         if "adr" in ckpt and self._env_adr() is not None:
             self._env_adr().load_state_dict(ckpt["adr"])
+        if "draw_adr" in ckpt and self._env_draw_adr() is not None:      # (before the first step; one that does not fit is refused)
+            self._env_draw_adr().load_state_dict(ckpt["draw_adr"])
         if self.fused_mixed:
             self.optimizer.refresh_shadow()
 
@@ -1616,11 +1624,12 @@ class A2CAgent(FastInferenceMixin):
     def write_adr_stats(self):
         """ENV_PARAMS_ADR: ``adr/<NAME>_lo``, ``adr/<NAME>_hi`` and ``adr/probing_reach_rate`` from one non-blocking copy of
         the observer's integers, here where the episode log's scalars are harvested (nothing inside the rollout waits)."""
-        adr = self._env_adr()
-        if adr is None or not self.writer:
+        if not self.writer:
             return
-        for k, v in adr.scalars().items():
-            self.writer.add_scalar(k, v, self.frame)
+        for adr in (self._env_adr(), self._env_draw_adr()):      # ENV_DRAW_ADR: ``draw_adr/*``, the same way
+            if adr is not None:
+                for k, v in adr.scalars().items():
+                    self.writer.add_scalar(k, v, self.frame)
 
     def write_stats(self, total_time, epoch_num, play_time, update_time, stats, curr_frames):
         if not self.writer:

@@ -52,6 +52,10 @@ SRC_TARGET = os.path.join(_HERE, "csrc", "vine_env_target.hip")
 # tests/test_env_target_cpu.py pins that spelling, colon included; the seventeenth, the controller's target tracking, cannot join
 # the expression: build() hands it to the loop's body (a local helper) once more behind the loop
 SRC_MPC_TRACK = os.path.join(_HERE, "csrc", "vine_mpc_track.hip")
+# tests/test_mpc_track_cpu.py pins that call and the number of calls build() spells out; the eighteenth, the ADR of the sensor's,
+# the push's and the target's draws, follows in LATER_UNITS, which build() maps the same helper over
+SRC_DRAW_ADR = os.path.join(_HERE, "csrc", "vine_env_draw_adr.hip")
+LATER_UNITS = (SRC_DRAW_ADR,)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -69,7 +73,11 @@ _NAMED_DRAW_HEADERS = [os.path.join(_INC, "vine_env_redraw.h"), os.path.join(_HE
 _REDRAW_HEADERS = [_COMPOSITES] + _NAMED_DRAW_HEADERS + [os.path.join(_HERE, "csrc", "vine_env_redraw_draw.h")]
 _MPC_SHARED = os.path.join(_HERE, "csrc", "vine_mpc_shared.h")      # the fork's and the pin's column copy and ring rebuild
 _TARGET_PATH = os.path.join(_HERE, "csrc", "vine_target_path.h")    # the target's path step and the words of a point of it
-_SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h")],
+_ADR_SHARED = os.path.join(_HERE, "csrc", "vine_adr_shared.h")      # a boundary after w steps and the decide launch's lane
+_SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _REDRAW_HEADERS + [os.path.join(_INC, "vine_env_adr.h"), _ADR_SHARED],
+                   SRC_DRAW_ADR: _NAMED_DRAW_HEADERS + [os.path.join(_INC, h) for h in ("vine_env_adr.h", "vine_env_sensor.h",
+                                                                                         "vine_env_push.h", "vine_env_target.h",
+                                                                                         "vine_env_draw_adr.h")] + [_ADR_SHARED],
                    SRC_SENSOR: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_sensor.h")],
                    SRC_PUSH: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_push.h")],
                    SRC_TARGET: _NAMED_DRAW_HEADERS + [os.path.join(_INC, "vine_env_target.h"), _TARGET_PATH],
@@ -96,12 +104,13 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # vine_env_target.hip forms an offset, off + vel * cdt, a target, ay - off * c, and an observation column, obs + w * inv, that
 # numpy must reproduce bit for bit: the same again
 # vine_mpc_track.hip forms the same offsets and targets H - 1 steps ahead, bit for bit those of vine_env_target.hip: the same again
+# vine_env_draw_adr.hip forms the range in force and draws from it as vine_env_adr.hip does: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_POLICY: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_OBSERVE: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"], SRC_TARGET: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC_TRACK: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC_TRACK: ["-ffp-contract=fast-honor-pragmas"], SRC_DRAW_ADR: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
         + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
@@ -109,7 +118,8 @@ DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, 
         + [SRC_MPC_OBSERVE, os.path.join(_INC, "vine_mpc_observe.h")]
         + [SRC_MPC_FILTER, os.path.join(_INC, "vine_mpc_filter.h")]
         + [SRC_TARGET, os.path.join(_INC, "vine_env_target.h")]
-        + [SRC_MPC_TRACK, os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH])
+        + [SRC_MPC_TRACK, os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH]
+        + [SRC_DRAW_ADR, os.path.join(_INC, "vine_env_draw_adr.h"), _ADR_SHARED])
 
 _lib = None
 
@@ -148,8 +158,8 @@ def _object_fingerprint(src):
 
 
 def build(force=False, verbose=False):
-    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The seventeen translation units are
-    compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
+    """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The seventeen translation units and the
+    eighteenth behind them (``LATER_UNITS``) are compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
     wild pointer on the GPU)."""
@@ -182,6 +192,8 @@ def build(force=False, verbose=False):
     for src in POLICY_UNITS + (SRC_MPC_OBSERVE,) + (SRC_MPC_FILTER,) + (SRC_TARGET,):
         compile_unit(src)
     compile_unit(SRC_MPC_TRACK)      # the seventeenth: started before any of the sixteen is waited for
+    for _ in map(compile_unit, LATER_UNITS):      # the eighteenth: likewise
+        pass
     for proc, cmd, obj, fp in jobs:
         if proc.wait() != 0:
             raise subprocess.CalledProcessError(proc.returncode, cmd)

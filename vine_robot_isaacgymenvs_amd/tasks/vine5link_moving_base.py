@@ -152,6 +152,7 @@ class Vine5LinkMovingBase(VecTask):
         self._env_sensor = None
         self._env_push = None
         self._env_target = None
+        self._env_draw_adr = None
         self._observers = []       # what rides behind every step: the video capture, the trajectory recorder, the episode log,
                                    # the per-episode redraw of the plants (last: it replaces what the others read)
 
@@ -167,6 +168,9 @@ class Vine5LinkMovingBase(VecTask):
         from ..utils import env_target
         self._target_cfg = env_target.target_config(self.cfg["env"], env_target.control_period(
             self.cfg["sim"]["dt"], self.cfg["env"].get("controlFrequencyInv", 1)))
+        from ..utils import env_draw_adr
+        self._draw_adr_cfg = env_draw_adr.draw_adr_config(self.cfg["env"], self._sensor_cfg, self._push_cfg, self._target_cfg,
+                                                          multi_gpu=int(os.getenv("WORLD_SIZE", "1")) > 1)
         super().__init__(config=self.cfg, rl_device=rl_device, sim_device=sim_device,
                          graphics_device_id=graphics_device_id, headless=headless,
                          virtual_screen_capture=virtual_screen_capture, force_render=force_render)
@@ -202,6 +206,8 @@ class Vine5LinkMovingBase(VecTask):
             self._setup_env_sensor()             # the redraw, which stays last
         if self._push_cfg is not None:           # every rank, by the global env id; behind the sensor (which has then sensed
             self._setup_env_push()               # what the step wrote), in front of the redraw
+        if self._draw_adr_cfg is not None:       # ENV_DRAW_ADR: behind the three whose freshly drawn rows it replaces
+            self._setup_env_draw_adr()
         if self._adr is not None:                # ENV_PARAMS_ADR: the redraw's place, with ranges that move
             self._setup_env_adr()
         elif self._per_episode:                  # every rank: each redraws its own shard, by the global env id
@@ -418,6 +424,29 @@ class Vine5LinkMovingBase(VecTask):
     def env_target(self):
         """The ``EnvTarget`` of this env (``None`` unless ``ENV_TARGET``)."""
         return self._env_target
+
+    # ------------------------------------------------------------------ ENV_DRAW_ADR (include/vine_env_draw_adr.h)
+    def _setup_env_draw_adr(self):
+        """Two launches behind every step, behind the target's, the sensor's and the push's, move the ranges of the names
+        under ``ENV_DRAW_ADR.NAMES`` and replace the rows those three have just drawn for a flagged env: the ranges begin at
+        START (the rows of episode 0 are overwritten here), the ``[lo, hi]`` of the three observers' mappings are their
+        limits.  The launches read the step's reward matrix, so one is bound here (arming introspection) before anything is
+        captured; one bound already is shared."""
+        from ..utils import env_draw_adr
+        if self._reward_matrix is None:
+            self.bind_reward_matrix()
+        self._env_draw_adr = self._add_observer(env_draw_adr.EnvDrawAdr(
+            self._lib, self._handle, self._vcfg, self._draw_adr_cfg, self.reset_buf, self._env_sensor, self._env_push,
+            self._env_target, self.device, self.logger))
+        if self._episode_log is not None:
+            self._episode_log.draw_adr = self._env_draw_adr
+        self.logger.info(f"ENV_DRAW_ADR: the ranges of {', '.join(self._draw_adr_cfg['NAMES'])} start at START and move on the "
+                         f"device by the reach rate of the episodes probing their boundaries")
+
+    @property
+    def env_draw_adr(self):
+        """The ``EnvDrawAdr`` of this env (``None`` unless ``ENV_DRAW_ADR``)."""
+        return self._env_draw_adr
 
     # ------------------------------------------------------------------ ENV_PARAMS_PER_EPISODE (include/vine_env_redraw.h)
     def _setup_env_redraw(self):
@@ -677,7 +706,7 @@ class Vine5LinkMovingBase(VecTask):
                 o.drain()
                 o.close()
             self._observers, self._video, self._trajectory, self._episode_log, self._env_redraw = [], None, None, None, None
-            self._env_sensor = self._env_push = self._env_target = None
+            self._env_sensor = self._env_push = self._env_target = self._env_draw_adr = None
         if self._handle is not None and self._lib is not None:
             torch.cuda.synchronize(self.device)
             self._lib.vine_destroy(self._handle)
@@ -756,6 +785,8 @@ class Vine5LinkMovingBase(VecTask):
             self._env_sensor.reset_envs(ids)
         if self._env_target is not None:         # ENV_TARGET: ... and their target starts from where this reset put it
             self._env_target.reset_envs(ids)
+        if self._env_draw_adr is not None:       # ENV_DRAW_ADR: ... and is not counted at a boundary of the draws' ranges
+            self._env_draw_adr.reset_envs(ids)
 
     # ------------------------------------------------------------------ metrics side channel (V5:1250-1322)
     def collect_stats(self):
@@ -869,8 +900,8 @@ class Vine5LinkMovingBase(VecTask):
     # ------------------------------------------------------------------ test / tooling hooks
     def bind_reward_matrix(self):
         """Ask the kernel to also write the [N,13] unweighted reward matrix (V5:1272) each step."""
-        if self._episode_log is not None or self.env_adr is not None:      # EPISODE_LOG and ENV_PARAMS_ADR read the matrix bound
-            return self._reward_matrix                                      # at set-up: that one is shared
+        if self._episode_log is not None or self.env_adr is not None or self._env_draw_adr is not None:
+            return self._reward_matrix      # EPISODE_LOG, ENV_PARAMS_ADR and ENV_DRAW_ADR read the matrix bound at set-up: that one is shared
         self._reward_matrix = torch.zeros((self.num_envs, abi.NUM_REWARDS), device=self.device)
         native.check(self._lib.vine_bind_reward_matrix(self._handle, self._reward_matrix.data_ptr()), self._lib)
         self._introspection = True           # the library arms VINE_FLAG_INTROSPECT together with the matrix

@@ -30,6 +30,15 @@ def launch(cfg):
         else:
             env_params.adr_config(env_cfg, multi_gpu=bool(cfg["multi_gpu"]))      # (refused here, before a rank starts)
 
+    if len(env_cfg.get("ENV_DRAW_ADR") or {}):
+        if cfg["test"]:                      # likewise: the sensor, the push and the target draw from their full limits
+            logging.getLogger(__name__).info("test=True: task.env.ENV_DRAW_ADR is forced off, the sensor's, the push's and the "
+                                             "target's values are drawn from their full limits")
+            env_cfg["ENV_DRAW_ADR"] = {}
+        elif cfg["multi_gpu"]:               # (refused here, before a rank starts; the task class checks the rest)
+            from .utils.config import ConfigError
+            raise ConfigError("task.env.ENV_DRAW_ADR with multi_gpu=True: every rank would grow its own ranges")
+
     rank = int(os.getenv("LOCAL_RANK", "0"))
     if cfg["multi_gpu"]:                                                 # train.py:71-75
         cfg["sim_device"] = f"cuda:{rank}"

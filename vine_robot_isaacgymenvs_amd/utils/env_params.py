@@ -449,12 +449,13 @@ def adr_draw(spec, adr, seed, gids, episodes, widen):
     return forms, drawn, probe
 
 
-def adr_decide(adr, max_widen, widen, counts, step_index, history, consumed=None):
+def adr_decide(adr, max_widen, widen, counts, step_index, history, consumed=None, slots=abi.ENV_REDRAW_NAMES):
     """Launch 1 on the host, in place: judge every boundary with ``counts.n >= QUEUE``, clear its counts (adding them to
     ``consumed`` when given), append one row ``[step index, boundary, new widen, 0]`` to the list ``history`` per boundary
-    that changed, in boundary order."""
+    that changed, in boundary order.  ``slots``: the names in slot order (``adr["NAMES"]`` is in that order too); the default
+    is the plant's, utils/env_draw_adr.py passes the nine draw names."""
     for name in adr["NAMES"]:
-        s = abi.ENV_REDRAW_NAMES.index(name)
+        s = slots.index(name)
         for side in (0, 1):
             n, r = int(counts[s, side, 0]), int(counts[s, side, 1])
             if n < adr["QUEUE"]:
@@ -526,15 +527,16 @@ def adr_replay(spec, adr, seed, gids, resets, reached_flags, vcfg, lib=None, ste
     return out
 
 
-def adr_widen_at(history, steps, widen0=None):
+def adr_widen_at(history, steps, widen0=None, num_slots=abi.VR_NAMES):
     """int64 [M, VR_NAMES, 2]: the ``widen`` launch 2 read behind each step of ``steps`` [M], from ``widen0`` [VR_NAMES, 2]
     (what was in force before the first step: zeros, or a restored checkpoint's) and the complete ``history`` [H, 4] (a row
-    of step s is in force for that step's own redraw: decide runs first)."""
+    of step s is in force for that step's own redraw: decide runs first).  ``num_slots``: the number of names when it is not
+    the plant's ``VR_NAMES`` (utils/env_draw_adr.py: nine)."""
     history = np.asarray(history, dtype=np.int64).reshape(-1, 4)
     steps = np.asarray(steps, dtype=np.int64).reshape(-1)
-    out = np.zeros((len(steps), abi.VR_NAMES, 2), dtype=np.int64)
+    out = np.zeros((len(steps), num_slots, 2), dtype=np.int64)
     if widen0 is not None:
-        out[:] = np.asarray(widen0, dtype=np.int64).reshape(1, abi.VR_NAMES, 2)
+        out[:] = np.asarray(widen0, dtype=np.int64).reshape(1, num_slots, 2)
     for s, b, w, _ in history:                       # in the order written: a later row of a boundary overrides
         out[steps >= s, b >> 1, b & 1] = w
     return out

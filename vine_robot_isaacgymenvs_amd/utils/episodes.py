@@ -223,8 +223,26 @@ def with_draw_params(rows, draw_params):
     return out
 
 
+def with_draw_adr_params(rows, episode_params):
+    """ENV_DRAW_ADR: ``rows`` (with ``episode``) with the ``param_<DRAW NAME>`` column of every name under ADR, from the range
+    in force at the step that drew the row's episode (in the place of the observer's own join, which knows the limits only),
+    and the ``draw_probe`` column (the boundary ``2 * slot + side`` the episode was pinned to, -1: none, -2: unknown).
+    ``episode_params(envs, episodes, drawn_at)`` -> ``({DRAW NAME: values [R]}, probe [R])``
+    (``env_draw_adr.draw_adr_episode_params``).  A row whose predecessor was dropped is NaN; ``(rows, unknown)`` with
+    ``unknown`` their number."""
+    out = dict(rows)
+    if not len(np.asarray(rows["env"])):
+        out["draw_probe"] = np.zeros(0, dtype=np.int64)
+        return out, 0
+    params, probe = episode_params(rows["env"], rows["episode"], drawn_at(rows["env"], rows["episode"], rows["end_step"]))
+    for name, values in params.items():
+        out["param_" + name] = values
+    out["draw_probe"] = probe
+    return out, int(np.count_nonzero(probe == -2))
+
+
 def save(path, rows, totals, dropped, task, env_params=None, env_param_names=None, env_inertia=None, env_inertia_names=None,
-         redraw=None, adr=None, sensor=None, push=None, target=None):
+         redraw=None, adr=None, sensor=None, push=None, target=None, draw_adr=None):
     """Rows as named columns, the folded totals, ``dropped`` and the task's keys (``task_<KEY>``), written beside the path
     and renamed.  With a bound per-env parameter table also ``env_params`` [VP_COUNT, N] and ``env_param_names``, with a
     bound inertia table ``env_inertia`` [VI_COUNT, N] and ``env_inertia_names``.  With ENV_PARAMS_PER_EPISODE (``redraw``: a
@@ -234,7 +252,9 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
     ``history`` [H, 4] (complete), ``history_dropped`` and ``widen0`` [VR_NAMES, 2] (the ``widen`` in force before the run's
     first step: zeros, or a restored checkpoint's).  With ENV_SENSOR, ENV_PUSH or ENV_TARGET (``sensor``, ``push``, ``target``: each a
     dict of ``spec``, ``seed`` and ``env_id_offset``) what ``load_env_draw`` needs to rebuild the ``param_SENSOR_*``,
-    ``param_PUSH_*`` and ``param_TARGET_*`` columns without a device, and, where the rows carry one, their ``episode`` column."""
+    ``param_PUSH_*`` and ``param_TARGET_*`` columns without a device, and, where the rows carry one, their ``episode`` column.
+    With ENV_DRAW_ADR also ``draw_adr``: a dict of ``config`` (``env_draw_adr.draw_adr_config``'s result), ``history`` [H, 4]
+    (complete), ``history_dropped``, ``widen0`` [9, 2], ``seed`` and ``env_id_offset``: what ``load_env_draw_adr`` needs."""
     out = {name: np.asarray(rows[name]) for name in COLUMNS}
     for prefix, draw in (("target", target), ("push", push), ("sensor", sensor)):
         if draw is not None:
@@ -244,6 +264,14 @@ def save(path, rows, totals, dropped, task, env_params=None, env_param_names=Non
             out[prefix + "_env_id_offset"] = np.array(int(draw["env_id_offset"]), dtype=np.int64)
             if "episode" in rows:
                 out["episode"] = np.asarray(rows["episode"], dtype=np.int64)
+    if draw_adr is not None:
+        import json
+        out["draw_adr_config"] = np.array(json.dumps(draw_adr["config"]))
+        out["draw_adr_history"] = np.asarray(draw_adr["history"], dtype=np.int64).reshape(-1, 4)
+        out["draw_adr_history_dropped"] = np.array(int(draw_adr["history_dropped"]), dtype=np.int64)
+        out["draw_adr_widen0"] = np.asarray(draw_adr["widen0"], dtype=np.int64).reshape(abi.VDA_NAMES, 2)
+        out["draw_adr_seed"] = np.array(int(draw_adr["seed"]), dtype=np.uint64)
+        out["draw_adr_env_id_offset"] = np.array(int(draw_adr["env_id_offset"]), dtype=np.int64)
     if adr is not None:
         import json
         out["adr_config"] = np.array(json.dumps(adr["config"]))
@@ -381,6 +409,25 @@ def load_env_draw(path, prefix):
     return spec, episode, draw_params
 
 
+def load_env_draw_adr(path):
+    """Of a file written under ENV_DRAW_ADR: ``(config, history [H, 4], history_dropped, widen0 [9, 2], episode_params)`` with
+    ``episode_params(envs, episodes, drawn_at)`` -> ``({DRAW NAME: values [M]}, probe [M])``,
+    ``env_draw_adr.draw_adr_episode_params`` rebuilt from what the file stores (no device; NaN and probe -2 where ``drawn_at``
+    is -1); else ``(None, None, 0, None, None)``."""
+    import json
+    from . import env_draw_adr
+    with np.load(path) as z:
+        if "draw_adr_config" not in z.files:
+            return None, None, 0, None, None
+        config, history, widen0 = json.loads(str(z["draw_adr_config"][()])), z["draw_adr_history"], z["draw_adr_widen0"]
+        dropped, seed, offset = int(z["draw_adr_history_dropped"]), int(z["draw_adr_seed"]), int(z["draw_adr_env_id_offset"])
+
+    def episode_params(envs, episodes_, drawn_at_):
+        return env_draw_adr.draw_adr_episode_params(config, seed, np.asarray(envs, dtype=np.int64) + offset, episodes_, drawn_at_,
+                                                    history, widen0)
+    return config, history, dropped, widen0, episode_params
+
+
 # the names the join and the loader had while each of the three observers had its own: files and callers written then still work
 with_sensor_params = with_push_params = with_target_params = with_draw_params
 load_env_sensor = functools.partial(load_env_draw, prefix="sensor")
@@ -391,7 +438,8 @@ load_env_target = functools.partial(load_env_draw, prefix="target")
 def load_rows_with_params(path):
     """The rows of a file written under ENV_PARAMS_PER_EPISODE with the ``param_<NAME>`` columns of every row's own episode
     (and ``episode``; under ENV_PARAMS_ADR also ``probe``), as ``EpisodeLog.rows_with_params`` gives them; no device.  Under
-    ENV_SENSOR, ENV_PUSH and ENV_TARGET also the ``param_SENSOR_*``, ``param_PUSH_*`` and ``param_TARGET_*`` columns."""
+    ENV_SENSOR, ENV_PUSH and ENV_TARGET also the ``param_SENSOR_*``, ``param_PUSH_*`` and ``param_TARGET_*`` columns; under
+    ENV_DRAW_ADR those of the names under ADR from the range in force, and ``draw_probe``."""
     rows = _load_rows_with_plant_params(path)
     for prefix in DRAW_OBSERVERS:
         _, episode, params = load_env_draw(path, prefix)
@@ -400,6 +448,9 @@ def load_rows_with_params(path):
         if episode is not None:
             rows["episode"] = episode
         rows = with_draw_params(rows, params)
+    draw_adr_params = load_env_draw_adr(path)[4]
+    if draw_adr_params is not None:                  # ENV_DRAW_ADR: the names under ADR from the range in force, and draw_probe
+        rows = with_draw_adr_params(rows, draw_adr_params)[0]
     return rows
 
 
@@ -459,6 +510,8 @@ class EpisodeLog:
         self.sensor = None           # ENV_SENSOR: the task's ``env_sensor.EnvSensor``; under its PER_EPISODE rows carry ``episode``
         self.push = None             # ENV_PUSH: the task's ``env_push.EnvPush``; likewise
         self.target = None           # ENV_TARGET: the task's ``env_target.EnvTarget``; likewise (the three of DRAW_OBSERVERS)
+        self.draw_adr = None         # ENV_DRAW_ADR: the task's ``env_draw_adr.EnvDrawAdr``
+        self.unknown_draws = 0       # ... and the rows of the last rows_with_params() whose range in force is unknown (NaN)
 
     def live_tensors(self):
         """What a caller that rolls steps back (the warm-up pass in front of a graph capture) must save and restore.  The
@@ -530,6 +583,8 @@ class EpisodeLog:
             self.part_counters.append(self._counters().episodes_now())
             if hasattr(self.redraw, "harvest_history"):      # ENV_PARAMS_ADR: and the moves of the ranges up to here
                 self.redraw.harvest_history()
+            if self.draw_adr is not None:                    # ENV_DRAW_ADR: likewise
+                self.draw_adr.harvest_history()
         self._rows = None
         return cursor - first
 
@@ -557,11 +612,18 @@ class EpisodeLog:
         """``rows()`` with ``param_<NAME>`` columns: under ENV_PARAMS_PER_EPISODE the plant of every row's episode
         (``with_episode_params`` of ``draw_columns(env, episode)``), else the bound table's column of its env.  Under
         ENV_SENSOR also ``param_SENSOR_*``, under ENV_PUSH ``param_PUSH_*``, under ENV_TARGET ``param_TARGET_*``
-        (``with_draw_params``)."""
+        (``with_draw_params``); under ENV_DRAW_ADR the names under ADR from the range in force, and ``draw_probe``
+        (``with_draw_adr_params``)."""
         out = self._rows_with_plant_params()
         for observer in (self.sensor, self.push, self.target):
             if observer is not None:
                 out = with_draw_params(out, observer.episode_params)
+        if self.draw_adr is not None:                # ENV_DRAW_ADR: the range in force when the episode was drawn
+            self.draw_adr.harvest_history()
+            out, self.unknown_draws = with_draw_adr_params(out, self.draw_adr.episode_params)
+            if self.unknown_draws:
+                self.logger.info(f"EPISODE_LOG: {self.unknown_draws} rows have no known draw range (the row of the episode before "
+                                 f"them was dropped)")
         return out
 
     def _rows_with_plant_params(self):
@@ -603,8 +665,13 @@ class EpisodeLog:
                    "widen0": self.redraw.widen0}
         sensor, push, target = (None if o is None else {"spec": o.spec, "seed": o.seed, "env_id_offset": o.env_id_offset}
                                 for o in (self.sensor, self.push, self.target))
+        draw_adr = None
+        if self.draw_adr is not None:
+            d = self.draw_adr
+            draw_adr = {"config": d.adr, "history": d.harvest_history(), "history_dropped": d.history_dropped, "widen0": d.widen0,
+                        "seed": d.seed, "env_id_offset": d.env_id_offset}
         save(self.path, self.rows(), self.folded_totals(), self.dropped, self.task, table, self.env_param_names, inertia,
-             self.env_inertia_names, redraw, adr, sensor, push, target)
+             self.env_inertia_names, redraw, adr, sensor, push, target, draw_adr)
         self.logger.info(f"EPISODE_LOG: {len(self.rows()['env'])} episodes -> {self.path}")
 
     def close(self):

@@ -80,6 +80,7 @@ FORCED = (
     ("env", "ENV_PARAMS_ADR", {}),
     ("env", "ENV_SENSOR", {}),                     # the planner reads the state as it is
     ("env", "ENV_PUSH", {}),                       # ... and nothing but its own actions moves a sample
+    ("env", "ENV_DRAW_ADR", {}),                   # ... and no range of those draws moves
     ("env", "ENV_TARGET", {}),                     # ... and no target moves by itself
 )
 
@@ -428,6 +429,9 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     from . import episodes
     logger = logger or logging.getLogger(__name__)
     cfg = copy.deepcopy(cfg)
+    if len(cfg["env"].get("ENV_DRAW_ADR") or {}):      # the plants are measured on the whole of what they may meet
+        logger.info("mpc: plant env.ENV_DRAW_ADR is forced off, the sensor, the push and the target draw from their full limits")
+        cfg["env"]["ENV_DRAW_ADR"] = {}
     if plants is not None:
         cfg["env"]["numEnvs"] = check_integer("plants", plants, 1)
     M = int(cfg["env"]["numEnvs"])

@@ -34,7 +34,11 @@ front of the redraw: it reads the inertia table's column of the episode that has
 ``env_target.EnvTarget`` (ENV_TARGET) moves the target in the state block for the NEXT step and adds the target's velocity to
 the observation the step has just written (``wants_obs``).  It stands behind the video, the recorder and the episode log,
 which must see the target the step used, and in front of the sensor, which then delays and perturbs the velocity columns
-with the rest of the frame.  So the order is: video, recorder, episode log, target, sensor, push, redraw / ADR.
+with the rest of the frame.  ``env_draw_adr.EnvDrawAdr`` (ENV_DRAW_ADR) moves the ranges the target, the sensor and the push
+redraw their values from, and replaces the rows those three have just drawn for a flagged env with the draw from the range in
+force: it stands behind all three -- each redraws as the last statement of its launch and reads the new row in a later
+launch only -- and in front of the redraw, which stays last.  So the order is: video, recorder, episode log, target, sensor,
+push, draw ADR, redraw / ADR.
 
 Those last observers keep no host account of the steps: ``StepObserver`` states the protocol's names that mean nothing to
 them once, and ``TableObserver`` what the target, the sensor and the push share -- a per-env table of named draws

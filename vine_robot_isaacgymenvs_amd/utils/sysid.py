@@ -204,6 +204,7 @@ FORCED = (
     ("env", "ENV_SENSOR", {}),                     # ... and the fit reads the state as it is: no sensor model
     ("env", "ENV_PUSH", {}),                       # ... and nothing but the recorded commands moves a candidate
     ("env", "ENV_TARGET", {}),                     # ... and no target moves by itself
+    ("env", "ENV_DRAW_ADR", {}),                   # ... and no range of those draws moves
 )
 
 
