@@ -95,7 +95,7 @@ def adapt_main():
         torch.cuda.get_device_name(0), M, K, M * K, H, W, E, model.step_kernel_name, bare_model.step_kernel_name))
     plant.step_into(ctl.plant_actions, ctl.plant_obs)
     ctl.run(2 * E)                                       # (two captured cycles: every lazy initialisation done)
-    ctl.cycle_graph = None
+    ctl.graph = None
     launches = (("anchor", ctl.anchor, None), ("trace node", ctl.trace, None), ("pin", ctl.pin, None),
                 ("score node in a window", ctl.score, "window"), ("score node outside one", ctl.score, None),
                 ("estimate", ctl.estimate, None))

@@ -660,6 +660,7 @@ def test_captured_cycles_against_eager_ones():
                                                                           plant_step=30, anchor=6, trace=30).items()}
             assert ctl.launches == counts and ctl.phase == 2
             assert plant.step_count == 32 and model.step_count == 32 * H + 6 * 4 and np.all(ctl.passes.cpu().numpy() == 6)
+            assert (plant.num_steps, model.num_steps) == (32, 32 * H + 6 * 4)  # replayed or eager: the steps the handles took
             runs.append(([t.cpu().numpy().copy() for t in ctl.tensors()], plant.state.cpu().numpy().copy(),
                          model.state.cpu().numpy().copy(), ctl.mean.cpu().numpy().copy()))
         finally:

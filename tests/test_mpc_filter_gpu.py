@@ -229,19 +229,22 @@ def test_filter_refusals_name_the_reason():
             others.append(_env(cfg))
             return others[-1]
 
-        def refused(rc, code, word):
-            assert rc == code and word in lib.vine_last_error(), (rc, lib.vine_last_error())
+        def refused(rc, code, word, whole=False):
+            assert rc == code and (lib.vine_last_error() == word if whole else word in lib.vine_last_error()), (rc, lib.vine_last_error())
 
         for launch in (rig.filter_pin, rig.filter_correct):
             refused(launch(predictor=other(_cfg(M + 1))), abi.ERR_INVALID_ARG, b"mpc filter: the predictor handle has 4 envs, not num_plants = 3")
             refused(launch(plant=others[-1]), abi.ERR_INVALID_ARG, b"mpc filter: the plant handle does not have num_plants envs")
             cfg = _cfg(M)
             cfg.set_flag(abi.FLAG_VINE_RANDOMIZE, True)
-            refused(launch(predictor=other(cfg)), abi.ERR_UNSUPPORTED, b"vine_randomize")
-            refused(launch(predictor=other(_cfg(M, pipe=True))), abi.ERR_UNSUPPORTED, b"CREATE_SHELF / CREATE_PIPE")
+            refused(launch(predictor=other(cfg)), abi.ERR_UNSUPPORTED, b"mpc filter: a predictor handle with vine_randomize is refused "
+                    b"(a replayed step must be a deterministic one)", whole=True)
+            refused(launch(predictor=other(_cfg(M, pipe=True))), abi.ERR_UNSUPPORTED,
+                    b"mpc filter: the predictor handle's CREATE_SHELF / CREATE_PIPE differ from the plant's", whole=True)
             cfg = _cfg(M)
             cfg.max_episode_length = 9
-            refused(launch(predictor=other(cfg)), abi.ERR_INVALID_ARG, b"max_episode_length")
+            refused(launch(predictor=other(cfg)), abi.ERR_INVALID_ARG,
+                    b"mpc filter: the predictor handle's max_episode_length differs from the plant's", whole=True)
             refused(launch(predictor=rig.plant), abi.ERR_INVALID_ARG, b"two handles")
             if torch.cuda.device_count() > 1:
                 from tests.hip_env import HipEnv

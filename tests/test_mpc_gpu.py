@@ -181,10 +181,10 @@ def test_fork_refusals_name_the_reason():
     try:
         lib = rig.lib
 
-        def refused(rc_want, word, **kw):
+        def refused(rc_want, word, whole=False, **kw):
             lib.vine_set_step_count(None, -1)
             assert rig.fork(**kw) == rc_want, lib.vine_last_error()
-            assert word in lib.vine_last_error(), lib.vine_last_error()
+            assert lib.vine_last_error() == word if whole else word in lib.vine_last_error(), lib.vine_last_error()
 
         def other(cfg):
             others.append(_env(cfg))
@@ -192,14 +192,17 @@ def test_fork_refusals_name_the_reason():
 
         rnd = _cfg(M * K)
         rnd.set_flag(abi.FLAG_VINE_RANDOMIZE, True)
-        refused(abi.ERR_UNSUPPORTED, b"vine_randomize", model=other(rnd))
-        refused(abi.ERR_UNSUPPORTED, b"CREATE_PIPE", model=other(_cfg(M * K, pipe=True)))
+        refused(abi.ERR_UNSUPPORTED, b"mpc fork: a model handle with vine_randomize is refused (a sample must be a deterministic plant)",
+                whole=True, model=other(rnd))
+        differ = b"mpc fork: the model handle's CREATE_SHELF / CREATE_PIPE differ from the plant's"
+        refused(abi.ERR_UNSUPPORTED, differ, whole=True, model=other(_cfg(M * K, pipe=True)))
         shelf = _cfg(M * K)
         shelf.set_flag(abi.FLAG_CREATE_SHELF, True)
-        refused(abi.ERR_UNSUPPORTED, b"CREATE_SHELF", model=other(shelf))
+        refused(abi.ERR_UNSUPPORTED, differ, whole=True, model=other(shelf))
         longer = _cfg(M * K)
         longer.max_episode_length = 101
-        refused(abi.ERR_INVALID_ARG, b"max_episode_length", model=other(longer))
+        refused(abi.ERR_INVALID_ARG, b"mpc fork: the model handle's max_episode_length differs from the plant's", whole=True,
+                model=other(longer))
         refused(abi.ERR_INVALID_ARG, b"num_plants * samples", model=other(_cfg(M * K + 1)))
         refused(abi.ERR_INVALID_ARG, b"num_plants envs", plant=other(_cfg(M * K)), mcfg=mpc.mpc_config(M * K // 2, 2, H))
         refused(abi.ERR_INVALID_ARG, b"two handles", plant=rig.model)
@@ -437,6 +440,7 @@ def test_captured_control_steps_against_eager_ones(tmp_path):
                 assert ctl.graph_launches == {"fork": 4, "step": 4 * H, "node": 4 * H, "update": 4, "plant_step": 4}
             assert ctl.launches == {"fork": 20, "step": 20 * H, "node": 20 * H, "update": 20, "plant_step": 20}
             assert plant.step_count == 20 and model.step_count == 20 * H and int(ctl.tick[0]) == 20
+            assert (plant.num_steps, model.num_steps) == (20, 20 * H)          # replayed or eager: the steps the handles took
             plant.episode_log.harvest()
             rows = plant.episode_log.rows()
             runs.append(([t.cpu().numpy().copy() for t in ctl.tensors()], plant.state.cpu().numpy().copy(),

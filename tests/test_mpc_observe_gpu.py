@@ -331,19 +331,22 @@ def test_pin_refusals_name_the_reason():
             others.append(_env(cfg))
             return others[-1]
 
-        def refused(rc, code, word):
-            assert rc == code and word in lib.vine_last_error(), (rc, lib.vine_last_error())
+        def refused(rc, code, word, whole=False):
+            assert rc == code and (lib.vine_last_error() == word if whole else word in lib.vine_last_error()), (rc, lib.vine_last_error())
 
         refused(rig.pin(predictor=other(_cfg(M + 1))), abi.ERR_INVALID_ARG, b"the predictor handle has 4 envs, not num_plants = 3")
         refused(rig.catchup(1, predictor=others[-1]), abi.ERR_INVALID_ARG, b"the predictor handle has 4 envs")
         refused(rig.pin(plant=others[-1]), abi.ERR_INVALID_ARG, b"the plant handle does not have num_plants envs")
         cfg = _cfg(M)
         cfg.set_flag(abi.FLAG_VINE_RANDOMIZE, True)
-        refused(rig.pin(predictor=other(cfg)), abi.ERR_UNSUPPORTED, b"vine_randomize")
-        refused(rig.pin(predictor=other(_cfg(M, pipe=True))), abi.ERR_UNSUPPORTED, b"CREATE_SHELF / CREATE_PIPE")
+        refused(rig.pin(predictor=other(cfg)), abi.ERR_UNSUPPORTED, b"mpc observe: a predictor handle with vine_randomize is refused "
+                b"(a replayed step must be a deterministic one)", whole=True)
+        refused(rig.pin(predictor=other(_cfg(M, pipe=True))), abi.ERR_UNSUPPORTED,
+                b"mpc observe: the predictor handle's CREATE_SHELF / CREATE_PIPE differ from the plant's", whole=True)
         cfg = _cfg(M)
         cfg.max_episode_length = 9
-        refused(rig.pin(predictor=other(cfg)), abi.ERR_INVALID_ARG, b"max_episode_length")
+        refused(rig.pin(predictor=other(cfg)), abi.ERR_INVALID_ARG,
+                b"mpc observe: the predictor handle's max_episode_length differs from the plant's", whole=True)
         if torch.cuda.device_count() > 1:
             from tests.hip_env import HipEnv
             others.append(HipEnv(_cfg(M), device_id=1))

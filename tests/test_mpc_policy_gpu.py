@@ -438,6 +438,7 @@ def test_captured_control_steps_against_eager_ones(H):
                 assert ctl.graph_launches == {k: 2 * v for k, v in want.items()}
             assert ctl.launches == {k: 6 * v for k, v in want.items()}
             assert rig.plant.step_count == 6 and rig.model.step_count == 6 * H and int(ctl.tick[0]) == 6
+            assert (rig.plant.num_steps, rig.model.num_steps) == (6, 6 * H)      # replayed or eager: the steps the handles took
             runs.append(([_np(t) for t in ctl.tensors()], _np(rig.plant.state), _np(rig.model.state), _np(ctl.plant_h),
                          _np(ctl.plant_c)))
         finally:

@@ -358,6 +358,7 @@ def test_captured_control_steps_against_eager_ones():
                 assert ctl.graph_launches == {"fork": 1, "step": H, "node": H, "update": 1, "plant_step": 1, "plan": 1, "track": H}
             assert ctl.launches == {"fork": 10, "step": 10 * H, "node": 10 * H, "update": 10, "plant_step": 10, "plan": 10, "track": 10 * H}
             assert plant.step_count == 10 and model.step_count == 10 * H
+            assert (plant.num_steps, model.num_steps) == (10, 10 * H)          # replayed or eager: the steps the handles took
             runs.append([t.cpu().numpy().copy() for t in ctl.tensors() + [plant.state, model.state]])
             assert ctl.live.any() and any(t is ctl.path for t in ctl.tensors()) and any(t is ctl.live for t in ctl.tensors())
         finally:

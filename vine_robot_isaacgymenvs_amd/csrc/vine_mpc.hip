@@ -46,9 +46,6 @@ struct MpcParams {
     CommandParams cmd;                     // the model configuration's
 };
 
-// 1 / sqrt(32 * (65536^2 - 1) / 12): the deviate's scale, in float64 (the statement of vine_env_sensor.hip)
-inline double noise_scale() { return 1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0); }
-
 // u[j][k][a] of sample e = p * K + j at control step `tick` around the nominal entry (nom0, nom1): include/vine_mpc.h NOISE.
 __device__ __forceinline__ float2 mpc_action(const MpcParams& S, unsigned e, bool first, long long tick, int k, float nom0,
                                              float nom1) {
@@ -249,14 +246,8 @@ int prepare(VineHandle* model, const VineMpcConfig* cfg, VineHandleInfo& info, M
     S.seed_lo = (unsigned)cfg->seed; S.seed_hi = (unsigned)(cfg->seed >> 32);
     for (int a = 0; a < 2; ++a) S.c[a] = (float)((double)cfg->sigma[a] * noise_scale());
     S.lambda = cfg->lambda;
-    S.cmd.clip_act = info.clip_act; S.cmd.act_noise = 0.0f; S.cmd.rail_scale = info.rail_scale;
-    S.cmd.fpam_span = info.fpam_span; S.cmd.fpam_min = info.fpam_min;
+    S.cmd = mpc_command_params(info);
     return VINE_OK;
-}
-
-int unsupported(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -295,13 +286,8 @@ int vine_mpc_fork(VineHandle* plant, VineHandle* model, const VineMpcConfig* cfg
     rc = prepare(model, cfg, info, S);
     if (rc) return rc;
     if (pinfo.n != cfg->num_plants) return vine_invalid_arg("mpc fork: the plant handle does not have num_plants envs");
-    if (info.device != pinfo.device) return vine_invalid_arg("mpc fork: the model handle sits on another device than the plant");
-    if (info.flags & VINE_FLAG_VINE_RANDOMIZE)
-        return unsupported("mpc fork: a model handle with vine_randomize is refused (a sample must be a deterministic plant)");
-    const unsigned obstacles = VINE_FLAG_CREATE_SHELF | VINE_FLAG_CREATE_PIPE;
-    if ((info.flags & obstacles) != (pinfo.flags & obstacles))
-        return unsupported("mpc fork: the model handle's CREATE_SHELF / CREATE_PIPE differ from the plant's");
-    if (info.max_len != pinfo.max_len) return vine_invalid_arg("mpc fork: the model handle's max_episode_length differs from the plant's");
+    rc = mpc_stand_in("mpc fork", "model", "a sample must be a deterministic plant", pinfo, info);
+    if (rc) return rc;
     VineDeviceScope scope(info.device);
     if (!scope.ok) return VINE_ERR_DEVICE;
     hipLaunchKernelGGL(vine_mpc_fork_kernel, dim3((S.n + THREADS - 1) / THREADS), dim3(THREADS), 0, (hipStream_t)stream, S,

@@ -54,7 +54,6 @@ struct AdaptParams {
     CommandParams cmd;                                   // the model configuration's
 };
 
-inline double noise_scale() { return 1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0); }
 
 // theta of sample e (candidate j of its plant) in dimension d during pass `pass`: include/vine_mpc_adapt.h CANDIDATES.
 __device__ __forceinline__ double adapt_theta(const AdaptParams& S, unsigned e, bool first, long long pass, int d, double mean,
@@ -311,11 +310,6 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_adapt_estimate_kernel(
     if (t == 0) passes[p] = pass + 1;
 }
 
-int unsupported(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_UNSUPPORTED;
-}
-
 int validate(const VineMpcAdaptConfig* c) {
     if (!c) return vine_invalid_arg("mpc adapt config is NULL");
     if (c->abi_version != VINE_MPC_ADAPT_ABI_VERSION) return vine_invalid_arg("VineMpcAdaptConfig.abi_version mismatch");
@@ -385,8 +379,7 @@ void fill(const VineMpcAdaptConfig* cfg, const VineHandleInfo& info, AdaptParams
         S.dim[d].hi = on ? cfg->dims[d].hi : 0.0;
         S.dim[d].floor = on ? cfg->dims[d].std_floor : 0.0;
     }
-    S.cmd.clip_act = info.clip_act; S.cmd.act_noise = 0.0f; S.cmd.rail_scale = info.rail_scale;
-    S.cmd.fpam_span = info.fpam_span; S.cmd.fpam_min = info.fpam_min;
+    S.cmd = mpc_command_params(info);
 }
 
 // The plant handle's part of a launch's parameters; refuses a handle that does not hold num_plants envs.

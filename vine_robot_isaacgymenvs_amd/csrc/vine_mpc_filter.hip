@@ -214,11 +214,6 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_filter_correct_kernel(
 }
 static_assert(VF_TIP_Y + 4 == VF_CART_Y && VF_CART_VY == VF_CART_Y + 1, "tip, tip velocity, cart: six fields in a row");
 
-int unsupported(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_UNSUPPORTED;
-}
-
 int validate(const VineMpcObserveConfig* c) {
     if (!c) return vine_invalid_arg("mpc filter: the observe config is NULL");
     if (c->abi_version != VINE_MPC_OBSERVE_ABI_VERSION) return vine_invalid_arg("mpc filter: VineMpcObserveConfig.abi_version mismatch");
@@ -240,20 +235,13 @@ int prepare(VineHandle* plant, VineHandle* predictor, const VineMpcObserveConfig
         snprintf(msg, sizeof msg, "mpc filter: the predictor handle has %d envs, not num_plants = %d", info.n, cfg->num_plants);
         return vine_invalid_arg(msg);
     }
-    if (info.device != pinfo.device) return vine_invalid_arg("mpc filter: the predictor handle sits on another device than the plant");
-    if (info.flags & VINE_FLAG_VINE_RANDOMIZE)
-        return unsupported("mpc filter: a predictor handle with vine_randomize is refused (a replayed step must be a deterministic one)");
-    const unsigned obstacles = VINE_FLAG_CREATE_SHELF | VINE_FLAG_CREATE_PIPE;
-    if ((info.flags & obstacles) != (pinfo.flags & obstacles))
-        return unsupported("mpc filter: the predictor handle's CREATE_SHELF / CREATE_PIPE differ from the plant's");
-    if (info.max_len != pinfo.max_len)
-        return vine_invalid_arg("mpc filter: the predictor handle's max_episode_length differs from the plant's");
+    rc = mpc_stand_in("mpc filter", "predictor", "a replayed step must be a deterministic one", pinfo, info);
+    if (rc) return rc;
     S = FilterParams{};
     S.m = cfg->num_plants; S.plant_glog = pinfo.glog; S.glog = info.glog; S.delay = info.delay;
     S.seed_lo = (unsigned)cfg->seed; S.seed_hi = (unsigned)(cfg->seed >> 32);
     S.L = pinfo.L; S.z1 = pinfo.z1; S.s0 = pinfo.s0; S.c0 = pinfo.c0;
-    S.cmd.clip_act = info.clip_act; S.cmd.act_noise = 0.0f; S.cmd.rail_scale = info.rail_scale;
-    S.cmd.fpam_span = info.fpam_span; S.cmd.fpam_min = info.fpam_min;
+    S.cmd = mpc_command_params(info);
     return VINE_OK;
 }
 

@@ -47,7 +47,6 @@ struct ObserveParams {
     CommandParams cmd;                     // the predictor configuration's
 };
 
-inline double noise_scale() { return 1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0); }
 
 __device__ __forceinline__ int clamp_delay(int v) { return min(max(v, 0), VINE_MAX_DELAY); }
 
@@ -198,11 +197,6 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_observe_pin_kernel(
     if (i < S.C) reinterpret_cast<float2*>(actions)[p] = observe_next_action(S, i, d, log);
 }
 
-int unsupported(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_UNSUPPORTED;
-}
-
 int validate(const VineMpcObserveConfig* c) {
     if (!c) return vine_invalid_arg("mpc observe config is NULL");
     if (c->abi_version != VINE_MPC_OBSERVE_ABI_VERSION) return vine_invalid_arg("VineMpcObserveConfig.abi_version mismatch");
@@ -236,17 +230,10 @@ int prepare_predictor(VineHandle* predictor, const VineMpcObserveConfig* cfg, co
         snprintf(msg, sizeof msg, "mpc observe: the predictor handle has %d envs, not num_plants = %d", info.n, cfg->num_plants);
         return vine_invalid_arg(msg);
     }
-    if (info.device != pinfo.device) return vine_invalid_arg("mpc observe: the predictor handle sits on another device than the plant");
-    if (info.flags & VINE_FLAG_VINE_RANDOMIZE)
-        return unsupported("mpc observe: a predictor handle with vine_randomize is refused (a replayed step must be a deterministic one)");
-    const unsigned obstacles = VINE_FLAG_CREATE_SHELF | VINE_FLAG_CREATE_PIPE;
-    if ((info.flags & obstacles) != (pinfo.flags & obstacles))
-        return unsupported("mpc observe: the predictor handle's CREATE_SHELF / CREATE_PIPE differ from the plant's");
-    if (info.max_len != pinfo.max_len)
-        return vine_invalid_arg("mpc observe: the predictor handle's max_episode_length differs from the plant's");
+    rc = mpc_stand_in("mpc observe", "predictor", "a replayed step must be a deterministic one", pinfo, info);
+    if (rc) return rc;
     S.glog = info.glog; S.delay = info.delay;
-    S.cmd.clip_act = info.clip_act; S.cmd.act_noise = 0.0f; S.cmd.rail_scale = info.rail_scale;
-    S.cmd.fpam_span = info.fpam_span; S.cmd.fpam_min = info.fpam_min;
+    S.cmd = mpc_command_params(info);
     return VINE_OK;
 }
 

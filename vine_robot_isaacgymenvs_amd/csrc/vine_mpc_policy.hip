@@ -27,6 +27,7 @@
 #include "vine_policy_head.h"
 #include "vine_task_shared.h"
 #pragma clang fp contract(off)
+#include "vine_mpc_shared.h"      // the launch functions' shared refusals
 
 namespace {
 
@@ -169,11 +170,6 @@ __global__ __launch_bounds__(THREADS) void vine_mpc_policy_compose_kernel(const 
     reinterpret_cast<float2*>(history)[(size_t)p * VINE_MAX_DELAY] = a;
 }
 
-int unsupported(const char* msg) {
-    vine_set_error(msg);
-    return VINE_ERR_UNSUPPORTED;
-}
-
 // The part of vine_mpc.h's configuration these launches read, checked as vine_mpc.hip checks it.
 int validate(const VineMpcConfig* c, const VineMpcPolicyConfig* pc) {
     if (!c) return vine_invalid_arg("mpc config is NULL");
@@ -262,7 +258,8 @@ int vine_mpc_policy_fork(VineHandle* plant, VineHandle* model, const VineMpcConf
     rc = prepare(model, cfg, pcfg, info, S);
     if (rc) return rc;
     if (pinfo.n != cfg->num_plants) return vine_invalid_arg("mpc policy fork: the plant handle does not have num_plants envs");
-    if (info.device != pinfo.device) return vine_invalid_arg("mpc policy fork: the model handle sits on another device than the plant");
+    rc = mpc_same_device("mpc policy fork", "model", pinfo, info);
+    if (rc) return rc;
     VineDeviceScope scope(info.device);
     if (!scope.ok) return VINE_ERR_DEVICE;
     hipLaunchKernelGGL(vine_mpc_policy_fork_kernel, quad_grid(S.n), dim3(THREADS), 0, (hipStream_t)stream, S, plant_obs, model_obs,

@@ -1,11 +1,16 @@
-// vine_mpc_shared.h — what vine_mpc.hip (the fork, the update) and vine_mpc_adapt.hip (the pin, the estimate) state once:
-// the copy of a plant's state-block column onto a sample, the rebuild of the sample's delay ring from an action history, and
-// the workgroup reduction's wave step.  Include it behind vine_task_shared.h (task_new_command, VF_*); that header keeps
-// the contraction it was included under, whatever holds here.
+// vine_mpc_shared.h — what the vine_mpc*.hip units state once.  For their kernels: the copy of a plant's state-block column
+// onto a sample, the rebuild of the sample's delay ring from an action history, and the workgroup reduction's wave step.  For
+// their launch functions (HOST, at the end): the unsupported status, the command constants of a handle, the deviate's scale
+// and the refusals of a second handle that could not stand in for the plant.  Include it behind vine_observer.h
+// (VineHandleInfo) and vine_task_shared.h (task_new_command, VF_*); that header keeps the contraction it was included under,
+// whatever holds here.
 #ifndef VINE_MPC_SHARED_H
 #define VINE_MPC_SHARED_H
 
 #include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
 
 static_assert(VF_PIPE_Y == VF_FIFO0 + 2 * VINE_MAX_DELAY, "the ring is the fields VF_FIFO0 .. VF_PIPE_Y - 1");
 
@@ -58,6 +63,45 @@ __device__ __forceinline__ int mpc_deviate_int(const unsigned w[4]) {
     const int sum = (int)((w[0] & 0xffffu) + (w[0] >> 16) + (w[1] & 0xffffu) + (w[1] >> 16) + (w[2] & 0xffffu) +
                           (w[2] >> 16) + (w[3] & 0xffffu) + (w[3] >> 16));
     return 2 * sum - 524280;
+}
+
+// ---- HOST: the launch functions' part
+inline int unsupported(const char* msg) {
+    vine_set_error(msg);
+    return VINE_ERR_UNSUPPORTED;
+}
+
+// The command constants of a handle's configuration; a sample, a candidate and a predictor add no action noise.
+inline CommandParams mpc_command_params(const VineHandleInfo& info) {
+    return CommandParams{info.clip_act, 0.0f, info.rail_scale, info.fpam_span, info.fpam_min};
+}
+
+// 1 / sqrt(32 * (65536^2 - 1) / 12): the deviate's scale, in float64 (the statement of vine_env_sensor.hip)
+inline double noise_scale() { return 1.0 / sqrt(32.0 * (65536.0 * 65536.0 - 1.0) / 12.0); }
+
+// "This second handle (`role`: model, predictor) can stand in for that plant": it sits on the plant's device, does not
+// randomize (`why`: what the launch needs that for), and has the plant's obstacles and episode length.  Refused in that order.
+inline int mpc_refuse(int status, const char* format, const char* prefix, const char* role, const char* why = "") {
+    char msg[200];
+    snprintf(msg, sizeof msg, format, prefix, role, why);
+    vine_set_error(msg);
+    return status;
+}
+inline int mpc_same_device(const char* prefix, const char* role, const VineHandleInfo& pinfo, const VineHandleInfo& info) {
+    if (info.device == pinfo.device) return VINE_OK;
+    return mpc_refuse(VINE_ERR_INVALID_ARG, "%s: the %s handle sits on another device than the plant", prefix, role);
+}
+inline int mpc_stand_in(const char* prefix, const char* role, const char* why, const VineHandleInfo& pinfo,
+                        const VineHandleInfo& info) {
+    const unsigned obstacles = VINE_FLAG_CREATE_SHELF | VINE_FLAG_CREATE_PIPE;
+    if (const int rc = mpc_same_device(prefix, role, pinfo, info)) return rc;
+    if (info.flags & VINE_FLAG_VINE_RANDOMIZE)
+        return mpc_refuse(VINE_ERR_UNSUPPORTED, "%s: a %s handle with vine_randomize is refused (%s)", prefix, role, why);
+    if ((info.flags & obstacles) != (pinfo.flags & obstacles))
+        return mpc_refuse(VINE_ERR_UNSUPPORTED, "%s: the %s handle's CREATE_SHELF / CREATE_PIPE differ from the plant's", prefix, role);
+    if (info.max_len != pinfo.max_len)
+        return mpc_refuse(VINE_ERR_INVALID_ARG, "%s: the %s handle's max_episode_length differs from the plant's", prefix, role);
+    return VINE_OK;
 }
 
 #endif

@@ -85,7 +85,7 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
                                    os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
-                   SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h")],
+                   SRC_MPC_POLICY: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_policy.h"), _MPC_SHARED],
                    SRC_MPC_OBSERVE: [os.path.join(_INC, "vine_mpc_observe.h"), _MPC_SHARED],
                    SRC_MPC_FILTER: [os.path.join(_INC, "vine_mpc_observe.h"), os.path.join(_INC, "vine_mpc_filter.h"), _MPC_SHARED]}
 # vine_env_redraw.hip forms table columns that must hold the bits numpy and the host pass give: a + b * c stays a multiply

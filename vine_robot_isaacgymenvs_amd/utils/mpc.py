@@ -199,39 +199,47 @@ def mpc_replay(nominal, cost, sigma, lam, seed, tick, clip, plant_reset=None, hi
 
 
 # ------------------------------------------------------------------------------------------------------------ the device
-class _Pair:
-    """The plant and the model as the one env ``graph_capture.capture_rolled_back`` rolls back."""
+class _Tasks:
+    """The controller's tasks as the one env ``graph_capture.capture_rolled_back`` rolls back."""
 
-    def __init__(self, plant, model):
-        self.plant, self.model = plant, model
+    def __init__(self, tasks):
+        self.tasks = tasks
 
     @property
     def step_count(self):
-        return (self.plant.step_count, self.model.step_count)
+        return tuple(t.step_count for t in self.tasks)
 
     @step_count.setter
     def step_count(self, v):
-        self.plant.step_count, self.model.step_count = v
+        for t, c in zip(self.tasks, v):
+            t.step_count = c
 
     @contextlib.contextmanager
     def observers_paused(self):
-        with self.plant.observers_paused(), self.model.observers_paused():
+        with contextlib.ExitStack() as stack:
+            for t in self.tasks:
+                stack.enter_context(t.observers_paused())
             yield
 
 
 class Controller:
     """The controller's buffers and launches for a plant task of M envs and a model task of M * K envs.
 
-    ``control_step()`` = ``fork()``, H x (``model.step_into`` + ``node()``), ``update()``, ``plant.step_into(plant_actions,
-    plant_obs)``.  ``run(n)`` issues n of them: ``graph_steps`` control steps are captured once as one hipGraph
-    (``graph_capture.capture_rolled_back``) and replayed with the plant's observers told of every replay
-    (``replay_observed``); what is left over, or everything where a task is not capturable (``graph=False`` forces that), is
-    issued eagerly.  ``launches`` counts what the host enqueued, by kind."""
+    ``control_step()`` = ``fork()``, H x ``model_step()`` (``model.step_into`` + ``node()``), ``update()``,
+    ``plant.step_into(plant_actions, plant_obs)``, stated here alone: a variant extends ``model_step``, puts launches between
+    those at ``after_fork``, ``before_update`` and ``after_update``, and in front of the fork or behind the plant step by
+    wrapping ``control_step``.  ``run(n)`` issues n of them: a *unit* (``unit()``: here ``graph_steps`` control steps) is
+    captured once as one hipGraph (``graph_capture.capture_rolled_back`` over ``tasks``) and replayed, the plant's observers
+    told of every replay (``replay_observed``), wherever a whole unit is left and ``at_boundary()`` holds; every other step,
+    or every step where a task is not capturable (``graph=False`` forces that), is an ``eager_step()``.  ``launches`` counts
+    what the host enqueued, by kind."""
 
     def __init__(self, plant_task, model_task, samples, horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
                  sigma=DEFAULTS["sigma"], seed=DEFAULTS["seed"], graph=True, graph_steps=1, keep_weights=False):
         import torch
         self.plant, self.model, self.lib = plant_task, model_task, plant_task._lib
+        self.tasks = (plant_task, model_task)        # what a capture rolls back, in order
+        self.fork_source = plant_task                # the task whose state the samples are forked from
         self.device = plant_task.device
         self.M, self.K, self.H = int(plant_task.num_envs), int(samples), int(horizon)
         self.mcfg = mpc_config(self.M, self.K, self.H, lam, sigma, seed)
@@ -253,7 +261,7 @@ class Controller:
         self.plant_obs = torch.zeros((self.M, plant_task.num_obs), dtype=f32, device=dev)
         # a diagnostic: the last update's weights (include/vine_mpc.h vine_mpc_update), stored only on request
         self.weights = torch.zeros(N, dtype=torch.float64, device=dev) if keep_weights else None
-        self.graph_steps = max(1, int(graph_steps))
+        self.graph_steps = self.unit_steps = max(1, int(graph_steps))
         self.use_graph = (bool(graph) and bool(getattr(plant_task, "graph_capturable", False))
                           and bool(getattr(model_task, "graph_capturable", False)) and getattr(plant_task, "video", None) is None)
         self.graph = None
@@ -272,7 +280,7 @@ class Controller:
     # -- the three launches ----------------------------------------------------------------------------------------------
     def fork(self):
         from .. import native
-        p, m = self.plant, self.model
+        p, m = self.fork_source, self.model
         native.check(self.lib.vine_mpc_fork(
             p._handle, m._handle, self.mcfg, p.progress_buf.data_ptr(), self.nominal.data_ptr(), self.history.data_ptr(),
             self.tick.data_ptr(), self.actions.data_ptr(), m.rew_buf.data_ptr(), m.reset_buf.data_ptr(),
@@ -303,52 +311,74 @@ class Controller:
         self.launches["step"] += 1
         self.node()
 
+    def after_fork(self):
+        pass
+
+    def before_update(self):
+        pass
+
+    def after_update(self):
+        pass
+
     def control_step(self):
         """One control step, eagerly (or into a capture)."""
         self.fork()
+        self.after_fork()
         for _ in range(self.H):
             self.model_step()
+        self.before_update()
         self.update()
+        self.after_update()
         self.plant.step_into(self.plant_actions, self.plant_obs)
         self.launches["plant_step"] += 1
 
     # -- many of them ----------------------------------------------------------------------------------------------------
-    def _capture(self, body=None):
-        """``body`` (default: ``graph_steps`` control steps) captured as one hipGraph, with nothing of it left behind."""
+    def unit(self):
+        """What one replay stands for: ``unit_steps`` control steps from a boundary."""
+        for _ in range(self.unit_steps):
+            self.control_step()
+
+    def at_boundary(self):
+        return True
+
+    def eager_step(self):
+        self.control_step()
+
+    def _capture(self, body):
+        """``body`` captured as one hipGraph, with nothing of it left behind but what one replay stands for: ``graph_launches``
+        by kind and ``graph_num_steps`` per task of ``tasks``."""
         from ..learning import graph_capture
-        plant, model = self.plant, self.model
-        counted, steps = dict(self.launches), (plant.num_steps, model.num_steps)
-
-        def control_steps():
-            for _ in range(self.graph_steps):
-                self.control_step()
-
-        body = body or control_steps
-        live = self.tensors() + plant.live_tensors() + model.live_tensors()
-        graph = graph_capture.capture_rolled_back(self.device, body, live, _Pair(plant, model))
+        counted, steps = dict(self.launches), [t.num_steps for t in self.tasks]
+        live = self.tensors()
+        for t in self.tasks:
+            live = live + t.live_tensors()
+        graph = graph_capture.capture_rolled_back(self.device, body, live, _Tasks(self.tasks))
         # the warm-up pass was rolled back and the capture pass executed nothing: what the capture pass enqueued is the graph
         self.graph_launches = {k: (v - counted[k]) // 2 for k, v in self.launches.items()}
+        self.graph_num_steps = [(t.num_steps - n) // 2 for t, n in zip(self.tasks, steps)]
         self.launches = counted
-        plant.num_steps, model.num_steps = steps
+        for t, n in zip(self.tasks, steps):
+            t.num_steps = n
         return graph
 
     def run(self, n):
         """``n`` control steps."""
         from ..learning import graph_capture
-        n, done = int(n), 0
-        if self.use_graph and n >= self.graph_steps:
-            if self.graph is None:
-                self.graph = self._capture()
-            for _ in range(n // self.graph_steps):
-                graph_capture.replay_observed(self.graph, self.plant, self.graph_steps)
-                self.plant.num_steps += self.graph_steps
-                self.model.num_steps += self.graph_steps * self.H
+        left, unit = int(n), self.unit_steps
+        while left > 0:
+            if self.use_graph and left >= unit and self.at_boundary():
+                if self.graph is None:
+                    self.graph = self._capture(self.unit)
+                graph_capture.replay_observed(self.graph, self.plant, unit)
+                for t, steps in zip(self.tasks, self.graph_num_steps):
+                    t.num_steps += steps
                 for k, v in self.graph_launches.items():
                     self.launches[k] += v
-            done = n // self.graph_steps * self.graph_steps
-        for _ in range(n - done):
-            self.control_step()
-        self.control_steps += n
+                left -= unit
+            else:
+                self.eager_step()
+                left -= 1
+        self.control_steps += int(n)
 
     # -- from outside the step -------------------------------------------------------------------------------------------
     def set_model_params(self, values):
@@ -364,12 +394,17 @@ class Controller:
         self.model.set_env_params(out)
 
     def reset_plants(self, ids):
-        """Plants reset from outside the step (``plant.reset_idx``): their nominal sequence and action history start anew."""
+        """Plants reset from outside the step (``plant.reset_idx``), and ``clear_rows`` for them."""
         import torch
         ids = torch.as_tensor(ids, device=self.device).to(torch.long)
         if ids.numel() == 0:
             return
         self.plant.reset_idx(ids)
+        self.clear_rows(ids)
+
+    def clear_rows(self, ids):
+        """What the controller keeps of the plants ``ids`` (a long tensor, not empty) starts anew: their nominal sequence
+        and action history.  A variant adds its own rows."""
         self.nominal[ids] = 0.0
         self.history[ids] = 0.0
 
@@ -381,6 +416,56 @@ def draw_model_params(spec, vcfg, lib, seed, num_plants):
     draws = {}
     env_params.draw_table(spec, env_params.config_row(lib, vcfg), seed, num_plants, draws=draws)
     return draws
+
+
+# What play() refuses, checked in this order before any task is created: the first entry whose keys all hold raises its message.
+# A key is a keyword of play() that was given, ``terminal_value`` where it is not zero, ``ENV_TARGET`` where the plant's
+# task.env has a target spec that is not empty; ``!key``: the key does not hold.
+RULES = (
+    (("track", "!ENV_TARGET"), "mpc: track= needs a plant with task.env.ENV_TARGET: there is no path to follow"),
+    (("track", "policy"), "mpc: track= together with policy= is refused: the samples' observation would need the target's velocity columns"),
+    (("track", "adapt"), "mpc: track= together with adapt= is refused: the adaptive controller's traces were built for a resting target"),
+    (("track", "observe"), "mpc: track= together with observe= or filter= is refused: the predictor was built for a resting target"),
+    (("track", "filter"), "mpc: track= together with observe= or filter= is refused: the predictor was built for a resting target"),
+    (("filter", "!observe"), "mpc: filter= needs observe=: the frames it corrects are the sensing path's"),
+    (("filter", "observe", "adapt"), "mpc: filter= together with adapt= is refused: the adaptive controller traces the plant's exact state"),
+    (("filter", "observe", "policy"), "mpc: filter= together with policy= is refused: the policy's memory is forked from the plant's exact state"),
+    (("observe", "adapt"), "mpc: observe= together with adapt= is refused: the adaptive controller traces the plant's exact state"),
+    (("observe", "policy"), "mpc: observe= together with policy= is refused: the policy's memory is forked from the plant's exact state"),
+    (("terminal_value", "!policy"), "mpc: terminal_value needs policy=<checkpoint>: the critic is the policy's"),
+    (("policy", "adapt"), "mpc: policy= together with adapt= is refused: the adaptive controller does not roll the policy yet"),
+)
+
+
+def refuse(holding):
+    """A ``ConfigError`` with the message of the first entry of ``RULES`` that the set of keys ``holding`` meets."""
+    for keys, message in RULES:
+        if all(k[1:] not in holding if k.startswith("!") else k in holding for k in keys):
+            raise ConfigError(message)
+
+
+class PlayVariant:
+    """What one keyword of ``play`` adds to a run.  Each variant's module states its own once, as ``Play``, and ``play`` walks
+    those given in the order of ``VARIANTS``, calling what each defines of: ``check(run)``, the argument ``spec`` checked before
+    any task is created; ``bind(run)``, the model's task config edited; ``make(run)``, what must exist before the controller (a
+    third task, a network); ``controller(run)``, asked of the last one given only; ``banner(run)``; ``stepped(ctl)`` behind every
+    ``ctl.run(1)``; ``result(run, out)``, its entries of the result and its lines in front of the timing; ``report_rows(run,
+    rows)``, columns added to the finished episodes; ``epilogue(run, out)`` behind the report.  ``run``: what ``play`` knows, by
+    name -- ``cfg`` and ``mcfg`` (the plant's and the model's task config), ``M``, ``samples``, ``planner`` (horizon, lambda,
+    sigma, seed: a controller's next four arguments), ``graph``, ``steps``, ``device``, ``model_params``, ``draws`` (the model's
+    drawn parameters still to be set, or ``None``), ``args`` (``play``'s keywords), ``given`` (the variants by key) and, once
+    made, ``plant``, ``model``, ``predictor``, ``ctl``."""
+    single_run = False         # True: one ``ctl.run(steps)`` that sums ``ctl.returns``, not ``run(1)`` + ``plant.rew_buf`` per step
+    report_params = False      # True: the report takes the plant's parameter columns even where it has no ENV_PARAMS
+
+    def __init__(self, spec):
+        self.spec = spec
+
+    def controller(self, run):
+        return Controller(run.plant, run.model, run.samples, *run.planner, graph=run.graph)
+
+
+VARIANTS = ("track", "observe", "filter", "policy", "adapt")      # the order they are walked in; each is utils/mpc_<key>.Play
 
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
@@ -425,6 +510,9 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     target).  The result then holds ``track``: ``PATH`` and ``live_fraction``, the share of (plant, control step) pairs whose
     samples followed a path; the per-parameter report has the plant's varying ``param_TARGET_*`` columns.  Without it nothing
     of this is constructed or launched."""
+    import importlib
+    import types
+
     import torch
     from . import episodes
     logger = logger or logging.getLogger(__name__)
@@ -438,48 +526,22 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = cfg.get("seed", 0) if seed is None else seed
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
-    if track is not None:
-        from . import mpc_track
-        track = mpc_track.track_config(track)
-        if not (cfg["env"].get("ENV_TARGET") or {}):
-            raise ConfigError("mpc: track= needs a plant with task.env.ENV_TARGET: there is no path to follow")
-        if policy is not None:
-            raise ConfigError("mpc: track= together with policy= is refused: the samples' observation would need the target's velocity columns")
-        if adapt is not None:
-            raise ConfigError("mpc: track= together with adapt= is refused: the adaptive controller's traces were built for a resting target")
-        if observe is not None or filter is not None:
-            raise ConfigError("mpc: track= together with observe= or filter= is refused: the predictor was built for a resting target")
-    if filter is not None:
-        from . import mpc_filter
-        if observe is None:
-            raise ConfigError("mpc: filter= needs observe=: the frames it corrects are the sensing path's")
-        if adapt is not None:
-            raise ConfigError("mpc: filter= together with adapt= is refused: the adaptive controller traces the plant's exact state")
-        if policy is not None:
-            raise ConfigError("mpc: filter= together with policy= is refused: the policy's memory is forked from the plant's exact state")
-        mpc_filter.filter_config(filter)
-    if observe is not None:
-        from . import mpc_observe
-        if adapt is not None:
-            raise ConfigError("mpc: observe= together with adapt= is refused: the adaptive controller traces the plant's exact state")
-        if policy is not None:
-            raise ConfigError("mpc: observe= together with policy= is refused: the policy's memory is forked from the plant's exact state")
-        checked = mpc_observe.observe_config(observe)
-        if filter is not None:
-            if model_params:
-                env_params.spec_forms(model_params)
-            mpc_filter.largest_reach(checked, mpc_filter.model_action_delay(cfg["env"], model_params))
-    if policy is None and terminal_value:
-        raise ConfigError("mpc: terminal_value needs policy=<checkpoint>: the critic is the policy's")
-    if policy is not None:
-        from . import mpc_policy
-        if adapt is not None:
-            raise ConfigError("mpc: policy= together with adapt= is refused: the adaptive controller does not roll the policy yet")
-        if policy_params is None:
-            raise ConfigError("mpc: policy= needs policy_params, the train.params block the network is built from")
-        mpc_policy.check_shape(M, samples)
-        mpc_policy.check_eps("terminal_value", terminal_value)
-    mcfg = model_config(cfg, M, samples, cost, logger)
+    args = {"adapt": adapt, "policy": policy, "terminal_value": terminal_value, "policy_params": policy_params,
+            "observe": observe, "filter": filter, "track": track}
+    refuse({k for k in VARIANTS if args[k] is not None} | ({"terminal_value"} if terminal_value else set())
+           | ({"ENV_TARGET"} if cfg["env"].get("ENV_TARGET") else set()))
+    given = {k: importlib.import_module(".mpc_" + k, __package__).Play(args[k]) for k in VARIANTS if args[k] is not None}
+    active = list(given.values())
+
+    def each(what, *a):
+        for v in active:
+            getattr(v, what, lambda *a: None)(*a)
+
+    run = types.SimpleNamespace(cfg=cfg, M=M, samples=samples, planner=(horizon, lam, sigma, seed), graph=graph, steps=int(steps),
+                                device=device, model_params=model_params, draws=None, args=args, given=given, plant=None,
+                                model=None, predictor=None, ctl=None)
+    each("check", run)
+    run.mcfg = mcfg = model_config(cfg, M, samples, cost, logger)
     if model_params:
         env_params.spec_forms(model_params)
         mcfg["env"]["ENV_PARAMS"] = copy.deepcopy(dict(model_params))       # binds the model's table(s); filled per plant below
@@ -487,53 +549,17 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
         logger.info("mpc: model env.ENV_PARAMS forced from %r to {} (the model is the configuration's own plant)",
                     mcfg["env"]["ENV_PARAMS"])
         mcfg["env"]["ENV_PARAMS"] = {}
-    if adapt is not None and not mcfg["env"].get("ENV_PARAMS"):
-        mcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}      # binds a table that holds the configuration's own row: what is adapted
-    plant = make_task(cfg, device)
-    model = predictor = None
+    each("bind", run)
+    run.plant = plant = make_task(cfg, device)
     try:
-        model = make_task(mcfg, device)
-        if observe is not None:                          # the model's plant once more, one env per real plant
-            pcfg = copy.deepcopy(mcfg)
-            pcfg["env"]["numEnvs"] = M
-            predictor = make_task(pcfg, device)
-            if filter is not None:
-                ctl = mpc_filter.FilteringController(plant, model, predictor, samples, observe, filter, horizon, lam, sigma, seed,
-                                                     graph=graph)
-            else:
-                ctl = mpc_observe.ObservingController(plant, model, predictor, samples, observe, horizon, lam, sigma, seed, graph=graph)
-            if model_params:
-                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
-            print("mpc: observing through DELAY %s, HOLD %s, NOISE_Q %s, NOISE_QD %s; %d catch-up steps, %s" % (
-                ctl.spec["DELAY"], ctl.spec["HOLD"], ctl.spec["NOISE_Q"], ctl.spec["NOISE_QD"], ctl.C,
-                "compensated" if ctl.spec["COMPENSATE"] else "not compensated"), flush=True)
-            if filter is not None:
-                print("mpc: filtering with GAIN_Q %s, GAIN_QD %s" % (ctl.filter_spec["GAIN_Q"], ctl.filter_spec["GAIN_QD"]), flush=True)
-        elif policy is not None:
-            proposal = mpc_policy.PolicyProposal(policy_params, M * int(samples), int(plant.num_obs), plant.device)
-            proposal.restore(policy)
-            ctl = mpc_policy.PolicyController(plant, model, samples, proposal, horizon, lam, sigma, seed, graph=graph,
-                                              terminal_value=terminal_value)
-            if model_params:
-                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
-            print("mpc: the samples roll the policy of %s; terminal_value %g" % (policy, float(terminal_value)), flush=True)
-        elif track is not None:
-            ctl = mpc_track.TrackingController(plant, model, samples, track, horizon, lam, sigma, seed, graph=graph)
-            if model_params:
-                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
-            print("mpc: the samples' targets follow the %s path of their plant's ENV_TARGET" % track["PATH"], flush=True)
-        elif adapt is None:
-            ctl = Controller(plant, model, samples, horizon, lam, sigma, seed, graph=graph)
-            if model_params:
-                ctl.set_model_params(draw_model_params(model_params, model._vcfg, model._lib, seed, M))
-        else:                                            # the prior is the model's value when the controller is made
-            from . import mpc_adapt
-            if model_params:
-                model.set_env_params({k: np.repeat(v, int(samples)) for k, v in
-                                      draw_model_params(model_params, model._vcfg, model._lib, seed, M).items()})
-            ctl = mpc_adapt.AdaptiveController(plant, model, samples, adapt, horizon, lam, sigma, seed, graph=graph,
-                                               forget_on_reset=env_params.per_episode(cfg["env"]))
-            print("mpc: adapting %s every %d control steps over a window of %d" % (", ".join(ctl.names), ctl.E, ctl.W), flush=True)
+        run.model = model = make_task(mcfg, device)
+        if model_params:
+            run.draws = draw_model_params(model_params, model._vcfg, model._lib, seed, M)
+        each("make", run)
+        run.ctl = ctl = (active[-1] if active else PlayVariant(None)).controller(run)
+        if run.draws:
+            ctl.set_model_params(run.draws)
+        each("banner", run)
         log = getattr(plant, "episode_log", None)
         start = None
         if log is not None:
@@ -543,49 +569,32 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
             M, ctl.K, ctl.H, float(lam), sigma, "hipGraph replay" if ctl.use_graph else "eager launches",
             model.step_kernel_name), flush=True)
         total = torch.zeros(M, dtype=torch.float64, device=plant.device)
-        lived = torch.zeros((), dtype=torch.int64, device=plant.device) if track is not None else None
         torch.cuda.synchronize(plant.device)
         t0 = time.perf_counter()
-        if adapt is None:
+        if any(v.single_run for v in active):            # whole units replay from one graph: the controller sums the reward
+            ctl.run(int(steps))
+            total += ctl.returns
+        else:
             for _ in range(int(steps)):
                 ctl.run(1)
                 total += plant.rew_buf
-                if lived is not None:
-                    lived += ctl.live.sum()
-        else:                                            # whole cycles replay from one graph: the trace node sums the reward
-            ctl.run(int(steps))
-            total += ctl.returns
+                each("stepped", ctl)
         torch.cuda.synchronize(plant.device)
         seconds = time.perf_counter() - t0
         out = {"report": None, "by_param": {}, "path": None, "control_steps_per_second": int(steps) / max(seconds, 1e-9),
                "plant_return": total.cpu().numpy(), "launches": dict(ctl.launches), "graphed": ctl.use_graph,
                "model_step_kernel": model.step_kernel_name, "model_table_bound": model.env_params is not None}
-        if policy is not None:
-            out["policy"] = policy
-        if track is not None:
-            out["track"] = {"PATH": track["PATH"], "live_fraction": float(lived) / max(1, int(steps) * M)}
-            print("mpc: tracked along the %s path on %.4g of the (plant, control step) pairs" % (
-                track["PATH"], out["track"]["live_fraction"]), flush=True)
-        if observe is not None:
-            out["observe"] = {"names": list(mpc_observe.NAMES), "table": ctl.table_host.copy(), "catchup": ctl.C,
-                              "compensate": ctl.spec["COMPENSATE"], "lag": float(ctl.lag.double().mean())}
-        if filter is not None:
-            out["filter"] = {"names": list(mpc_filter.NAMES), "gain": ctl.gain_host.copy(),
-                             "innov": ctl.innov.double().mean(dim=1).cpu().numpy()}
-            print("mpc: mean lag %.3g, mean innovation (sum of squares) q %.4g, qd %.4g" % (
-                out["observe"]["lag"], out["filter"]["innov"][0], out["filter"]["innov"][1]), flush=True)
+        each("result", run, out)
         print("mpc: %d control steps in %.3f s (%.4g control steps/s, %.4g model env-steps/s)" % (
             int(steps), seconds, out["control_steps_per_second"], out["control_steps_per_second"] * M * ctl.K * ctl.H), flush=True)
         if log is not None:
             from ..learning.player import format_report
             log.harvest()
-            rows = log.rows_with_params() if plant.env_params is not None or track is not None else log.rows()
+            with_params = plant.env_params is not None or any(v.report_params for v in active)
+            rows = log.rows_with_params() if with_params else log.rows()
             keep = rows["end_step"] >= start
             rows = {k: v[keep] for k, v in rows.items()}
-            if filter is not None:                       # a gain that varies over the plants is a parameter of the report
-                for slot, name in enumerate(mpc_filter.DRAW_NAMES):
-                    if len(np.unique(ctl.gain_host[slot])) > 1:
-                        rows["param_" + name] = ctl.gain_host[slot][rows["env"]]
+            each("report_rows", run, rows)
             out["report"] = episodes.report(rows)
             print(format_report(out["report"]), flush=True)
             for column in [k for k in rows if k.startswith("param_")]:
@@ -599,23 +608,9 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
                     print("    [%.4g, %.4g%s  %.4g  (%d episodes)" % (edges[i], edges[i + 1], "]" if i == len(rate) - 1 else ")",
                                                                       rate[i], count[i]), flush=True)
             out["path"] = log.path                       # (written when the plant is closed, below)
-        if adapt is not None:
-            mean, std = ctl.belief()
-            prior, truth = ctl.prior_mean.cpu().numpy(), ctl.truth()
-            out["adapt"] = {"names": list(ctl.names), "mean": mean, "std": std, "prior_mean": prior, "truth": truth,
-                            "passes": ctl.passes.cpu().numpy(), "prior_error": {}, "final_error": {}}
-            for d, name in enumerate(ctl.names):
-                if truth is None:
-                    print("  adapt %s: final mean %s" % (name, np.array2string(mean[:, d], precision=4)), flush=True)
-                    continue
-                out["adapt"]["prior_error"][name] = float(np.abs(prior[:, d] - truth[:, d]).mean())
-                out["adapt"]["final_error"][name] = float(np.abs(mean[:, d] - truth[:, d]).mean())
-                print("  adapt %s: mean |prior - truth| %.4g, mean |belief - truth| %.4g" % (
-                    name, out["adapt"]["prior_error"][name], out["adapt"]["final_error"][name]), flush=True)
+        each("epilogue", run, out)
         return out
     finally:
-        if predictor is not None:
-            predictor.close()
-        if model is not None:
-            model.close()
-        plant.close()
+        for task in (run.predictor, run.model, plant):
+            if task is not None:
+                task.close()

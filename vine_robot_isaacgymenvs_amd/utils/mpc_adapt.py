@@ -13,7 +13,7 @@ from .. import abi
 from . import env_sensor
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
-from .mpc import Controller, check_integer, check_real
+from .mpc import Controller, PlayVariant, check_integer, check_real
 
 # temperature, rate, spread and floor: see DESIGN.md section 25 ("The four constants") for what they were checked against
 DEFAULTS = {"window": 8, "every": 8, "min_steps": 4, "temperature": 0.1, "rate": 0.5, "spread": 0.25, "floor": 0.01}
@@ -229,11 +229,12 @@ class AdaptiveController(Controller):
     """A ``Controller`` whose model follows its plants: the extra buffers of include/vine_mpc_adapt.h and the five launches.
 
     A cycle is ``anchor()``, ``every`` x (``control_step()`` + ``trace()``), ``pin()``, ``window`` x (model step +
-    ``score()``), ``estimate()``.  ``run(n)`` issues n control steps: whole cycles that start on a cycle's boundary are
-    replayed from one captured hipGraph, what is left over is issued eagerly with the phase (control steps done in the running
-    cycle) kept on the host.  The model task must have a parameter table bound (``task.env.ENV_PARAMS``): the device writes
-    its adapted rows, so ``model._env_params_host`` is stale for them; ``set_model_params`` refuses an adapted name and
-    refreshes those rows of the mirror from the device before it rewrites any other."""
+    ``score()``), ``estimate()``.  ``run(n)`` issues n control steps: the unit of ``Controller.run`` is ``graph_cycles`` whole
+    cycles, replayed from one captured hipGraph where they start on a cycle's boundary; what is left over is issued eagerly
+    with the phase (control steps done in the running cycle) kept on the host.  The model task must have a parameter table
+    bound (``task.env.ENV_PARAMS``): the device writes its adapted rows, so ``model._env_params_host`` is stale for them;
+    ``set_model_params`` refuses an adapted name and refreshes those rows of the mirror from the device before it rewrites
+    any other."""
 
     def __init__(self, plant_task, model_task, samples, adapt, horizon=MPC_DEFAULTS["horizon"], lam=MPC_DEFAULTS["lambda"],
                  sigma=MPC_DEFAULTS["sigma"], seed=MPC_DEFAULTS["seed"], graph=True, graph_cycles=1, keep_weights=False,
@@ -272,7 +273,7 @@ class AdaptiveController(Controller):
         self.adapt_weights = torch.zeros(N, dtype=f64, device=dev) if keep_weights else None
         self.phase = 0
         self.graph_cycles = max(1, int(graph_cycles))
-        self.cycle_graph = None
+        self.unit_steps = self.E * self.graph_cycles
         self.launches.update({"anchor": 0, "trace": 0, "pin": 0, "adapt_step": 0, "score": 0, "estimate": 0})
         self._write_plan()
 
@@ -371,38 +372,24 @@ class AdaptiveController(Controller):
             self.trace()
         self.adapt_pass()
 
-    # -- many of them ----------------------------------------------------------------------------------------------------
-    def run(self, n):
-        """``n`` control steps."""
-        from ..learning import graph_capture
-        n = int(n)
-        left, chunk = n, self.E * self.graph_cycles
+    # -- many of them: Controller.run with whole cycles as the unit ---------------------------------------------------------
+    def at_boundary(self):
+        return self.phase == 0
 
-        def cycles():
-            for _ in range(self.graph_cycles):
-                self.cycle()
+    def unit(self):
+        for _ in range(self.graph_cycles):
+            self.cycle()
 
-        while left > 0:
-            if self.use_graph and self.phase == 0 and left >= chunk:
-                if self.cycle_graph is None:
-                    self.cycle_graph = self._capture(cycles)
-                graph_capture.replay_observed(self.cycle_graph, self.plant, chunk)
-                self.plant.num_steps += chunk
-                self.model.num_steps += (self.E * self.H + self.W) * self.graph_cycles
-                for k, v in self.graph_launches.items():
-                    self.launches[k] += v
-                left -= chunk
-                continue
-            if self.phase == 0:
-                self.anchor()
-            self.control_step()
-            self.trace()
-            self.phase += 1
-            if self.phase == self.E:
-                self.adapt_pass()
-                self.phase = 0
-            left -= 1
-        self.control_steps += n
+    def eager_step(self):
+        """One control step of the running cycle, the phase kept on the host."""
+        if self.phase == 0:
+            self.anchor()
+        self.control_step()
+        self.trace()
+        self.phase += 1
+        if self.phase == self.E:
+            self.adapt_pass()
+            self.phase = 0
 
     # -- from outside the step -------------------------------------------------------------------------------------------
     def adapted_rows(self):
@@ -443,3 +430,40 @@ class AdaptiveController(Controller):
                 v = table[nz[0]] / np.float64(self.base_row[nz[0]]) if nz else np.ones(self.M)
             out[:, d] = v
         return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ a run
+class Play(PlayVariant):
+    """``adapt=`` of ``mpc.play``."""
+    single_run = True          # whole cycles replay from one graph: the trace node sums the reward into ``ctl.returns``
+
+    def bind(self, run):
+        if not run.mcfg["env"].get("ENV_PARAMS"):
+            run.mcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}      # binds a table of the configuration's own row: what is adapted
+
+    def controller(self, run):
+        from . import env_params
+        if run.draws:              # the one exception: the prior is the model's value when the controller is made
+            run.model.set_env_params({k: np.repeat(v, int(run.samples)) for k, v in run.draws.items()})
+            run.draws = None
+        return AdaptiveController(run.plant, run.model, run.samples, self.spec, *run.planner, graph=run.graph,
+                                  forget_on_reset=env_params.per_episode(run.cfg["env"]))
+
+    def banner(self, run):
+        ctl = run.ctl
+        print("mpc: adapting %s every %d control steps over a window of %d" % (", ".join(ctl.names), ctl.E, ctl.W), flush=True)
+
+    def epilogue(self, run, out):
+        ctl = run.ctl
+        mean, std = ctl.belief()
+        prior, truth = ctl.prior_mean.cpu().numpy(), ctl.truth()
+        out["adapt"] = {"names": list(ctl.names), "mean": mean, "std": std, "prior_mean": prior, "truth": truth,
+                        "passes": ctl.passes.cpu().numpy(), "prior_error": {}, "final_error": {}}
+        for d, name in enumerate(ctl.names):
+            if truth is None:
+                print("  adapt %s: final mean %s" % (name, np.array2string(mean[:, d], precision=4)), flush=True)
+                continue
+            out["adapt"]["prior_error"][name] = float(np.abs(prior[:, d] - truth[:, d]).mean())
+            out["adapt"]["final_error"][name] = float(np.abs(mean[:, d] - truth[:, d]).mean())
+            print("  adapt %s: mean |prior - truth| %.4g, mean |belief - truth| %.4g" % (
+                name, out["adapt"]["prior_error"][name], out["adapt"]["final_error"][name]), flush=True)

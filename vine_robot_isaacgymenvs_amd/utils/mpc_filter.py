@@ -18,6 +18,7 @@ from .. import abi
 from . import env_params, named_draw
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
+from .mpc import PlayVariant
 from .mpc_observe import LOG, NOT_RING, RING, SLOTS, ObservingController, hold_uniform
 
 _KEY = "mpc: filter"
@@ -264,17 +265,37 @@ class FilteringController(ObservingController):
         self.advance()
         super().predict()
 
-    def run(self, n):
-        """``n`` control steps."""
-        super().run(n)
-        if self.graph is not None and int(n) >= self.graph_steps:      # the filter's own predictor step of every replayed one
-            self.predictor.num_steps += int(n) // self.graph_steps * self.graph_steps
-
-    def reset_plants(self, ids):
-        """``ObservingController.reset_plants``; the estimate of each is forgotten."""
-        import torch
-        ids = torch.as_tensor(ids, device=self.device).to(torch.long)
-        if ids.numel() == 0:
-            return
-        super().reset_plants(ids)
+    def clear_rows(self, ids):
+        """The estimate of each is forgotten."""
+        super().clear_rows(ids)
         self.est_index[ids] = -1
+
+
+# ------------------------------------------------------------------------------------------------------------------ a run
+class Play(PlayVariant):
+    """``filter=`` of ``mpc.play``; ``observe=`` is given with it and has been checked."""
+
+    def check(self, run):
+        filter_config(self.spec)
+        if run.model_params:
+            env_params.spec_forms(run.model_params)
+        largest_reach(run.given["observe"].checked, model_action_delay(run.cfg["env"], run.model_params))
+
+    def controller(self, run):
+        return FilteringController(run.plant, run.model, run.predictor, run.samples, run.given["observe"].spec, self.spec,
+                                   *run.planner, graph=run.graph)
+
+    def banner(self, run):
+        print("mpc: filtering with GAIN_Q %s, GAIN_QD %s" % (run.ctl.filter_spec["GAIN_Q"], run.ctl.filter_spec["GAIN_QD"]),
+              flush=True)
+
+    def result(self, run, out):
+        out["filter"] = {"names": list(NAMES), "gain": run.ctl.gain_host.copy(),
+                         "innov": run.ctl.innov.double().mean(dim=1).cpu().numpy()}
+        print("mpc: mean lag %.3g, mean innovation (sum of squares) q %.4g, qd %.4g" % (
+            out["observe"]["lag"], out["filter"]["innov"][0], out["filter"]["innov"][1]), flush=True)
+
+    def report_rows(self, run, rows):
+        for slot, name in enumerate(DRAW_NAMES):             # a gain that varies over the plants is a parameter of the report
+            if len(np.unique(run.ctl.gain_host[slot])) > 1:
+                rows["param_" + name] = run.ctl.gain_host[slot][rows["env"]]

@@ -16,7 +16,7 @@ The semantics are stated once, in include/vine_mpc_observe.h.  What is left for 
                    drawn once per plant with the sensor's draw under the keys ``OBSERVE_<NAME>``
   ``COMPENSATE``   True (default): the delivered frame is predicted forward through the model; False: it is planned from as is
   ``CATCHUP``      predictor steps per control step, the largest ``DELAY`` (default) .. ``abi.MAX_DELAY``"""
-import contextlib
+import copy
 
 import numpy as np
 
@@ -24,7 +24,7 @@ from .. import abi
 from . import env_sensor, named_draw
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
-from .mpc import Controller
+from .mpc import Controller, PlayVariant, make_task
 
 _KEY = "mpc: observe"
 NAMES = tuple(abi.MPC_OBSERVE_NAMES)                  # the table's rows, the order of the mixed radix
@@ -258,29 +258,6 @@ def pin_replay(table, state, plant_column, plant_progress, plant_steps, catchup,
 
 
 # ------------------------------------------------------------------------------------------------------------ the device
-class _Triple:
-    """The plant, the model and the predictor as the one env ``graph_capture.capture_rolled_back`` rolls back."""
-
-    def __init__(self, plant, model, predictor):
-        self.tasks = (plant, model, predictor)
-
-    @property
-    def step_count(self):
-        return tuple(t.step_count for t in self.tasks)
-
-    @step_count.setter
-    def step_count(self, v):
-        for t, c in zip(self.tasks, v):
-            t.step_count = c
-
-    @contextlib.contextmanager
-    def observers_paused(self):
-        with contextlib.ExitStack() as stack:
-            for t in self.tasks:
-                stack.enter_context(t.observers_paused())
-            yield
-
-
 class ObservingController(Controller):
     """A ``Controller`` that sees its plants through the sensing path of include/vine_mpc_observe.h.  It owns the predictor
     task (``predictor_task``: ``model_config(cfg, M, 1, ...)``, the model's plant with one env per real plant; closed by
@@ -296,6 +273,8 @@ class ObservingController(Controller):
         super().__init__(plant_task, model_task, samples, horizon, lam, sigma, seed, graph=graph, graph_steps=graph_steps,
                          keep_weights=keep_weights)
         self.predictor = predictor_task
+        self.tasks += (predictor_task,)
+        self.fork_source = predictor_task            # the samples start where the controller believes the plant to be
         if int(predictor_task.num_envs) != self.M:
             raise ConfigError("%s: the predictor task has %d envs, not plants = %d" % (_KEY, int(predictor_task.num_envs), self.M))
         if predictor_task.device != self.device:
@@ -347,17 +326,6 @@ class ObservingController(Controller):
             self.fresh.data_ptr(), self._stream()), self.lib)
         self.launches["measure"] += 1
 
-    def fork(self):
-        """``vine_mpc_fork`` with the predictor in the plant's place."""
-        from .. import native
-        r, m = self.predictor, self.model
-        native.check(self.lib.vine_mpc_fork(
-            r._handle, m._handle, self.mcfg, r.progress_buf.data_ptr(), self.nominal.data_ptr(), self.history.data_ptr(),
-            self.tick.data_ptr(), self.actions.data_ptr(), m.rew_buf.data_ptr(), m.reset_buf.data_ptr(),
-            m.progress_buf.data_ptr(), self.cost.data_ptr(), self.alive.data_ptr(), self.window.data_ptr(), self._stream()),
-            self.lib)
-        self.launches["fork"] += 1
-
     def predict(self):
         """The pin and the catch-up: behind it the predictor stands where the controller believes the plant to be."""
         self.pin()
@@ -372,48 +340,44 @@ class ObservingController(Controller):
         super().control_step()
         self.measure()
 
-    # -- many of them ----------------------------------------------------------------------------------------------------
-    def _capture(self, body=None):
-        """``Controller._capture`` with the predictor rolled back beside the plant and the model."""
-        from ..learning import graph_capture
-        tasks = (self.plant, self.model, self.predictor)
-        counted, steps = dict(self.launches), [t.num_steps for t in tasks]
-
-        def control_steps():
-            for _ in range(self.graph_steps):
-                self.control_step()
-
-        live = self.tensors()
-        for t in tasks:
-            live = live + t.live_tensors()
-        graph = graph_capture.capture_rolled_back(self.device, body or control_steps, live, _Triple(*tasks))
-        self.graph_launches = {k: (v - counted[k]) // 2 for k, v in self.launches.items()}
-        self.launches = counted
-        for t, n in zip(tasks, steps):
-            t.num_steps = n
-        return graph
-
-    def run(self, n):
-        """``n`` control steps."""
-        super().run(n)
-        if self.graph is not None and int(n) >= self.graph_steps:      # the replayed ones: an eager step counted itself
-            self.predictor.num_steps += int(n) // self.graph_steps * self.graph_steps * self.C
-
     # -- from outside the step -------------------------------------------------------------------------------------------
     def set_model_params(self, values):
         """``Controller.set_model_params``, and each plant's value into the predictor's bound table, not repeated."""
         super().set_model_params(values)
         self.predictor.set_env_params({k: np.asarray(v, dtype=np.float64) for k, v in values.items()})
 
-    def reset_plants(self, ids):
-        """``Controller.reset_plants``; the next frame of each is its episode's first, and its action log starts anew."""
-        import torch
-        ids = torch.as_tensor(ids, device=self.device).to(torch.long)
-        if ids.numel() == 0:
-            return
-        super().reset_plants(ids)
+    def clear_rows(self, ids):
+        """The next frame of each is its episode's first, and its action log starts anew."""
+        super().clear_rows(ids)
         self.fresh[ids] = 1
         self.act_log[ids] = 0.0
 
     def close(self):
         self.predictor.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ a run
+class Play(PlayVariant):
+    """``observe=`` of ``mpc.play``."""
+
+    def check(self, run):
+        self.checked = observe_config(self.spec)
+
+    def make(self, run):
+        pcfg = copy.deepcopy(run.mcfg)                   # the model's plant once more, one env per real plant
+        pcfg["env"]["numEnvs"] = run.M
+        run.predictor = make_task(pcfg, run.device)
+
+    def controller(self, run):
+        return ObservingController(run.plant, run.model, run.predictor, run.samples, self.spec, *run.planner, graph=run.graph)
+
+    def banner(self, run):
+        ctl = run.ctl
+        print("mpc: observing through DELAY %s, HOLD %s, NOISE_Q %s, NOISE_QD %s; %d catch-up steps, %s" % (
+            ctl.spec["DELAY"], ctl.spec["HOLD"], ctl.spec["NOISE_Q"], ctl.spec["NOISE_QD"], ctl.C,
+            "compensated" if ctl.spec["COMPENSATE"] else "not compensated"), flush=True)
+
+    def result(self, run, out):
+        ctl = run.ctl
+        out["observe"] = {"names": list(NAMES), "table": ctl.table_host.copy(), "catchup": ctl.C,
+                          "compensate": ctl.spec["COMPENSATE"], "lag": float(ctl.lag.double().mean())}

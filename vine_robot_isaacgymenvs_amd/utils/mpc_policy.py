@@ -12,7 +12,7 @@ from .. import abi
 from ..learning.fast_inference import FastInferenceMixin
 from .config import ConfigError
 from .mpc import DEFAULTS as MPC_DEFAULTS
-from .mpc import Controller
+from .mpc import Controller, PlayVariant
 
 DEFAULTS = {"ln_eps": 1e-5, "value_eps": 1e-5, "terminal_value": 0.0}
 UNITS = abi.MPC_POLICY_UNITS
@@ -293,27 +293,46 @@ class PolicyController(Controller):
         self.policy_act(self.infer())
         super().model_step()
 
+    def after_fork(self):
+        self.policy_fork()
+
+    def before_update(self):
+        if self.terminal_value != 0.0:
+            self.policy_terminal(self.infer(commit=False))
+
+    def after_update(self):
+        self.policy_compose()
+
     def control_step(self):
-        """One control step, eagerly (or into a capture)."""
         import torch
         with torch.no_grad():
-            self.fork()
-            self.policy_fork()
-            for _ in range(self.H):
-                self.model_step()
-            if self.terminal_value != 0.0:
-                self.policy_terminal(self.infer(commit=False))
-            self.update()
-            self.policy_compose()
-            self.plant.step_into(self.plant_actions, self.plant_obs)
-            self.launches["plant_step"] += 1
+            super().control_step()
 
-    def reset_plants(self, ids):
-        """``Controller.reset_plants``; the policy's LSTM state of those plants starts anew too."""
-        import torch
-        ids = torch.as_tensor(ids, device=self.device).to(torch.long)
-        if ids.numel() == 0:
-            return
-        super().reset_plants(ids)
+    def clear_rows(self, ids):
+        """The policy's LSTM state of those plants starts anew too."""
+        super().clear_rows(ids)
         self.plant_h[ids] = 0.0
         self.plant_c[ids] = 0.0
+
+
+# ------------------------------------------------------------------------------------------------------------------ a run
+class Play(PlayVariant):
+    """``policy=`` of ``mpc.play``, with its ``policy_params`` and ``terminal_value``."""
+
+    def check(self, run):
+        if run.args["policy_params"] is None:
+            raise ConfigError("mpc: policy= needs policy_params, the train.params block the network is built from")
+        check_shape(run.M, run.samples)
+        check_eps("terminal_value", run.args["terminal_value"])
+
+    def controller(self, run):
+        proposal = PolicyProposal(run.args["policy_params"], run.M * int(run.samples), int(run.plant.num_obs), run.plant.device)
+        proposal.restore(self.spec)
+        return PolicyController(run.plant, run.model, run.samples, proposal, *run.planner, graph=run.graph,
+                                terminal_value=run.args["terminal_value"])
+
+    def banner(self, run):
+        print("mpc: the samples roll the policy of %s; terminal_value %g" % (self.spec, float(run.args["terminal_value"])), flush=True)
+
+    def result(self, run, out):
+        out["policy"] = self.spec

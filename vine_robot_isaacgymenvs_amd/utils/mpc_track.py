@@ -182,3 +182,28 @@ class TrackingController(mpc.Controller):
     def control_step(self):
         self.plan()
         super().control_step()
+
+
+# ---- a run
+class Play(mpc.PlayVariant):
+    """``track=`` of ``mpc.play``."""
+    report_params = True       # the plant's varying param_TARGET_* columns
+
+    def check(self, run):
+        self.spec = track_config(self.spec)
+
+    def controller(self, run):
+        import torch
+        self.lived = torch.zeros((), dtype=torch.int64, device=run.plant.device)
+        return TrackingController(run.plant, run.model, run.samples, self.spec, *run.planner, graph=run.graph)
+
+    def banner(self, run):
+        print("mpc: the samples' targets follow the %s path of their plant's ENV_TARGET" % self.spec["PATH"], flush=True)
+
+    def stepped(self, ctl):
+        self.lived += ctl.live.sum()
+
+    def result(self, run, out):
+        out["track"] = {"PATH": self.spec["PATH"], "live_fraction": float(self.lived) / max(1, run.steps * run.M)}
+        print("mpc: tracked along the %s path on %.4g of the (plant, control step) pairs" % (
+            self.spec["PATH"], out["track"]["live_fraction"]), flush=True)
