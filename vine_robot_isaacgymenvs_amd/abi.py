@@ -1025,6 +1025,39 @@ def declare_mpc_track(lib):
     return lib
 
 
+# ---- include/vine_mpc_noise.h (product library only)
+MPC_NOISE_ABI_VERSION = 1
+MPC_NOISE_THREADS = 256
+
+
+class VineMpcNoiseConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("beta", C.c_float * 2),
+        ("adapt", C.c_int32),
+        ("rate", C.c_double),
+        ("sigma_min", C.c_float * 2),
+        ("sigma_max", C.c_float * 2),
+    ]
+
+
+_MPC_NOISE_HEAD = [_H, _P(VineMpcConfig), _P(VineMpcNoiseConfig)]
+MPC_NOISE_PROTOTYPES = {
+    "vine_mpc_noise_config_default": (C.c_int, [_P(VineMpcNoiseConfig)]),
+    "vine_mpc_noise_config_size": (C.c_int, []),
+    "vine_mpc_noise_draw": (C.c_int, _MPC_NOISE_HEAD + [_VP] * 3),
+    "vine_mpc_noise_scheduled": (C.c_int, _MPC_NOISE_HEAD + [_VP] * 6),
+    "vine_mpc_noise_update": (C.c_int, _MPC_NOISE_HEAD + [_VP] * 10),
+}
+
+
+def declare_mpc_noise(lib):
+    _attach(lib, MPC_NOISE_PROTOTYPES)
+    if lib.vine_mpc_noise_config_size() != C.sizeof(VineMpcNoiseConfig):
+        raise RuntimeError("VineMpcNoiseConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_env_draw_adr.h (product library only)
 ENV_DRAW_ADR_ABI_VERSION = 1
 ENV_DRAW_ADR_THREADS = 256
@@ -1099,6 +1132,6 @@ def declare_all(lib):
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
                         declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track,
-                        declare_env_draw_adr):
+                        declare_env_draw_adr, declare_mpc_noise):
         declare_one(lib)
     return lib

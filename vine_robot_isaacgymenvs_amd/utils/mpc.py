@@ -166,18 +166,19 @@ def cost_sums(rew, reset):
     return cost, alive.astype(np.uint8)
 
 
-def mpc_replay(nominal, cost, sigma, lam, seed, tick, clip, plant_reset=None, history=None):
+def mpc_replay(nominal, cost, sigma, lam, seed, tick, clip, plant_reset=None, history=None, u=None):
     """One control step's update on the host: the numpy statement of ``u``, the weights, the new nominal, the shift, the
     reset branch and the history.  ``nominal`` [M, H, 2] float32; ``cost`` [M * K] float64 (+inf allowed); ``tick`` [M];
     ``clip``: the model's clipActions; ``plant_reset`` [M] (default none raised); ``history`` [M, MAX_DELAY, 2] (default
-    zeros).  Returns a dict: ``u`` [M, K, H, 2], ``weights`` [M, K] float64, ``new`` [M, H, 2] float32 (before the shift),
-    ``nominal`` (after), ``plant_actions`` [M, 2], ``history``, ``tick``."""
+    zeros); ``u`` [M, K, H, 2]: the samples' actions where they are not ``sample_actions``' (utils/mpc_noise.py).  Returns a
+    dict: ``u`` [M, K, H, 2], ``weights`` [M, K] float64, ``new`` [M, H, 2] float32 (before the shift), ``nominal`` (after),
+    ``plant_actions`` [M, 2], ``history``, ``tick``."""
     nominal = np.asarray(nominal, dtype=np.float32)
     M, H = nominal.shape[0], nominal.shape[1]
     cost = np.asarray(cost, dtype=np.float64).reshape(M, -1)
     K = cost.shape[1]
     tick = np.broadcast_to(np.asarray(tick, dtype=np.int64), (M,))
-    u = sample_actions(nominal, sigma, seed, K, tick, clip)
+    u = sample_actions(nominal, sigma, seed, K, tick, clip) if u is None else np.asarray(u, dtype=np.float32)
     beta = cost.min(axis=1)
     finite = np.isfinite(beta)
     with np.errstate(invalid="ignore", over="ignore"):
@@ -465,12 +466,15 @@ class PlayVariant:
         return Controller(run.plant, run.model, run.samples, *run.planner, graph=run.graph)
 
 
-VARIANTS = ("track", "observe", "filter", "policy", "adapt")      # the order they are walked in; each is utils/mpc_<key>.Play
+# the order they are walked in; each is utils/mpc_<key>.Play.  "noise" stands alone, and stands first: its check is the refusal of
+# every other, which must come before any of theirs (it is not in RULES, whose keys a test pins)
+VARIANTS = ("noise", "track", "observe", "filter", "policy", "adapt")
 
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
-         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None, track=None):
+         logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None, track=None,
+         noise=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -509,7 +513,14 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     velocity columns) and with ``adapt``, ``observe`` or ``filter`` (their third handles and traces were built for a resting
     target).  The result then holds ``track``: ``PATH`` and ``live_fraction``, the share of (plant, control step) pairs whose
     samples followed a path; the per-parameter report has the plant's varying ``param_TARGET_*`` columns.  Without it nothing
-    of this is constructed or launched."""
+    of this is constructed or launched.
+
+    ``noise``: a spec of ``mpc_noise.noise_config``, ``{BETA: 0.8}`` or ``{BETA: [0.9, 0.7], ADAPT: {RATE: .., SIGMA_MIN: ..,
+    SIGMA_MAX: ..}}`` -- the samples' perturbations are correlated over the horizon and, with ``ADAPT``, each plant's amplitude
+    follows the spread of the samples its weights preferred (include/vine_mpc_noise.h, ``mpc_noise.NoiseController``).  It is
+    refused together with every other variant (``mpc_noise.Play.check``, not ``RULES``: they compute their own perturbations).
+    The result then holds ``noise``: ``BETA``, ``ADAPT`` and the mean, minimum and maximum of the final ``sigma_p``.  Without it
+    nothing of this is constructed or launched."""
     import importlib
     import types
 
@@ -527,7 +538,7 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
     args = {"adapt": adapt, "policy": policy, "terminal_value": terminal_value, "policy_params": policy_params,
-            "observe": observe, "filter": filter, "track": track}
+            "observe": observe, "filter": filter, "track": track, "noise": noise}
     refuse({k for k in VARIANTS if args[k] is not None} | ({"terminal_value"} if terminal_value else set())
            | ({"ENV_TARGET"} if cfg["env"].get("ENV_TARGET") else set()))
     given = {k: importlib.import_module(".mpc_" + k, __package__).Play(args[k]) for k in VARIANTS if args[k] is not None}
