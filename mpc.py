@@ -11,6 +11,9 @@
   python mpc.py plants=64 steps=2000 'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1]}' \\
       'adapt={params: {DAMPING: [0.005, 0.1], FPAM_K: [0.7, 1.3]}, window: 8, every: 8}'   # the model follows each plant
 
+  python mpc.py plants=64 steps=2000 'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1], LINK_MASS: [0.7, 1.4]}' \\
+      'adapt={params: {DAMPING: [0.005, 0.1]}, masses: {LINK_MASS: [0.7, 1.4]}}'       # ... in its masses too
+
   python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True policy=runs/Vine5LinkMovingBase/nn/Vine5LinkMovingBase.pth \\
       terminal_value=1.0                                                             # the samples roll this policy
 
@@ -31,7 +34,9 @@
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
 DESIGN.md section 25: ``params`` maps names of the ``ENV_PARAMS`` table to the range ``[lo, hi]`` the belief lives in; ``window``,
-``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``), ``policy`` (a checkpoint of ``train.py``:
+``every``, ``min_steps``, ``temperature``, ``rate``, ``spread``, ``floor``, ``weights``; ``masses`` maps ``CART_MASS`` (kg), ``LINK_MASS``
+and ``TIP_LINK_MASS`` (factors on the model configuration's link masses and inertias) to such a range and may stand without
+``params``), ``policy`` (a checkpoint of ``train.py``:
 the samples roll it and the planner's sequence is a residual on its mean; the network is the composed
 configuration's ``train.params``; plants * samples must be a multiple of 512), ``terminal_value`` (the weight of the critic's
 value behind the horizon; default 0), ``observe`` (the planner sees its plants through a sensing path of its own, DESIGN.md

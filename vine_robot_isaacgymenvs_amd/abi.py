@@ -1058,6 +1058,50 @@ def declare_mpc_noise(lib):
     return lib
 
 
+# ---- include/vine_mpc_adapt_inertia.h (product library only)
+MPC_ADAPT_INERTIA_ABI_VERSION = 1
+MPC_ADAPT_INERTIA_MAX_DIMS = 3
+MPC_ADAPT_INERTIA_CART, MPC_ADAPT_INERTIA_LINK, MPC_ADAPT_INERTIA_TIP = range(3)      # in the order of ENV_INERTIA_NAMES
+
+
+class VineMpcAdaptInertiaDim(C.Structure):
+    _fields_ = [
+        ("name", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lo", C.c_double),
+        ("hi", C.c_double),
+        ("std_floor", C.c_double),
+    ]
+
+
+class VineMpcAdaptInertiaConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("num_mass_dims", C.c_int32),
+        ("dims", VineMpcAdaptInertiaDim * MPC_ADAPT_INERTIA_MAX_DIMS),
+        ("base_inertia", C.c_float * VI_PRIMARY_COUNT),
+        ("link_length", C.c_float),
+        ("link_com", C.c_float),
+        ("gravity", C.c_float),
+    ]
+
+
+_MPC_ADAPT_INERTIA_HEAD = [_H, _P(VineMpcAdaptConfig), _P(VineMpcAdaptInertiaConfig)]
+MPC_ADAPT_INERTIA_PROTOTYPES = {
+    "vine_mpc_adapt_inertia_config_default": (C.c_int, [_P(VineMpcAdaptInertiaConfig)]),
+    "vine_mpc_adapt_inertia_config_size": (C.c_int, []),
+    "vine_mpc_adapt_inertia_pin": (C.c_int, _MPC_ADAPT_INERTIA_HEAD + [_VP] * 5),
+    "vine_mpc_adapt_inertia_estimate": (C.c_int, _MPC_ADAPT_INERTIA_HEAD + [_VP] * 11),
+}
+
+
+def declare_mpc_adapt_inertia(lib):
+    _attach(lib, MPC_ADAPT_INERTIA_PROTOTYPES)
+    if lib.vine_mpc_adapt_inertia_config_size() != C.sizeof(VineMpcAdaptInertiaConfig):
+        raise RuntimeError("VineMpcAdaptInertiaConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_env_draw_adr.h (product library only)
 ENV_DRAW_ADR_ABI_VERSION = 1
 ENV_DRAW_ADR_THREADS = 256
@@ -1132,6 +1176,6 @@ def declare_all(lib):
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
                         declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track,
-                        declare_env_draw_adr, declare_mpc_noise):
+                        declare_env_draw_adr, declare_mpc_noise, declare_mpc_adapt_inertia):
         declare_one(lib)
     return lib

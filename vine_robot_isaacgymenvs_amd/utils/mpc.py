@@ -486,7 +486,9 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     ``adapt``: a spec of ``mpc_adapt.adapt_config`` -- the model follows each plant online (include/vine_mpc_adapt.h), with
     ``forget_on_reset`` when the plant has ``ENV_PARAMS_PER_EPISODE``.  The result then holds ``adapt``: ``names``, the final
     ``mean`` and ``std`` [M, D], ``prior_mean``, and, where the plant carries an ``ENV_PARAMS`` table, ``truth`` and per name
-    the mean absolute error of the prior and of the final belief (printed too).  Without it nothing of this is launched.
+    the mean absolute error of the prior and of the final belief (printed too).  With ``masses`` in the spec the belief carries
+    mass dimensions too (include/vine_mpc_adapt_inertia.h, ``mpc_adapt_inertia.AdaptiveInertiaController``) and ``adapt`` gains
+    ``mass_names``, ``mass_mean``, ``mass_std``, ``mass_prior_mean`` and ``mass_truth``.  Without it nothing of this is launched.
 
     ``policy``: a checkpoint of ``train.py`` -- the samples roll that policy and the planner's sequence is a residual on its
     mean (include/vine_mpc_policy.h, ``mpc_policy.PolicyController``); ``policy_params`` is the ``train.params`` block of the

@@ -17,7 +17,7 @@ from .mpc import Controller, PlayVariant, check_integer, check_real
 
 # temperature, rate, spread and floor: see DESIGN.md section 25 ("The four constants") for what they were checked against
 DEFAULTS = {"window": 8, "every": 8, "min_steps": 4, "temperature": 0.1, "rate": 0.5, "spread": 0.25, "floor": 0.01}
-KEYS = ("params",) + tuple(DEFAULTS) + ("weights",)
+KEYS = ("params", "masses") + tuple(DEFAULTS) + ("weights",)      # masses: utils/mpc_adapt_inertia.py
 REFUSED = {
     "ACTION_DELAY": "an integer: its belief is not Gaussian, and a weighted mean of delays is no delay",
     "CART_MASS": "it lives in the inertia table, whose derived rows need the composites formed on the host",
@@ -235,12 +235,16 @@ class AdaptiveController(Controller):
     bound (``task.env.ENV_PARAMS``): the device writes its adapted rows, so ``model._env_params_host`` is stale for them;
     ``set_model_params`` refuses an adapted name and refreshes those rows of the mirror from the device before it rewrites
     any other."""
+    owns_masses = False        # utils/mpc_adapt_inertia.py AdaptiveInertiaController: the mass dimensions of ``adapt.masses``
 
     def __init__(self, plant_task, model_task, samples, adapt, horizon=MPC_DEFAULTS["horizon"], lam=MPC_DEFAULTS["lambda"],
                  sigma=MPC_DEFAULTS["sigma"], seed=MPC_DEFAULTS["seed"], graph=True, graph_cycles=1, keep_weights=False,
                  forget_on_reset=False):
         import torch
         from . import env_params
+        if hasattr(adapt, "keys") and "masses" in adapt.keys() and not self.owns_masses:
+            raise ConfigError("mpc adapt: masses is mpc_adapt_inertia.AdaptiveInertiaController's key; this controller has no mass "
+                              "dimensions")
         super().__init__(plant_task, model_task, samples, horizon, lam, sigma, seed, graph=graph, graph_steps=1,
                          keep_weights=keep_weights)
         if model_task.env_params is None:
@@ -437,12 +441,28 @@ class Play(PlayVariant):
     """``adapt=`` of ``mpc.play``."""
     single_run = True          # whole cycles replay from one graph: the trace node sums the reward into ``ctl.returns``
 
+    def masses(self):
+        """utils/mpc_adapt_inertia.py where the spec has ``masses``, else ``None``: without the key
+        nothing of that module is imported."""
+        if not (hasattr(self.spec, "keys") and "masses" in self.spec.keys()):
+            return None
+        from . import mpc_adapt_inertia
+        return mpc_adapt_inertia
+
+    def check(self, run):
+        if self.masses() is not None:
+            self.masses().check_masses(self.spec)
+
     def bind(self, run):
         if not run.mcfg["env"].get("ENV_PARAMS"):
             run.mcfg["env"]["ENV_PARAMS"] = {"FPAM_K": 1.0}      # binds a table of the configuration's own row: what is adapted
+        if self.masses() is not None:
+            self.masses().bind(run)                              # ... and an inertia table of it, likewise
 
     def controller(self, run):
         from . import env_params
+        if self.masses() is not None:
+            return self.masses().controller(run, self.spec, env_params.per_episode(run.cfg["env"]))
         if run.draws:              # the one exception: the prior is the model's value when the controller is made
             run.model.set_env_params({k: np.repeat(v, int(run.samples)) for k, v in run.draws.items()})
             run.draws = None
@@ -451,7 +471,8 @@ class Play(PlayVariant):
 
     def banner(self, run):
         ctl = run.ctl
-        print("mpc: adapting %s every %d control steps over a window of %d" % (", ".join(ctl.names), ctl.E, ctl.W), flush=True)
+        names = list(ctl.names) + list(getattr(ctl, "mass_names", ()))
+        print("mpc: adapting %s every %d control steps over a window of %d" % (", ".join(names), ctl.E, ctl.W), flush=True)
 
     def epilogue(self, run, out):
         ctl = run.ctl
@@ -467,3 +488,5 @@ class Play(PlayVariant):
             out["adapt"]["final_error"][name] = float(np.abs(mean[:, d] - truth[:, d]).mean())
             print("  adapt %s: mean |prior - truth| %.4g, mean |belief - truth| %.4g" % (
                 name, out["adapt"]["prior_error"][name], out["adapt"]["final_error"][name]), flush=True)
+        if self.masses() is not None:
+            self.masses().epilogue(ctl, out)
