@@ -30,6 +30,11 @@
   python mpc.py plants=64 steps=2000 task.env.EPISODE_LOG=True \\
       'noise={BETA: 0.8, ADAPT: {RATE: 0.2, SIGMA_MIN: 0.05, SIGMA_MAX: 1.0}}'       # correlated samples, a sigma per plant
 
+  python mpc.py plants=64 samples=1024 steps=2000 task.env.EPISODE_LOG=True \\
+      'task.env.ENV_PARAMS={DAMPING: [0.005, 0.1], LINK_MASS: [0.7, 1.4]}' \\
+      'ensemble={params: {DAMPING: [0.005, 0.1], LINK_MASS: [0.7, 1.4]}, MEMBERS: 4, RISK: entropic, THETA: 0.5}'
+                                                                                     # every sequence on four candidate plants
+
 ``plants``, ``samples``, ``horizon``, ``lambda``, ``sigma`` (one number or ``[rail, fpam]``), ``steps``, ``cost`` (a mapping of
 ``*_REWARD_WEIGHT`` keys for the model only; default ``{POSITION_REWARD_WEIGHT: 1.0}``), ``model_params`` (an ``ENV_PARAMS``-style
 spec, drawn once per plant and repeated over the plant's samples), ``adapt`` (online adaptation of the model to each plant,
@@ -45,14 +50,17 @@ section 27: ``DELAY``, ``HOLD``, ``NOISE_Q``, ``NOISE_QD`` as ``ENV_SENSOR`` tak
 (the samples' targets follow their plant's ``task.env.ENV_TARGET`` path over the horizon, DESIGN.md section 30: ``PATH`` is
 ``exact``, ``linear`` or ``held``; refused with ``policy``, ``adapt``, ``observe`` and ``filter``), ``noise`` (the samples'
 perturbations are correlated over the horizon, DESIGN.md section 32: ``BETA`` in [0, 1), one number or ``[rail, fpam]``, and
-optionally ``ADAPT`` with ``RATE``, ``SIGMA_MIN``, ``SIGMA_MAX`` for a sigma per plant; refused with every other variant) and ``out``
+optionally ``ADAPT`` with ``RATE``, ``SIGMA_MIN``, ``SIGMA_MAX`` for a sigma per plant; refused with every other variant),
+``ensemble`` (every action sequence is rolled through ``MEMBERS`` candidate plants drawn from the ``ENV_PARAMS``-style ``params``
+and weighted by ``RISK`` -- ``mean``, ``max`` or ``entropic`` with ``THETA`` -- over their costs; ``samples``
+must be a multiple of ``MEMBERS``; refused with every other variant and with ``model_params``) and ``out``
 (directory of the episode log's .npz; default ``runs/mpc``) are this tool's own keys; every other ``key=value`` is an override of the project's configuration for the PLANT, in its syntax (``seed=``, ``task.env.CREATE_PIPE=`` ...)."""
 import logging
 import sys
 
 OWN = {"plants": 64, "samples": 256, "horizon": 20, "lambda": 0.05, "sigma": 0.5, "steps": 500, "cost": None,
        "model_params": None, "adapt": None, "policy": None, "terminal_value": 0.0, "observe": None, "filter": None,
-       "track": None, "noise": None, "out": "runs/mpc"}
+       "track": None, "noise": None, "ensemble": None, "out": "runs/mpc"}
 
 
 def main(argv=None):
@@ -66,7 +74,7 @@ def main(argv=None):
             own[key] = val if key in ("out", "policy") else parse_scalar(val)
         else:
             overrides.append(arg)
-    for key in ("cost", "model_params", "adapt", "observe", "filter", "track", "noise"):
+    for key in ("cost", "model_params", "adapt", "observe", "filter", "track", "noise", "ensemble"):
         if own[key] is not None and not hasattr(own[key], "keys"):
             raise ConfigError("mpc: %s={NAME: value, ...} must be a mapping, not %r" % (key, own[key]))
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -81,7 +89,7 @@ def main(argv=None):
                     seed=int(seed) if isinstance(seed, int) and seed >= 0 else 0, device=cfg.get("sim_device", "cuda:0"),
                     adapt=own["adapt"], policy=own["policy"], terminal_value=own["terminal_value"],
                     policy_params=cfg["train"]["params"] if own["policy"] else None, observe=own["observe"],
-                    filter=own["filter"], track=own["track"], noise=own["noise"])
+                    filter=own["filter"], track=own["track"], noise=own["noise"], ensemble=own["ensemble"])
 
 
 if __name__ == "__main__":

@@ -1058,6 +1058,38 @@ def declare_mpc_noise(lib):
     return lib
 
 
+# ---- include/vine_mpc_ensemble.h (product library only)
+MPC_ENSEMBLE_ABI_VERSION = 1
+MPC_ENSEMBLE_MAX_MEMBERS = 16
+MPC_RISK_MEAN, MPC_RISK_MAX, MPC_RISK_ENTROPIC = range(3)
+MPC_RISK_NAMES = ("mean", "max", "entropic")                     # the RISK of an ``ensemble=`` mapping, by VINE_MPC_RISK_*
+
+
+class VineMpcEnsembleConfig(C.Structure):
+    _fields_ = [
+        ("abi_version", C.c_int32),
+        ("members", C.c_int32),
+        ("risk", C.c_int32),
+        ("theta", C.c_double),
+    ]
+
+
+_MPC_ENSEMBLE_HEAD = [_H, _P(VineMpcConfig), _P(VineMpcEnsembleConfig)]
+MPC_ENSEMBLE_PROTOTYPES = {
+    "vine_mpc_ensemble_config_default": (C.c_int, [_P(VineMpcEnsembleConfig)]),
+    "vine_mpc_ensemble_config_size": (C.c_int, []),
+    "vine_mpc_ensemble_scheduled": (C.c_int, _MPC_ENSEMBLE_HEAD + [_VP] * 5),
+    "vine_mpc_ensemble_update": (C.c_int, _MPC_ENSEMBLE_HEAD + [_VP] * 9),
+}
+
+
+def declare_mpc_ensemble(lib):
+    _attach(lib, MPC_ENSEMBLE_PROTOTYPES)
+    if lib.vine_mpc_ensemble_config_size() != C.sizeof(VineMpcEnsembleConfig):
+        raise RuntimeError("VineMpcEnsembleConfig: the library's struct size differs from the ctypes mirror")
+    return lib
+
+
 # ---- include/vine_mpc_adapt_inertia.h (product library only)
 MPC_ADAPT_INERTIA_ABI_VERSION = 1
 MPC_ADAPT_INERTIA_MAX_DIMS = 3
@@ -1176,6 +1208,6 @@ def declare_all(lib):
     for declare_one in (declare, declare_ppo, declare_render, declare_record, declare_episodes, declare_env_params, declare_env_inertia,
                         declare_env_redraw, declare_env_adr, declare_env_sensor, declare_env_push, declare_env_target, declare_sysid, declare_mpc,
                         declare_mpc_adapt, declare_mpc_policy, declare_mpc_observe, declare_mpc_filter, declare_mpc_track,
-                        declare_env_draw_adr, declare_mpc_noise, declare_mpc_adapt_inertia):
+                        declare_env_draw_adr, declare_mpc_noise, declare_mpc_adapt_inertia, declare_mpc_ensemble):
         declare_one(lib)
     return lib

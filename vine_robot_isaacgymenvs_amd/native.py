@@ -64,6 +64,10 @@ NOISE_UNITS = (SRC_MPC_NOISE,)
 # the mass dimensions of the controller's model adaptation, follows in INERTIA_UNITS, which build() maps the helper over behind it
 SRC_MPC_ADAPT_INERTIA = os.path.join(_HERE, "csrc", "vine_mpc_adapt_inertia.hip")
 INERTIA_UNITS = (SRC_MPC_ADAPT_INERTIA,)
+# tests/test_mpc_adapt_inertia_cpu.py pins INERTIA_UNITS to that one and the line of build() that maps the helper over it; the
+# twenty-first, the controller's ensemble of candidate plants, follows in ENSEMBLE_UNITS, which build() maps the helper over behind it
+SRC_MPC_ENSEMBLE = os.path.join(_HERE, "csrc", "vine_mpc_ensemble.hip")
+ENSEMBLE_UNITS = (SRC_MPC_ENSEMBLE,)
 LIB = os.path.join(_HERE, "libvine_hip.so")
 ARCH = "gfx950"
 
@@ -93,6 +97,7 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
                                    os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH],
                    SRC_MPC: [os.path.join(_INC, "vine_mpc.h"), _MPC_SHARED],
                    SRC_MPC_NOISE: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_noise.h"), _MPC_SHARED],
+                   SRC_MPC_ENSEMBLE: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_ensemble.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED],
                    SRC_MPC_ADAPT_INERTIA: [os.path.join(_INC, "vine_mpc.h"), os.path.join(_INC, "vine_mpc_adapt.h"),
                                            os.path.join(_INC, "vine_mpc_adapt_inertia.h"), _COMPOSITES, _MPC_SHARED],
@@ -119,6 +124,8 @@ _SOURCE_HEADERS = {SRC: [_COMPOSITES], SRC_REDRAW: _REDRAW_HEADERS, SRC_ADR: _RE
 # vine_mpc_noise.hip forms a perturbation, b * eps + g * z, and vine_mpc.hip's action around it, bit for bit numpy's: the same again
 # vine_mpc_adapt_inertia.hip forms a candidate mass, mean + z * std, and the composites of a column, m l + L distal, bit for bit
 # those of numpy and of vine_env_inertia_derive: the same again
+# vine_mpc_ensemble.hip forms vine_mpc.hip's action for a group and a group's cost, cmax + log(sum / E) / theta, in the float64
+# operations numpy performs: the same again
 _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_SENSOR: ["-ffp-contract=fast-honor-pragmas"], SRC_PUSH: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC: ["-ffp-contract=fast-honor-pragmas"], SRC_MPC_ADAPT: ["-ffp-contract=fast-honor-pragmas"],
@@ -126,7 +133,8 @@ _SOURCE_FLAGS = {SRC_REDRAW: ["-ffp-contract=off"], SRC_ADR: ["-ffp-contract=fas
                  SRC_MPC_FILTER: ["-ffp-contract=fast-honor-pragmas"], SRC_TARGET: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_TRACK: ["-ffp-contract=fast-honor-pragmas"], SRC_DRAW_ADR: ["-ffp-contract=fast-honor-pragmas"],
                  SRC_MPC_NOISE: ["-ffp-contract=fast-honor-pragmas"],
-                 SRC_MPC_ADAPT_INERTIA: ["-ffp-contract=fast-honor-pragmas"]}
+                 SRC_MPC_ADAPT_INERTIA: ["-ffp-contract=fast-honor-pragmas"],
+                 SRC_MPC_ENSEMBLE: ["-ffp-contract=fast-honor-pragmas"]}
 DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, "vine_env_sensor.h")]
         + [SRC_PUSH, os.path.join(_INC, "vine_env_push.h")] + [SRC_MPC, os.path.join(_INC, "vine_mpc.h")]
         + [SRC_MPC_ADAPT, os.path.join(_INC, "vine_mpc_adapt.h"), _MPC_SHARED]
@@ -137,7 +145,8 @@ DEPS = (list(UNITS) + _HEADERS + _SOURCE_HEADERS[SRC_ADR] + [os.path.join(_INC, 
         + [SRC_MPC_TRACK, os.path.join(_INC, "vine_mpc_track.h"), _TARGET_PATH]
         + [SRC_DRAW_ADR, os.path.join(_INC, "vine_env_draw_adr.h"), _ADR_SHARED]
         + [SRC_MPC_NOISE, os.path.join(_INC, "vine_mpc_noise.h")]
-        + [SRC_MPC_ADAPT_INERTIA, os.path.join(_INC, "vine_mpc_adapt_inertia.h")])
+        + [SRC_MPC_ADAPT_INERTIA, os.path.join(_INC, "vine_mpc_adapt_inertia.h")]
+        + [SRC_MPC_ENSEMBLE, os.path.join(_INC, "vine_mpc_ensemble.h")])
 
 _lib = None
 
@@ -177,7 +186,7 @@ def _object_fingerprint(src):
 
 def build(force=False, verbose=False):
     """hipcc cross-compiles for gfx950 (works without a GPU); output stays in-tree.  The seventeen translation units and the
-    eighteenth, nineteenth and twentieth behind them (``LATER_UNITS``, ``NOISE_UNITS``, ``INERTIA_UNITS``) are compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
+    eighteenth to twenty-first behind them (``LATER_UNITS``, ``NOISE_UNITS``, ``INERTIA_UNITS``, ``ENSEMBLE_UNITS``) are compiled side by side into ``build/obj`` (each object is reused while its source, the headers and the flags are
     unchanged) and linked into the one library.  A sidecar fingerprint of the sources is written next to the library:
     ``load()`` refuses to call into a library built from other sources (a stale binary behind a changed C signature is a
     wild pointer on the GPU)."""
@@ -215,6 +224,8 @@ def build(force=False, verbose=False):
     for _ in map(compile_unit, NOISE_UNITS):      # the nineteenth: likewise
         pass
     for _ in map(compile_unit, INERTIA_UNITS):      # the twentieth: likewise
+        pass
+    for _ in map(compile_unit, ENSEMBLE_UNITS):      # the twenty-first: likewise
         pass
     for proc, cmd, obj, fp in jobs:
         if proc.wait() != 0:

@@ -469,12 +469,15 @@ class PlayVariant:
 # the order they are walked in; each is utils/mpc_<key>.Play.  "noise" stands alone, and stands first: its check is the refusal of
 # every other, which must come before any of theirs (it is not in RULES, whose keys a test pins)
 VARIANTS = ("noise", "track", "observe", "filter", "policy", "adapt")
+# ... and in front of them all, from a tuple of its own (a test pins VARIANTS): "ensemble" (utils/mpc_ensemble.Play), whose check
+# is the refusal of every key of VARIANTS and of model_params=, as noise's is of the others
+FIRST = ("ensemble",)
 
 
 def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizon"], lam=DEFAULTS["lambda"],
          sigma=DEFAULTS["sigma"], steps=500, cost=None, model_params=None, seed=None, device="cuda:0", graph=True,
          logger=None, adapt=None, policy=None, terminal_value=0.0, policy_params=None, observe=None, filter=None, track=None,
-         noise=None):
+         noise=None, ensemble=None):
     """Run ``steps`` control steps of MPC on the task config ``cfg`` (the ``task`` block of the composed configuration; its
     ``env.numEnvs`` plants unless ``plants`` is given) and report through the plant's ``EPISODE_LOG`` when it is on:
     ``episodes.report`` of the episodes finished in the run, and ``reached_ever_rate`` by every varying plant parameter when
@@ -522,7 +525,17 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     follows the spread of the samples its weights preferred (include/vine_mpc_noise.h, ``mpc_noise.NoiseController``).  It is
     refused together with every other variant (``mpc_noise.Play.check``, not ``RULES``: they compute their own perturbations).
     The result then holds ``noise``: ``BETA``, ``ADAPT`` and the mean, minimum and maximum of the final ``sigma_p``.  Without it
-    nothing of this is constructed or launched."""
+    nothing of this is constructed or launched.
+
+    ``ensemble``: a spec of ``mpc_ensemble.ensemble_config``, ``{params: {DAMPING: [0.005, 0.1], ...}, MEMBERS: 4, RISK: mean | max
+    | entropic, THETA: .., SEED: ..}`` -- a plant's samples are ``samples / MEMBERS`` action sequences, each rolled through
+    ``MEMBERS`` candidate plants drawn from ``params`` once per run, and a sequence is weighted by ``RISK`` over its members' costs
+    (include/vine_mpc_ensemble.h, ``mpc_ensemble.EnsembleController``): the planner knows the range of its plant, as a
+    domain-randomised policy does.  It is refused together with every key of ``VARIANTS`` and with ``model_params``
+    (``mpc_ensemble.Play.check``, not ``RULES``), and where ``samples`` is no multiple of ``MEMBERS``.  The result then holds
+    ``ensemble``: the spec, the seed of the draw, per parameter the members' mean, minimum and maximum, and ``disagreement``, the
+    mean over the last update's sequences of the largest minus the smallest member cost.  Without it nothing of this is
+    constructed or launched."""
     import importlib
     import types
 
@@ -540,10 +553,11 @@ def play(cfg, plants=None, samples=DEFAULTS["samples"], horizon=DEFAULTS["horizo
     seed = int(seed) if isinstance(seed, (int, np.integer)) and seed >= 0 else 0
     mpc_config(M, samples, horizon, lam, sigma, seed)                      # refuse a bad key before anything is created
     args = {"adapt": adapt, "policy": policy, "terminal_value": terminal_value, "policy_params": policy_params,
-            "observe": observe, "filter": filter, "track": track, "noise": noise}
+            "observe": observe, "filter": filter, "track": track, "noise": noise, "ensemble": ensemble,
+            "model_params": model_params}
     refuse({k for k in VARIANTS if args[k] is not None} | ({"terminal_value"} if terminal_value else set())
            | ({"ENV_TARGET"} if cfg["env"].get("ENV_TARGET") else set()))
-    given = {k: importlib.import_module(".mpc_" + k, __package__).Play(args[k]) for k in VARIANTS if args[k] is not None}
+    given = {k: importlib.import_module(".mpc_" + k, __package__).Play(args[k]) for k in FIRST + VARIANTS if args[k] is not None}
     active = list(given.values())
 
     def each(what, *a):
